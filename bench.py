@@ -45,6 +45,20 @@ SOLVE_STEPS_DEFAULT = 14          # real Newton/PCG steps of the reference sched
 SOLVE_STEPS_TOTAL_DEFAULT = 25    # ... and the solve goes on to this step after the timed regions: per-step in-solve kernel rates up to the plateau of the
                                   # dt = 0.1 segment (steps 3..21 of test/data/custom_dt.txt) and into the dt = 0.2 segment (22..27)
 PREP_DTS = [0.005, 0.195, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.1]   # first 10 steps of the reference schedule: 0.1 % strain, plastic
+DUMP_POINTS = 131072              # --dump-outputs: seeded sample of quadrature points; 6 stress + 28 state doubles each = 35.7 MB, under the 64 MB cap
+DUMP_SEED = 20241015
+
+
+def dump_outputs(L, drv, out_dir):
+    """--dump-outputs: what the last timed constitutive pass handed its caller - end-of-step Cauchy stress (6 Voigt components) and state variables
+    (28) per quadrature point - as out_dir/stress.npy (S, 6) and out_dir/state.npy (S, 28), float64, rows in the driver's [element][point] order.
+    S = every local point up to DUMP_POINTS, else a fixed seeded sample of DUMP_POINTS of them (sorted), the same for the same arguments.  Call it
+    before anything else runs a constitutive pass on `drv` (the PCG and adapter blocks and the continued solve overwrite these fields)."""
+    P = L.exa_driver_local_qpts(drv.h)
+    idx = np.arange(P) if P <= DUMP_POINTS else np.sort(np.random.default_rng(DUMP_SEED).choice(P, DUMP_POINTS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "stress.npy"), np.stack([drv.qf_component(3, c)[idx] for c in range(6)], axis=1))
+    np.save(os.path.join(out_dir, "state.npy"), np.stack([drv.qf_component(1, c)[idx] for c in range(28)], axis=1))
 
 
 def host_cores():
@@ -204,6 +218,8 @@ def bench_order2(args, L, N, props, quats, mk, rank, world, fresh_uid, barrier, 
     barrier(); t_model = max_over_ranks(time.perf_counter() - t0)
     kern_ms = max_over_ranks(m["kernel_ms"]) / args.steps
     nfev = drv.nfev_hist()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(L, drv, args.dump_outputs)
     drv.bench_pcg(10)
     barrier(); t0 = time.perf_counter()
     pc = drv.bench_pcg(args.pcg_iters)
@@ -266,6 +282,9 @@ def main():
                     help="real Newton/PCG time steps of the reference schedule that bring the RVE to the benchmark state (0: kinematically driven state only)")
     ap.add_argument("--solve-steps-total", type=int, default=int(os.environ.get("EXA_BENCH_SOLVE_STEPS_TOTAL", str(SOLVE_STEPS_TOTAL_DEFAULT))),
                     help="after the timed regions the solve continues (committing --solve-steps) up to this step of the schedule, for the in-solve rates")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed constitutive passes, write what the last of them computed (end-of-step stress and state at a seeded sample of "
+                         f"at most {DUMP_POINTS} quadrature points; rank 0's share with several ranks) as DIR/stress.npy and DIR/state.npy, float64")
     args = ap.parse_args()
     if args.n is None:
         args.n = 128 if args.order == 1 else 64
@@ -429,6 +448,8 @@ def main():
         t_model, kern_ms, failed, nfev = t_kin, kin_kern_ms, kin_failed, kin_hist
     m = {"failed": failed}
     value = P_global * args.steps / t_model
+    if args.dump_outputs and rank == 0:
+        dump_outputs(L, drv, args.dump_outputs)
     # ---- timed region 2: PCG iterations (same state) ----------------------------------------------------------------------------------
     drv.bench_pcg(max(2, args.pcg_iters // 10))   # warm-up
     barrier()

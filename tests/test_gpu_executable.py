@@ -66,13 +66,13 @@ def test_executable_under_mpirun_one_rank(tmp_path):
     _check_against_golden(tmp_path, "mtsdd_bcc")
 
 
-@pytest.mark.parametrize("np_", [2, 8])
+@pytest.mark.parametrize("np_", [2, 4])
 def test_executable_ranks(tmp_path, np_):
-    """The reference's regression command line, `mpirun -np N mechanics -opt voce_pa.toml` (test/test_mechanics.py:38), N = 2 and N = 8 (the 10^3
-    mesh on 2 x 2 x 2 blocks).  One GPU per rank: RCCL; a one-GPU box: the ranks hand the identity of their device to rank 0 in the rendez-vous,
+    """The reference's regression command line, `mpirun -np N mechanics -opt voce_pa.toml` (test/test_mechanics.py:38), N = 2 and N = 4 (the 10^3
+    mesh on 1 x 2 x 2 blocks; at most 4 rank processes, so that the test and its ranks keep within 6 processes with the GPU open).  One GPU per rank: RCCL; a one-GPU box: the ranks hand the identity of their device to rank 0 in the rendez-vous,
     which finds them on one device and answers with the id of the shared-device inter-process transport instead of a RCCL id (stderr says so)."""
     mpirun = _mpirun()
-    nsteps = 40 if np_ == 2 else 4      # (eight processes share one GPU through the host-synchronous transport: the first 4 of the 40 steps there)
+    nsteps = 40 if np_ == 2 else 4      # (four processes share one GPU through the host-synchronous transport: the first 4 of the 40 steps there)
     toml = _stage(tmp_path, "voce_pa", nsteps=None if nsteps == 40 else nsteps)
     env = dict(os.environ, EXA_MASTER_PORT=str(29533 + np_))
     if mpirun:

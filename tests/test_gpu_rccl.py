@@ -79,15 +79,16 @@ def test_two_ranks_two_processes(oracle, tmp_path):
     assert one["newton"] == two["newton"]
 
 
-@pytest.mark.parametrize("nproc", [2, 8])
+@pytest.mark.parametrize("nproc", [2, 4])
 def test_bench_ranks_under_torchrun(tmp_path, nproc):
-    """The driver's scaling launch line, `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`, with N = 2 and N = 8 (the first
-    SCALE run of the driver is N = 8: a 2 x 2 x 2 decomposition, 7 neighbours per rank): torch's process group and the library's own communicator
+    """The driver's scaling launch line, `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`, with N = 2 and N = 4 (a 1 x 2 x 2
+    decomposition, 3 neighbours per rank; at most 4 rank processes, so that the test and its ranks keep within 6 processes with the GPU open - the
+    2 x 2 x 2 decomposition of the driver's N = 8 SCALE run is checked in one process, test_gpu_multirank.py): torch's process group and the library's own communicator
     side by side, max-over-ranks timing, one JSON line from rank 0 that names the transport, the rank count the transport itself reports
     (ncclCommCount over RCCL; the shared-device transport on a one-GPU box) and every rank's share of the partition."""
     import torch
     root = os.path.dirname(HERE)
-    ss = 3 if nproc == 2 else 2      # (eight processes on one GPU through the host-synchronous transport: one step fewer)
+    ss = 3
     env = dict(os.environ, EXA_BENCH_N="32", EXA_BENCH_SOLVE_STEPS=str(ss), EXA_BENCH_SOLVE_STEPS_TOTAL=str(ss + 1)); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # (the driver's line carries no size flags)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(29573 + nproc),
            os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1"]
@@ -100,7 +101,7 @@ def test_bench_ranks_under_torchrun(tmp_path, nproc):
     assert d["nonconverged_points"] == 0 and d["value"] > 0 and d["newton_pcg_solve"]["steps"] == ss
     pr = d["comm"]["per_rank"]
     assert [p["rank"] for p in pr] == list(range(nproc)) and sum(p["elements"] for p in pr) == 32 ** 3
-    assert all(p["neighbours"] == (1 if nproc == 2 else 7) and p["halo_bytes_per_exchange"] > 0 for p in pr)
+    assert all(p["neighbours"] == (1 if nproc == 2 else 3) and p["halo_bytes_per_exchange"] > 0 for p in pr)
     assert d["roofline"]["in_solve"]["solved_to_step"] == ss + 1 and os.path.basename(d["library"]["path"]).startswith("libexaconstit_hip")
 
 
