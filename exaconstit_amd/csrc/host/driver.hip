@@ -1,6 +1,7 @@
 // Implementation of the stand-alone host driver (see driver.hpp for the reference classes each part follows).
 #include "driver.hpp"
 #include "roctx.hpp"
+#include "vtu.hpp"
 #include <rccl/rccl.h>
 #include <atomic>
 #include <chrono>
@@ -814,15 +815,16 @@ void NonlinearMechOperator::SwapCoords() { x_beg.copy_from(x_cur, stream_); }
 // =====================================================================================================================
 // SystemDriver
 // =====================================================================================================================
-static void load_case_data(const ExaOptions& opt, const Partition& part, std::vector<double>& props, std::vector<double>& quats_local) {
+static void load_case_data(const ExaOptions& opt, const Partition& part, std::vector<double>& props, std::vector<double>& quats_local, std::vector<int32_t>& attr) {
    props = ExaOptions::load_numbers(opt.resolve(opt.props_file));
    if ((int)props.size() != opt.nprops) throw std::runtime_error("Properties file does not hold num_props values");
    std::vector<double> ori = ExaOptions::load_numbers(opt.resolve(opt.ori_file));
-   quats_local.resize((size_t)4 * part.E);
+   quats_local.resize((size_t)4 * part.E); attr.resize((size_t)part.E);
    if (part.from_file) {   // grain id = element attribute (reference src/mechanics_driver.cpp:1117-1125)
       for (int e = 0; e < part.E; e++) {
          const int grain = part.elem_attr[e] - 1;
          if (grain < 0 || 4 * (grain + 1) > (int)ori.size()) throw std::runtime_error("Element attribute outside the orientation file");
+         attr[e] = grain + 1;
          for (int q = 0; q < 4; q++) quats_local[4 * (size_t)e + q] = ori[4 * (size_t)grain + q];
       }
       return;
@@ -838,6 +840,7 @@ static void load_case_data(const ExaOptions& opt, const Partition& part, std::ve
       // uniform refinement: children inherit the parent's grain id (setElementGrainIDs, src/mechanics_driver.cpp:1257-1270)
       const int grain = (int)gmap[(i / f) + c0 * ((j / f) + c1 * (k / f))] - 1;
       if (grain < 0 || 4 * (grain + 1) > (int)ori.size()) throw std::runtime_error("Grain id outside the orientation file");
+      attr[e] = grain + 1;
       for (int q = 0; q < 4; q++) quats_local[4 * (size_t)e + q] = ori[4 * (size_t)grain + q];
    }
 }
@@ -862,7 +865,7 @@ SystemDriver::SystemDriver(const ExaOptions& opt, int rank, int nranks, const vo
    } else part.build_from_mfem_mesh(opt.resolve(opt.mesh_file), rank, nranks, opt.order);
    add_selftest_neighbour(part, comm);
    if (opt.order == 1) part.order_boundary_first();   // several ranks: elements at shared nodes first (exchange overlapped with the interior, GradMult)
-   std::vector<double> props, quats; load_case_data(opt, part, props, quats);
+   std::vector<double> props, quats; load_case_data(opt, part, props, quats, elem_attr);
    init(props, quats);
 }
 
@@ -874,6 +877,8 @@ SystemDriver::SystemDriver(const ExaOptions& opt, const std::vector<double>& pro
    if (opt.order == 1) part.order_boundary_first();
    std::vector<double> quats((size_t)4 * part.E);
    for (int e = 0; e < part.E; e++) for (int q = 0; q < 4; q++) quats[4 * (size_t)e + q] = quats_global[4 * (size_t)part.elem_gid[e] + q];
+   elem_attr.resize((size_t)part.E);   // one grain per element
+   for (int e = 0; e < part.E; e++) elem_attr[e] = (int32_t)(part.elem_gid[e] + 1);
    init(props, quats);
 }
 
@@ -1229,6 +1234,8 @@ void SystemDriver::UpdateModel() {
 bool SystemDriver::Step(int ti, bool commit) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream(); const int64_t nd = op.Height();
+   // ParaView cycle 0: the initial state at t = 0, saved before the first step (reference src/mechanics_driver.cpp:640-700), outside the timed region
+   if (opt_.paraview && write_files && commit && steps_done == 0 && !cycle0_saved_) { SaveFields(vis_dir(), 0, 0.0); cycle0_saved_ = true; }
    double dt_real;
    if (opt_.dt_cust) dt_real = opt_.cust_dt[ti - 1];
    else if (opt_.dt_auto) dt_real = std::min(dt_class, opt_.t_final - time);
@@ -1253,6 +1260,12 @@ bool SystemDriver::Step(int ti, bool commit) {
    if (!ok) return false;
    if (!commit) return true;   // the converged state stays the END-of-step state: the next constitutive pass repeats this step's last residual evaluation
    CommitStep();
+   // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
+   if (opt_.paraview && write_files) {
+      bool last = ti >= opt_.nsteps;
+      if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
+      if (last || ti % opt_.vis_steps == 0) SaveFields(vis_dir(), ti, time);
+   }
    return true;
 }
 // end-of-step update of a solved step (also called later for a step solved with commit = false, as long as only residual evaluations at the
@@ -1273,6 +1286,31 @@ int SystemDriver::RunAll() {
    }
    WriteStepTimes();
    return steps_done;
+}
+
+void SystemDriver::ElementFields(std::vector<double>& out) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   exa_ctx* ctx = op.GetModel()->ctx();
+   DevBuf<double> xe((size_t)3 * part.n * part.E), f((size_t)EXA_NFIELDS * part.E), jac;
+   abi_check(ctx, exa_restrict(ctx, op.x_cur.p, xe.p, s), "exa_restrict");
+   if (part.p != 1) {   // p = 1: det J comes from the node coordinates inside the launch
+      jac.alloc((size_t)exa_qf_size(ctx, 9));
+      abi_check(ctx, exa_jacobians(ctx, xe.p, jac.p, s), "exa_jacobians");
+   }
+   abi_check(ctx, exa_element_fields(ctx, jac.p, op.stress0.p, op.matVars0.p, xe.p, f.p, s), "exa_element_fields");
+   out = f.to_host(s);
+}
+
+void SystemDriver::SaveFields(const std::string& dir, int cycle, double t) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   std::vector<double> fields; ElementFields(fields);
+   const std::vector<double> xc = op.x_cur.to_host(s), xr = op.x_ref.to_host(s), v = v_sol.to_host(s);
+   vtu::Piece p;
+   p.E = part.E; p.NN = part.NN; p.n = part.n; p.conn = part.conn.data();
+   p.x_cur = xc.data(); p.x_ref = xr.data(); p.vel = v.data(); p.fields = fields.data(); p.attr = elem_attr.data(); p.gid = part.elem_gid.data();
+   vtu::save_cycle(dir, comm.rank, comm.nranks, cycle, t, opt_.light_up, p, pvd_cycles_[dir]);
 }
 
 // per-rank wall time of every step's solve, one value per line with 8 digits: ./time/time_solve.<rank>.txt of the reference

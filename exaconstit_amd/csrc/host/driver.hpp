@@ -9,6 +9,7 @@
 //   SystemDriver                         reference src/system_driver.cpp:221-558
 //   time-step loop                       reference src/mechanics_driver.cpp:837-907
 #pragma once
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -197,6 +198,13 @@ class SystemDriver {
    bool write_files = true; std::string out_dir = ".";
    std::vector<double> step_wall_s;            // wall time of each step (solve part), written to time/time_solve.<rank>.txt by RunAll
    void WriteStepTimes();
+   // per-element output fields (reference SystemDriver::Project*, src/system_driver.cpp:560-870) of the begin-of-step state - after a completed
+   // step the converged one - and the current coordinates: host [E][EXA_NFIELDS] in local element order
+   void ElementFields(std::vector<double>& out);
+   // ParaView save of those fields as cycle `cycle` at time t under dir (host/vtu.hpp); every rank calls it
+   void SaveFields(const std::string& dir, int cycle, double t);
+   std::string vis_dir() const { return (opt_.vis_floc.empty() || opt_.vis_floc[0] == '/') ? opt_.vis_floc : out_dir + "/" + opt_.vis_floc; }
+   std::vector<int32_t> elem_attr;             // grain id (element attribute) of every local element
    Precond precond = Precond::IDENTITY;
    int cg_check_every = 16;
    int64_t cg_graph_max_dofs = 3 * 33 * 33 * 33;   // PCG iterations replayed from a hipGraph up to this many local dofs (32^3 elements at p = 1: +9 % at 16^3, +3 % at 32^3, a loss from 48^3 on); EXA_PCG_GRAPH=0 | all
@@ -214,6 +222,8 @@ class SystemDriver {
    std::vector<uint8_t> ess_host_; std::vector<double> ess_val_host_;
    DevBuf<uint8_t> vel_mask_, vg_mask_; bool have_vel_ = false, have_vgrad_ = false; double vgrad_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
    double last_dt_ = 0.0;
+   bool cycle0_saved_ = false;
+   std::map<std::string, std::vector<std::pair<int, double>>> pvd_cycles_;   // saved cycles of each output directory (rank 0 writes the .pvd)
    void* cg_graph_ = nullptr; const double* cg_graph_x_ = nullptr; int64_t cg_graph_key_ = -1;   // captured PCG chunk (hipGraphExec_t) and what it was captured for
 };
 

@@ -4,6 +4,7 @@
 // with Caliper (ecmech_kernel, krylov_solver: src/mechanics_ecmech.cpp:237-257, src/mechanics_solver.cpp:99-103).
 #include "driver.hpp"
 #include "roctx.hpp"
+#include "vtu.hpp"
 #include "../../../include/exaconstit_driver.h"
 #include <unistd.h>
 #include <cmath>
@@ -488,6 +489,60 @@ int exa_driver_bench_adapter_route(exa_driver* d, int steps, int iters, double* 
 
 int exa_choose_newton_cap(const int* hist64, double tail_cost) { return choose_newton_cap(hist64, tail_cost); }
 int exa_choose_newton_caps(const int* hist64, double tail_cost, int* k1, int* k2) { if (!hist64 || !k1 || !k2) return -1; choose_newton_caps_resume(hist64, tail_cost, *k1, *k2); return 0; }
+
+int exa_driver_element_fields(exa_driver* d, double* out, int64_t* elem_gid, int32_t* attribute, char* err, int errlen) {
+   try {
+      SystemDriver& sd = *d->sd;
+      if (out) { std::vector<double> f; sd.ElementFields(f); std::memcpy(out, f.data(), sizeof(double) * f.size()); }
+      if (elem_gid) std::memcpy(elem_gid, sd.part.elem_gid.data(), sizeof(int64_t) * sd.part.E);
+      if (attribute) std::memcpy(attribute, sd.elem_attr.data(), sizeof(int32_t) * sd.part.E);
+      return sd.part.E;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_driver_write_fields(exa_driver* d, const char* dir, int cycle, double t, char* err, int errlen) {
+   try {
+      if (!dir || !*dir) throw std::runtime_error("exa_driver_write_fields: no directory");
+      d->sd->SaveFields(dir, cycle, t);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      if (paraview) *paraview = o.paraview ? 1 : 0;
+      if (steps) *steps = o.vis_steps;
+      if (light_up) *light_up = o.light_up ? 1 : 0;
+      if (floc && floclen > 0) { if ((int)o.vis_floc.size() >= floclen) throw std::runtime_error("Visualizations.floc longer than the buffer"); std::strcpy(floc, o.vis_floc.c_str()); }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// two unit hexahedra side by side (12 nodes byNODES, node g = i + 3 (j + 2 k) at (i, j, k)) saved as cycles 0 (t = 0) and 1 (t = 0.5) with the
+// given field rows: x_cur = x_ref + 0.01 m, velocity 0.5 m for the value index m = g + 12 c; attribute = {1, 2}, GlobalElementId = {10, 11}
+int exa_vtu_selftest(const char* dir, const double* fields, int light_up, char* err, int errlen) {
+   try {
+      const int NN = 12;
+      std::vector<double> xr(3 * NN), xc(3 * NN), v(3 * NN);
+      for (int g = 0; g < NN; g++) {
+         const double ijk[3] = { (double)(g % 3), (double)((g / 3) % 2), (double)(g / 6) };
+         for (int c = 0; c < 3; c++) { const int m = g + NN * c; xr[m] = ijk[c]; xc[m] = ijk[c] + 0.01 * m; v[m] = 0.5 * m; }
+      }
+      std::vector<int32_t> conn(16);
+      for (int e = 0; e < 2; e++) {
+         static const int V[8][3] = { { 0, 0, 0 }, { 1, 0, 0 }, { 1, 1, 0 }, { 0, 1, 0 }, { 0, 0, 1 }, { 1, 0, 1 }, { 1, 1, 1 }, { 0, 1, 1 } };
+         for (int a = 0; a < 8; a++) conn[a + 8 * e] = (e + V[a][0]) + 3 * (V[a][1] + 2 * V[a][2]);
+      }
+      const int32_t attr[2] = { 1, 2 }; const int64_t gid[2] = { 10, 11 };
+      vtu::Piece p;
+      p.E = 2; p.NN = NN; p.n = 8; p.conn = conn.data(); p.x_cur = xc.data(); p.x_ref = xr.data(); p.vel = v.data(); p.fields = fields; p.attr = attr; p.gid = gid;
+      std::vector<std::pair<int, double>> cycles;
+      vtu::save_cycle(dir, 0, 1, 0, 0.0, light_up != 0, p, cycles);
+      vtu::save_cycle(dir, 0, 1, 1, 0.5, light_up != 0, p, cycles);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
 
 int exa_options_query(const char* toml_path, double* out, char* err, int errlen) {
    try {

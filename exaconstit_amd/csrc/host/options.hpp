@@ -99,6 +99,9 @@ struct ExaOptions {
    double dt_min = 1.0, dt_scale = 0.25; int nsteps = 1; std::string auto_dt_fname = "auto_dt_out.txt";
    std::string avg_stress_fname = "avg_stress.txt", avg_def_grad_fname = "avg_def_grad.txt", avg_pl_work_fname = "avg_pl_work.txt", avg_dp_tensor_fname = "avg_dp_tensor.txt";
    bool additional_avgs = false;
+   // ParaView output of the per-element fields (reference src/option_parser.cpp:540-570): Visualizations.paraview / steps / floc / light_up.
+   // visit, conduit and adios2 are read by the reference too; nothing is written for them here.
+   bool paraview = false, light_up = false; int vis_steps = 1; std::string vis_floc = "results/exaconstit";
    Assembly assembly = Assembly::EA; NLSolver nl_solver = NLSolver::NR; std::string integ_model = "FULL";
    int newton_iter = 25; double newton_rel = 1e-5, newton_abs = 1e-10;
    int krylov_iter = 200; double krylov_rel = 1e-10, krylov_abs = 1e-30; std::string krylov_solver = "PCG";
@@ -181,6 +184,9 @@ struct ExaOptions {
       } else { dt = d.num("Time.Fixed.dt", 1.0); t_final = d.num("Time.Fixed.t_final", 1.0); nsteps = (int)std::ceil(t_final / dt - 1e-9); }
       avg_stress_fname = d.str("Visualizations.avg_stress_fname", "avg_stress.txt");
       additional_avgs = d.boolean("Visualizations.additional_avgs", false);
+      paraview = d.boolean("Visualizations.paraview", false); light_up = d.boolean("Visualizations.light_up", false);
+      vis_steps = (int)d.num("Visualizations.steps", 1); vis_floc = d.str("Visualizations.floc", "results/exaconstit");
+      if (vis_steps < 1) throw std::runtime_error("Visualizations.steps must be at least 1");
       avg_def_grad_fname = d.str("Visualizations.avg_def_grad_fname", "avg_def_grad.txt");
       avg_pl_work_fname = d.str("Visualizations.avg_pl_work_fname", "avg_pl_work.txt");
       avg_dp_tensor_fname = d.str("Visualizations.avg_dp_tensor_fname", "avg_dp_tensor.txt");

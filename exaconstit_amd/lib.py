@@ -96,6 +96,12 @@ exa_set_ea_matrix_free = _sig("exa_set_ea_matrix_free", C.c_int, C.c_void_p, C.c
 exa_grad_set_coords = _sig("exa_grad_set_coords", C.c_int, C.c_void_p, dptr)
 exa_residual_lvec = _sig("exa_residual_lvec", C.c_int, C.c_void_p, dptr, dptr, dptr, C.c_void_p)
 exa_vol_avg = _sig("exa_vol_avg", C.c_int, C.c_void_p, dptr, dptr, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p)
+exa_element_fields = _sig("exa_element_fields", C.c_int, C.c_void_p, dptr, dptr, dptr, dptr, dptr, C.c_void_p)
+# columns of the exa_element_fields rows (include/exaconstit_hip.h)
+EXA_NFIELDS = 37
+ELEMENT_FIELDS = {"ElementVolume": (0, 1), "ElemCentroid": (1, 3), "Stress": (4, 6), "VonMisesStress": (10, 1), "HydrostaticStress": (11, 1),
+                  "DpEff": (12, 1), "EffPlasticStrain": (13, 1), "Hardness": (14, 1), "ShearRate": (15, 12), "LatticeOrientation": (27, 4),
+                  "XtalElasticStrain": (31, 6)}
 
 MODEL_IDS = {("fcc", "powervoce"): EXA_FCC_VOCE, ("fcc", "powervocenl"): EXA_FCC_VOCE_NL, ("bcc", "powervoce"): EXA_BCC_VOCE,
              ("bcc", "powervocenl"): EXA_BCC_VOCE_NL, ("fcc", "mtsdd"): EXA_FCC_KMDD, ("bcc", "mtsdd"): EXA_BCC_KMDD}
@@ -193,6 +199,22 @@ exa_driver_bench_pcg = _sig("exa_driver_bench_pcg", C.c_int, C.c_void_p, C.c_int
 exa_choose_newton_cap = _sig("exa_choose_newton_cap", C.c_int, C.POINTER(C.c_int), C.c_double)
 exa_choose_newton_caps = _sig("exa_choose_newton_caps", C.c_int, C.POINTER(C.c_int), C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int))
 exa_options_query = _sig("exa_options_query", C.c_int, C.c_char_p, C.POINTER(C.c_double), C.c_char_p, C.c_int)
+exa_options_query_vis = _sig("exa_options_query_vis", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_char_p, C.c_int,
+                             C.c_char_p, C.c_int)
+exa_vtu_selftest = _sig("exa_vtu_selftest", C.c_int, C.c_char_p, C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_int)
+exa_driver_element_fields = _sig("exa_driver_element_fields", C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                 C.c_char_p, C.c_int)
+exa_driver_write_fields = _sig("exa_driver_write_fields", C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_char_p, C.c_int)
+
+
+def options_vis(path):
+    """Visualizations table of an options file: dict(paraview, steps, light_up, floc)."""
+    pv, st, lu = C.c_int(), C.c_int(), C.c_int()
+    floc = C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_query_vis(path.encode(), C.byref(pv), C.byref(st), C.byref(lu), floc, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(paraview=bool(pv.value), steps=st.value, light_up=bool(lu.value), floc=floc.value.decode())
 exa_mesh_partition_query_order = _sig("exa_mesh_partition_query_order", C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int)
 exa_mesh_partition_query = _sig("exa_mesh_partition_query", C.c_int, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int)
 exa_partition_query_boundary_first = _sig("exa_partition_query_boundary_first", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p)
@@ -312,6 +334,25 @@ class Driver:
         out = np.zeros(exa_driver_local_qpts(self.h))
         self._chk(exa_driver_get_qf_component(self.h, which, comp, out.ctypes.data_as(C.c_void_p), self._err, 512))
         return out
+
+    def element_fields(self):
+        """Per-element fields of the current begin-of-step state on this rank (after a completed step: the converged one), local element order:
+        {field name: array (E, ncomp)} for the ELEMENT_FIELDS names, plus "GlobalElementId" (int64) and "attribute" (grain id, int32)."""
+        import numpy as np
+        E = self._chk(exa_driver_element_fields(self.h, None, None, None, self._err, 512))
+        rows = np.zeros((E, EXA_NFIELDS))
+        gid = np.zeros(E, np.int64)
+        attr = np.zeros(E, np.int32)
+        self._chk(exa_driver_element_fields(self.h, rows.ctypes.data_as(C.POINTER(C.c_double)), gid.ctypes.data_as(C.POINTER(C.c_int64)),
+                                            attr.ctypes.data_as(C.POINTER(C.c_int32)), self._err, 512))
+        out = {k: rows[:, c0:c0 + n].copy() for k, (c0, n) in ELEMENT_FIELDS.items()}
+        out["GlobalElementId"] = gid
+        out["attribute"] = attr
+        return out
+
+    def write_fields(self, directory, cycle, t):
+        """ParaView save of the per-element fields as cycle `cycle` at time t under directory (every rank of a group calls it)."""
+        self._chk(exa_driver_write_fields(self.h, str(directory).encode(), cycle, t, self._err, 512))
 
     def bench_model(self, steps):
         import numpy as np

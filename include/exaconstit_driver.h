@@ -100,6 +100,13 @@ int exa_driver_nfev_hist_of(exa_driver* d, int which, int* hist64, char* err, in
 /* one component of a quadrature function of the operator, de-blocked on the host: which = 0 begin-of-step state, 1 end-of-step state (28),
  * 2 begin stress, 3 end stress (6); out receives E * Q doubles ordered [element][point] (diagnostics: nFEval maps, parity tools) */
 int exa_driver_get_qf_component(exa_driver* d, int which, int comp, double* out, char* err, int errlen);
+/* Per-element output fields of the current begin-of-step state (after a completed step: the converged one) on this rank, without any file:
+ * out [E][EXA_NFIELDS] (column table at exa_element_fields, include/exaconstit_hip.h), elem_gid [E] global element index, attribute [E] grain id;
+ * every pointer may be NULL.  Local element order of the driver.  Returns E (>= 0) or -1 (err). */
+int exa_driver_element_fields(exa_driver* d, double* out, int64_t* elem_gid, int32_t* attribute, char* err, int errlen);
+/* ParaView save of those fields on demand: <dir>/Cycle%06d/proc%06d.vtu (every rank), data.pvtu and <dir>/<basename(dir)>.pvd (rank 0; the
+ * collection lists the cycles saved to dir through this driver).  Every rank of the group calls it.  Returns 0 or -1 (err). */
+int exa_driver_write_fields(exa_driver* d, const char* dir, int cycle, double t, char* err, int errlen);
 int exa_driver_bench_prepare(exa_driver* d, int nsteps, const double* dts, double perturb, char* err, int errlen);
 int exa_driver_bench_model(exa_driver* d, int steps, double* out3, char* err, int errlen);
 int exa_driver_bench_pcg(exa_driver* d, int iters, double* out3, char* err, int errlen);
@@ -113,6 +120,12 @@ int exa_driver_bench_adapter_route(exa_driver* d, int steps, int iters, double* 
  * {temp_k, nprops, num_grains, xtal, slip, dt_cust, dt_auto, nsteps, assembly(0 PA,1 EA), nl_solver(0 NR,1 NRLS), newton_iter, newton_rel,
  *  newton_abs, krylov_iter, krylov_rel, krylov_abs, ref_ser, ncuts0, additional_avgs, number of BC change steps}; returns 0 or -1 (err) */
 int exa_options_query(const char* toml_path, double* out20, char* err, int errlen);
+/* Visualizations table (reference src/option_parser.cpp:540-570): paraview (default 0), steps (1), light_up (0), floc ("results/exaconstit",
+ * relative to the driver's output directory); returns 0 or -1 (err) */
+int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen);
+/* the ParaView writer on a fixed two-hexahedron piece (host only): fields = 2 rows of EXA_NFIELDS doubles, saved under dir as cycles 0 (t = 0)
+ * and 1 (t = 0.5); mesh and point data documented at the definition (host/driver_capi.hip) */
+int exa_vtu_selftest(const char* dir, const double* fields, int light_up, char* err, int errlen);
 /* the driver's tail-split controller as a pure function (host logic; tests): cap on local-solver evaluations chosen from a 64-bin
  * histogram of evaluation counts, 0 = leave the launch uncapped.  tail_cost = relative cost of a point in the second launch. */
 int exa_choose_newton_cap(const int* hist64, double tail_cost);

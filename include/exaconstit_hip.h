@@ -278,6 +278,28 @@ int exa_set_deterministic(exa_ctx* ctx, int on);
  * p = 1 full integration: jacobian_dev may be NULL when exa_grad_set_coords has named the nodal coordinates of the configuration -
  * adj(J) is then recomputed from them (the scatter gathers the connectivity anyway) instead of read from a Jacobian field. */
 int exa_residual_lvec(exa_ctx* ctx, const double* jacobian_dev, const double* stress1_dev, double* y_lvec_dev, exa_stream s);
+/* Per-element output fields: the element averages behind the reference's SystemDriver::Project* calls (src/system_driver.cpp:560-870), one row
+ * of EXA_NFIELDS doubles per element, out_dev [E][EXA_NFIELDS] row-major.  With w_q = W_q det J_q of the configuration the Jacobians / coordinates
+ * describe (the stand-alone driver passes the converged one, like its volume averages):
+ *   EXA_F_VOLUME               1   ElementVolume       sum_q w_q
+ *   EXA_F_CENTROID             3   ElemCentroid        sum_q w_q x(xi_q) / vol, x interpolated from xe_dev (ProjectCentroid)
+ *   EXA_F_STRESS               6   Stress              sum_q w_q sigma_q / vol, Voigt (11,22,33,23,13,12) (ProjectModelStress = CalcElementAvg)
+ *   EXA_F_VONMISES             1   VonMisesStress      of the averaged stress, sqrt(((s0-s1)^2 + (s1-s2)^2 + (s2-s0)^2 + 6 (s3^2 + s4^2 + s5^2)) / 2)
+ *   EXA_F_HYDROSTATIC          1   HydrostaticStress   (s0 + s1 + s2) / 3 of the averaged stress
+ *   EXA_F_DPEFF                1   DpEff               average of state slot 0 (shrateEff)
+ *   EXA_F_EFFPLASTICSTRAIN     1   EffPlasticStrain    average of state slot 1 (shrEff)
+ *   EXA_F_HARDNESS             1   Hardness            average of state slot 13
+ *   EXA_F_SHEARRATE           12   ShearRate           averages of state slots 14..25
+ *   EXA_F_ORIENTATION          4   LatticeOrientation  averages of state slots 9..12 normalised to unit length (ProjectOrientation)
+ *   EXA_F_XTALELASTICSTRAIN    6   XtalElasticStrain   ProjectElasticStrains from the averaged slots 4..8 (e) and 26 (rel_vol): t1 = e0/sqrt 2,
+ *                                                      t2 = e1/sqrt 6, v = ln rel_vol -> (t1-t2+v, -t1-t2+v, sqrt(2/3) e1+v, e4/sqrt 2, e3/sqrt 2, e2/sqrt 2)
+ * Both quadrature layouts, p = 1..6.  jacobian_dev may be NULL at p = 1: det J is then recomputed from the 24 node coordinates of xe_dev
+ * (the current nodal coordinates as an E-vector (n,3,E), needed for the centroid in any case).  One launch, no atomics, fixed summation order:
+ * every call on the same data gives the same bits. */
+enum { EXA_NFIELDS = 37, EXA_F_VOLUME = 0, EXA_F_CENTROID = 1, EXA_F_STRESS = 4, EXA_F_VONMISES = 10, EXA_F_HYDROSTATIC = 11, EXA_F_DPEFF = 12,
+       EXA_F_EFFPLASTICSTRAIN = 13, EXA_F_HARDNESS = 14, EXA_F_SHEARRATE = 15, EXA_F_ORIENTATION = 27, EXA_F_XTALELASTICSTRAIN = 31 };
+int exa_element_fields(exa_ctx* ctx, const double* jacobian_dev, const double* stress_dev, const double* state_dev, const double* xe_dev,
+                       double* out_dev, exa_stream s);
 /* volume average  sum_q W detJ val / sum_q W detJ  (src/mechanics_kernels.hpp:19-134); out_host[vdim] (+ volume in out_host[vdim]).
  * Synchronises the stream. */
 int exa_vol_avg(exa_ctx* ctx, const double* jacobian_dev, const double* qf_dev, int vdim, int normalise, double* out_host, exa_stream s);
