@@ -1261,10 +1261,21 @@ bool SystemDriver::Step(int ti, bool commit) {
    if (!commit) return true;   // the converged state stays the END-of-step state: the next constitutive pass repeats this step's last residual evaluation
    CommitStep();
    // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
+   bool save = false;
    if (opt_.paraview && write_files) {
       bool last = ti >= opt_.nsteps;
       if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
-      if (last || ti % opt_.vis_steps == 0) SaveFields(vis_dir(), ti, time);
+      save = last || ti % opt_.vis_steps == 0;
+   }
+   // light-up analysis: one row of lattice strains and one of fibre volume fractions per converged step, from the same element rows
+   const bool lattice = opt_.lightup() && write_files;
+   if (save || lattice) ComputeElementFields();
+   if (save) SaveFields(vis_dir(), ti, time, true);
+   if (lattice) {
+      const int H = (int)opt_.lightup_hkl.size() / 3;
+      std::vector<double> strain(H), vf(H);
+      LatticeStrains(opt_.lightup_hkl, opt_.lightup_s_dir, opt_.lightup_tol_deg, strain.data(), vf.data(), true);
+      if (comm.rank == 0) { append_row(out_dir + "/" + opt_.lightup_strain_fname, strain.data(), H); append_row(out_dir + "/" + opt_.lightup_volume_fname, vf.data(), H); }
    }
    return true;
 }
@@ -1288,24 +1299,59 @@ int SystemDriver::RunAll() {
    return steps_done;
 }
 
-void SystemDriver::ElementFields(std::vector<double>& out) {
+void SystemDriver::ComputeElementFields() {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
    exa_ctx* ctx = op.GetModel()->ctx();
-   DevBuf<double> xe((size_t)3 * part.n * part.E), f((size_t)EXA_NFIELDS * part.E), jac;
+   DevBuf<double> xe((size_t)3 * part.n * part.E), jac;
+   if (fields_dev_.n != (size_t)EXA_NFIELDS * part.E) fields_dev_.alloc((size_t)EXA_NFIELDS * part.E);
    abi_check(ctx, exa_restrict(ctx, op.x_cur.p, xe.p, s), "exa_restrict");
    if (part.p != 1) {   // p = 1: det J comes from the node coordinates inside the launch
       jac.alloc((size_t)exa_qf_size(ctx, 9));
       abi_check(ctx, exa_jacobians(ctx, xe.p, jac.p, s), "exa_jacobians");
    }
-   abi_check(ctx, exa_element_fields(ctx, jac.p, op.stress0.p, op.matVars0.p, xe.p, f.p, s), "exa_element_fields");
-   out = f.to_host(s);
+   abi_check(ctx, exa_element_fields(ctx, jac.p, op.stress0.p, op.matVars0.p, xe.p, fields_dev_.p, s), "exa_element_fields");
+   EXA_HC(hipStreamSynchronize(s));   // xe and jac leave scope
 }
 
-void SystemDriver::SaveFields(const std::string& dir, int cycle, double t) {
+void SystemDriver::ElementFields(std::vector<double>& out) {
+   ComputeElementFields();
+   out = fields_dev_.to_host(oper_->stream());
+}
+
+void SystemDriver::LatticeStrains(const std::vector<int>& hkl, const double s_dir[3], double tol_deg, double* strain, double* volfrac, bool fields_current) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
-   std::vector<double> fields; ElementFields(fields);
+   exa_ctx* ctx = op.GetModel()->ctx();
+   double sd[3] = { s_dir[0], s_dir[1], s_dir[2] };
+   ExaOptions::check_lightup(hkl, sd, tol_deg);
+   const int H = (int)hkl.size() / 3;
+   if (H < 1) throw std::runtime_error("lattice strains: no {hkl} family given");
+   std::vector<double> axes; std::vector<int> off(1, 0);
+   for (int j = 0; j < H; j++) {
+      double a[3 * 24];
+      const int na = exa_cubic_fiber_axes(hkl[3 * j], hkl[3 * j + 1], hkl[3 * j + 2], a, 24);
+      if (na < 1 || na > 24) throw std::runtime_error("lattice strains: no fibre axes for a family");
+      axes.insert(axes.end(), a, a + 3 * na); off.push_back(off.back() + na);
+   }
+   if (!fields_current) ComputeElementFields();
+   if (lattice_sums_.n < (size_t)(2 * H + 1)) lattice_sums_.alloc(2 * EXA_LATTICE_MAX_HKL + 1);
+   const double cos_tol = std::cos(tol_deg * (M_PI / 180.0));
+   abi_check(ctx, exa_lattice_strains(ctx, fields_dev_.p, H, axes.data(), off.data(), sd, cos_tol, lattice_sums_.p, s), "exa_lattice_strains");
+   comm.allreduce_sum(lattice_sums_.p, 2 * H + 1, s);   // elements are not shared across ranks
+   std::vector<double> h(2 * H + 1); lattice_sums_.download(h.data(), 2 * H + 1, s);
+   for (int j = 0; j < H; j++) {
+      const double v = h[2 * j + 1];
+      strain[j] = v > 0.0 ? h[2 * j] / v : std::numeric_limits<double>::quiet_NaN();   // empty fibre: no lattice strain (written as nan)
+      volfrac[j] = v / h[2 * H];
+   }
+}
+
+void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool fields_current) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   if (!fields_current) ComputeElementFields();
+   const std::vector<double> fields = fields_dev_.to_host(s);
    const std::vector<double> xc = op.x_cur.to_host(s), xr = op.x_ref.to_host(s), v = v_sol.to_host(s);
    vtu::Piece p;
    p.E = part.E; p.NN = part.NN; p.n = part.n; p.conn = part.conn.data();

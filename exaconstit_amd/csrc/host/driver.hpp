@@ -201,8 +201,14 @@ class SystemDriver {
    // per-element output fields (reference SystemDriver::Project*, src/system_driver.cpp:560-870) of the begin-of-step state - after a completed
    // step the converged one - and the current coordinates: host [E][EXA_NFIELDS] in local element order
    void ElementFields(std::vector<double>& out);
-   // ParaView save of those fields as cycle `cycle` at time t under dir (host/vtu.hpp); every rank calls it
-   void SaveFields(const std::string& dir, int cycle, double t);
+   // the same rows into the device buffer fields_dev_, kept across steps (allocated on first use)
+   void ComputeElementFields();
+   // ParaView save of those fields as cycle `cycle` at time t under dir (host/vtu.hpp); every rank calls it.  fields_current: fields_dev_
+   // already holds the rows of this state (computed once for both the save and the lattice strains of a step)
+   void SaveFields(const std::string& dir, int cycle, double t, bool fields_current = false);
+   // lattice strains of the {hkl} families (3 integers each; options.hpp check_lightup) of the same state, summed over all ranks (every rank calls
+   // it): strain[j] = volume-weighted mean of s^T eps s over the elements of fibre j (NaN when the fibre is empty), volfrac[j] = its volume fraction
+   void LatticeStrains(const std::vector<int>& hkl, const double s_dir[3], double tol_deg, double* strain, double* volfrac, bool fields_current = false);
    std::string vis_dir() const { return (opt_.vis_floc.empty() || opt_.vis_floc[0] == '/') ? opt_.vis_floc : out_dir + "/" + opt_.vis_floc; }
    std::vector<int32_t> elem_attr;             // grain id (element attribute) of every local element
    Precond precond = Precond::IDENTITY;
@@ -223,6 +229,7 @@ class SystemDriver {
    DevBuf<uint8_t> vel_mask_, vg_mask_; bool have_vel_ = false, have_vgrad_ = false; double vgrad_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
    double last_dt_ = 0.0;
    bool cycle0_saved_ = false;
+   DevBuf<double> fields_dev_, lattice_sums_;   // [E][EXA_NFIELDS] element rows; 2 H + 1 lattice-strain sums
    std::map<std::string, std::vector<std::pair<int, double>>> pvd_cycles_;   // saved cycles of each output directory (rank 0 writes the .pvd)
    void* cg_graph_ = nullptr; const double* cg_graph_x_ = nullptr; int64_t cg_graph_key_ = -1;   // captured PCG chunk (hipGraphExec_t) and what it was captured for
 };

@@ -519,6 +519,36 @@ int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int*
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+int exa_driver_lattice_strains(exa_driver* d, int nhkl, const int* hkl3, const double* s_dir3, double tol_deg, double* strain_out, double* volfrac_out,
+                               char* err, int errlen) {
+   try {
+      if (nhkl < 1 || nhkl > EXA_LATTICE_MAX_HKL || !hkl3 || !s_dir3 || !strain_out || !volfrac_out) throw std::runtime_error("exa_driver_lattice_strains: 1 to 16 families, a direction and two outputs are required");
+      const std::vector<int> hkl(hkl3, hkl3 + 3 * nhkl);
+      d->sd->LatticeStrains(hkl, s_dir3, tol_deg, strain_out, volfrac_out);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_options_query_lightup(const char* toml_path, int* enabled, int* nhkl, int* hkl48, double* s_dir3, double* tol_deg, char* strain_fname,
+                              char* volume_fname, int fnamelen, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      if (enabled) *enabled = o.lightup() ? 1 : 0;
+      if (nhkl) *nhkl = (int)o.lightup_hkl.size() / 3;
+      if (hkl48) for (size_t i = 0; i < o.lightup_hkl.size(); i++) hkl48[i] = o.lightup_hkl[i];
+      if (s_dir3) for (int i = 0; i < 3; i++) s_dir3[i] = o.lightup_s_dir[i];
+      if (tol_deg) *tol_deg = o.lightup_tol_deg;
+      auto put = [&](char* dst, const std::string& v, const char* what) {
+         if (!dst || fnamelen <= 0) return;
+         if ((int)v.size() >= fnamelen) throw std::runtime_error(std::string(what) + " longer than the buffer");
+         std::strcpy(dst, v.c_str());
+      };
+      put(strain_fname, o.lightup_strain_fname, "Visualizations.light_up_strain_fname");
+      put(volume_fname, o.lightup_volume_fname, "Visualizations.light_up_volume_fname");
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
 // two unit hexahedra side by side (12 nodes byNODES, node g = i + 3 (j + 2 k) at (i, j, k)) saved as cycles 0 (t = 0) and 1 (t = 0.5) with the
 // given field rows: x_cur = x_ref + 0.01 m, velocity 0.5 m for the value index m = g + 12 c; attribute = {1, 2}, GlobalElementId = {10, 11}
 int exa_vtu_selftest(const char* dir, const double* fields, int light_up, char* err, int errlen) {

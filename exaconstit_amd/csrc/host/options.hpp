@@ -102,6 +102,22 @@ struct ExaOptions {
    // ParaView output of the per-element fields (reference src/option_parser.cpp:540-570): Visualizations.paraview / steps / floc / light_up.
    // visit, conduit and adios2 are read by the reference too; nothing is written for them here.
    bool paraview = false, light_up = false; int vis_steps = 1; std::string vis_floc = "results/exaconstit";
+   // in-situ lattice strains of {hkl} fibres (the reference's light-up post-processing, scripts/postprocessing/calc_lattice_strain.py):
+   // on when light_up = true and Visualizations.light_up_hkl is given.  lightup_hkl holds 3 integers per family; lightup_s_dir is unit.
+   std::vector<int> lightup_hkl; double lightup_s_dir[3] = { 0, 0, 1 }; double lightup_tol_deg = 5.0;
+   std::string lightup_strain_fname = "lattice_strains.txt", lightup_volume_fname = "lattice_volumes.txt";
+   bool lightup() const { return light_up && !lightup_hkl.empty(); }
+   // the checks of the light-up keys, shared with exa_driver_lattice_strains (hkl may be empty here); normalises s in place
+   static void check_lightup(const std::vector<int>& hkl, double s[3], double tol_deg) {
+      if (hkl.size() % 3 != 0) throw std::runtime_error("Visualizations.light_up_hkl must hold [h, k, l] triples");
+      if (hkl.size() > 3 * 16) throw std::runtime_error("Visualizations.light_up_hkl holds at most 16 triples");
+      for (size_t j = 0; j < hkl.size(); j += 3)
+         if (hkl[j] == 0 && hkl[j + 1] == 0 && hkl[j + 2] == 0) throw std::runtime_error("Visualizations.light_up_hkl: [0, 0, 0] is not a plane family");
+      const double n = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+      if (!(n > 0.0) || !std::isfinite(n)) throw std::runtime_error("Visualizations.light_up_s_dir must be a non-zero vector");
+      for (int i = 0; i < 3; i++) s[i] /= n;
+      if (!(tol_deg > 0.0 && tol_deg <= 90.0)) throw std::runtime_error("Visualizations.light_up_dist_tol_deg must lie in (0, 90]");
+   }
    Assembly assembly = Assembly::EA; NLSolver nl_solver = NLSolver::NR; std::string integ_model = "FULL";
    int newton_iter = 25; double newton_rel = 1e-5, newton_abs = 1e-10;
    int krylov_iter = 200; double krylov_rel = 1e-10, krylov_abs = 1e-30; std::string krylov_solver = "PCG";
@@ -187,6 +203,25 @@ struct ExaOptions {
       paraview = d.boolean("Visualizations.paraview", false); light_up = d.boolean("Visualizations.light_up", false);
       vis_steps = (int)d.num("Visualizations.steps", 1); vis_floc = d.str("Visualizations.floc", "results/exaconstit");
       if (vis_steps < 1) throw std::runtime_error("Visualizations.steps must be at least 1");
+      if (const TomlValue* h = d.get("Visualizations.light_up_hkl")) {
+         if (h->kind != TomlValue::ARR || h->arr.empty()) throw std::runtime_error("Visualizations.light_up_hkl must be an array of [h, k, l] triples");
+         if (h->arr.size() > 16) throw std::runtime_error("Visualizations.light_up_hkl holds at most 16 triples");
+         for (auto& t : h->arr) {
+            if (t.kind != TomlValue::ARR || t.arr.size() != 3) throw std::runtime_error("Visualizations.light_up_hkl: every entry must be an [h, k, l] triple of 3 integers");
+            for (auto& x : t.arr) {
+               if (x.kind != TomlValue::NUM || x.num != std::floor(x.num) || std::fabs(x.num) > 1000.0) throw std::runtime_error("Visualizations.light_up_hkl: Miller indices must be integers");
+               lightup_hkl.push_back((int)x.num);
+            }
+         }
+      }
+      if (const TomlValue* sd = d.get("Visualizations.light_up_s_dir")) {
+         if (sd->kind != TomlValue::ARR || sd->arr.size() != 3) throw std::runtime_error("Visualizations.light_up_s_dir must contain 3 components");
+         for (int i = 0; i < 3; i++) lightup_s_dir[i] = sd->arr[i].num;
+      }
+      lightup_tol_deg = d.num("Visualizations.light_up_dist_tol_deg", 5.0);
+      lightup_strain_fname = d.str("Visualizations.light_up_strain_fname", "lattice_strains.txt");
+      lightup_volume_fname = d.str("Visualizations.light_up_volume_fname", "lattice_volumes.txt");
+      check_lightup(lightup_hkl, lightup_s_dir, lightup_tol_deg);
       avg_def_grad_fname = d.str("Visualizations.avg_def_grad_fname", "avg_def_grad.txt");
       avg_pl_work_fname = d.str("Visualizations.avg_pl_work_fname", "avg_pl_work.txt");
       avg_dp_tensor_fname = d.str("Visualizations.avg_dp_tensor_fname", "avg_dp_tensor.txt");

@@ -97,6 +97,10 @@ exa_grad_set_coords = _sig("exa_grad_set_coords", C.c_int, C.c_void_p, dptr)
 exa_residual_lvec = _sig("exa_residual_lvec", C.c_int, C.c_void_p, dptr, dptr, dptr, C.c_void_p)
 exa_vol_avg = _sig("exa_vol_avg", C.c_int, C.c_void_p, dptr, dptr, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p)
 exa_element_fields = _sig("exa_element_fields", C.c_int, C.c_void_p, dptr, dptr, dptr, dptr, dptr, C.c_void_p)
+exa_lattice_strains = _sig("exa_lattice_strains", C.c_int, C.c_void_p, dptr, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double),
+                           C.c_double, dptr, C.c_void_p)
+exa_cubic_fiber_axes = _sig("exa_cubic_fiber_axes", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int)
+EXA_LATTICE_MAX_HKL = 16
 # columns of the exa_element_fields rows (include/exaconstit_hip.h)
 EXA_NFIELDS = 37
 ELEMENT_FIELDS = {"ElementVolume": (0, 1), "ElemCentroid": (1, 3), "Stress": (4, 6), "VonMisesStress": (10, 1), "HydrostaticStress": (11, 1),
@@ -204,6 +208,10 @@ exa_options_query_vis = _sig("exa_options_query_vis", C.c_int, C.c_char_p, C.POI
 exa_vtu_selftest = _sig("exa_vtu_selftest", C.c_int, C.c_char_p, C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_int)
 exa_driver_element_fields = _sig("exa_driver_element_fields", C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                  C.c_char_p, C.c_int)
+exa_driver_lattice_strains = _sig("exa_driver_lattice_strains", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_double,
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_int)
+exa_options_query_lightup = _sig("exa_options_query_lightup", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
 exa_driver_write_fields = _sig("exa_driver_write_fields", C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_char_p, C.c_int)
 
 
@@ -215,6 +223,30 @@ def options_vis(path):
     if exa_options_query_vis(path.encode(), C.byref(pv), C.byref(st), C.byref(lu), floc, 4096, err, 512) != 0:
         raise RuntimeError(err.value.decode())
     return dict(paraview=bool(pv.value), steps=st.value, light_up=bool(lu.value), floc=floc.value.decode())
+
+
+def cubic_fiber_axes(h, k, l):
+    """distinct unit axes (n, 3) of the cubic plane family {hkl}, a direction and its negative counted once (exa_cubic_fiber_axes)"""
+    import numpy as np
+    out = np.zeros((24, 3))
+    n = exa_cubic_fiber_axes(int(h), int(k), int(l), out.ctypes.data_as(C.POINTER(C.c_double)), 24)
+    if n < 0:
+        raise ValueError("(0, 0, 0) is not a plane family")
+    return out[:n].copy()
+
+
+def options_lightup(path):
+    """light-up analysis keys of the Visualizations table: dict(enabled, hkl (list of triples), s_dir, tol_deg, strain_fname, volume_fname)"""
+    en, nh = C.c_int(), C.c_int()
+    hkl = (C.c_int * 48)()
+    sd = (C.c_double * 3)()
+    tol = C.c_double()
+    f1, f2 = C.create_string_buffer(4096), C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_query_lightup(path.encode(), C.byref(en), C.byref(nh), hkl, sd, C.byref(tol), f1, f2, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(enabled=bool(en.value), hkl=[tuple(hkl[3 * j:3 * j + 3]) for j in range(nh.value)], s_dir=tuple(sd), tol_deg=tol.value,
+                strain_fname=f1.value.decode(), volume_fname=f2.value.decode())
 exa_mesh_partition_query_order = _sig("exa_mesh_partition_query_order", C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int)
 exa_mesh_partition_query = _sig("exa_mesh_partition_query", C.c_int, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int)
 exa_partition_query_boundary_first = _sig("exa_partition_query_boundary_first", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p)
@@ -349,6 +381,19 @@ class Driver:
         out["GlobalElementId"] = gid
         out["attribute"] = attr
         return out
+
+    def lattice_strains(self, hkl, s_dir=(0, 0, 1), tol_deg=5.0):
+        """Lattice strains of the plane families hkl (list of [h, k, l]) along the sample direction s_dir on the current begin-of-step state
+        (after a completed step: the converged one), over all ranks of the group (every rank calls it): {"strain": (H,), "volume_fraction": (H,)};
+        strain is NaN for a fibre without elements within tol_deg degrees."""
+        import numpy as np
+        h = np.ascontiguousarray(np.asarray(hkl, dtype=np.int32).reshape(-1, 3))
+        sd = np.ascontiguousarray(np.asarray(s_dir, dtype=np.float64).reshape(3))
+        H = h.shape[0]
+        strain, vf = np.zeros(H), np.zeros(H)
+        self._chk(exa_driver_lattice_strains(self.h, H, h.ctypes.data_as(C.POINTER(C.c_int)), sd.ctypes.data_as(C.POINTER(C.c_double)), float(tol_deg),
+                                             strain.ctypes.data_as(C.POINTER(C.c_double)), vf.ctypes.data_as(C.POINTER(C.c_double)), self._err, 512))
+        return {"strain": strain, "volume_fraction": vf}
 
     def write_fields(self, directory, cycle, t):
         """ParaView save of the per-element fields as cycle `cycle` at time t under directory (every rank of a group calls it)."""

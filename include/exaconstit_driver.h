@@ -107,6 +107,12 @@ int exa_driver_element_fields(exa_driver* d, double* out, int64_t* elem_gid, int
 /* ParaView save of those fields on demand: <dir>/Cycle%06d/proc%06d.vtu (every rank), data.pvtu and <dir>/<basename(dir)>.pvd (rank 0; the
  * collection lists the cycles saved to dir through this driver).  Every rank of the group calls it.  Returns 0 or -1 (err). */
 int exa_driver_write_fields(exa_driver* d, const char* dir, int cycle, double t, char* err, int errlen);
+/* Lattice strains of nhkl (1..16) plane families {hkl} (hkl3: 3 integers each) along the sample direction s_dir3 (normalised here) with fibre
+ * tolerance tol_deg in (0, 90], on the current begin-of-step state (after a completed step: the converged one), summed over all ranks (every rank
+ * of the group calls it): strain_out[j] = volume-weighted mean of s^T eps s over the elements whose <hkl> lies within tol_deg of s (NaN for an
+ * empty fibre), volfrac_out[j] = their volume fraction (exa_lattice_strains, include/exaconstit_hip.h).  Returns 0 or -1 (err). */
+int exa_driver_lattice_strains(exa_driver* d, int nhkl, const int* hkl3, const double* s_dir3, double tol_deg, double* strain_out, double* volfrac_out,
+                               char* err, int errlen);
 int exa_driver_bench_prepare(exa_driver* d, int nsteps, const double* dts, double perturb, char* err, int errlen);
 int exa_driver_bench_model(exa_driver* d, int steps, double* out3, char* err, int errlen);
 int exa_driver_bench_pcg(exa_driver* d, int iters, double* out3, char* err, int errlen);
@@ -123,6 +129,11 @@ int exa_options_query(const char* toml_path, double* out20, char* err, int errle
 /* Visualizations table (reference src/option_parser.cpp:540-570): paraview (default 0), steps (1), light_up (0), floc ("results/exaconstit",
  * relative to the driver's output directory); returns 0 or -1 (err) */
 int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen);
+/* light-up analysis keys of the Visualizations table: enabled = light_up and light_up_hkl given; nhkl families in hkl48 (3 integers each, room for
+ * 48); s_dir3 the normalised light_up_s_dir (default 0 0 1); tol_deg light_up_dist_tol_deg (5); light_up_strain_fname ("lattice_strains.txt") and
+ * light_up_volume_fname ("lattice_volumes.txt") into buffers of fnamelen bytes.  Every pointer may be NULL.  Returns 0 or -1 (err). */
+int exa_options_query_lightup(const char* toml_path, int* enabled, int* nhkl, int* hkl48, double* s_dir3, double* tol_deg, char* strain_fname,
+                              char* volume_fname, int fnamelen, char* err, int errlen);
 /* the ParaView writer on a fixed two-hexahedron piece (host only): fields = 2 rows of EXA_NFIELDS doubles, saved under dir as cycles 0 (t = 0)
  * and 1 (t = 0.5); mesh and point data documented at the definition (host/driver_capi.hip) */
 int exa_vtu_selftest(const char* dir, const double* fields, int light_up, char* err, int errlen);

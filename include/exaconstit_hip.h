@@ -300,6 +300,21 @@ enum { EXA_NFIELDS = 37, EXA_F_VOLUME = 0, EXA_F_CENTROID = 1, EXA_F_STRESS = 4,
        EXA_F_EFFPLASTICSTRAIN = 13, EXA_F_HARDNESS = 14, EXA_F_SHEARRATE = 15, EXA_F_ORIENTATION = 27, EXA_F_XTALELASTICSTRAIN = 31 };
 int exa_element_fields(exa_ctx* ctx, const double* jacobian_dev, const double* stress_dev, const double* state_dev, const double* xe_dev,
                        double* out_dev, exa_stream s);
+/* Lattice strains of {hkl} fibres (the light-up analysis; reference scripts/postprocessing/calc_lattice_strain.py) on the rows of
+ * exa_element_fields: fields_dev [E][EXA_NFIELDS] (device).  axes [naxes][3] (host) are unit axes grouped by family: family j owns
+ * axes[axis_offsets[j] .. axis_offsets[j + 1]) (host offsets, axis_offsets[0] = 0), 1 to 24 axes that are signed permutations of the family's
+ * first axis - the cubic orbit of exa_cubic_fiber_axes.  s_dir (host) is the unit sample direction.  Per element, with u = R(q)^T s
+ * (R = quat_to_mat of EXA_F_ORIENTATION, crystal -> sample) and eps the EXA_F_XTALELASTICSTRAIN tensor: the element is in fibre j iff
+ * max_c |u . c| > cos_tol, and eps_s = u^T eps u.  out_dev (device) receives 2 nhkl + 1 local sums: out[2j] = sum_{e in j} V_e eps_s,
+ * out[2j + 1] = sum_{e in j} V_e, out[2 nhkl] = sum_e V_e (V = EXA_F_VOLUME).  1 <= nhkl <= EXA_LATTICE_MAX_HKL.  Two launches (partial sums
+ * per block in the context's scratch, then one block), no atomics: every call on the same data gives the same bits.  Does not synchronise. */
+enum { EXA_LATTICE_MAX_HKL = 16 };
+int exa_lattice_strains(exa_ctx* ctx, const double* fields_dev, int nhkl, const double* axes, const int* axis_offsets, const double* s_dir,
+                        double cos_tol, double* out_dev, exa_stream s);
+/* host only: the distinct fibre axes of the plane family {hkl} of a cubic crystal - the orbit of (h, k, l) / |(h, k, l)| under the 24 proper
+ * rotations, a direction and its negative counted once (first non-zero component positive).  Writes min(count, max) axes to out [.][3]
+ * (out may be NULL) and returns the count (4 for 111, 3 for 200, 6 for 220, 12 for 311, 24 for 123), or -1 for (0, 0, 0). */
+int exa_cubic_fiber_axes(int h, int k, int l, double* out, int max);
 /* volume average  sum_q W detJ val / sum_q W detJ  (src/mechanics_kernels.hpp:19-134); out_host[vdim] (+ volume in out_host[vdim]).
  * Synchronises the stream. */
 int exa_vol_avg(exa_ctx* ctx, const double* jacobian_dev, const double* qf_dev, int vdim, int normalise, double* out_host, exa_stream s);
