@@ -1,5 +1,6 @@
 // Implementation of the stand-alone host driver (see driver.hpp for the reference classes each part follows).
 #include "driver.hpp"
+#include "multigrid.hpp"
 #include "roctx.hpp"
 #include "vtu.hpp"
 #include <rccl/rccl.h>
@@ -718,6 +719,7 @@ void NonlinearMechOperator::GetGradient() {
       // (B-bar, p = 2: the element-average gradients the action reads; the residual refreshes them as well, but GetUpdateBCsAction applies the gradient first)
       if (!fast_p1_) abi_check(ctx_, exa_grad_refresh_bbar(ctx_, el_jac.p, stream_), "exa_grad_refresh_bbar");
       vk_jacobi_setup(nd_, ess_mask.p, diag.p, 1, dinv.p, stream_);
+      if (precond == Precond::MULTIGRID) mg->Build();
       return;
    }
    // compact tangent form of the p = 1 PA action (include/exaconstit_hip.h): valid for ExaCMech tangents; verified on the data of
@@ -738,7 +740,7 @@ void NonlinearMechOperator::GetGradient() {
    // The reference assembles the operator diagonal here on every call, but its Jacobi smoother never reads it (dinv is built once
    // from diag = 1).  With that default the assembly is skipped: no result depends on it, and for p = 2 element
    // assembly it would be the only consumer of the 81 x 81 matrices.
-   if (precond != Precond::IDENTITY) {
+   if (precond == Precond::JACOBI) {
       el_y_.zero(stream_);
       abi_check(ctx_, exa_grad_diagonal(ctx_, el_y_.p, stream_), "exa_grad_diagonal");
       diag.zero(stream_);
@@ -746,7 +748,22 @@ void NonlinearMechOperator::GetGradient() {
       comm_.halo_sum(part_, diag.p, stream_);
       vk_mask_one(nd_, ess_mask.p, diag.p, stream_);
    }
-   vk_jacobi_setup(nd_, ess_mask.p, diag.p, precond == Precond::IDENTITY ? 1 : 0, dinv.p, stream_);
+   vk_jacobi_setup(nd_, ess_mask.p, diag.p, precond == Precond::JACOBI ? 0 : 1, dinv.p, stream_);
+   if (precond == Precond::MULTIGRID) mg->Build();
+}
+
+void NonlinearMechOperator::GradMultLocal(const double* x, double* y) {
+   EXA_HC(hipMemsetAsync(y, 0, sizeof(double) * nd_, stream_));
+   if (lvec_grad_) abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, ess_mask.p, nullptr, stream_), "exa_grad_apply_lvec");
+   else {
+      EXA_HC(hipMemcpyAsync(tmp_l_.p, x, sizeof(double) * nd_, hipMemcpyDeviceToDevice, stream_));
+      vk_mask_zero(nd_, ess_mask.p, tmp_l_.p, stream_);
+      abi_check(ctx_, exa_restrict(ctx_, tmp_l_.p, el_x2_.p, stream_), "exa_restrict");
+      el_y_.zero(stream_);
+      abi_check(ctx_, exa_grad_apply(ctx_, el_x2_.p, el_y_.p, stream_), "exa_grad_apply");
+      abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
+   }
+   vk_mask_zero(nd_, ess_mask.p, y, stream_);
 }
 
 void NonlinearMechOperator::GradMult(const double* x, double* y, bool constrained, const double* done_flag, bool y_prezeroed, bool skip_out_mask) {
@@ -1006,6 +1023,7 @@ void SystemDriver::drop_cg_graph() {
 #define EXA_PCG_CONSUMER_REDUCE_MAX_DOFS INT64_MAX   // consumer-side reductions of the PCG scalars up to this many local dofs (EXA_PCG_REDUCE_LAUNCH=1: never, =<n>: up to n)
 #endif
 int SystemDriver::CGSolve(const double* b, double* x) {
+   if (oper_->precond == Precond::MULTIGRID) return CGSolveMG(b, x);
    if ((comm.nranks > 1 || comm.forced()) && std::getenv("EXA_PCG_TWO_REDUCTIONS") == nullptr) return CGSolveSingleReduction(b, x);
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
@@ -1106,6 +1124,76 @@ int SystemDriver::CGSolve(const double* b, double* x) {
    note_cg_reduction(hS);
    report_cg(hS, iters);
    return iters;
+}
+
+// PCG preconditioned by one multigrid V-cycle per iteration (host/multigrid.hpp): MFEM CGSolver::Mult with iterative_mode = false, its order of
+// operations and stopping test (r, z) <= max(rel^2 (r0, z0), abs^2), on one rank and on several.  The host reads every scalar (the V-cycle
+// synchronises for nothing else); no graph capture.  Fills the same diagnostics as the identity loops.
+int SystemDriver::CGSolveMG(const double* b, double* x) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   const int64_t nd = op.Height();
+   ProfRegion prof("krylov_solver");
+   if (cg_s_.n < (size_t)nd) { cg_s_.alloc(nd); cg_q_.alloc(nd); }
+   hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s));
+   double* r = cg_r_.p; double* z = cg_z_.p; double* d = cg_d_.p;
+   EXA_HC(hipMemsetAsync(x, 0, sizeof(double) * nd, s));
+   EXA_HC(hipMemcpyAsync(r, b, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
+   op.mg->Apply(r, z);
+   EXA_HC(hipMemcpyAsync(d, z, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
+   double nom0 = op.dot(d, r), nom = nom0, betanom = nom0;
+   // hS: the slots of the device loops' scalar array that report_cg / note_cg_reduction read ([2] (r, z), [6] flag, [7] iterations, [10] (Ad, d) < 0, [11] (r0, z0))
+   double hS[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+   hS[11] = nom0; hS[2] = nom0;
+   int it = 0; double flag = 2.0;
+   const double r0 = std::max(nom0 * opt_.krylov_rel * opt_.krylov_rel, opt_.krylov_abs * opt_.krylov_abs);
+   if (nom0 < 0.0) flag = 2.0;                      // the preconditioner is not positive definite: MFEM stops, not converged
+   else if (nom0 <= r0) flag = 1.0;
+   else {
+      op.GradMult(d, z, true);
+      double den = op.dot(z, d);
+      if (den <= 0.0 && op.dot(d, d) > 0.0) hS[10] += 1.0;
+      if (den == 0.0) flag = -1.0;
+      else
+         for (it = 1; true; it++) {
+            const double alpha = nom / den;
+            vk_axpby(nd, alpha, d, 1.0, x, s);
+            vk_axpby(nd, -alpha, z, 1.0, r, s);
+            op.mg->Apply(r, z);
+            betanom = op.dot(r, z);
+            if (betanom < 0.0) { flag = 2.0; break; }
+            if (betanom <= r0) { flag = 1.0; break; }
+            if (it >= opt_.krylov_iter) { flag = 2.0; break; }
+            const double beta = betanom / nom;
+            vk_axpby(nd, 1.0, z, beta, d, s);      // d = z + beta d
+            op.GradMult(d, z, true);
+            den = op.dot(d, z);
+            if (den <= 0.0 && op.dot(d, d) > 0.0) hS[10] += 1.0;
+            if (den == 0.0) { flag = -1.0; break; }
+            nom = betanom;
+         }
+   }
+   hS[2] = betanom; hS[6] = flag; hS[7] = it;
+   EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1));
+   float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e0, e1)); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+   op.timers.t_krylov_ms += ms; op.timers.krylov_iters += it;
+   last_cg_flag = (int)flag; cg_indefinite_iters += (int64_t)hS[10];
+   if (flag != 1.0) cg_not_converged++;
+   note_cg_reduction(hS);
+   report_cg(hS, it);
+   return it;
+}
+
+void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
+   if (kind < 0 || kind > 2) throw std::runtime_error("preconditioner kind must be 0 (identity), 1 (jacobi) or 2 (multigrid)");
+   NonlinearMechOperator& op = *oper_;
+   if (kind == 2) {
+      if (ExaOptions::lower(opt_.integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
+      op.mg.reset(new Multigrid(op, levels, degree));   // throws where no hierarchy can be built
+   } else op.mg.reset();
+   drop_cg_graph();
+   precond = kind == 0 ? Precond::IDENTITY : (kind == 1 ? Precond::JACOBI : Precond::MULTIGRID);
+   op.precond = precond;
 }
 
 // ExaNewtonSolver::Mult / ExaNewtonLSSolver::Mult with b = 0 (reference src/mechanics_solver.cpp:39-143,155-281)

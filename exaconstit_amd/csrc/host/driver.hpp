@@ -64,7 +64,8 @@ class Comm {
    void exchange(const Partition& part, hipStream_t s);   // send buffers -> neighbours' receive buffers (RCCL grouped send/recv or loopback copies) on stream s
 };
 
-enum class Precond { IDENTITY, JACOBI };
+enum class Precond { IDENTITY, JACOBI, MULTIGRID };
+class Multigrid;
 
 struct SolverStats { int newton_iters = 0; int krylov_iters = 0; int model_calls = 0; bool converged = false; };
 
@@ -116,6 +117,8 @@ class NonlinearMechOperator {
    // y = K x with essential columns/rows masked (constrained) or the plain local action
    // y_prezeroed / skip_out_mask: the PCG loop folds the zero fill into its direction update and the output mask into its dot product
    void GradMult(const double* x, double* y, bool constrained, const double* done_flag = nullptr, bool y_prezeroed = false, bool skip_out_mask = false);
+   // this rank's part of the constrained action (no halo exchange): what the multigrid hierarchy probes (host/multigrid.hpp)
+   void GradMultLocal(const double* x, double* y);
    // reference src/mechanics_operator.cpp:446-483
    void GetUpdateBCsAction(const double* k, const double* x, double* y);
    void ResidualAction(double* y);
@@ -133,6 +136,7 @@ class NonlinearMechOperator {
    DevBuf<uint8_t> ess_mask;
    DevBuf<int32_t> conn;
    Precond precond = Precond::IDENTITY;
+   std::unique_ptr<Multigrid> mg;   // precond == MULTIGRID: rebuilt after every gradient set-up
    Timers timers;
    int model_calls = 0;
    std::vector<double> props;     // material parameters the context was created with (the adapter-route bench creates a second, AOS context from them)
@@ -156,7 +160,7 @@ class NonlinearMechOperator {
    std::vector<EvPair> ev_ring_; int ev_head_ = 0;   // event pairs around the constitutive launches, read back lazily
    int nn_, nd_, E_, npe_ = 8; double dt_ = 1.0;
    bool records_setup_ = false;   // gradient records written by the constitutive launch (p = 1 fast path, identity preconditioner)
-   bool use_records() const { return records_setup_ && precond == Precond::IDENTITY; }
+   bool use_records() const { return records_setup_ && precond != Precond::JACOBI; }
    bool geo_resid_ = true, jac_stale_ = false;   // record route + L-vector residual: no Jacobian field is written, both actions recompute the geometry (EXA_JAC_FIELD=on keeps it)
    bool geo_resid() const { return geo_resid_ && lvec_resid_ && fast_p1_; }      // (p = 2: the Jacobian field is written by the geometry pre-pass and read by the residual)
    void ensure_mat_grad();
@@ -185,6 +189,10 @@ class SystemDriver {
    bool NewtonSolve(double* x, SolverStats& st);
    int CGSolve(const double* b, double* x);   // device PCG, returns iterations
    int CGSolveSingleReduction(const double* b, double* x);   // more than one rank: one fused 16-byte all-reduce per iteration
+   int CGSolveMG(const double* b, double* x);   // multigrid-preconditioned CG (MFEM CGSolver::Mult order of operations), any rank count
+   // preconditioner of the PCG (set before the first step; takes effect at the next gradient set-up): kind 0 identity, 1 Jacobi, 2 multigrid with at most `levels` coarse levels (0: as
+   // many as the mesh allows) and a Chebyshev smoother of `degree`; refuses multigrid where no hierarchy can be built
+   void SetPreconditioner(int kind, int levels, int degree);
    void note_cg_reduction(const double* hS);
    double last_cg_reduction = 0.0, worst_capped_cg_reduction = 0.0;   // |r|_M / |r0|_M of the last PCG solve / the worst among the solves that stopped at max_iter
    void drop_cg_graph();                      // forget the captured PCG chunk (its solution buffer is about to go away)

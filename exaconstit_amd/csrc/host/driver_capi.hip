@@ -3,6 +3,7 @@
 // the per-step loop, the avg_* outputs (reference src/system_driver.cpp:444-553) and the timing regions the reference marks
 // with Caliper (ecmech_kernel, krylov_solver: src/mechanics_ecmech.cpp:237-257, src/mechanics_solver.cpp:99-103).
 #include "driver.hpp"
+#include "multigrid.hpp"
 #include "roctx.hpp"
 #include "vtu.hpp"
 #include "../../../include/exaconstit_driver.h"
@@ -145,6 +146,10 @@ exa_driver* exa_driver_create(const char* toml_path, const char* out_dir, int ra
       d->sd.reset(new SystemDriver(opt, rank, nranks, uid));
       d->sd->out_dir = out_dir ? out_dir : "."; d->sd->write_files = write_files != 0;
       d->sd->precond = jacobi ? Precond::JACOBI : Precond::IDENTITY; d->sd->oper().precond = d->sd->precond;
+      if (opt.precond != 0) {   // Solvers.Krylov.preconditioner decides when it is present
+         try { d->sd->SetPreconditioner(opt.precond, opt.mg_levels, opt.mg_degree); }
+         catch (...) { delete d; throw; }
+      }
       return d;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return nullptr; }
 }
@@ -183,6 +188,102 @@ exa_driver* exa_driver_create_synthetic(const exa_synth_config* c, int rank, int
 }
 
 void exa_driver_destroy(exa_driver* d) { delete d; }
+
+int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen) {
+   try { d->sd->SetPreconditioner(kind, levels, degree); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+}  // extern "C"
+namespace {
+Multigrid& mg_of(exa_driver* d) {
+   NonlinearMechOperator& op = d->sd->oper();
+   if (op.precond != Precond::MULTIGRID || !op.mg) throw std::runtime_error("the driver has no multigrid preconditioner (exa_driver_set_preconditioner)");
+   return *op.mg;
+}
+void check_level(Multigrid& mg, int l, bool transfer) {
+   if (l < 0 || l > mg.levels() - (transfer ? 1 : 0)) throw std::runtime_error("multigrid: level " + std::to_string(l) + " does not exist");
+}
+}
+extern "C" {
+
+// out (>= 4 + 4 (levels + 1) doubles): { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree,
+// then per level l = 0 ... L: local elements per direction (3), lmax estimate of D^-1 A_l (0 before the first set-up) }
+int exa_driver_mg_info(exa_driver* d, double* out) {
+   try {
+      Multigrid& mg = mg_of(d);
+      out[0] = mg.levels(); out[1] = mg.setup_ms; out[2] = mg.vcycle_ms(); out[3] = mg.degree();
+      for (int l = 0; l <= mg.levels(); l++) {
+         for (int k = 0; k < 3; k++) out[4 + 4 * l + k] = mg.grid(l).n[k] - 1;
+         out[4 + 4 * l + 3] = mg.lmax(l);
+      }
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_info: %s\n", e.what()); return -1; }
+}
+
+// gradient set-up of the current state (what the next Newton iteration would do first) and the hierarchy build that follows it
+int exa_driver_mg_setup(exa_driver* d, char* err, int errlen) {
+   try { (void)mg_of(d); d->sd->oper().GetGradient(); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int64_t exa_driver_mg_level_dofs(exa_driver* d, int level) {
+   try { Multigrid& mg = mg_of(d); check_level(mg, level, false); return mg.level_dofs(level); }
+   catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_level_dofs: %s\n", e.what()); return -1; }
+}
+
+int exa_driver_mg_apply(exa_driver* d, int level, const double* x, double* y) {
+   try {
+      Multigrid& mg = mg_of(d); check_level(mg, level, false);
+      const size_t n = mg.level_dofs(level); hipStream_t s = d->sd->oper().stream();
+      DevBuf<double> dx(n), dy(n); dx.upload(x, n, s);
+      mg.LevelApply(level, dx.p, dy.p); dy.download(y, n, s);
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_apply: %s\n", e.what()); return -1; }
+}
+
+int exa_driver_mg_diag(exa_driver* d, int level, double* out) {
+   try {
+      Multigrid& mg = mg_of(d); check_level(mg, level, false);
+      const size_t n = mg.level_dofs(level); hipStream_t s = d->sd->oper().stream();
+      DevBuf<double> dy(n); mg.LevelDiag(level, dy.p); dy.download(out, n, s);
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_diag: %s\n", e.what()); return -1; }
+}
+
+// dir 0: out (level l) = P in (level l + 1); dir 1: out (level l + 1) = restriction of in (level l)
+int exa_driver_mg_transfer(exa_driver* d, int level, int dir, const double* in, double* out) {
+   try {
+      Multigrid& mg = mg_of(d); check_level(mg, level, true);
+      if (dir != 0 && dir != 1) throw std::runtime_error("dir must be 0 (prolongation) or 1 (restriction)");
+      const size_t nf = mg.level_dofs(level), nc = mg.level_dofs(level + 1); hipStream_t s = d->sd->oper().stream();
+      DevBuf<double> di(dir == 0 ? nc : nf), dout(dir == 0 ? nf : nc);
+      di.upload(in, di.n, s);
+      if (dir == 0) mg.Prolong(level, di.p, dout.p); else mg.Restrict(level, di.p, dout.p);
+      dout.download(out, dout.n, s);
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_transfer: %s\n", e.what()); return -1; }
+}
+
+// the coarse operator of level l >= 1 as stored: 243 doubles per node, [(o * 9 + 3 r + c) * NN + node] (mg_kernels.hip)
+int exa_driver_mg_stencil(exa_driver* d, int level, double* out) {
+   try {
+      Multigrid& mg = mg_of(d); check_level(mg, level, false);
+      if (level < 1) throw std::runtime_error("level 0 has no stored stencil");
+      const size_t n = (size_t)MG_STENCIL * (mg.level_dofs(level) / 3);
+      EXA_HC(hipMemcpyAsync(out, mg.stencil(level), sizeof(double) * n, hipMemcpyDeviceToHost, d->sd->oper().stream()));
+      EXA_HC(hipStreamSynchronize(d->sd->oper().stream()));
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_stencil: %s\n", e.what()); return -1; }
+}
+
+int exa_driver_precond_apply(exa_driver* d, const double* r, double* z) {
+   try {
+      Multigrid& mg = mg_of(d);
+      const size_t n = mg.level_dofs(0); hipStream_t s = d->sd->oper().stream();
+      DevBuf<double> dr(n), dz(n); dr.upload(r, n, s);
+      mg.Apply(dr.p, dz.p); dz.download(z, n, s);
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_precond_apply: %s\n", e.what()); return -1; }
+}
 
 int exa_driver_num_steps(exa_driver* d) { return d->sd->options().nsteps; }
 int64_t exa_driver_local_qpts(exa_driver* d) { return (int64_t)d->sd->part.E * d->sd->part.n; }
@@ -507,6 +608,17 @@ int exa_driver_write_fields(exa_driver* d, const char* dir, int cycle, double t,
       return 0;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
+
+// out3 = { preconditioner: 0 key absent, 1 "jacobi", 2 "multigrid"; mg_levels (0: as many as the mesh allows); mg_smoother_degree }
+int exa_options_query_solver(const char* toml_path, int* out3, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      out3[0] = o.precond; out3[1] = o.mg_levels; out3[2] = o.mg_degree;
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_mg_level_count(const int* N, int nranks, int cap) { return (nranks < 1 || N[0] < 1 || N[1] < 1 || N[2] < 1) ? -1 : mg_level_count(N, nranks, cap); }
 
 int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen) {
    try {

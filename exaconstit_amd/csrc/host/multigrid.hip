@@ -1,0 +1,208 @@
+// Geometric multigrid preconditioner: hierarchy build and V-cycle (see multigrid.hpp; kernels in mg_kernels.hip).
+#include "multigrid.hpp"
+#include "driver.hpp"
+#include <chrono>
+#include <cmath>
+#include <stdexcept>
+
+namespace exa_host {
+
+Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op_(op), degree_(degree) {
+   const Partition& part = op.part();
+   if (part.from_file || part.p != 1) throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\") at p_refinement = 1");
+   if (degree < 1 || degree > 8) throw std::runtime_error("Solvers.Krylov.mg_smoother_degree must lie in 1 ... 8");
+   if (levels_cap < 0) throw std::runtime_error("Solvers.Krylov.mg_levels must be >= 0 (0: as many as the mesh allows)");
+   const int L = mg_level_count(part.N, part.nranks, levels_cap);
+   if (L < 1)
+      throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\": no coarse level can be built for " + std::to_string(part.N[0]) + " x " + std::to_string(part.N[1]) + " x " +
+                               std::to_string(part.N[2]) + " elements on " + std::to_string(part.nranks) + " rank(s) (every rank's element box must be even, with at least 2 elements per direction after coarsening)");
+   for (int d = 0; d < 3; d++) ng_[d] = part.N[d];
+   hipStream_t s = op.stream();
+   lv_.resize(L + 1);
+   for (int l = 0; l <= L; l++) {
+      Level& v = lv_[l];
+      v.stride = 1 << l;
+      for (int d = 0; d < 3; d++) { v.g.n[d] = (part.ne[d] >> l) + 1; v.g.g0[d] = part.e0[d] >> l; }
+      v.nn = (int64_t)v.g.n[0] * v.g.n[1] * v.g.n[2]; v.nd = 3 * v.nn;
+      v.deg = l == L ? MG_COARSE_DEGREE : degree;
+      v.diag.alloc(v.nd); v.dinv.alloc(v.nd); v.r.alloc(v.nd); v.d.alloc(v.nd); v.t.alloc(v.nd); v.u.alloc(v.nd); v.v.alloc(v.nd);
+      if (l > 0) {
+         v.S.alloc((size_t)MG_STENCIL * v.nn); v.b.alloc(v.nd); v.x.alloc(v.nd); v.mask_own.alloc(v.nd);
+         v.mask = v.mask_own.p;
+         std::vector<double> w((size_t)v.nn);      // node multiplicity weight = the fine node's
+         for (int k = 0; k < v.g.n[2]; k++) for (int j = 0; j < v.g.n[1]; j++) for (int i = 0; i < v.g.n[0]; i++)
+            w[i + (size_t)v.g.n[0] * (j + (size_t)v.g.n[1] * k)] = part.weight[(size_t)v.stride * i + (size_t)part.nn[0] * ((size_t)v.stride * j + (size_t)part.nn[1] * v.stride * k)];
+         v.w.upload(w, s); v.wp = v.w.p;
+      }
+   }
+   if ((int64_t)lv_[0].nn != part.NN) throw std::runtime_error("multigrid: the partition is not a structured p = 1 box");
+   fine_tmp_.alloc(lv_[0].nd); partial_.alloc(DOT_BLOCKS * 4); scal_.alloc(4);
+   EXA_HC(hipEventCreate(&ev0_)); EXA_HC(hipEventCreate(&ev1_));
+}
+
+Multigrid::~Multigrid() {
+   if (ev0_) (void)hipEventDestroy(ev0_);
+   if (ev1_) (void)hipEventDestroy(ev1_);
+}
+
+// coarse halo sum on the fine exchange plan: the level-l nodes are level-0 nodes, and the fine neighbour lists hold every shared one
+void Multigrid::halo(int l, double* y) {
+   Comm& comm = op_.comm();
+   if (comm.nranks == 1 && !comm.forced()) return;
+   hipStream_t s = op_.stream();
+   if (l == 0) { comm.halo_sum(op_.part(), y, s); return; }
+   fine_tmp_.zero(s);
+   mg_to_fine(lv_[0].g, lv_[l].g, lv_[l].stride, y, fine_tmp_.p, s);
+   comm.halo_sum(op_.part(), fine_tmp_.p, s);
+   mg_from_fine(lv_[0].g, lv_[l].g, lv_[l].stride, fine_tmp_.p, y, s);
+}
+
+void Multigrid::ALocal(int l, const double* x, double* y) {
+   if (l == 0) op_.GradMultLocal(x, y);
+   else mg_stencil_apply(lv_[l].g, lv_[l].S.p, x, y, op_.stream());
+}
+
+void Multigrid::A(int l, const double* x, double* y) {
+   if (l == 0) { op_.GradMult(x, y, true); return; }
+   mg_stencil_apply(lv_[l].g, lv_[l].S.p, x, y, op_.stream());
+   halo(l, y);
+}
+
+double Multigrid::dot(int l, const double* a, const double* b) {
+   if (l == 0) return op_.dot(a, b);
+   hipStream_t s = op_.stream();
+   vk_dot(lv_[l].nd, lv_[l].nn, lv_[l].wp, a, b, nullptr, partial_.p, scal_.p, s);
+   op_.comm().allreduce_sum(scal_.p, 1, s);
+   double h; EXA_HC(hipMemcpyAsync(&h, scal_.p, sizeof(double), hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
+   return h;
+}
+
+void Multigrid::Build() {
+   const auto t0 = std::chrono::steady_clock::now();
+   hipStream_t s = op_.stream();
+   const int L = levels();
+   lv_[0].mask = op_.ess_mask.p; lv_[0].wp = op_.weight.p;
+   for (int l = 1; l <= L; l++) mg_mask_coarsen(lv_[l - 1].g, lv_[l].g, lv_[l - 1].mask, lv_[l].mask_own.p, s);
+   // fine diagonal: the fine operator couples nodes at most one apart, so probes of the 8 colours mod 2 (per component) read it off
+   {
+      Level& f = lv_[0];
+      f.diag.zero(s);
+      for (int colour = 0; colour < 8; colour++)
+         for (int c = 0; c < 3; c++) {
+            mg_probe(f.g, 2, colour, c, f.mask, f.t.p, s);
+            op_.GradMult(f.t.p, f.u.p, true);
+            mg_diag_probe(f.g, 2, colour, c, f.u.p, f.diag.p, s);
+         }
+   }
+   // Galerkin stencils, level by level: probe, interpolate, this rank's part of the level l - 1 action, restrict, mask, read off
+   for (int l = 1; l <= L; l++) {
+      Level& c = lv_[l]; Level& f = lv_[l - 1];
+      for (int colour = 0; colour < 27; colour++)
+         for (int k = 0; k < 3; k++) {
+            mg_probe(c.g, 3, colour, k, c.mask, c.x.p, s);
+            mg_prolong(f.g, c.g, c.x.p, f.t.p, 0.0, s);
+            ALocal(l - 1, f.t.p, f.u.p);
+            mg_restrict(f.g, c.g, nullptr, f.u.p, c.r.p, s);
+            vk_mask_zero(c.nd, c.mask, c.r.p, s);
+            mg_extract(c.g, colour, k, c.r.p, c.S.p, s);
+         }
+      mg_stencil_diag(c.g, c.S.p, c.diag.p, s);
+      halo(l, c.diag.p);
+   }
+   // D^-1 and the largest eigenvalue of D^-1 A per level (power iteration from the same start vector on every decomposition)
+   for (int l = 0; l <= L; l++) {
+      Level& v = lv_[l];
+      mg_dinv(v.nd, v.mask, v.diag.p, v.dinv.p, s);
+      int ng[3]; for (int d = 0; d < 3; d++) ng[d] = (ng_[d] >> l) + 1;
+      mg_seed(v.g, ng, v.mask, v.v.p, s);
+      double lam = 0.0;
+      for (int it = 0; it < MG_POWER_ITERS; it++) {
+         const double nrm = std::sqrt(dot(l, v.v.p, v.v.p));
+         if (!(nrm > 0.0)) break;
+         vk_axpby(v.nd, 0.0, v.v.p, 1.0 / nrm, v.v.p, s);
+         A(l, v.v.p, v.t.p);
+         vk_pointwise(v.nd, v.dinv.p, v.t.p, v.u.p, s);
+         lam = dot(l, v.v.p, v.u.p);
+         v.v.swap(v.u);
+      }
+      v.lmax = lam;
+   }
+   EXA_HC(hipStreamSynchronize(s));
+   setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+   built_ = true;
+}
+
+// Chebyshev smoother with zero initial guess: x = p(D^-1 A) D^-1 b, degree lv_[l].deg (Saad, Iterative Methods, Alg. 12.1)
+void Multigrid::smooth(int l, const double* b, double* x) {
+   Level& v = lv_[l];
+   hipStream_t s = op_.stream();
+   const double hi = 1.2 * v.lmax, lo = 0.3 * hi;
+   const double theta = 0.5 * (hi + lo), delta = 0.5 * (hi - lo), sigma = theta / delta;
+   double rho = 1.0 / sigma;
+   EXA_HC(hipMemcpyAsync(v.r.p, b, sizeof(double) * v.nd, hipMemcpyDeviceToDevice, s));
+   if (!(v.lmax > 0.0)) { EXA_HC(hipMemsetAsync(x, 0, sizeof(double) * v.nd, s)); return; }
+   mg_cheb(v.nd, x, v.r.p, v.d.p, nullptr, v.dinv.p, 0.0, 1.0 / theta, true, s);
+   for (int k = 1; k < v.deg; k++) {
+      A(l, v.d.p, v.t.p);
+      const double rho1 = 1.0 / (2.0 * sigma - rho);
+      mg_cheb(v.nd, x, v.r.p, v.d.p, v.t.p, v.dinv.p, rho1 * rho, 2.0 * rho1 / delta, false, s);
+      rho = rho1;
+   }
+}
+
+void Multigrid::vcycle(int l, const double* b, double* x) {
+   Level& v = lv_[l];
+   hipStream_t s = op_.stream();
+   if (l == levels()) { smooth(l, b, x); return; }
+   Level& c = lv_[l + 1];
+   smooth(l, b, x);                                        // pre-smoothing
+   A(l, x, v.t.p); mg_resid(v.nd, v.mask, b, v.t.p, v.u.p, s);
+   Restrict(l, v.u.p, c.b.p);
+   vk_mask_zero(c.nd, c.mask, c.b.p, s);                   // (M P)^T r: the transpose of the masked prolongation below
+   vcycle(l + 1, c.b.p, c.x.p);                            // coarse correction
+   mg_prolong(v.g, c.g, c.x.p, x, 1.0, s);
+   vk_mask_zero(v.nd, v.mask, x, s);
+   A(l, x, v.t.p); mg_resid(v.nd, v.mask, b, v.t.p, v.u.p, s);
+   smooth(l, v.u.p, v.v.p);                                // post-smoothing: the same polynomial
+   vk_axpby(v.nd, 1.0, v.v.p, 1.0, x, s);
+}
+
+void Multigrid::Apply(const double* b, double* x) {
+   if (!built_) throw std::runtime_error("multigrid: the hierarchy has not been built (no gradient set-up yet)");
+   hipStream_t s = op_.stream();
+   EXA_HC(hipEventRecord(ev0_, s));
+   vcycle(0, b, x);
+   EXA_HC(hipEventRecord(ev1_, s));
+   ev_pending_ = true;
+}
+
+double Multigrid::vcycle_ms() {
+   if (ev_pending_) {
+      EXA_HC(hipEventSynchronize(ev1_));
+      float ms = 0; EXA_HC(hipEventElapsedTime(&ms, ev0_, ev1_)); vcycle_ms_ = ms; ev_pending_ = false;
+   }
+   return vcycle_ms_;
+}
+
+void Multigrid::LevelApply(int l, const double* x, double* y) {
+   if (l < 0 || l > levels()) throw std::runtime_error("multigrid: no level " + std::to_string(l));
+   if (l > 0 && !built_) throw std::runtime_error("multigrid: the hierarchy has not been built (no gradient set-up yet)");
+   A(l, x, y);
+}
+void Multigrid::LevelDiag(int l, double* out) {
+   if (l < 0 || l > levels()) throw std::runtime_error("multigrid: no level " + std::to_string(l));
+   if (!built_) throw std::runtime_error("multigrid: the hierarchy has not been built (no gradient set-up yet)");
+   EXA_HC(hipMemcpyAsync(out, lv_[l].diag.p, sizeof(double) * lv_[l].nd, hipMemcpyDeviceToDevice, op_.stream()));
+}
+void Multigrid::Prolong(int l, const double* xc, double* xf) {
+   if (l < 0 || l >= levels()) throw std::runtime_error("multigrid: no transfer below level " + std::to_string(l));
+   mg_prolong(lv_[l].g, lv_[l + 1].g, xc, xf, 0.0, op_.stream());
+}
+void Multigrid::Restrict(int l, const double* rf, double* rc) {
+   if (l < 0 || l >= levels()) throw std::runtime_error("multigrid: no transfer below level " + std::to_string(l));
+   const Level& f = lv_[l];
+   mg_restrict(f.g, lv_[l + 1].g, (op_.comm().nranks == 1 && !op_.comm().forced()) ? nullptr : (l == 0 ? op_.weight.p : f.wp), rf, rc, op_.stream());
+   halo(l + 1, rc);
+}
+
+}  // namespace exa_host

@@ -121,6 +121,10 @@ struct ExaOptions {
    Assembly assembly = Assembly::EA; NLSolver nl_solver = NLSolver::NR; std::string integ_model = "FULL";
    int newton_iter = 25; double newton_rel = 1e-5, newton_abs = 1e-10;
    int krylov_iter = 200; double krylov_rel = 1e-10, krylov_abs = 1e-30; std::string krylov_solver = "PCG";
+   // Solvers.Krylov.preconditioner (not a key of the reference, whose TOML reader ignores it): 0 absent (the jacobi flag of exa_driver_create
+   // decides), 1 "jacobi", 2 "multigrid" (host/multigrid.hpp) with mg_levels coarse levels at most (0: as many as the mesh allows) and a
+   // Chebyshev smoother of degree mg_smoother_degree (1 ... 8)
+   int precond = 0, mg_levels = 0, mg_degree = 2;
    int ref_ser = 0, order = 1; int ncuts[3] = { 1, 1, 1 }; double length[3] = { 1, 1, 1 }; std::string mesh_type = "auto", mesh_file;
 
    static std::vector<double> load_numbers(const std::string& path) {
@@ -255,6 +259,20 @@ struct ExaOptions {
          for (int i = 0; i < 3; i++) { ncuts[i] = (int)nc->arr[i].num; length[i] = ln->arr[i].num; }
       } else throw std::runtime_error("Mesh.type must be \"auto\", \"other\" or \"cubit\"");
       if (order < 1 || order > 6) throw std::runtime_error("p_refinement must be between 1 and 6");
+      if (const TomlValue* pc = d.get("Solvers.Krylov.preconditioner")) {
+         const std::string k = pc->kind == TomlValue::STR ? lower(pc->str) : std::string("?");
+         if (k == "jacobi") precond = 1;
+         else if (k == "multigrid") {
+            precond = 2;
+            const double lv = d.num("Solvers.Krylov.mg_levels", 0.0), dg = d.num("Solvers.Krylov.mg_smoother_degree", 2.0);
+            if (lv < 0 || lv != std::floor(lv) || lv > 30) throw std::runtime_error("Solvers.Krylov.mg_levels must be a whole number >= 0 (0: as many levels as the mesh allows)");
+            if (dg < 1 || dg > 8 || dg != std::floor(dg)) throw std::runtime_error("Solvers.Krylov.mg_smoother_degree must be a whole number in 1 ... 8");
+            mg_levels = (int)lv; mg_degree = (int)dg;
+            if (order != 1) throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is built for p_refinement = 1 only");
+            if (lower(integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
+            if (mesh_type != "auto") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\"): file meshes need algebraic coarsening");
+         } else throw std::runtime_error("Solvers.Krylov.preconditioner must be \"jacobi\" or \"multigrid\"");
+      }
    }
 };
 

@@ -213,6 +213,35 @@ exa_driver_lattice_strains = _sig("exa_driver_lattice_strains", C.c_int, C.c_voi
 exa_options_query_lightup = _sig("exa_options_query_lightup", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
 exa_driver_write_fields = _sig("exa_driver_write_fields", C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_char_p, C.c_int)
+_dp = C.POINTER(C.c_double)
+exa_driver_set_preconditioner = _sig("exa_driver_set_preconditioner", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int)
+exa_driver_mg_info = _sig("exa_driver_mg_info", C.c_int, C.c_void_p, _dp)
+exa_driver_mg_setup = _sig("exa_driver_mg_setup", C.c_int, C.c_void_p, C.c_char_p, C.c_int)
+exa_driver_mg_level_dofs = _sig("exa_driver_mg_level_dofs", C.c_int64, C.c_void_p, C.c_int)
+exa_driver_mg_apply = _sig("exa_driver_mg_apply", C.c_int, C.c_void_p, C.c_int, _dp, _dp)
+exa_driver_mg_diag = _sig("exa_driver_mg_diag", C.c_int, C.c_void_p, C.c_int, _dp)
+exa_driver_mg_transfer = _sig("exa_driver_mg_transfer", C.c_int, C.c_void_p, C.c_int, C.c_int, _dp, _dp)
+exa_driver_mg_stencil = _sig("exa_driver_mg_stencil", C.c_int, C.c_void_p, C.c_int, _dp)
+exa_driver_precond_apply = _sig("exa_driver_precond_apply", C.c_int, C.c_void_p, _dp, _dp)
+exa_options_query_solver = _sig("exa_options_query_solver", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int)
+exa_mg_level_count = _sig("exa_mg_level_count", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int)
+
+PRECOND_KINDS = {"identity": 0, "jacobi": 1, "multigrid": 2}
+
+
+def options_solver(path):
+    """Solvers.Krylov preconditioner keys of an options file: dict(preconditioner (None = key absent, "jacobi", "multigrid"), mg_levels, mg_smoother_degree)"""
+    out = (C.c_int * 3)()
+    err = C.create_string_buffer(512)
+    if exa_options_query_solver(path.encode(), out, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(preconditioner={0: None, 1: "jacobi", 2: "multigrid"}[out[0]], mg_levels=out[1], mg_smoother_degree=out[2])
+
+
+def mg_level_count(N, nranks=1, cap=0):
+    """coarse multigrid levels of an N0 x N1 x N2 element grid on nranks block ranks (0: multigrid refused), capped by cap > 0"""
+    n = (C.c_int * 3)(*([int(N)] * 3 if isinstance(N, int) else [int(v) for v in N]))
+    return exa_mg_level_count(n, int(nranks), int(cap))
 
 
 def options_vis(path):
@@ -420,6 +449,81 @@ class Driver:
         o = np.zeros(3)
         self._chk(exa_driver_bench_pcg(self.h, iters, o.ctypes.data_as(C.POINTER(C.c_double)), self._err, 512))
         return dict(pcg_ms=o[0], iters=int(o[1]), apply_ms=o[2])
+
+    # ---- preconditioner (exa_driver_set_preconditioner) and the multigrid test hooks ---------------------------------------
+    def set_preconditioner(self, kind, levels=0, degree=2):
+        """kind: "identity", "jacobi" or "multigrid" (or 0 / 1 / 2); levels: max coarse levels (0 = as many as the mesh allows); degree: Chebyshev degree"""
+        k = PRECOND_KINDS[kind] if isinstance(kind, str) else int(kind)
+        self._chk(exa_driver_set_preconditioner(self.h, k, int(levels), int(degree), self._err, 512))
+
+    def mg_info(self):
+        """dict(levels, setup_ms, vcycle_ms, degree, boxes (L+1, 3) local elements per direction, lmax (L+1,))"""
+        import numpy as np
+        out = np.zeros(4 + 4 * 32)
+        if exa_driver_mg_info(self.h, out.ctypes.data_as(_dp)) != 0:
+            raise RuntimeError("exa_driver_mg_info failed (no multigrid preconditioner)")
+        L = int(out[0])
+        per = out[4:4 + 4 * (L + 1)].reshape(L + 1, 4)
+        return dict(levels=L, setup_ms=float(out[1]), vcycle_ms=float(out[2]), degree=int(out[3]), boxes=per[:, :3].astype(int), lmax=per[:, 3].copy())
+
+    def mg_setup(self):
+        """gradient set-up of the current state + hierarchy build (the hooks then act on the operator the driver holds now)"""
+        self._chk(exa_driver_mg_setup(self.h, self._err, 512))
+
+    def mg_level_dofs(self, level):
+        n = exa_driver_mg_level_dofs(self.h, int(level))
+        if n < 0:
+            raise RuntimeError(f"no multigrid level {level}")
+        return int(n)
+
+    def _mg_vec(self, level, x):
+        import numpy as np
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size != self.mg_level_dofs(level):
+            raise ValueError(f"level {level} holds {self.mg_level_dofs(level)} dofs, got {x.size}")
+        return x
+
+    def mg_apply(self, level, x):
+        """y = A_level x (level 0: the constrained operator the PCG applies)"""
+        import numpy as np
+        x = self._mg_vec(level, x)
+        y = np.empty_like(x)
+        if exa_driver_mg_apply(self.h, int(level), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp)) != 0:
+            raise RuntimeError("exa_driver_mg_apply failed")
+        return y
+
+    def mg_diag(self, level):
+        import numpy as np
+        y = np.empty(self.mg_level_dofs(level))
+        if exa_driver_mg_diag(self.h, int(level), y.ctypes.data_as(_dp)) != 0:
+            raise RuntimeError("exa_driver_mg_diag failed")
+        return y
+
+    def mg_transfer(self, level, direction, x):
+        """direction 0: P x (level + 1 -> level); 1: restriction (level -> level + 1)"""
+        import numpy as np
+        x = self._mg_vec(level + 1 if direction == 0 else level, x)
+        y = np.empty(self.mg_level_dofs(level if direction == 0 else level + 1))
+        if exa_driver_mg_transfer(self.h, int(level), int(direction), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp)) != 0:
+            raise RuntimeError("exa_driver_mg_transfer failed")
+        return y
+
+    def mg_stencil(self, level):
+        """stored coarse operator of level >= 1: (243, nodes), row (o * 9 + 3 r + c)"""
+        import numpy as np
+        out = np.empty(243 * (self.mg_level_dofs(level) // 3))
+        if exa_driver_mg_stencil(self.h, int(level), out.ctypes.data_as(_dp)) != 0:
+            raise RuntimeError("exa_driver_mg_stencil failed")
+        return out.reshape(243, -1)
+
+    def precond_apply(self, r):
+        """z = B r, one multigrid V-cycle"""
+        import numpy as np
+        r = self._mg_vec(0, r)
+        z = np.empty_like(r)
+        if exa_driver_precond_apply(self.h, r.ctypes.data_as(_dp), z.ctypes.data_as(_dp)) != 0:
+            raise RuntimeError("exa_driver_precond_apply failed")
+        return z
 
     def close(self):
         if self.h:

@@ -72,6 +72,28 @@ void exa_loopback_group_destroy(const void* id128);
 exa_driver* exa_driver_create(const char* toml_path, const char* out_dir, int rank, int nranks, const void* uid, int jacobi, int write_files, char* err, int errlen);
 exa_driver* exa_driver_create_synthetic(const exa_synth_config* c, int rank, int nranks, const void* uid, char* err, int errlen);
 void exa_driver_destroy(exa_driver* d);
+/* Preconditioner of the PCG (Solvers.Krylov.preconditioner in an options file; this call overrides it), valid before the first step (so
+ * synthetic and exa_driver_bench_prepare'd drivers can use it): kind 0 identity, 1 Jacobi, 2 geometric multigrid V-cycle (generated p = 1
+ * meshes, not B-bar) with at most `levels` coarse levels (0: as many as the mesh allows) and a Chebyshev smoother of `degree` (1 ... 8).
+ * Refused (-1, err) where no coarse level can be built for the decomposition. */
+int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen);
+/* out (>= 4 + 4 (L + 1) doubles) = { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree, then per level
+ * l = 0 ... L: local elements per direction (3), lmax estimate of D^-1 A_l }.  Returns 0 or -1 (no multigrid preconditioner). */
+int exa_driver_mg_info(exa_driver* d, double* out);
+/* Test hooks on the hierarchy of the last gradient set-up; host arrays of exa_driver_mg_level_dofs(level) doubles (node-major per component,
+ * node = i + n0 (j + n1 k) of the rank's local box at that level).  Level 0 is the constrained operator the PCG applies. */
+int64_t exa_driver_mg_level_dofs(exa_driver* d, int level);
+/* gradient set-up of the current state and the hierarchy build after it: a residual evaluation after the last set-up (the one that ends a
+ * Newton solve) renews the fine operator, this makes the hierarchy match it again */
+int exa_driver_mg_setup(exa_driver* d, char* err, int errlen);
+int exa_driver_mg_apply(exa_driver* d, int level, const double* x, double* y);
+int exa_driver_mg_diag(exa_driver* d, int level, double* out);
+/* dir 0: out (level l) = P_{l+1} in (level l + 1), trilinear interpolation; dir 1: out (level l + 1) = restriction of in (level l) */
+int exa_driver_mg_transfer(exa_driver* d, int level, int dir, const double* in, double* out);
+/* stored coarse operator of level >= 1: 243 doubles per node, [(o * 9 + 3 r + c) * NN + node], o = (dx+1) + 3 (dy+1) + 9 (dz+1) */
+int exa_driver_mg_stencil(exa_driver* d, int level, double* out);
+/* z = B r: one application of the multigrid preconditioner (level-0 sized host arrays) */
+int exa_driver_precond_apply(exa_driver* d, const double* r, double* z);
 int exa_driver_num_steps(exa_driver* d);
 int64_t exa_driver_local_qpts(exa_driver* d);
 int64_t exa_driver_local_dofs(exa_driver* d);
@@ -126,6 +148,11 @@ int exa_driver_bench_adapter_route(exa_driver* d, int steps, int iters, double* 
  * {temp_k, nprops, num_grains, xtal, slip, dt_cust, dt_auto, nsteps, assembly(0 PA,1 EA), nl_solver(0 NR,1 NRLS), newton_iter, newton_rel,
  *  newton_abs, krylov_iter, krylov_rel, krylov_abs, ref_ser, ncuts0, additional_avgs, number of BC change steps}; returns 0 or -1 (err) */
 int exa_options_query(const char* toml_path, double* out20, char* err, int errlen);
+/* Solvers.Krylov keys of the multigrid preconditioner: out3 = { 0 key absent (the jacobi flag of exa_driver_create decides), 1 "jacobi",
+ * 2 "multigrid"; mg_levels (default 0 = as many as the mesh allows); mg_smoother_degree (default 2) }; returns 0 or -1 (err) */
+int exa_options_query_solver(const char* toml_path, int* out3, char* err, int errlen);
+/* number of coarse multigrid levels of an N0 x N1 x N2 element grid on nranks block ranks (0: multigrid refused), capped by cap > 0 */
+int exa_mg_level_count(const int* N, int nranks, int cap);
 /* Visualizations table (reference src/option_parser.cpp:540-570): paraview (default 0), steps (1), light_up (0), floc ("results/exaconstit",
  * relative to the driver's output directory); returns 0 or -1 (err) */
 int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen);

@@ -1,0 +1,65 @@
+"""Identity against multigrid PCG preconditioning (Solvers.Krylov.preconditioner = "multigrid", exaconstit_amd/csrc/host/multigrid.hpp) on the
+synthetic FCC Voce RVE, both in one invocation, at each --n: three steps through first yield (0.01 %, 0.03 %, 0.06 % z-strain), the
+tolerances of BASELINE config 1 (Newton 5e-5, PCG rel 1e-7, 1000-iteration cap).  Prints one JSON document:
+  per case and preconditioner: per step wall ms, Newton and Krylov iterations; the worst residual reduction reached; PCG ms per iteration;
+  multigrid only: hierarchy set-up ms (last Newton iteration), V-cycle ms, levels and the lmax estimates.
+    python scripts/mg_compare.py --n 64 128 > profiles/mg_compare.json"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def run(L, N, kind, dts, props, quats):
+    d = L.Driver.synthetic(N, props, quats, dts, assembly=0)
+    if kind != "identity":
+        d.set_preconditioner(kind)
+    steps = []
+    worst = 0.0
+    setups = []
+    for ti in range(1, len(dts) + 1):
+        t0 = time.perf_counter()
+        ok = d.step(ti)
+        wall = (time.perf_counter() - t0) * 1e3
+        newton, krylov, _ = d.stats()
+        dg = d.diagnostics()
+        worst = max(worst, dg["pcg_last_reduction"], dg["pcg_worst_capped_reduction"])
+        steps.append(dict(step=ti, converged=bool(ok), wall_ms=round(wall, 2), newton=int(newton[-1]), krylov=int(krylov[-1])))
+        if kind == "multigrid":
+            setups.append(d.mg_info()["setup_ms"])
+    tm = d.timers()
+    out = dict(steps=steps, krylov_total=int(sum(s["krylov"] for s in steps)), pcg_not_converged=d.diagnostics()["pcg_not_converged"],
+               worst_residual_reduction_reached=worst, pcg_ms_per_iter=tm["krylov_ms"] / max(tm["krylov_iters"], 1),
+               wall_ms_total=round(sum(s["wall_ms"] for s in steps), 2))
+    if kind == "multigrid":
+        info = d.mg_info()
+        out.update(levels=info["levels"], setup_ms_per_newton_iter=float(np.mean(setups)), vcycle_ms=info["vcycle_ms"],
+                   lmax=[float(v) for v in info["lmax"]])
+    d.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, nargs="+", default=[64, 128])
+    a = ap.parse_args()
+    import exaconstit_amd.lib as L
+    import hipref
+    props = np.loadtxt(os.path.join(ROOT, "tests", "golden", "refdata", "props_cp_voce.txt")).ravel()
+    dts = np.array([0.1, 0.2, 0.3])
+    res = dict(schedule=dict(dts=dts.tolist(), vz=1e-3, newton_rel=5e-5, krylov_rel=1e-7, krylov_iter=1000), cases={})
+    for N in a.n:
+        quats = hipref.random_quats(N ** 3, seed=16)
+        res["cases"][str(N)] = {k: run(L, N, k, dts, props, quats) for k in ("identity", "multigrid")}
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()
