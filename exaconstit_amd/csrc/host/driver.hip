@@ -119,7 +119,7 @@ void Comm::loopback_destroy(const void* id128) {
 // of this kind instead of a RCCL id.  Control data lives in a POSIX shared-memory segment named after the id; the halo segments travel
 // device-to-device through hipIpcMemHandle mappings of the neighbours' send buffers; reductions go through the segment in rank order.
 // Exchanges are host-synchronous (stream sync + barrier), so this is NOT a performance path.
-constexpr int IPC_MAX_RANKS = 64, IPC_MAX_NBR = 32, IPC_MAX_RED = 32;
+constexpr int IPC_MAX_RANKS = 64, IPC_MAX_NBR = 32, IPC_MAX_RED = 32;   // reductions longer than IPC_MAX_RED doubles pass through the slots in pieces
 struct IpcShared {
    std::atomic<uint32_t> ready; uint32_t n;
    std::atomic<uint64_t> arrived, generation;
@@ -236,16 +236,19 @@ Comm::~Comm() {
 void Comm::loopback_reduce(double* dev, int n, int op, hipStream_t s) {
    if (ipc_) {
       IpcGroup* g = (IpcGroup*)ipc_;
-      if (n > IPC_MAX_RED) throw std::runtime_error("ipc transport: reduction too long");
-      double mine[IPC_MAX_RED];
-      EXA_HC(hipMemcpyAsync(mine, dev, sizeof(double) * n, hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
-      for (int i = 0; i < n; i++) g->sh->red[rank][i] = mine[i];
-      g->barrier();
-      double r[IPC_MAX_RED];
-      for (int i = 0; i < n; i++) r[i] = g->sh->red[0][i];
-      for (int k = 1; k < g->n; k++) for (int i = 0; i < n; i++) { const double v = g->sh->red[k][i]; r[i] = op == 0 ? r[i] + v : (op == 1 ? std::min(r[i], v) : std::max(r[i], v)); }
-      g->barrier();   // everybody has read before the next reduction overwrites
-      EXA_HC(hipMemcpyAsync(dev, r, sizeof(double) * n, hipMemcpyHostToDevice, s)); EXA_HC(hipStreamSynchronize(s));
+      std::vector<double> v((size_t)n);
+      EXA_HC(hipMemcpyAsync(v.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
+      for (int i0 = 0; i0 < n; i0 += IPC_MAX_RED) {   // piece by piece through the rank slots, every rank in the same order
+         const int m = std::min(IPC_MAX_RED, n - i0);
+         for (int i = 0; i < m; i++) g->sh->red[rank][i] = v[i0 + i];
+         g->barrier();
+         double r[IPC_MAX_RED];
+         for (int i = 0; i < m; i++) r[i] = g->sh->red[0][i];
+         for (int k = 1; k < g->n; k++) for (int i = 0; i < m; i++) { const double x = g->sh->red[k][i]; r[i] = op == 0 ? r[i] + x : (op == 1 ? std::min(r[i], x) : std::max(r[i], x)); }
+         g->barrier();   // everybody has read before the next piece overwrites
+         for (int i = 0; i < m; i++) v[i0 + i] = r[i];
+      }
+      EXA_HC(hipMemcpyAsync(dev, v.data(), sizeof(double) * n, hipMemcpyHostToDevice, s)); EXA_HC(hipStreamSynchronize(s));
       return;
    }
    LoopbackGroup* g = (LoopbackGroup*)loop_;
@@ -264,6 +267,11 @@ void Comm::allreduce_sum(double* dev, int n, hipStream_t s) {
 void Comm::allreduce_min(double* dev, int n, hipStream_t s) {
    if (loop_ || ipc_) { if (nranks > 1) loopback_reduce(dev, n, 1, s); return; }
    if (nranks > 1 || force_) nccl_check(rccl().AllReduce(dev, dev, n, ncclDouble, ncclMin, (ncclComm_t)comm_, s), "ncclAllReduce");
+}
+
+void Comm::allreduce_max(double* dev, int n, hipStream_t s) {
+   if (loop_ || ipc_) { if (nranks > 1) loopback_reduce(dev, n, 2, s); return; }
+   if (nranks > 1 || force_) nccl_check(rccl().AllReduce(dev, dev, n, ncclDouble, ncclMax, (ncclComm_t)comm_, s), "ncclAllReduce");
 }
 
 double Comm::max_over_ranks(double v) {
@@ -832,10 +840,11 @@ void NonlinearMechOperator::SwapCoords() { x_beg.copy_from(x_cur, stream_); }
 // =====================================================================================================================
 // SystemDriver
 // =====================================================================================================================
-static void load_case_data(const ExaOptions& opt, const Partition& part, std::vector<double>& props, std::vector<double>& quats_local, std::vector<int32_t>& attr) {
+static void load_case_data(const ExaOptions& opt, const Partition& part, std::vector<double>& props, std::vector<double>& quats_local, std::vector<int32_t>& attr,
+                           std::vector<double>& ori) {
    props = ExaOptions::load_numbers(opt.resolve(opt.props_file));
    if ((int)props.size() != opt.nprops) throw std::runtime_error("Properties file does not hold num_props values");
-   std::vector<double> ori = ExaOptions::load_numbers(opt.resolve(opt.ori_file));
+   ori = ExaOptions::load_numbers(opt.resolve(opt.ori_file));
    quats_local.resize((size_t)4 * part.E); attr.resize((size_t)part.E);
    if (part.from_file) {   // grain id = element attribute (reference src/mechanics_driver.cpp:1117-1125)
       for (int e = 0; e < part.E; e++) {
@@ -864,6 +873,13 @@ static void load_case_data(const ExaOptions& opt, const Partition& part, std::ve
 
 SystemDriver::~SystemDriver() { drop_cg_graph(); }
 
+static void normalise_quats(std::vector<double>& q) {
+   for (size_t i = 0; i + 3 < q.size(); i += 4) {
+      const double n = std::sqrt(q[i] * q[i] + q[i + 1] * q[i + 1] + q[i + 2] * q[i + 2] + q[i + 3] * q[i + 3]);
+      if (n > 0.0 && std::isfinite(n)) for (int k = 0; k < 4; k++) q[i + k] /= n;
+   }
+}
+
 // EXA_HALO_SELFTEST (Comm::init): the one rank lists itself as neighbour with the dofs of the nodes on its x-max face - (N + 1)^2 nodes x 3 components, the
 // size of a face exchange of a block decomposition - so that every halo_sum / halo_begin of a solve runs a real grouped send / receive (of zeros) over RCCL
 static void add_selftest_neighbour(Partition& part, const Comm& comm) {
@@ -882,7 +898,9 @@ SystemDriver::SystemDriver(const ExaOptions& opt, int rank, int nranks, const vo
    } else part.build_from_mfem_mesh(opt.resolve(opt.mesh_file), rank, nranks, opt.order);
    add_selftest_neighbour(part, comm);
    if (opt.order == 1) part.order_boundary_first();   // several ranks: elements at shared nodes first (exchange overlapped with the interior, GradMult)
-   std::vector<double> props, quats; load_case_data(opt, part, props, quats, elem_attr);
+   std::vector<double> props, quats; load_case_data(opt, part, props, quats, elem_attr, grain_qref_);
+   grain_qref_.resize(grain_qref_.size() / 4 * 4);
+   normalise_quats(grain_qref_);   // grain g: row g - 1 of the orientation file
    init(props, quats);
 }
 
@@ -894,8 +912,11 @@ SystemDriver::SystemDriver(const ExaOptions& opt, const std::vector<double>& pro
    if (opt.order == 1) part.order_boundary_first();
    std::vector<double> quats((size_t)4 * part.E);
    for (int e = 0; e < part.E; e++) for (int q = 0; q < 4; q++) quats[4 * (size_t)e + q] = quats_global[4 * (size_t)part.elem_gid[e] + q];
-   elem_attr.resize((size_t)part.E);   // one grain per element
+   elem_attr.resize((size_t)part.E);   // one grain per element (SetGrains: a grain map)
    for (int e = 0; e < part.E; e++) elem_attr[e] = (int32_t)(part.elem_gid[e] + 1);
+   synthetic_ = true;
+   grain_qref_.assign(quats_global.begin(), quats_global.begin() + 4 * part.E_global());
+   normalise_quats(grain_qref_);
    init(props, quats);
 }
 
@@ -1349,16 +1370,26 @@ bool SystemDriver::Step(int ti, bool commit) {
    if (!commit) return true;   // the converged state stays the END-of-step state: the next constitutive pass repeats this step's last residual evaluation
    CommitStep();
    // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
-   bool save = false;
-   if (opt_.paraview && write_files) {
+   // per-grain averages on the same cadence, whether or not ParaView output is on
+   bool due = false;
+   if ((opt_.paraview || opt_.grain_avgs) && write_files) {
       bool last = ti >= opt_.nsteps;
       if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
-      save = last || ti % opt_.vis_steps == 0;
+      due = last || ti % opt_.vis_steps == 0;
    }
+   const bool save = opt_.paraview && due, grains = opt_.grain_avgs && due;
    // light-up analysis: one row of lattice strains and one of fibre volume fractions per converged step, from the same element rows
    const bool lattice = opt_.lightup() && write_files;
-   if (save || lattice) ComputeElementFields();
+   if (save || lattice || grains) ComputeElementFields();
    if (save) SaveFields(vis_dir(), ti, time, true);
+   if (grains) {
+      std::vector<int32_t> ids; std::vector<double> vals;
+      GrainAverages(ids, vals, true);
+      if (comm.rank == 0) {
+         char tag[16]; std::snprintf(tag, sizeof(tag), "_%06d.txt", ti);
+         write_grain_avgs(out_dir + "/" + opt_.grain_avgs_fname + tag, (int)ids.size(), ids.data(), vals.data());
+      }
+   }
    if (lattice) {
       const int H = (int)opt_.lightup_hkl.size() / 3;
       std::vector<double> strain(H), vf(H);
@@ -1433,6 +1464,131 @@ void SystemDriver::LatticeStrains(const std::vector<int>& hkl, const double s_di
       strain[j] = v > 0.0 ? h[2 * j] / v : std::numeric_limits<double>::quiet_NaN();   // empty fibre: no lattice strain (written as nan)
       volfrac[j] = v / h[2 * H];
    }
+}
+
+// angle (degrees) of the rotation between unit quaternions a and b: d = conj(a) (x) b, 2 atan2(|d_vec|, |d_0|) (accurate near 0, unlike 2 acos |a . b|)
+static double misorientation_deg(const double* a, const double* b) {
+   const double d0 = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
+   const double d1 = a[0] * b[1] - b[0] * a[1] - (a[2] * b[3] - a[3] * b[2]);
+   const double d2 = a[0] * b[2] - b[0] * a[2] - (a[3] * b[1] - a[1] * b[3]);
+   const double d3 = a[0] * b[3] - b[0] * a[3] - (a[1] * b[2] - a[2] * b[1]);
+   return 2.0 * std::atan2(std::sqrt(d1 * d1 + d2 * d2 + d3 * d3), std::fabs(d0)) * (180.0 / M_PI);
+}
+
+void SystemDriver::EnsureGrainPlan() {
+   if (!grain_plan_.empty()) return;
+   int gmax = 0;
+   for (int32_t a : elem_attr) gmax = std::max(gmax, (int)a);
+   const int G = (int)comm.max_over_ranks((double)gmax);
+   if (G < 1) throw std::runtime_error("grain averages: the mesh has no elements");
+   if ((int64_t)4 * G > (int64_t)grain_qref_.size()) throw std::runtime_error("grain averages: grain " + std::to_string(G) + " has no reference orientation");
+   if ((int64_t)G * EXA_GRAIN_NSUMS > (int64_t)INT32_MAX) throw std::runtime_error("grain averages: too many grains");
+   int64_t len = 0, work = 0;
+   if (exa_grain_plan(part.E, elem_attr.data(), nullptr, 0, &len, &work) != 0) throw std::runtime_error("grain averages: grain ids must be at least 1");
+   std::vector<int32_t> plan((size_t)len);
+   if (exa_grain_plan(part.E, elem_attr.data(), plan.data(), len, &len, &work) != 0) throw std::runtime_error("exa_grain_plan failed");
+   hipStream_t s = oper_->stream();
+   grain_plan_dev_.alloc((size_t)len); grain_plan_dev_.upload(plan.data(), (size_t)len, s);
+   grain_work_.alloc((size_t)std::max<int64_t>(work, 1));
+   grain_sums_.alloc((size_t)G * EXA_GRAIN_NSUMS);
+   grain_quat_dev_.alloc((size_t)4 * G);
+   grain_G_ = G;
+   grain_plan_ = std::move(plan);
+}
+
+void SystemDriver::GrainAverages(std::vector<int32_t>& ids, std::vector<double>& vals, bool fields_current) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   exa_ctx* ctx = op.GetModel()->ctx();
+   EnsureGrainPlan();
+   const int G = grain_G_; constexpr int K = EXA_GRAIN_NSUMS;
+   if (!fields_current) ComputeElementFields();
+   // pass 1: the 39 sums of every grain; elements are not shared across ranks, grains are
+   grain_quat_dev_.upload(grain_qref_.data(), (size_t)4 * G, s);
+   grain_sums_.zero(s);
+   abi_check(ctx, exa_grain_sums(ctx, 1, fields_dev_.p, grain_plan_.data(), grain_plan_dev_.p, G, grain_quat_dev_.p, grain_work_.p, grain_sums_.p, s), "exa_grain_sums");
+   comm.allreduce_sum(grain_sums_.p, G * K, s);
+   std::vector<double> h((size_t)G * K); grain_sums_.download(h.data(), h.size(), s);
+   // the grain means, identical on every rank
+   std::vector<double> qbar(grain_qref_.begin(), grain_qref_.begin() + 4 * (size_t)G);
+   double vtot = 0.0;
+   for (int g = 0; g < G; g++) {
+      const double* r = &h[(size_t)g * K];
+      if (!(r[1] > 0.0)) continue;
+      vtot += r[0];
+      const double n = std::sqrt(r[35] * r[35] + r[36] * r[36] + r[37] * r[37] + r[38] * r[38]);
+      if (n > 0.0) for (int k = 0; k < 4; k++) qbar[4 * (size_t)g + k] = r[35 + k] / n;
+   }
+   // pass 2: sum V theta and max theta about the means
+   grain_quat_dev_.upload(qbar.data(), (size_t)4 * G, s);
+   EXA_HC(hipMemsetAsync(grain_sums_.p, 0, sizeof(double) * 2 * G, s));
+   abi_check(ctx, exa_grain_sums(ctx, 2, fields_dev_.p, grain_plan_.data(), grain_plan_dev_.p, G, grain_quat_dev_.p, grain_work_.p, grain_sums_.p, s), "exa_grain_sums");
+   comm.allreduce_sum(grain_sums_.p, G, s);
+   comm.allreduce_max(grain_sums_.p + G, G, s);
+   std::vector<double> h2((size_t)2 * G); grain_sums_.download(h2.data(), h2.size(), s);
+   ids.clear(); vals.clear();
+   for (int g = 0; g < G; g++) {
+      const double* r = &h[(size_t)g * K];
+      if (!(r[1] > 0.0)) continue;
+      const double V = r[0], iv = 1.0 / V;
+      double o[GRAIN_NVALS];
+      o[0] = r[1]; o[1] = V; o[2] = V / vtot;
+      for (int k = 0; k < 6; k++) o[3 + k] = r[2 + k] * iv;
+      const double* t = o + 3;
+      const double d01 = t[0] - t[1], d12 = t[1] - t[2], d20 = t[2] - t[0];   // EXA_F_VONMISES, EXA_F_HYDROSTATIC of the mean stress
+      o[9] = std::sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20 + 6.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5])));
+      o[10] = (t[0] + t[1] + t[2]) * (1.0 / 3.0);
+      for (int k = 0; k < 12; k++) o[11 + k] = r[8 + k] * iv;    // elastic strain in the sample and the crystal frame
+      for (int k = 0; k < 15; k++) o[23 + k] = r[20 + k] * iv;   // EffPlasticStrain, DpEff, Hardness, ShearRate (12)
+      for (int k = 0; k < 4; k++) o[38 + k] = qbar[4 * (size_t)g + k];
+      o[42] = h2[g] * iv; o[43] = h2[(size_t)G + g];
+      o[44] = misorientation_deg(&qbar[4 * (size_t)g], &grain_qref_[4 * (size_t)g]);
+      ids.push_back(g + 1);
+      vals.insert(vals.end(), o, o + GRAIN_NVALS);
+   }
+}
+
+void SystemDriver::SetGrains(const int32_t* grain, int64_t n_global, const double* grain_quats, int G) {
+   if (!synthetic_) throw std::runtime_error("set_grains: only a synthetic driver takes a grain map (a file-driven one has its grains from the options)");
+   if (steps_done > 0 || !stats.empty()) throw std::runtime_error("set_grains: the grain map can only be set before the first step");
+   if (n_global != part.E_global()) throw std::runtime_error("set_grains: one grain id per global element is required");
+   if (G < 1 || !grain || !grain_quats) throw std::runtime_error("set_grains: at least one grain, its orientation and a grain id per element are required");
+   for (int64_t e = 0; e < n_global; e++) if (grain[e] < 1 || grain[e] > G) throw std::runtime_error("set_grains: grain ids must lie in 1 .. G");
+   std::vector<double> q(grain_quats, grain_quats + 4 * (size_t)G);
+   for (double x : q) if (!std::isfinite(x)) throw std::runtime_error("set_grains: orientations must be finite");
+   for (int g = 0; g < G; g++) if (q[4 * g] == 0.0 && q[4 * g + 1] == 0.0 && q[4 * g + 2] == 0.0 && q[4 * g + 3] == 0.0) throw std::runtime_error("set_grains: an orientation is zero");
+   normalise_quats(q);
+   std::vector<double> ql((size_t)4 * part.E);
+   for (int e = 0; e < part.E; e++) {
+      const int32_t g = grain[part.elem_gid[e]];
+      elem_attr[e] = g;
+      for (int k = 0; k < 4; k++) ql[4 * (size_t)e + k] = q[4 * (size_t)(g - 1) + k];
+   }
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   exa_ctx* ctx = op.GetModel()->ctx();
+   { DevBuf<double> d; d.upload(ql, s); abi_check(ctx, exa_init_state(ctx, op.matVars0.p, d.p, s), "exa_init_state"); EXA_HC(hipStreamSynchronize(s)); }
+   grain_qref_ = std::move(q);
+   grain_plan_.clear(); grain_G_ = 0;
+}
+
+void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const double* vals) {
+   std::ofstream f(path);
+   if (!f) throw std::runtime_error("grain averages: cannot write " + path);
+   f << "# grain_id n_elements volume volume_fraction stress_11 stress_22 stress_33 stress_23 stress_13 stress_12 von_mises hydrostatic"
+        " elastic_strain_sample_11 elastic_strain_sample_22 elastic_strain_sample_33 elastic_strain_sample_23 elastic_strain_sample_13 elastic_strain_sample_12"
+        " elastic_strain_xtal_11 elastic_strain_xtal_22 elastic_strain_xtal_33 elastic_strain_xtal_23 elastic_strain_xtal_13 elastic_strain_xtal_12"
+        " eff_plastic_strain dp_eff hardness";
+   for (int k = 1; k <= 12; k++) f << " shear_rate_" << k;
+   f << " quat_0 quat_1 quat_2 quat_3 misori_mean_deg misori_max_deg rotation_deg\n";
+   f << std::setprecision(17);
+   for (int i = 0; i < n; i++) {
+      const double* v = vals + (size_t)i * GRAIN_NVALS;
+      f << ids[i] << ' ' << (int64_t)v[0];
+      for (int k = 1; k < GRAIN_NVALS; k++) f << ' ' << v[k];
+      f << '\n';
+   }
+   if (!f) throw std::runtime_error("grain averages: writing " + path + " failed");
 }
 
 void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool fields_current) {

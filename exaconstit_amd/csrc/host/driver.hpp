@@ -38,6 +38,7 @@ class Comm {
    static void loopback_destroy(const void* id128);
    void allreduce_sum(double* dev, int n, hipStream_t s);
    void allreduce_min(double* dev, int n, hipStream_t s);
+   void allreduce_max(double* dev, int n, hipStream_t s);
    // y(shared dofs) <- sum over all ranks holding them
    void halo_sum(const Partition& part, double* y, hipStream_t s);
    // the same in two halves for overlap with work on stream s: begin = pack + exchange on the communication stream once everything
@@ -63,6 +64,11 @@ class Comm {
    hipStream_t cs_ = nullptr; hipEvent_t ev_ready_ = nullptr, ev_done_ = nullptr;   // communication stream of halo_begin / halo_end
    void exchange(const Partition& part, hipStream_t s);   // send buffers -> neighbours' receive buffers (RCCL grouped send/recv or loopback copies) on stream s
 };
+
+// per-grain averages: value columns per grain (after the grain id) of SystemDriver::GrainAverages and the grain_avgs files
+constexpr int GRAIN_NVALS = 45;
+// one grain_avgs file: a '#' header naming the 46 columns, then one row per grain (id, element count, 43 values with 17 significant digits)
+void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const double* vals);
 
 enum class Precond { IDENTITY, JACOBI, MULTIGRID };
 class Multigrid;
@@ -217,6 +223,12 @@ class SystemDriver {
    // lattice strains of the {hkl} families (3 integers each; options.hpp check_lightup) of the same state, summed over all ranks (every rank calls
    // it): strain[j] = volume-weighted mean of s^T eps s over the elements of fibre j (NaN when the fibre is empty), volfrac[j] = its volume fraction
    void LatticeStrains(const std::vector<int>& hkl, const double s_dir[3], double tol_deg, double* strain, double* volfrac, bool fields_current = false);
+   // per-grain averages of the same state over all ranks (every rank calls it): ids = the ascending 1-based ids of the grains with
+   // elements, vals = GRAIN_NVALS values per grain (the value columns of the grain_avgs files, write_grain_avgs)
+   void GrainAverages(std::vector<int32_t>& ids, std::vector<double>& vals, bool fields_current = false);
+   // grain map of a synthetic driver before its first step: grain (1..G) of every global element and the orientation of every grain (normalised
+   // here); the elements' initial orientations and states become their grain's
+   void SetGrains(const int32_t* grain_of_global_elem, int64_t n_global, const double* grain_quats, int G);
    std::string vis_dir() const { return (opt_.vis_floc.empty() || opt_.vis_floc[0] == '/') ? opt_.vis_floc : out_dir + "/" + opt_.vis_floc; }
    std::vector<int32_t> elem_attr;             // grain id (element attribute) of every local element
    Precond precond = Precond::IDENTITY;
@@ -238,6 +250,11 @@ class SystemDriver {
    double last_dt_ = 0.0;
    bool cycle0_saved_ = false;
    DevBuf<double> fields_dev_, lattice_sums_;   // [E][EXA_NFIELDS] element rows; 2 H + 1 lattice-strain sums
+   bool synthetic_ = false;
+   std::vector<double> grain_qref_;             // unit reference orientation of every grain: [grain id - 1][4]
+   // plan of exa_grain_sums for elem_attr (built on first use, dropped by SetGrains), its device copy and workspace; G = largest grain id over all ranks
+   std::vector<int32_t> grain_plan_; DevBuf<int32_t> grain_plan_dev_; DevBuf<double> grain_work_, grain_sums_, grain_quat_dev_; int grain_G_ = 0;
+   void EnsureGrainPlan();
    std::map<std::string, std::vector<std::pair<int, double>>> pvd_cycles_;   // saved cycles of each output directory (rank 0 writes the .pvd)
    void* cg_graph_ = nullptr; const double* cg_graph_x_ = nullptr; int64_t cg_graph_key_ = -1;   // captured PCG chunk (hipGraphExec_t) and what it was captured for
 };

@@ -641,6 +641,46 @@ int exa_driver_lattice_strains(exa_driver* d, int nhkl, const int* hkl3, const d
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+int exa_driver_grain_averages(exa_driver* d, int32_t* grain_ids, double* vals, int64_t cap, char* err, int errlen) {
+   try {
+      std::vector<int32_t> ids; std::vector<double> v;
+      d->sd->GrainAverages(ids, v);
+      const int64_t n = (int64_t)ids.size();
+      if (n <= cap) {
+         if (grain_ids) std::memcpy(grain_ids, ids.data(), sizeof(int32_t) * n);
+         if (vals) std::memcpy(vals, v.data(), sizeof(double) * v.size());
+      }
+      return (int)n;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_driver_set_grains(exa_driver* d, const int32_t* grain_of_global_element, const double* grain_quats, int G, int64_t n_global, char* err, int errlen) {
+   try {
+      d->sd->SetGrains(grain_of_global_element, n_global, grain_quats, G);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_options_query_grains(const char* toml_path, int* enabled, char* fname, int fnamelen, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      if (enabled) *enabled = o.grain_avgs ? 1 : 0;
+      if (fname && fnamelen > 0) {
+         if ((int)o.grain_avgs_fname.size() >= fnamelen) throw std::runtime_error("Visualizations.grain_avgs_fname longer than the buffer");
+         std::strcpy(fname, o.grain_avgs_fname.c_str());
+      }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_grain_avgs_write(const char* path, int n, const int32_t* grain_ids, const double* vals, char* err, int errlen) {
+   try {
+      if (!path || n < 0 || (n > 0 && (!grain_ids || !vals))) throw std::runtime_error("exa_grain_avgs_write: a path and n rows are required");
+      write_grain_avgs(path, n, grain_ids, vals);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
 int exa_options_query_lightup(const char* toml_path, int* enabled, int* nhkl, int* hkl48, double* s_dir3, double* tol_deg, char* strain_fname,
                               char* volume_fname, int fnamelen, char* err, int errlen) {
    try {

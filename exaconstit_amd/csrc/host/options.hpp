@@ -118,6 +118,8 @@ struct ExaOptions {
       for (int i = 0; i < 3; i++) s[i] /= n;
       if (!(tol_deg > 0.0 && tol_deg <= 90.0)) throw std::runtime_error("Visualizations.light_up_dist_tol_deg must lie in (0, 90]");
    }
+   // per-grain averages written every Visualizations.steps steps (driver.hip, SystemDriver::GrainAverages): <out_dir>/<grain_avgs_fname>_<step %06d>.txt
+   bool grain_avgs = false; std::string grain_avgs_fname = "grain_avgs";
    Assembly assembly = Assembly::EA; NLSolver nl_solver = NLSolver::NR; std::string integ_model = "FULL";
    int newton_iter = 25; double newton_rel = 1e-5, newton_abs = 1e-10;
    int krylov_iter = 200; double krylov_rel = 1e-10, krylov_abs = 1e-30; std::string krylov_solver = "PCG";
@@ -226,6 +228,15 @@ struct ExaOptions {
       lightup_strain_fname = d.str("Visualizations.light_up_strain_fname", "lattice_strains.txt");
       lightup_volume_fname = d.str("Visualizations.light_up_volume_fname", "lattice_volumes.txt");
       check_lightup(lightup_hkl, lightup_s_dir, lightup_tol_deg);
+      if (const TomlValue* g = d.get("Visualizations.grain_avgs")) {
+         if (g->kind != TomlValue::BOOL) throw std::runtime_error("Visualizations.grain_avgs must be true or false");
+         grain_avgs = g->b;
+      }
+      if (const TomlValue* g = d.get("Visualizations.grain_avgs_fname")) {
+         if (g->kind != TomlValue::STR || g->str.empty() || g->str.find('/') != std::string::npos)
+            throw std::runtime_error("Visualizations.grain_avgs_fname must be a non-empty file name without '/'");
+         grain_avgs_fname = g->str;
+      }
       avg_def_grad_fname = d.str("Visualizations.avg_def_grad_fname", "avg_def_grad.txt");
       avg_pl_work_fname = d.str("Visualizations.avg_pl_work_fname", "avg_pl_work.txt");
       avg_dp_tensor_fname = d.str("Visualizations.avg_dp_tensor_fname", "avg_dp_tensor.txt");

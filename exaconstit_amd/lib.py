@@ -101,6 +101,9 @@ exa_lattice_strains = _sig("exa_lattice_strains", C.c_int, C.c_void_p, dptr, C.c
                            C.c_double, dptr, C.c_void_p)
 exa_cubic_fiber_axes = _sig("exa_cubic_fiber_axes", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int)
 EXA_LATTICE_MAX_HKL = 16
+exa_grain_sums = _sig("exa_grain_sums", C.c_int, C.c_void_p, C.c_int, dptr, C.POINTER(C.c_int32), C.c_void_p, C.c_int, dptr, dptr, dptr, C.c_void_p)
+exa_grain_plan = _sig("exa_grain_plan", C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+EXA_GRAIN_NSUMS = 39
 # columns of the exa_element_fields rows (include/exaconstit_hip.h)
 EXA_NFIELDS = 37
 ELEMENT_FIELDS = {"ElementVolume": (0, 1), "ElemCentroid": (1, 3), "Stress": (4, 6), "VonMisesStress": (10, 1), "HydrostaticStress": (11, 1),
@@ -212,6 +215,44 @@ exa_driver_lattice_strains = _sig("exa_driver_lattice_strains", C.c_int, C.c_voi
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_int)
 exa_options_query_lightup = _sig("exa_options_query_lightup", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
+exa_driver_grain_averages = _sig("exa_driver_grain_averages", C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, C.c_char_p, C.c_int)
+exa_driver_set_grains = _sig("exa_driver_set_grains", C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_char_p, C.c_int)
+exa_options_query_grains = _sig("exa_options_query_grains", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.c_char_p, C.c_int)
+exa_grain_avgs_write = _sig("exa_grain_avgs_write", C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, C.c_int)
+EXA_GRAIN_NVALS = 45
+# value columns of exa_driver_grain_averages and of the grain_avgs files after the grain id (include/exaconstit_driver.h): name -> (first, count)
+GRAIN_COLUMNS = {"n_elements": (0, 1), "volume": (1, 1), "volume_fraction": (2, 1), "Stress": (3, 6), "VonMisesStress": (9, 1), "HydrostaticStress": (10, 1),
+                 "ElasticStrainSample": (11, 6), "XtalElasticStrain": (17, 6), "EffPlasticStrain": (23, 1), "DpEff": (24, 1), "Hardness": (25, 1),
+                 "ShearRate": (26, 12), "LatticeOrientation": (38, 4), "MisorientationMean": (42, 1), "MisorientationMax": (43, 1), "GrainRotation": (44, 1)}
+
+
+def grain_dict(ids, vals):
+    """{"grain_id": (n,), column name: (n,) or (n, count)} from grain ids and (n, EXA_GRAIN_NVALS) values"""
+    import numpy as np
+    out = {"grain_id": np.asarray(ids, dtype=np.int64)}
+    for k, (c0, n) in GRAIN_COLUMNS.items():
+        out[k] = vals[:, c0] if n == 1 else vals[:, c0:c0 + n].copy()
+    out["n_elements"] = np.rint(out["n_elements"]).astype(np.int64)
+    return out
+
+
+def write_grain_avgs(path, ids, vals):
+    """the driver's grain_avgs file writer (host only): header line, then one row per grain"""
+    import numpy as np
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    vals = np.ascontiguousarray(vals, dtype=np.float64).reshape(len(ids), EXA_GRAIN_NVALS)
+    err = C.create_string_buffer(512)
+    if exa_grain_avgs_write(str(path).encode(), len(ids), ids.ctypes.data_as(C.POINTER(C.c_int32)), vals.ctypes.data_as(C.POINTER(C.c_double)), err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+
+
+def read_grain_avgs(path):
+    """a grain_avgs file as the dict of Driver.grain_averages()"""
+    import numpy as np
+    a = np.loadtxt(path, ndmin=2).reshape(-1, 1 + EXA_GRAIN_NVALS)
+    return grain_dict(np.rint(a[:, 0]).astype(np.int64), a[:, 1:])
+
+
 exa_driver_write_fields = _sig("exa_driver_write_fields", C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_char_p, C.c_int)
 _dp = C.POINTER(C.c_double)
 exa_driver_set_preconditioner = _sig("exa_driver_set_preconditioner", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int)
@@ -262,6 +303,16 @@ def cubic_fiber_axes(h, k, l):
     if n < 0:
         raise ValueError("(0, 0, 0) is not a plane family")
     return out[:n].copy()
+
+
+def options_grains(path):
+    """per-grain averages keys of the Visualizations table: dict(enabled, fname)"""
+    en = C.c_int()
+    f = C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_query_grains(path.encode(), C.byref(en), f, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(enabled=bool(en.value), fname=f.value.decode())
 
 
 def options_lightup(path):
@@ -423,6 +474,32 @@ class Driver:
         self._chk(exa_driver_lattice_strains(self.h, H, h.ctypes.data_as(C.POINTER(C.c_int)), sd.ctypes.data_as(C.POINTER(C.c_double)), float(tol_deg),
                                              strain.ctypes.data_as(C.POINTER(C.c_double)), vf.ctypes.data_as(C.POINTER(C.c_double)), self._err, 512))
         return {"strain": strain, "volume_fraction": vf}
+
+    def grain_averages(self):
+        """Per-grain averages of the current begin-of-step state (after a completed step: the converged one), over all ranks of the
+        group (every rank calls it): {"grain_id": (n,), "n_elements", "volume", "volume_fraction", "Stress": (n, 6), "VonMisesStress",
+        "HydrostaticStress", "ElasticStrainSample": (n, 6), "XtalElasticStrain": (n, 6), "EffPlasticStrain", "DpEff", "Hardness",
+        "ShearRate": (n, 12), "LatticeOrientation": (n, 4), "MisorientationMean", "MisorientationMax", "GrainRotation"} (angles in degrees),
+        one row per grain with elements, ascending id."""
+        import numpy as np
+        cap = getattr(self, "_grain_cap", 4096)       # the row count of the last call: one call in the common case
+        while True:
+            ids = np.zeros(cap, np.int32)
+            vals = np.zeros((cap, EXA_GRAIN_NVALS))
+            n = self._chk(exa_driver_grain_averages(self.h, ids.ctypes.data_as(C.POINTER(C.c_int32)), vals.ctypes.data_as(C.POINTER(C.c_double)), cap,
+                                                    self._err, 512))
+            if n <= cap:
+                return grain_dict(ids[:n], vals[:n])
+            cap = self._grain_cap = n
+
+    def set_grains(self, grain_ids, quats):
+        """Grain map of a synthetic driver before its first step: grain_ids (N^3,) in 1..G by global element index (x fastest), quats (G, 4);
+        the elements start from their grain's orientation, which is the grain's reference orientation."""
+        import numpy as np
+        g = np.ascontiguousarray(np.asarray(grain_ids).reshape(-1), dtype=np.int32)
+        q = np.ascontiguousarray(np.asarray(quats, dtype=np.float64).reshape(-1, 4))
+        self._chk(exa_driver_set_grains(self.h, g.ctypes.data_as(C.POINTER(C.c_int32)), q.ctypes.data_as(C.POINTER(C.c_double)), q.shape[0], g.size,
+                                        self._err, 512))
 
     def write_fields(self, directory, cycle, t):
         """ParaView save of the per-element fields as cycle `cycle` at time t under directory (every rank of a group calls it)."""

@@ -135,6 +135,17 @@ int exa_driver_write_fields(exa_driver* d, const char* dir, int cycle, double t,
  * empty fibre), volfrac_out[j] = their volume fraction (exa_lattice_strains, include/exaconstit_hip.h).  Returns 0 or -1 (err). */
 int exa_driver_lattice_strains(exa_driver* d, int nhkl, const int* hkl3, const double* s_dir3, double tol_deg, double* strain_out, double* volfrac_out,
                                char* err, int errlen);
+/* Per-grain averages of the current begin-of-step state (after a completed step: the converged one), over all ranks (every rank
+ * of the group calls it).  Grains are the element attributes (1-based); only grains with elements are reported, in ascending id.  Writes, when
+ * the row count n <= cap, grain_ids[n] and vals[n][EXA_GRAIN_NVALS]: n_elements, volume, volume_fraction, Stress (6), VonMisesStress,
+ * HydrostaticStress, ElasticStrainSample (6), XtalElasticStrain (6), EffPlasticStrain, DpEff, Hardness, ShearRate (12), LatticeOrientation (4),
+ * MisorientationMean, MisorientationMax, GrainRotation (degrees).  Either pointer may be NULL.  Returns n or -1 (err). */
+enum { EXA_GRAIN_NVALS = 45 };
+int exa_driver_grain_averages(exa_driver* d, int32_t* grain_ids, double* vals, int64_t cap, char* err, int errlen);
+/* Grain map of a synthetic driver (exa_driver_create_synthetic), before its first step: grain_of_global_element[n_global] in 1..G (n_global =
+ * N^3, global element index x fastest) and grain_quats[G][4] (scalar first, normalised here).  Every element's initial orientation and state
+ * become its grain's, and the grain's orientation is its reference q_ref.  Every rank of the group calls it with the same map.  Returns 0 or -1 (err). */
+int exa_driver_set_grains(exa_driver* d, const int32_t* grain_of_global_element, const double* grain_quats, int G, int64_t n_global, char* err, int errlen);
 int exa_driver_bench_prepare(exa_driver* d, int nsteps, const double* dts, double perturb, char* err, int errlen);
 int exa_driver_bench_model(exa_driver* d, int steps, double* out3, char* err, int errlen);
 int exa_driver_bench_pcg(exa_driver* d, int iters, double* out3, char* err, int errlen);
@@ -161,6 +172,12 @@ int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int*
  * light_up_volume_fname ("lattice_volumes.txt") into buffers of fnamelen bytes.  Every pointer may be NULL.  Returns 0 or -1 (err). */
 int exa_options_query_lightup(const char* toml_path, int* enabled, int* nhkl, int* hkl48, double* s_dir3, double* tol_deg, char* strain_fname,
                               char* volume_fname, int fnamelen, char* err, int errlen);
+/* per-grain averages keys of the Visualizations table: enabled = grain_avgs (default 0), grain_avgs_fname ("grain_avgs") into a buffer of
+ * fnamelen bytes.  Either pointer may be NULL.  Returns 0 or -1 (err). */
+int exa_options_query_grains(const char* toml_path, int* enabled, char* fname, int fnamelen, char* err, int errlen);
+/* the grain_avgs file writer (host only): a '#' header naming the 46 columns, then n rows of grain_ids[i] and vals[i][EXA_GRAIN_NVALS] (the
+ * element count as an integer, the rest with 17 significant digits).  Returns 0 or -1 (err). */
+int exa_grain_avgs_write(const char* path, int n, const int32_t* grain_ids, const double* vals, char* err, int errlen);
 /* the ParaView writer on a fixed two-hexahedron piece (host only): fields = 2 rows of EXA_NFIELDS doubles, saved under dir as cycles 0 (t = 0)
  * and 1 (t = 0.5); mesh and point data documented at the definition (host/driver_capi.hip) */
 int exa_vtu_selftest(const char* dir, const double* fields, int light_up, char* err, int errlen);

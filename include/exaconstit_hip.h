@@ -315,6 +315,27 @@ int exa_lattice_strains(exa_ctx* ctx, const double* fields_dev, int nhkl, const 
  * rotations, a direction and its negative counted once (first non-zero component positive).  Writes min(count, max) axes to out [.][3]
  * (out may be NULL) and returns the count (4 for 111, 3 for 200, 6 for 220, 12 for 311, 24 for 123), or -1 for (0, 0, 0). */
 int exa_cubic_fiber_axes(int h, int k, int l, double* out, int max);
+/* Per-grain sums of the rows of exa_element_fields (fields_dev [E][EXA_NFIELDS], device), the reductions behind the grain averages.
+ * plan (int32) describes a grain map of the context's E elements; exa_grain_plan builds it on the host once per map, and the caller keeps the
+ * host copy (plan_host) and a device copy (plan_dev).  Grain ids are 1-based; row g - 1 of the outputs belongs to grain g, 1 <= g <= G.
+ *   pass 1: out_dev [G][EXA_GRAIN_NSUMS] receives, for every grain with local elements, the sums over them of
+ *           V, 1, V sigma (6), V eps_s (6), V eps_x (6), V EffPlasticStrain, V DpEff, V Hardness, V ShearRate (12), V s q (4)
+ *           (V = EXA_F_VOLUME, sigma = EXA_F_STRESS, eps_x = EXA_F_XTALELASTICSTRAIN, eps_s = R(q) eps_x R(q)^T with R = quat_to_mat of
+ *           q = EXA_F_ORIENTATION (crystal -> sample), tensor components in Voigt order 11 22 33 23 13 12; s = +1 if q . q_ref >= 0, else -1),
+ *           quats_dev [G][4] (device) = the reference orientations q_ref.
+ *   pass 2: quats_dev [G][4] = the unit grain means qbar; out_dev is planar [2][G]: out[g - 1] = sum V theta, out[G + g - 1] = max theta, with
+ *           theta = 2 atan2(|d_vec|, |d_0|) in degrees, d = conj(qbar) (x) q.
+ * Rows of grains without local elements are not written: the caller zero-fills out_dev.  work_dev (device) holds work_doubles doubles
+ * (exa_grain_plan).  Grain-sorted 64-element chunks, levels of boundary partials, no atomics: every call on the same data gives the same bits.
+ * Does not synchronise. */
+enum { EXA_GRAIN_NSUMS = 39 };
+int exa_grain_sums(exa_ctx* ctx, int pass, const double* fields_dev, const int32_t* plan_host, const int32_t* plan_dev, int G, const double* quats_dev,
+                   double* work_dev, double* out_dev, exa_stream s);
+/* host only: the plan of exa_grain_sums for E elements with 1-based grain ids grain_of_elem[E] (elements sorted by grain, stable in element
+ * index, cut into 64-element chunks, and the levels of the chunks' boundary partials).  Reports its length in *plan_len and the workspace in
+ * *work_doubles (either may be NULL) and writes it to plan when plan_cap suffices (plan may be NULL: a size query).  Returns 0, or
+ * EXA_ERR_ARG for an id < 1 or a too small plan_cap. */
+int exa_grain_plan(int64_t E, const int32_t* grain_of_elem, int32_t* plan, int64_t plan_cap, int64_t* plan_len, int64_t* work_doubles);
 /* volume average  sum_q W detJ val / sum_q W detJ  (src/mechanics_kernels.hpp:19-134); out_host[vdim] (+ volume in out_host[vdim]).
  * Synchronises the stream. */
 int exa_vol_avg(exa_ctx* ctx, const double* jacobian_dev, const double* qf_dev, int vdim, int normalise, double* out_host, exa_stream s);
