@@ -1344,7 +1344,12 @@ bool SystemDriver::Step(int ti, bool commit) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream(); const int64_t nd = op.Height();
    // ParaView cycle 0: the initial state at t = 0, saved before the first step (reference src/mechanics_driver.cpp:640-700), outside the timed region
-   if (opt_.paraview && write_files && commit && steps_done == 0 && !cycle0_saved_) { SaveFields(vis_dir(), 0, 0.0); cycle0_saved_ = true; }
+   // texture file of step 0 (the initial texture) at the same point; the two share the element rows
+   const bool cycle0 = opt_.paraview && write_files && commit && steps_done == 0 && !cycle0_saved_;
+   const bool texture0 = opt_.texture && write_files && commit && steps_done == 0 && !texture0_written_;
+   if (cycle0 || texture0) ComputeElementFields();
+   if (cycle0) { SaveFields(vis_dir(), 0, 0.0, true); cycle0_saved_ = true; }
+   if (texture0) { WriteTexture(0, time); texture0_written_ = true; }
    double dt_real;
    if (opt_.dt_cust) dt_real = opt_.cust_dt[ti - 1];
    else if (opt_.dt_auto) dt_real = std::min(dt_class, opt_.t_final - time);
@@ -1370,18 +1375,19 @@ bool SystemDriver::Step(int ti, bool commit) {
    if (!commit) return true;   // the converged state stays the END-of-step state: the next constitutive pass repeats this step's last residual evaluation
    CommitStep();
    // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
-   // per-grain averages on the same cadence, whether or not ParaView output is on
+   // per-grain averages and texture on the same cadence, whether or not ParaView output is on
    bool due = false;
-   if ((opt_.paraview || opt_.grain_avgs) && write_files) {
+   if ((opt_.paraview || opt_.grain_avgs || opt_.texture) && write_files) {
       bool last = ti >= opt_.nsteps;
       if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
       due = last || ti % opt_.vis_steps == 0;
    }
-   const bool save = opt_.paraview && due, grains = opt_.grain_avgs && due;
+   const bool save = opt_.paraview && due, grains = opt_.grain_avgs && due, texture = opt_.texture && due;
    // light-up analysis: one row of lattice strains and one of fibre volume fractions per converged step, from the same element rows
    const bool lattice = opt_.lightup() && write_files;
-   if (save || lattice || grains) ComputeElementFields();
+   if (save || lattice || grains || texture) ComputeElementFields();
    if (save) SaveFields(vis_dir(), ti, time, true);
+   if (texture) WriteTexture(ti, time);
    if (grains) {
       std::vector<int32_t> ids; std::vector<double> vals;
       GrainAverages(ids, vals, true);
@@ -1570,6 +1576,89 @@ void SystemDriver::SetGrains(const int32_t* grain, int64_t n_global, const doubl
    { DevBuf<double> d; d.upload(ql, s); abi_check(ctx, exa_init_state(ctx, op.matVars0.p, d.p, s), "exa_init_state"); EXA_HC(hipStreamSynchronize(s)); }
    grain_qref_ = std::move(q);
    grain_plan_.clear(); grain_G_ = 0;
+}
+
+void SystemDriver::PoleFigures(const std::vector<int>& hkl, std::vector<double> dirs, double res_deg, std::vector<double>& mrd, bool fields_current) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   exa_ctx* ctx = op.GetModel()->ctx();
+   ExaOptions::check_texture(hkl, dirs, res_deg, false);
+   const int H = (int)hkl.size() / 3, D = (int)dirs.size() / 3, nset = H + D;
+   int na = 0, nb = 0;
+   exa_texture_grid(res_deg, &na, &nb);
+   std::vector<double> axes; std::vector<int> off(1, 0);
+   for (int j = 0; j < H; j++) {
+      double a[3 * 24];
+      const int n = exa_cubic_fiber_axes(hkl[3 * j], hkl[3 * j + 1], hkl[3 * j + 2], a, 24);
+      if (n < 1 || n > 24) throw std::runtime_error("texture: no pole axes for a family");
+      axes.insert(axes.end(), a, a + 3 * n); off.push_back(off.back() + n);
+   }
+   if (!fields_current) ComputeElementFields();
+   // the quantum 2^q of the integer weights, the same on every rank and for any rank count: from the largest element volume and the element
+   // count over all ranks (a max and a sum of integers are exact)
+   if (texture_vmax_.n < 2) texture_vmax_.alloc(2);
+   abi_check(ctx, exa_texture_volume_max(ctx, fields_dev_.p, texture_vmax_.p, s), "exa_texture_volume_max");
+   const double ne = (double)part.E;
+   EXA_HC(hipMemcpyAsync(texture_vmax_.p + 1, &ne, sizeof(double), hipMemcpyHostToDevice, s));
+   comm.allreduce_max(texture_vmax_.p, 1, s);
+   comm.allreduce_sum(texture_vmax_.p + 1, 1, s);
+   double vn[2] = { 0.0, 0.0 }; texture_vmax_.download(vn, 2, s);
+   const int qlog2 = exa_texture_quantum_log2(vn[0], (int64_t)vn[1]);
+   const size_t nbins = (size_t)nset * na * nb;
+   if (texture_counts_.n < nbins) texture_counts_.alloc(nbins);
+   abi_check(ctx, exa_texture_weights(ctx, fields_dev_.p, H, axes.data(), off.data(), D, dirs.data(), res_deg, qlog2, texture_counts_.p, s), "exa_texture_weights");
+   std::vector<int64_t> c(nbins); texture_counts_.download(c.data(), nbins, s);
+   if (comm.nranks > 1) {   // exact sums over the ranks: the counts (< 2^62) travel as two 32-bit halves in doubles, whose sums stay below 2^53
+      std::vector<double> h2(2 * nbins);
+      for (size_t b = 0; b < nbins; b++) { h2[b] = (double)(uint64_t)(c[b] >> 32); h2[nbins + b] = (double)(uint64_t)(c[b] & 0xffffffffll); }
+      DevBuf<double> d; d.upload(h2, s);
+      comm.allreduce_sum(d.p, (int)(2 * nbins), s);
+      d.download(h2.data(), 2 * nbins, s);
+      for (size_t b = 0; b < nbins; b++) c[b] = (int64_t)(((uint64_t)h2[b] << 32) + (uint64_t)h2[nbins + b]);
+   }
+   // MRD_ik = (W_ik / W_tot) 2 pi / dOmega_i with dOmega_i = res (cos i res - cos (i + 1) res)
+   const double r = res_deg * (M_PI / 180.0);
+   std::vector<double> f(na);
+   for (int i = 0; i < na; i++) f[i] = 2.0 * M_PI / (r * (std::cos(i * r) - std::cos((i + 1) * r)));
+   mrd.assign(nbins, 0.0);
+   for (int j = 0; j < nset; j++) {
+      const int64_t* w = c.data() + (size_t)j * na * nb;
+      int64_t tot = 0;
+      for (int b = 0; b < na * nb; b++) tot += w[b];
+      const double inv = 1.0 / (double)tot;   // an empty set (no volume): NaN
+      for (int i = 0; i < na; i++)
+         for (int k = 0; k < nb; k++) mrd[(size_t)j * na * nb + (size_t)i * nb + k] = (double)w[i * nb + k] * inv * f[i];
+   }
+}
+
+void SystemDriver::WriteTexture(int step, double t) {
+   std::vector<double> dirs = opt_.texture_dirs, mrd;
+   PoleFigures(opt_.texture_hkl, dirs, opt_.texture_res_deg, mrd, true);
+   if (comm.rank != 0) return;
+   char tag[16]; std::snprintf(tag, sizeof(tag), "_%06d.txt", step);
+   write_texture(out_dir + "/" + opt_.texture_fname + tag, step, t, opt_.texture_res_deg, opt_.texture_hkl, dirs, mrd);
+}
+
+void write_texture(const std::string& path, int step, double t, double res_deg, const std::vector<int>& hkl, const std::vector<double>& dirs,
+                   const std::vector<double>& mrd) {
+   int na = 0, nb = 0;
+   if (exa_texture_grid(res_deg, &na, &nb) != 0) throw std::runtime_error("texture: bad res_deg");
+   const int H = (int)hkl.size() / 3, D = (int)dirs.size() / 3;
+   if (mrd.size() != (size_t)(H + D) * na * nb) throw std::runtime_error("texture: " + path + ": MRD of the wrong size");
+   std::ofstream f(path);
+   if (!f) throw std::runtime_error("texture: cannot write " + path);
+   f << std::setprecision(17);
+   f << "# texture step " << step << " time " << t << " res_deg " << res_deg << " n_alpha " << na << " n_beta " << nb << "\n";
+   for (int j = 0; j < H + D; j++) {
+      if (j < H) f << "# pole figure {" << hkl[3 * j] << ' ' << hkl[3 * j + 1] << ' ' << hkl[3 * j + 2] << "}\n";
+      else f << "# inverse pole figure [" << dirs[3 * (j - H)] << ' ' << dirs[3 * (j - H) + 1] << ' ' << dirs[3 * (j - H) + 2] << "]\n";
+      const double* m = mrd.data() + (size_t)j * na * nb;
+      for (int i = 0; i < na; i++) {
+         for (int k = 0; k < nb; k++) f << (k ? " " : "") << m[i * nb + k];
+         f << '\n';
+      }
+   }
+   if (!f) throw std::runtime_error("texture: writing " + path + " failed");
 }
 
 void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const double* vals) {

@@ -69,6 +69,10 @@ class Comm {
 constexpr int GRAIN_NVALS = 45;
 // one grain_avgs file: a '#' header naming the 46 columns, then one row per grain (id, element count, 43 values with 17 significant digits)
 void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const double* vals);
+// one texture file: a '# texture step .. time .. res_deg .. n_alpha .. n_beta ..' header, then per set a '# pole figure {h k l}' or
+// '# inverse pole figure [d0 d1 d2]' line and n_alpha rows of n_beta MRD values (17 significant digits); mrd [nhkl + ndir][n_alpha][n_beta]
+void write_texture(const std::string& path, int step, double t, double res_deg, const std::vector<int>& hkl, const std::vector<double>& dirs,
+                   const std::vector<double>& mrd);
 
 enum class Precond { IDENTITY, JACOBI, MULTIGRID };
 class Multigrid;
@@ -229,6 +233,10 @@ class SystemDriver {
    // grain map of a synthetic driver before its first step: grain (1..G) of every global element and the orientation of every grain (normalised
    // here); the elements' initial orientations and states become their grain's
    void SetGrains(const int32_t* grain_of_global_elem, int64_t n_global, const double* grain_quats, int G);
+   // texture of the same state over all ranks (every rank calls it): pole figures of the {hkl} families (3 integers each) and
+   // inverse pole figures of the sample directions dirs (3 components each, normalised here; options.hpp check_texture) on the grid of
+   // res_deg; mrd = [nhkl + ndir][n_alpha][n_beta] multiples of random distribution, the same bits on every rank and for any rank count
+   void PoleFigures(const std::vector<int>& hkl, std::vector<double> dirs, double res_deg, std::vector<double>& mrd, bool fields_current = false);
    std::string vis_dir() const { return (opt_.vis_floc.empty() || opt_.vis_floc[0] == '/') ? opt_.vis_floc : out_dir + "/" + opt_.vis_floc; }
    std::vector<int32_t> elem_attr;             // grain id (element attribute) of every local element
    Precond precond = Precond::IDENTITY;
@@ -255,6 +263,9 @@ class SystemDriver {
    // plan of exa_grain_sums for elem_attr (built on first use, dropped by SetGrains), its device copy and workspace; G = largest grain id over all ranks
    std::vector<int32_t> grain_plan_; DevBuf<int32_t> grain_plan_dev_; DevBuf<double> grain_work_, grain_sums_, grain_quat_dev_; int grain_G_ = 0;
    void EnsureGrainPlan();
+   bool texture0_written_ = false;
+   DevBuf<double> texture_vmax_; DevBuf<int64_t> texture_counts_;   // largest element volume; [set][n_alpha][n_beta] counts of exa_texture_weights
+   void WriteTexture(int step, double t);
    std::map<std::string, std::vector<std::pair<int, double>>> pvd_cycles_;   // saved cycles of each output directory (rank 0 writes the .pvd)
    void* cg_graph_ = nullptr; const double* cg_graph_x_ = nullptr; int64_t cg_graph_key_ = -1;   // captured PCG chunk (hipGraphExec_t) and what it was captured for
 };

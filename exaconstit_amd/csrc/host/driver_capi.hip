@@ -661,6 +661,36 @@ int exa_driver_set_grains(exa_driver* d, const int32_t* grain_of_global_element,
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+int exa_driver_pole_figures(exa_driver* d, int nhkl, const int* hkl3, int ndir, const double* dirs3, double res_deg, double* mrd_out, char* err, int errlen) {
+   try {
+      if (nhkl < 0 || nhkl > EXA_TEXTURE_MAX_HKL || ndir < 0 || ndir > EXA_TEXTURE_MAX_DIRS || nhkl + ndir < 1 || (nhkl > 0 && !hkl3) || (ndir > 0 && !dirs3) || !mrd_out)
+         throw std::runtime_error("exa_driver_pole_figures: 0 to 16 families, 0 to 3 directions (at least one set) and an output are required");
+      const std::vector<int> hkl(hkl3, hkl3 + 3 * nhkl);
+      std::vector<double> mrd;
+      d->sd->PoleFigures(hkl, std::vector<double>(dirs3, dirs3 + 3 * ndir), res_deg, mrd);
+      std::memcpy(mrd_out, mrd.data(), sizeof(double) * mrd.size());
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_options_query_texture(const char* toml_path, int* enabled, int* nhkl, int* hkl48, int* ndir, double* dirs9, double* res_deg, char* fname, int fnamelen,
+                              char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      if (enabled) *enabled = o.texture ? 1 : 0;
+      if (nhkl) *nhkl = (int)o.texture_hkl.size() / 3;
+      if (hkl48) for (size_t i = 0; i < o.texture_hkl.size(); i++) hkl48[i] = o.texture_hkl[i];
+      if (ndir) *ndir = (int)o.texture_dirs.size() / 3;
+      if (dirs9) for (size_t i = 0; i < o.texture_dirs.size(); i++) dirs9[i] = o.texture_dirs[i];
+      if (res_deg) *res_deg = o.texture_res_deg;
+      if (fname && fnamelen > 0) {
+         if ((int)o.texture_fname.size() >= fnamelen) throw std::runtime_error("Visualizations.texture_fname longer than the buffer");
+         std::strcpy(fname, o.texture_fname.c_str());
+      }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
 int exa_options_query_grains(const char* toml_path, int* enabled, char* fname, int fnamelen, char* err, int errlen) {
    try {
       ExaOptions o; o.parse_options(toml_path);

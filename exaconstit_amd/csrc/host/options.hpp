@@ -13,6 +13,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "../../../include/exaconstit_hip.h"
 
 namespace exa_host {
 
@@ -120,6 +121,28 @@ struct ExaOptions {
    }
    // per-grain averages written every Visualizations.steps steps (driver.hip, SystemDriver::GrainAverages): <out_dir>/<grain_avgs_fname>_<step %06d>.txt
    bool grain_avgs = false; std::string grain_avgs_fname = "grain_avgs";
+   // texture (driver.hip, SystemDriver::PoleFigures): pole figures of the texture_hkl families and inverse pole figures of the
+   // texture_ipf_dirs (unit) in multiples of random distribution, written at step 0, every Visualizations.steps steps and at the last step
+   // to <out_dir>/<texture_fname>_<step %06d>.txt
+   bool texture = false; std::vector<int> texture_hkl = { 1, 1, 1, 2, 0, 0, 2, 2, 0 }; std::vector<double> texture_dirs = { 0, 0, 1 };
+   double texture_res_deg = 5.0; std::string texture_fname = "texture";
+   // the checks of the texture keys, shared with exa_driver_pole_figures (hkl: 3 integers per family, dirs: 3 components per direction,
+   // normalised in place; the driver takes 0 families as long as there is a direction)
+   static void check_texture(const std::vector<int>& hkl, std::vector<double>& dirs, double res_deg, bool need_hkl = true) {
+      if (hkl.size() % 3 != 0) throw std::runtime_error("Visualizations.texture_hkl must hold [h, k, l] triples");
+      if ((need_hkl && hkl.empty()) || hkl.size() > 3 * 16) throw std::runtime_error("Visualizations.texture_hkl holds 1 to 16 triples");
+      for (size_t j = 0; j < hkl.size(); j += 3)
+         if (hkl[j] == 0 && hkl[j + 1] == 0 && hkl[j + 2] == 0) throw std::runtime_error("Visualizations.texture_hkl: [0, 0, 0] is not a plane family");
+      if (dirs.size() % 3 != 0 || dirs.size() > 9) throw std::runtime_error("Visualizations.texture_ipf_dirs holds 0 to 3 directions of 3 components");
+      if (hkl.empty() && dirs.empty()) throw std::runtime_error("texture: no pole figure family and no inverse pole figure direction given");
+      for (size_t m = 0; m < dirs.size(); m += 3) {
+         const double n = std::sqrt(dirs[m] * dirs[m] + dirs[m + 1] * dirs[m + 1] + dirs[m + 2] * dirs[m + 2]);
+         if (!(n > 0.0) || !std::isfinite(n)) throw std::runtime_error("Visualizations.texture_ipf_dirs: every direction must be a non-zero vector");
+         for (int i = 0; i < 3; i++) dirs[m + i] /= n;
+      }
+      if (exa_texture_grid(res_deg, nullptr, nullptr) != 0)
+         throw std::runtime_error("Visualizations.texture_res_deg must divide 90 and lie in [2, 30] degrees");
+   }
    Assembly assembly = Assembly::EA; NLSolver nl_solver = NLSolver::NR; std::string integ_model = "FULL";
    int newton_iter = 25; double newton_rel = 1e-5, newton_abs = 1e-10;
    int krylov_iter = 200; double krylov_rel = 1e-10, krylov_abs = 1e-30; std::string krylov_solver = "PCG";
@@ -237,6 +260,42 @@ struct ExaOptions {
             throw std::runtime_error("Visualizations.grain_avgs_fname must be a non-empty file name without '/'");
          grain_avgs_fname = g->str;
       }
+      if (const TomlValue* t = d.get("Visualizations.texture")) {
+         if (t->kind != TomlValue::BOOL) throw std::runtime_error("Visualizations.texture must be true or false");
+         texture = t->b;
+      }
+      if (const TomlValue* h = d.get("Visualizations.texture_hkl")) {
+         if (h->kind != TomlValue::ARR || h->arr.empty() || h->arr.size() > 16) throw std::runtime_error("Visualizations.texture_hkl must be an array of 1 to 16 [h, k, l] triples");
+         texture_hkl.clear();
+         for (auto& t : h->arr) {
+            if (t.kind != TomlValue::ARR || t.arr.size() != 3) throw std::runtime_error("Visualizations.texture_hkl: every entry must be an [h, k, l] triple of 3 integers");
+            for (auto& x : t.arr) {
+               if (x.kind != TomlValue::NUM || x.num != std::floor(x.num) || std::fabs(x.num) > 1000.0) throw std::runtime_error("Visualizations.texture_hkl: Miller indices must be integers");
+               texture_hkl.push_back((int)x.num);
+            }
+         }
+      }
+      if (const TomlValue* v = d.get("Visualizations.texture_ipf_dirs")) {
+         if (v->kind != TomlValue::ARR || v->arr.size() > 3) throw std::runtime_error("Visualizations.texture_ipf_dirs must be an array of 0 to 3 directions [x, y, z]");
+         texture_dirs.clear();
+         for (auto& t : v->arr) {
+            if (t.kind != TomlValue::ARR || t.arr.size() != 3) throw std::runtime_error("Visualizations.texture_ipf_dirs: every entry must be a direction of 3 numbers");
+            for (auto& x : t.arr) {
+               if (x.kind != TomlValue::NUM) throw std::runtime_error("Visualizations.texture_ipf_dirs: every entry must be a direction of 3 numbers");
+               texture_dirs.push_back(x.num);
+            }
+         }
+      }
+      if (const TomlValue* r = d.get("Visualizations.texture_res_deg")) {
+         if (r->kind != TomlValue::NUM) throw std::runtime_error("Visualizations.texture_res_deg must be a number of degrees");
+         texture_res_deg = r->num;
+      }
+      if (const TomlValue* f = d.get("Visualizations.texture_fname")) {
+         if (f->kind != TomlValue::STR || f->str.empty() || f->str.find('/') != std::string::npos)
+            throw std::runtime_error("Visualizations.texture_fname must be a non-empty file name without '/'");
+         texture_fname = f->str;
+      }
+      check_texture(texture_hkl, texture_dirs, texture_res_deg);
       avg_def_grad_fname = d.str("Visualizations.avg_def_grad_fname", "avg_def_grad.txt");
       avg_pl_work_fname = d.str("Visualizations.avg_pl_work_fname", "avg_pl_work.txt");
       avg_dp_tensor_fname = d.str("Visualizations.avg_dp_tensor_fname", "avg_dp_tensor.txt");

@@ -104,6 +104,15 @@ EXA_LATTICE_MAX_HKL = 16
 exa_grain_sums = _sig("exa_grain_sums", C.c_int, C.c_void_p, C.c_int, dptr, C.POINTER(C.c_int32), C.c_void_p, C.c_int, dptr, dptr, dptr, C.c_void_p)
 exa_grain_plan = _sig("exa_grain_plan", C.c_int, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 EXA_GRAIN_NSUMS = 39
+exa_texture_weights = _sig("exa_texture_weights", C.c_int, C.c_void_p, dptr, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double),
+                           C.c_double, C.c_int, dptr, C.c_void_p)
+exa_texture_volume_max = _sig("exa_texture_volume_max", C.c_int, C.c_void_p, dptr, dptr, C.c_void_p)
+exa_texture_quantum_log2 = _sig("exa_texture_quantum_log2", C.c_int, C.c_double, C.c_int64)
+exa_texture_grid = _sig("exa_texture_grid", C.c_int, C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int))
+exa_texture_bin = _sig("exa_texture_bin", C.c_int, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int))
+EXA_TEXTURE_MAX_HKL, EXA_TEXTURE_MAX_DIRS = 16, 3
+TEXTURE_HKL = ((1, 1, 1), (2, 0, 0), (2, 2, 0))     # the defaults of Visualizations.texture_hkl and texture_ipf_dirs
+TEXTURE_IPF_DIRS = ((0, 0, 1),)
 # columns of the exa_element_fields rows (include/exaconstit_hip.h)
 EXA_NFIELDS = 37
 ELEMENT_FIELDS = {"ElementVolume": (0, 1), "ElemCentroid": (1, 3), "Stress": (4, 6), "VonMisesStress": (10, 1), "HydrostaticStress": (11, 1),
@@ -251,6 +260,94 @@ def read_grain_avgs(path):
     import numpy as np
     a = np.loadtxt(path, ndmin=2).reshape(-1, 1 + EXA_GRAIN_NVALS)
     return grain_dict(np.rint(a[:, 0]).astype(np.int64), a[:, 1:])
+
+
+exa_driver_pole_figures = _sig("exa_driver_pole_figures", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.c_double,
+                               C.POINTER(C.c_double), C.c_char_p, C.c_int)
+exa_options_query_texture = _sig("exa_options_query_texture", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_int, C.c_char_p, C.c_int)
+
+
+def texture_grid(res_deg):
+    """(n_alpha, n_beta) of the texture grid of resolution res_deg (exa_texture_grid); ValueError unless res_deg divides 90 and lies in [2, 30]"""
+    na, nb = C.c_int(), C.c_int()
+    if exa_texture_grid(float(res_deg), C.byref(na), C.byref(nb)) != 0:
+        raise ValueError(f"res_deg = {res_deg} must divide 90 and lie in [2, 30]")
+    return na.value, nb.value
+
+
+def texture_bin(p, res_deg):
+    """(ring i, sector k) of the direction p on the texture grid - the kernel's binning code (exa_texture_bin)"""
+    v = (C.c_double * 3)(*[float(x) for x in p])
+    i, k = C.c_int(), C.c_int()
+    if exa_texture_bin(v, float(res_deg), C.byref(i), C.byref(k)) != 0:
+        raise ValueError(f"res_deg = {res_deg} must divide 90 and lie in [2, 30]")
+    return i.value, k.value
+
+
+def texture_cells(res_deg):
+    """alpha_edges (n_alpha + 1,), beta_edges (n_beta + 1,) in degrees and the solid angle (n_alpha,) of one bin of each ring:
+    res (cos i res - cos (i + 1) res), res in radians (the n_alpha x n_beta bins sum to 2 pi)"""
+    import numpy as np
+    na, nb = texture_grid(res_deg)
+    r = np.radians(res_deg)
+    i = np.arange(na)
+    return res_deg * np.arange(na + 1), res_deg * np.arange(nb + 1), r * (np.cos(i * r) - np.cos((i + 1) * r))
+
+
+def texture_weights(ctx, fields_dev, hkl, ipf_dirs, res_deg, quantum_log2, out_dev, stream=None):
+    """launch exa_texture_weights on the device rows fields_dev (pointer, [E][EXA_NFIELDS]) of the context ctx: the pole figures of the families
+    hkl and the inverse pole figures of the directions ipf_dirs into the int64 counts out_dev (pointer, [H + D][n_alpha][n_beta]); does not synchronise"""
+    import numpy as np
+    hkl = [tuple(h) for h in hkl]
+    axes = [cubic_fiber_axes(*h) for h in hkl]
+    off = np.concatenate([[0], np.cumsum([len(a) for a in axes])]).astype(np.int32)
+    ax = np.ascontiguousarray(np.concatenate(axes) if axes else np.zeros((1, 3)))
+    d = np.ascontiguousarray(np.asarray(ipf_dirs, dtype=np.float64).reshape(-1, 3) if len(ipf_dirs) else np.zeros((1, 3)))
+    ctx.check(exa_texture_weights(ctx.h, fields_dev, len(hkl), ax.ctypes.data_as(C.POINTER(C.c_double)), off.ctypes.data_as(C.POINTER(C.c_int)),
+                                  len(ipf_dirs), d.ctypes.data_as(C.POINTER(C.c_double)), float(res_deg), int(quantum_log2), out_dev, stream),
+              "exa_texture_weights")
+
+
+def options_texture(path):
+    """texture keys of the Visualizations table: dict(enabled, hkl (list of triples), ipf_dirs (list of unit triples), res_deg, fname)"""
+    en, nh, nd = C.c_int(), C.c_int(), C.c_int()
+    hkl = (C.c_int * 48)()
+    dirs = (C.c_double * 9)()
+    res = C.c_double()
+    f = C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_query_texture(path.encode(), C.byref(en), C.byref(nh), hkl, C.byref(nd), dirs, C.byref(res), f, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(enabled=bool(en.value), hkl=[tuple(hkl[3 * j:3 * j + 3]) for j in range(nh.value)],
+                ipf_dirs=[tuple(dirs[3 * m:3 * m + 3]) for m in range(nd.value)], res_deg=res.value, fname=f.value.decode())
+
+
+def read_texture(path):
+    """a texture file of the driver: dict(step, time, res_deg, hkl (list of triples), ipf_dirs (list of triples), pf (H, n_alpha, n_beta),
+    ipf (D, n_alpha, n_beta))"""
+    import numpy as np
+    lines = open(path).read().splitlines()
+    h = lines[0].split()
+    assert h[:3] == ["#", "texture", "step"], h
+    kv = dict(zip(h[2::2], h[3::2]))
+    na, nb = int(kv["n_alpha"]), int(kv["n_beta"])
+    hkl, dirs, pf, ipf = [], [], [], []
+    i = 1
+    while i < len(lines):
+        head = lines[i]
+        block = np.array([[float(x) for x in ln.split()] for ln in lines[i + 1:i + 1 + na]]).reshape(na, nb)
+        if head.startswith("# pole figure {"):
+            hkl.append(tuple(int(x) for x in head[head.index("{") + 1:head.index("}")].split()))
+            pf.append(block)
+        elif head.startswith("# inverse pole figure ["):
+            dirs.append(tuple(float(x) for x in head[head.index("[") + 1:head.index("]")].split()))
+            ipf.append(block)
+        else:
+            raise ValueError(f"{path}: unexpected line {head!r}")
+        i += 1 + na
+    return dict(step=int(kv["step"]), time=float(kv["time"]), res_deg=float(kv["res_deg"]), hkl=hkl, ipf_dirs=dirs,
+                pf=np.array(pf).reshape(len(pf), na, nb), ipf=np.array(ipf).reshape(len(ipf), na, nb))
 
 
 exa_driver_write_fields = _sig("exa_driver_write_fields", C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_double, C.c_char_p, C.c_int)
@@ -500,6 +597,22 @@ class Driver:
         q = np.ascontiguousarray(np.asarray(quats, dtype=np.float64).reshape(-1, 4))
         self._chk(exa_driver_set_grains(self.h, g.ctypes.data_as(C.POINTER(C.c_int32)), q.ctypes.data_as(C.POINTER(C.c_double)), q.shape[0], g.size,
                                         self._err, 512))
+
+    def pole_figures(self, hkl=TEXTURE_HKL, ipf_dirs=TEXTURE_IPF_DIRS, res_deg=5.0):
+        """Texture of the current begin-of-step state (after a completed step: the converged one), over all ranks of the group
+        (every rank calls it), in multiples of random distribution: {"pf": (H, n_alpha, n_beta) pole figures of the families hkl,
+        "ipf": (D, n_alpha, n_beta) inverse pole figures of the sample directions ipf_dirs, "alpha_edges", "beta_edges" (degrees),
+        "solid_angle": (n_alpha,) of one bin of each ring}."""
+        import numpy as np
+        h = np.ascontiguousarray(np.asarray(hkl, dtype=np.int32).reshape(-1, 3))
+        d = np.ascontiguousarray(np.asarray(ipf_dirs, dtype=np.float64).reshape(-1, 3))
+        na, nb = texture_grid(res_deg)
+        H, D = h.shape[0], d.shape[0]
+        mrd = np.zeros((H + D, na, nb))
+        self._chk(exa_driver_pole_figures(self.h, H, h.ctypes.data_as(C.POINTER(C.c_int)), D, d.ctypes.data_as(C.POINTER(C.c_double)), float(res_deg),
+                                          mrd.ctypes.data_as(C.POINTER(C.c_double)), self._err, 512))
+        ae, be, sa = texture_cells(res_deg)
+        return {"pf": mrd[:H].copy(), "ipf": mrd[H:].copy(), "alpha_edges": ae, "beta_edges": be, "solid_angle": sa}
 
     def write_fields(self, directory, cycle, t):
         """ParaView save of the per-element fields as cycle `cycle` at time t under directory (every rank of a group calls it)."""

@@ -146,6 +146,13 @@ int exa_driver_grain_averages(exa_driver* d, int32_t* grain_ids, double* vals, i
  * N^3, global element index x fastest) and grain_quats[G][4] (scalar first, normalised here).  Every element's initial orientation and state
  * become its grain's, and the grain's orientation is its reference q_ref.  Every rank of the group calls it with the same map.  Returns 0 or -1 (err). */
 int exa_driver_set_grains(exa_driver* d, const int32_t* grain_of_global_element, const double* grain_quats, int G, int64_t n_global, char* err, int errlen);
+/* Texture of the current begin-of-step state (after a completed step: the converged one), over all ranks (every rank of the group
+ * calls it): pole figures of the nhkl families hkl3 [nhkl][3] and inverse pole figures of the ndir sample directions dirs3 [ndir][3] (normalised
+ * here) on the grid of res_deg (exa_texture_grid), in multiples of random distribution: mrd_out [nhkl + ndir][n_alpha][n_beta] receives
+ * MRD_ik = (W_ik / W_tot) 2 pi / dOmega_i, dOmega_i = res (cos i res - cos (i + 1) res) (res in radians), from the integer weights of
+ * exa_texture_weights summed exactly over the ranks: the same bits for any rank count.  0 <= nhkl <= 16, 0 <= ndir <= 3, nhkl + ndir >= 1.
+ * Returns 0 or -1 (err). */
+int exa_driver_pole_figures(exa_driver* d, int nhkl, const int* hkl3, int ndir, const double* dirs3, double res_deg, double* mrd_out, char* err, int errlen);
 int exa_driver_bench_prepare(exa_driver* d, int nsteps, const double* dts, double perturb, char* err, int errlen);
 int exa_driver_bench_model(exa_driver* d, int steps, double* out3, char* err, int errlen);
 int exa_driver_bench_pcg(exa_driver* d, int iters, double* out3, char* err, int errlen);
@@ -174,6 +181,11 @@ int exa_options_query_lightup(const char* toml_path, int* enabled, int* nhkl, in
                               char* volume_fname, int fnamelen, char* err, int errlen);
 /* per-grain averages keys of the Visualizations table: enabled = grain_avgs (default 0), grain_avgs_fname ("grain_avgs") into a buffer of
  * fnamelen bytes.  Either pointer may be NULL.  Returns 0 or -1 (err). */
+/* texture keys of the Visualizations table: enabled = texture (default 0); texture_hkl (default [[1,1,1],[2,0,0],[2,2,0]]) as *nhkl triples
+ * into hkl48; texture_ipf_dirs (default [[0,0,1]]), normalised, as *ndir directions into dirs9; texture_res_deg (5); texture_fname ("texture")
+ * into a buffer of fnamelen bytes.  Every pointer may be NULL.  Returns 0 or -1 (err). */
+int exa_options_query_texture(const char* toml_path, int* enabled, int* nhkl, int* hkl48, int* ndir, double* dirs9, double* res_deg, char* fname, int fnamelen,
+                              char* err, int errlen);
 int exa_options_query_grains(const char* toml_path, int* enabled, char* fname, int fnamelen, char* err, int errlen);
 /* the grain_avgs file writer (host only): a '#' header naming the 46 columns, then n rows of grain_ids[i] and vals[i][EXA_GRAIN_NVALS] (the
  * element count as an integer, the rest with 17 significant digits).  Returns 0 or -1 (err). */

@@ -336,6 +336,31 @@ int exa_grain_sums(exa_ctx* ctx, int pass, const double* fields_dev, const int32
  * *work_doubles (either may be NULL) and writes it to plan when plan_cap suffices (plan may be NULL: a size query).  Returns 0, or
  * EXA_ERR_ARG for an id < 1 or a too small plan_cap. */
 int exa_grain_plan(int64_t E, const int32_t* grain_of_elem, int32_t* plan, int64_t plan_cap, int64_t* plan_len, int64_t* work_doubles);
+/* Texture: pole-figure and inverse-pole-figure weights of the rows of exa_element_fields (fields_dev [E][EXA_NFIELDS], device) on
+ * the equal-angle grid of resolution res_deg (exa_texture_grid).  Sets 0 .. npf - 1 are pole figures: family j owns the unit crystal axes
+ * pf_axes[pf_axis_offsets[j] .. pf_axis_offsets[j + 1]) [3] (host; 1 to 24 signed permutations of its first axis - the cubic orbit of
+ * exa_cubic_fiber_axes), and each element adds its N_j poles p = R(q) c.  Sets npf .. npf + nipf - 1 are inverse pole figures of the sample
+ * directions ipf_dirs [nipf][3] (host, normalised here): u = R(q)^T d and its 24 images S_k u under the proper cubic rotations.  R = quat_to_mat of
+ * EXA_F_ORIENTATION (crystal -> sample).  Every pole is binned by exa_texture_bin and carries the count rint(V 2^-quantum_log2 / N) (N = N_j or
+ * 24, V = EXA_F_VOLUME); out_dev [npf + nipf][n_alpha][n_beta] (device, int64) receives the summed counts.  Integer sums only: every call on
+ * the same rows gives the same bits in any element order and on any split of the rows.  0 <= npf <= EXA_TEXTURE_MAX_HKL, 0 <= nipf <=
+ * EXA_TEXTURE_MAX_DIRS, npf + nipf >= 1; the caller picks quantum_log2 so that the counts cannot overflow (exa_texture_quantum_log2).
+ * Does not synchronise. */
+enum { EXA_TEXTURE_MAX_HKL = 16, EXA_TEXTURE_MAX_DIRS = 3 };
+int exa_texture_weights(exa_ctx* ctx, const double* fields_dev, int npf, const double* pf_axes, const int* pf_axis_offsets, int nipf,
+                        const double* ipf_dirs, double res_deg, int quantum_log2, int64_t* out_dev, exa_stream s);
+/* out_dev[0] (device) = the largest EXA_F_VOLUME of the rows (0 without rows).  Does not synchronise. */
+int exa_texture_volume_max(exa_ctx* ctx, const double* fields_dev, double* out_dev, exa_stream s);
+/* host only: the quantum exponent for rows whose largest volume over all ranks is vmax and whose element count over all ranks is n_elements:
+ * the q with 2^(q + 60) <= vmax n_elements < 2^(q + 61), so that every set sums to at most about 2^61 counts (0 when vmax <= 0). */
+int exa_texture_quantum_log2(double vmax, int64_t n_elements);
+/* host only: the grid of resolution res_deg, n_alpha = 90 / res_deg rings and n_beta = 360 / res_deg sectors.  res_deg must lie in [2, 30]
+ * and divide 90.  Returns 0, or -1 for any other res_deg. */
+int exa_texture_grid(double res_deg, int* n_alpha, int* n_beta);
+/* host only: the bin (ring *i, sector *k) of the direction p3 [3] - the code the kernel runs: p -> -p when p_z < 0, or p_z = 0 and (p_y < 0, or
+ * p_y = 0 and p_x < 0); alpha = atan2(sqrt(p_x^2 + p_y^2), p_z), beta = atan2(p_y, p_x) in [0, 360) degrees (0 at the pole);
+ * i = min(floor(alpha / res_deg), n_alpha - 1), k = floor(beta / res_deg) mod n_beta.  Returns 0, or -1 for a bad res_deg. */
+int exa_texture_bin(const double* p3, double res_deg, int* i, int* k);
 /* volume average  sum_q W detJ val / sum_q W detJ  (src/mechanics_kernels.hpp:19-134); out_host[vdim] (+ volume in out_host[vdim]).
  * Synchronises the stream. */
 int exa_vol_avg(exa_ctx* ctx, const double* jacobian_dev, const double* qf_dev, int vdim, int normalise, double* out_host, exa_stream s);
