@@ -8,8 +8,12 @@ Metric (BASELINE.json): "quadrature-point constitutive updates/s + Newton-PCG it
                          residual evaluation of a Newton solve does.  The state is the one a REAL Newton/PCG solve of the
                          reference schedule reaches in step --solve-steps (default 14: plastic regime); the passes repeat
                          that step's converged (last) residual evaluation.  --solve-steps 0 times the kinematically driven state of the
-                         earlier rounds instead (reported beside it as `kinematic_state` in the default run).
-  * `pcg_iters_per_s`  = partial-assembly PCG iterations/s on the same RVE (second timed region of the same run).
+                         earlier rounds instead (reported beside it as `kinematic_state` with --full).
+  * `pcg_iters_per_s`  = partial-assembly PCG iterations/s on the same RVE (second timed region, --full).
+A plain run does what `value` needs and nothing else: set-up (the real solve to the benchmark state), --warmup untimed passes, --steps timed
+passes, --dump-outputs, the JSON line (with the roofline of the timed launch and the solve's own figures, which cost no extra GPU work).
+--full adds the elastic-regime and kinematic-state blocks, the PCG timed region, the adapter route, the continued solve to --solve-steps-total
+(in-solve rates) and the CPU baseline; none of them changes what the timed passes of `value` compute.
 Inputs are synthetic (seeded orientations, reference test properties) and resident in HBM before the timed regions.
 Multi-GPU: one process per GPU (torchrun), block domain decomposition of the SAME 128^3 problem (strong scaling, BASELINE config 4),
 RCCL halo-sum + dot all-reduce on the PCG path; the constitutive pass needs no communication.
@@ -285,6 +289,10 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed constitutive passes, write what the last of them computed (end-of-step stress and state at a seeded sample of "
                          f"at most {DUMP_POINTS} quadrature points; rank 0's share with several ranks) as DIR/stress.npy and DIR/state.npy, float64")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("EXA_BENCH_FULL") == "1",
+                    help="(or EXA_BENCH_FULL=1) also measure what the headline figure does not need: the elastic-regime and kinematic-state blocks, the PCG timed region, "
+                         "the adapter route, the continued solve (in-solve rates) and the CPU baseline.  Without it the run sets up, warms up, times "
+                         "--steps, dumps and prints the line.  --order 2 prints its whole line either way")
     args = ap.parse_args()
     if args.n is None:
         args.n = 128 if args.order == 1 else 64
@@ -353,9 +361,7 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    drv = L.Driver.synthetic(N, props, quats.ravel(), np.array(PREP_DTS), assembly=asm,
-                             krylov=(1000, 1e-7, 1e-27), rank=rank, nranks=world, uid=fresh_uid(), jacobi=args.jacobi, **mk)
-    del quats
+    full = args.full
     P_global = 8 * N ** 3
     # Untimed passes in front of a timed region.  The kinematic state is timed right after a cold prepare phase, where the first dozens of launches read
     # ~4 % slow: SETTLE_PASSES there.  The headline region follows a 14-step real solve (24 s of GPU work): measured in round 5, --warmup 5 and 60 settle
@@ -376,26 +382,35 @@ def main():
         barrier(); tw = max_over_ranks(time.perf_counter() - t0)
         return tw, max_over_ranks(mm["kernel_ms"]) / steps, mm["failed"], d.nfev_hist()
 
-    # elastic regime (first step of the schedule from the virgin state), reported beside the headline plastic-regime value
-    drv.bench_prepare(PREP_DTS[:1], advance=False)
-    drv.bench_model(1)
-    barrier(); t0 = time.perf_counter()
-    me = drv.bench_model(max(1, args.steps // 2))
-    barrier(); t_el = max_over_ranks(time.perf_counter() - t0)
-    elastic = {"value": P_global * max(1, args.steps // 2) / t_el, "unit": "qpt-updates/s", "avg_kernel_ms": max_over_ranks(me["kernel_ms"]) / max(1, args.steps // 2),
-               "regime": "elastic (step 1 of the schedule, dt = 0.005, virgin state)"}
-    # kinematically driven plastic state (the benchmark state of rounds 1-3): 10 prescribed-velocity passes, no equilibrium solve
-    t0 = time.perf_counter(); drv.bench_prepare(PREP_DTS); barrier(); prep_s = time.perf_counter() - t0
-    P_local = L.exa_driver_local_qpts(drv.h)
-    kin_steps = args.steps if args.solve_steps <= 0 else max(5, args.steps // 2)
-    t_kin, kin_kern_ms, kin_failed, kin_hist = timed_passes(drv, kin_steps, settle_cold)
-    kinematic = {"value": P_global * kin_steps / t_kin, "unit": "qpt-updates/s", "avg_kernel_ms": kin_kern_ms, "passes": kin_steps, "nonconverged_points": kin_failed,
-                 "local_solver_evals": hist_dict(kin_hist), "prepare_wall_s": prep_s,
-                 "state": "10 prescribed-velocity passes (v = L0 x + seeded perturbation) through the elastic-plastic transition, no equilibrium solve"}
+    # The kinematically driven driver: the headline state with --solve-steps 0, otherwise only the elastic-regime and kinematic-state blocks of --full use it
+    # (the real solve below runs on a fresh driver of its own)
+    drv = None; elastic = None; kinematic = None
+    if full or args.solve_steps <= 0:
+        drv = L.Driver.synthetic(N, props, quats.ravel(), np.array(PREP_DTS), assembly=asm,
+                                 krylov=(1000, 1e-7, 1e-27), rank=rank, nranks=world, uid=fresh_uid(), jacobi=args.jacobi, **mk)
+        if full:
+            # elastic regime (first step of the schedule from the virgin state), reported beside the headline plastic-regime value
+            drv.bench_prepare(PREP_DTS[:1], advance=False)
+            drv.bench_model(1)
+            barrier(); t0 = time.perf_counter()
+            me = drv.bench_model(max(1, args.steps // 2))
+            barrier(); t_el = max_over_ranks(time.perf_counter() - t0)
+            elastic = {"value": P_global * max(1, args.steps // 2) / t_el, "unit": "qpt-updates/s", "avg_kernel_ms": max_over_ranks(me["kernel_ms"]) / max(1, args.steps // 2),
+                       "regime": "elastic (step 1 of the schedule, dt = 0.005, virgin state)"}
+        # kinematically driven plastic state (the benchmark state of rounds 1-3): 10 prescribed-velocity passes, no equilibrium solve
+        t0 = time.perf_counter(); drv.bench_prepare(PREP_DTS); barrier(); prep_s = time.perf_counter() - t0
+        P_local = L.exa_driver_local_qpts(drv.h)
+        kin_steps = args.steps if args.solve_steps <= 0 else max(5, args.steps // 2)
+        t_kin, kin_kern_ms, kin_failed, kin_hist = timed_passes(drv, kin_steps, settle_cold)
+        kinematic = {"value": P_global * kin_steps / t_kin, "unit": "qpt-updates/s", "avg_kernel_ms": kin_kern_ms, "passes": kin_steps, "nonconverged_points": kin_failed,
+                     "local_solver_evals": hist_dict(kin_hist), "prepare_wall_s": prep_s,
+                     "state": "10 prescribed-velocity passes (v = L0 x + seeded perturbation) through the elastic-plastic transition, no equilibrium solve"}
+    del quats
     solve = None
     if args.solve_steps > 0:
         # ---- real time stepping (Newton + PCG with the reference's settings) on a fresh driver: the benchmark state ------------------------------
-        drv.close()
+        if drv is not None:
+            drv.close()
         rng = np.random.default_rng(20240928)
         quats = rng.standard_normal((N ** 3, 4)); quats /= np.linalg.norm(quats, axis=1, keepdims=True)
         sched = np.loadtxt(os.path.join(ROOT, "tests", "golden", "refdata", "custom_dt.txt")).ravel()[:max(args.solve_steps, args.solve_steps_total)]
@@ -450,15 +465,16 @@ def main():
     value = P_global * args.steps / t_model
     if args.dump_outputs and rank == 0:
         dump_outputs(L, drv, args.dump_outputs)
-    # ---- timed region 2: PCG iterations (same state) ----------------------------------------------------------------------------------
-    drv.bench_pcg(max(2, args.pcg_iters // 10))   # warm-up
-    barrier()
-    t0 = time.perf_counter()
-    pc = drv.bench_pcg(args.pcg_iters)
-    barrier()
-    t_pcg_wall = max_over_ranks(time.perf_counter() - t0)
-    pcg_ms = max_over_ranks(pc["pcg_ms"]); apply_ms = max_over_ranks(pc["apply_ms"]) / args.pcg_iters
-    pcg_it_s = pc["iters"] / (pcg_ms * 1e-3)
+    # ---- timed region 2 (--full): PCG iterations (same state) ----------------------------------------------------------------------------
+    if full:
+        drv.bench_pcg(max(2, args.pcg_iters // 10))   # warm-up
+        barrier()
+        t0 = time.perf_counter()
+        pc = drv.bench_pcg(args.pcg_iters)
+        barrier()
+        t_pcg_wall = max_over_ranks(time.perf_counter() - t0)
+        pcg_ms = max_over_ranks(pc["pcg_ms"]); apply_ms = max_over_ranks(pc["apply_ms"]) / args.pcg_iters
+        pcg_it_s = pc["iters"] / (pcg_ms * 1e-3)
     comm_ranks, comm_transport = drv.comm_info()
     comm_details = drv.comm_details()
     per_rank = None
@@ -467,7 +483,7 @@ def main():
         dist.all_gather_object(per_rank, dict(rank=rank, **comm_details))
     # ---- the drop-in route at the same state: what include/exaconstit_mfem_adapters.hpp calls (never `value`) --------------------------------------------
     adapter = None
-    if world == 1 and not args.no_adapter_route and args.assembly.upper() == "PA" and N <= 160:
+    if full and world == 1 and not args.no_adapter_route and args.assembly.upper() == "PA" and N <= 160:
         try:
             ar = drv.bench_adapter_route(max(5, min(args.steps, 40)), max(5, min(args.pcg_iters, 40)))
             Pq = float(P_local)
@@ -521,7 +537,7 @@ def main():
             adapter = {"failed": str(e)}
     # ---- the solve goes on: in-solve kernel rates up to the plateau (qpt updates/s = sum of P over ModelSetup calls / kernel time) ----------
     in_solve = None
-    if solve is not None and args.solve_steps_total > args.solve_steps:
+    if full and solve is not None and args.solve_steps_total > args.solve_steps:
         total = len(sched)
         barrier(); t0 = time.perf_counter()
         drv.commit_step()                         # end-of-step update of the step whose converged launch was timed
@@ -595,7 +611,6 @@ def main():
         geo = os.environ.get("EXA_APPLY_GEO", "on") != "off" and not ea_streamed
         compact = geo and os.environ.get("EXA_TANGENT_FORM", "compact") != "full"
         moved = 616.0 if ea_streamed else (APPLY_MOVED_BYTES_COMPACT if compact else (APPLY_MOVED_BYTES_PER_QPT if geo else APPLY_BYTES_PER_QPT))
-        apply_gbs = APPLY_BYTES_PER_QPT * P_local / (apply_ms * 1e-3) / 1e9
         iter_bytes = APPLY_BYTES_PER_QPT * P_local + PCG_VEC_BYTES_PER_DOF * ndof_local
         out = {
             "metric": "quadrature-point constitutive updates/s + Newton-PCG iter/s, 128^3 hex RVE",
@@ -609,49 +624,53 @@ def main():
                        "qpts": P_global, "decomposition": f"{world} block(s)"},
             "library": {"path": L.LIB_PATH, "build_id": L.exa_build_id().decode(), "kernel_build_id": L.exa_kernel_build_id().decode()},
             "comm": {"transport": comm_transport, "ranks_reported_by_transport": comm_ranks, "rank0": comm_details, "per_rank": per_rank,
-                     "note": "rccl: ncclCommCount of the library's communicator; ipc: shared-device inter-process transport (more ranks than devices)"},
-            "pcg_iters_per_s": pcg_it_s, "pcg_iters": pc["iters"], "pcg_ms_per_iter": pcg_ms / max(pc["iters"], 1),
-            "pcg_wall_s": t_pcg_wall, "nonconverged_points": m["failed"],
-            "local_solver_evals": dict(hist_dict(nfev), note="residual/Jacobian evaluations of the 8-unknown point solve per quadrature point (rank 0), last timed pass"),
-            "elastic_regime": elastic,
-            "kinematic_state": kinematic,
-            "roofline": {"kernel": f"k_model_setup<{'KM-DD' if 'kmdd' in args.model else 'Voce'}> (fused node gather + grad_calc + ExaCMech update + tangent)", "bound": "hbm",
-                         "achieved": model_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": model_gbs / HBM_PEAK_GBS,
-                         "traffic": traffic["k_model_setup"] * P_local if "k_model_setup" in traffic else None, "traffic_source": traffic.get("_file"), "kernel_build_id": kid,
-                         "bytes_per_qpt": MODEL_BYTES_PER_QPT, "avg_kernel_ms": kern_ms,
-                         # the same launch priced at what it moves by construction on the record route (648 B/qpt): the figure to compare with PMC traffic
-                         "frac_on_bytes_moved": (648.0 * P_local / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (records and args.model in ("fcc_voce", "bcc_voce", "fcc_voce_nl")) else None,
-                         "state_key": "value / roofline: converged launch of the last --solve-steps step of a real Newton/PCG solve (since round 4); `kinematic_state` "
-                                      "(prescribed-velocity passes, the benchmark state of rounds 1-3) is reported under its own key every round: compare rounds on like keys",
-                         "bytes_written_per_qpt_note": ("this launch writes the 26-number gradient record instead of the 36 tangent entries (AssembleGradPA fused in)") if records else None,
-                         "fp64_flop_per_qpt": flops, "fp64_tflops": (flops * P_local / (kern_ms * 1e-3) / 1e12) if flops else None,
-                         "fp64_vector_frac": (flops * P_local / (kern_ms * 1e-3) / 1e12 / FP64_VEC_PEAK_TFLOPS) if flops else None,
-                         # FP64 issue roofline: a wave64 FP64 VALU instruction occupies its SIMD for 4 cycles (16 FMA lanes per clock and SIMD = the
-                         # 78.6 TFLOP/s vector peak); issue time = instructions per wave x 4 cycles x waves per SIMD / 2.4 GHz
-                         "fp64_issue": ({"valu_insts_per_wave": valu_per_wave, "ms_at_full_issue": valu_per_wave * 4.0 * (P_local / 64.0 / 1024.0) / 2.4e9 * 1e3,
-                                         "frac": valu_per_wave * 4.0 * (P_local / 64.0 / 1024.0) / 2.4e9 * 1e3 / kern_ms} if valu_per_wave else None),
-                         "bytes_moved_per_qpt_note": "by construction the launch moves 648 B/qpt (read ~6 velocity / coordinate, 15 state, 6 stress doubles; write 28 state, 6 stress, "
-                                                      "26 record doubles: no Jacobian field, effective shear rate from state slot 0); frac stays priced at SURVEY 8(d)'s 928 B/qpt",
-                         "note": "the contract's HBM fraction of the ALGORITHMIC bytes (928 B/qpt) is reported in frac; the launch is bound by FP64 VALU issue at the clock "
-                                 "the chip sustains at its 1 400 W package limit (~1.93 GHz, not the nominal 2.4 GHz the fp64_issue figures are priced at): SQ counters "
-                                 + ("(profiles/r06_sq_fcc_voce.txt) show the VALU busy 90 % of the wave cycles and waiting 12 % of them, 6 943 VALU instructions per wave, "
-                                    "no scratch (round 4: 86 % / 19.5 % / 6 845; profiles/r05_kernel_experiments.txt); " if args.model == "fcc_voce" else
-                                    f"of the Kocks-Mecking launches (main + tail) in profiles/r06_sq_{args.model}.txt; fp64_* figures are quoted for the Voce kernel only; ")
-                                 + "traffic = L2-boundary bytes from the PMC "
-                                 "passes of THIS kernel build and instantiation (profiles/*_pmc_traffic.json with the library's kernel_build_id; null otherwise); "
-                                 "roofline_pcg_apply is the HBM-bound half of the metric"},
-            "roofline_pcg_apply": {"kernel": ("k_ea_apply_p1 (element mat-vec)" if ea_streamed else "k_grad_apply_p1<LVEC,GEO,CMP> (AddMultGradPA / matrix-free element-assembly action + gather/scatter)"), "bound": "hbm",
-                                   "achieved": moved * P_local / (apply_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                   "frac": moved * P_local / (apply_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                   "traffic": traffic["k_grad_apply_p1"] * P_local if "k_grad_apply_p1" in traffic else None,
-                                   "bytes_per_qpt": moved, "avg_kernel_ms": apply_ms,
-                                   "geometry_recomputed": geo, "compact_tangent": compact,
-                                   "survey_8d_bytes_per_qpt": APPLY_BYTES_PER_QPT, "survey_8d_equivalent_gbs": apply_gbs,
-                                   "note": "bytes_per_qpt = what this kernel has to move (tangent 26 or 36 doubles [+ 10 geometry doubles when streamed] + "
-                                           "L-vector gather/scatter); SURVEY 8(d) prices the reference's algorithm at 408 B/qpt (tangent 36 + Jacobian 9 + "
-                                           "E-vector x 3 + y 3), survey_8d_equivalent_gbs is the rate a kernel streaming those bytes would need for the same time",
-                                   "pcg_iteration_frac": (moved * P_local + PCG_VEC_BYTES_PER_DOF * ndof_local) / (pcg_ms * 1e-3 / max(pc["iters"], 1)) / 1e9 / HBM_PEAK_GBS},
-        }
+                     "note": "rccl: ncclCommCount of the library's communicator; ipc: shared-device inter-process transport (more ranks than devices)"}}
+        if full:
+            out.update({"pcg_iters_per_s": pcg_it_s, "pcg_iters": pc["iters"], "pcg_ms_per_iter": pcg_ms / max(pc["iters"], 1), "pcg_wall_s": t_pcg_wall})
+        out["nonconverged_points"] = m["failed"]
+        out["local_solver_evals"] = dict(hist_dict(nfev), note="residual/Jacobian evaluations of the 8-unknown point solve per quadrature point (rank 0), last timed pass")
+        if full:
+            out["elastic_regime"] = elastic
+        if kinematic is not None:
+            out["kinematic_state"] = kinematic
+        out["roofline"] = {"kernel": f"k_model_setup<{'KM-DD' if 'kmdd' in args.model else 'Voce'}> (fused node gather + grad_calc + ExaCMech update + tangent)", "bound": "hbm",
+                          "achieved": model_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": model_gbs / HBM_PEAK_GBS,
+                          "traffic": traffic["k_model_setup"] * P_local if "k_model_setup" in traffic else None, "traffic_source": traffic.get("_file"), "kernel_build_id": kid,
+                          "bytes_per_qpt": MODEL_BYTES_PER_QPT, "avg_kernel_ms": kern_ms,
+                          # the same launch priced at what it moves by construction on the record route (648 B/qpt): the figure to compare with PMC traffic
+                          "frac_on_bytes_moved": (648.0 * P_local / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if (records and args.model in ("fcc_voce", "bcc_voce", "fcc_voce_nl")) else None,
+                          "state_key": "value / roofline: converged launch of the last --solve-steps step of a real Newton/PCG solve (since round 4); `kinematic_state` "
+                                       "(prescribed-velocity passes, the benchmark state of rounds 1-3) is reported under its own key with --full: compare rounds on like keys",
+                          "bytes_written_per_qpt_note": ("this launch writes the 26-number gradient record instead of the 36 tangent entries (AssembleGradPA fused in)") if records else None,
+                          "fp64_flop_per_qpt": flops, "fp64_tflops": (flops * P_local / (kern_ms * 1e-3) / 1e12) if flops else None,
+                          "fp64_vector_frac": (flops * P_local / (kern_ms * 1e-3) / 1e12 / FP64_VEC_PEAK_TFLOPS) if flops else None,
+                          # FP64 issue roofline: a wave64 FP64 VALU instruction occupies its SIMD for 4 cycles (16 FMA lanes per clock and SIMD = the
+                          # 78.6 TFLOP/s vector peak); issue time = instructions per wave x 4 cycles x waves per SIMD / 2.4 GHz
+                          "fp64_issue": ({"valu_insts_per_wave": valu_per_wave, "ms_at_full_issue": valu_per_wave * 4.0 * (P_local / 64.0 / 1024.0) / 2.4e9 * 1e3,
+                                          "frac": valu_per_wave * 4.0 * (P_local / 64.0 / 1024.0) / 2.4e9 * 1e3 / kern_ms} if valu_per_wave else None),
+                          "bytes_moved_per_qpt_note": "by construction the launch moves 648 B/qpt (read ~6 velocity / coordinate, 15 state, 6 stress doubles; write 28 state, 6 stress, "
+                                                       "26 record doubles: no Jacobian field, effective shear rate from state slot 0); frac stays priced at SURVEY 8(d)'s 928 B/qpt",
+                          "note": "the contract's HBM fraction of the ALGORITHMIC bytes (928 B/qpt) is reported in frac; the launch is bound by FP64 VALU issue at the clock "
+                                  "the chip sustains at its 1 400 W package limit (~1.93 GHz, not the nominal 2.4 GHz the fp64_issue figures are priced at): SQ counters "
+                                  + ("(profiles/r06_sq_fcc_voce.txt) show the VALU busy 90 % of the wave cycles and waiting 12 % of them, 6 943 VALU instructions per wave, "
+                                     "no scratch (round 4: 86 % / 19.5 % / 6 845; profiles/r05_kernel_experiments.txt); " if args.model == "fcc_voce" else
+                                     f"of the Kocks-Mecking launches (main + tail) in profiles/r06_sq_{args.model}.txt; fp64_* figures are quoted for the Voce kernel only; ")
+                                  + "traffic = L2-boundary bytes from the PMC "
+                                  "passes of THIS kernel build and instantiation (profiles/*_pmc_traffic.json with the library's kernel_build_id; null otherwise); "
+                                  "roofline_pcg_apply is the HBM-bound half of the metric"}
+        if full:
+            apply_gbs = APPLY_BYTES_PER_QPT * P_local / (apply_ms * 1e-3) / 1e9
+            out["roofline_pcg_apply"] = {"kernel": ("k_ea_apply_p1 (element mat-vec)" if ea_streamed else "k_grad_apply_p1<LVEC,GEO,CMP> (AddMultGradPA / matrix-free element-assembly action + gather/scatter)"), "bound": "hbm",
+                                          "achieved": moved * P_local / (apply_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                          "frac": moved * P_local / (apply_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                          "traffic": traffic["k_grad_apply_p1"] * P_local if "k_grad_apply_p1" in traffic else None,
+                                          "bytes_per_qpt": moved, "avg_kernel_ms": apply_ms,
+                                          "geometry_recomputed": geo, "compact_tangent": compact,
+                                          "survey_8d_bytes_per_qpt": APPLY_BYTES_PER_QPT, "survey_8d_equivalent_gbs": apply_gbs,
+                                          "note": "bytes_per_qpt = what this kernel has to move (tangent 26 or 36 doubles [+ 10 geometry doubles when streamed] + "
+                                                  "L-vector gather/scatter); SURVEY 8(d) prices the reference's algorithm at 408 B/qpt (tangent 36 + Jacobian 9 + "
+                                                  "E-vector x 3 + y 3), survey_8d_equivalent_gbs is the rate a kernel streaming those bytes would need for the same time",
+                                          "pcg_iteration_frac": (moved * P_local + PCG_VEC_BYTES_PER_DOF * ndof_local) / (pcg_ms * 1e-3 / max(pc["iters"], 1)) / 1e9 / HBM_PEAK_GBS}
         if solve is not None:
             out["newton_pcg_solve"] = solve
         if in_solve is not None:
@@ -676,7 +695,7 @@ def main():
             except Exception:
                 pass
             out["adapter_route"] = adapter
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             try:
                 voce = np.loadtxt(os.path.join(ROOT, "tests", "golden", "refdata", "props_cp_voce.txt")).ravel()
                 out["cpu_baseline"] = cpu_baseline(props, gpu_step=gpu_config1_step(L, voce))

@@ -1,6 +1,7 @@
 #!/bin/bash
 # run on the GPU box: the bench records of the round-6 evidence set -> gpurun_out/r06_*.json.  bench.py fills roofline.traffic from profiles/r06_pmc_traffic.json when that file
 # carries the loaded library's kernel_build_id (scripts/profile_round6.sh puts it there before it calls this script), so these records are taken AFTER the counter passes.
+export EXA_BENCH_FULL=1     # every bench.py run below is the --full one: the blocks and the dispatch sequence it reads come from it
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 T=r06
 python bench.py --gpus 1 --steps 20 --warmup 5 2> gpurun_out/${T}_bench_driver_form.err | grep '^{"metric"' > gpurun_out/${T}_bench_driver_form.json

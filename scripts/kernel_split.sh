@@ -1,5 +1,6 @@
 #!/bin/bash
 # run on the GPU box: per-dispatch durations of the constitutive kernel (main launch and tail launch of the split) for one model
+export EXA_BENCH_FULL=1     # every bench.py run below is the --full one: the blocks and the dispatch sequence it reads come from it
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 tag=${1:-ksplit}
 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/$tag -- python bench.py --model ${MODEL:-bcc_kmdd} --steps 20 --warmup 2 --pcg-iters 10 --no-cpu-baseline > gpurun_out/$tag.log 2>&1

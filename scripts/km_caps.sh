@@ -4,5 +4,5 @@
 MODEL=${MODEL:-fcc_kmdd}
 cd $GRAFT_REPO_ROOT
 for cap in "$@"; do
-  env ${cap:+EXA_NEWTON_CAP=$cap} python bench.py --model $MODEL --steps 5 --warmup 1 --pcg-iters 10 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$MODEL cap=[${cap:-controller}]', 'kernel_ms %.3f' % d['roofline']['avg_kernel_ms'], 'elastic_ms %.3f' % d['elastic_regime']['avg_kernel_ms'], 'fail', d['nonconverged_points'])"
+  env ${cap:+EXA_NEWTON_CAP=$cap} python bench.py --full --model $MODEL --steps 5 --warmup 1 --pcg-iters 10 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$MODEL cap=[${cap:-controller}]', 'kernel_ms %.3f' % d['roofline']['avg_kernel_ms'], 'elastic_ms %.3f' % d['elastic_regime']['avg_kernel_ms'], 'fail', d['nonconverged_points'])"
 done

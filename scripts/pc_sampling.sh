@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 tag=${1:-pcs}
 export ROCPROFILER_PC_SAMPLING_BETA_ENABLED=1
-CMD="python bench.py --model ${MODEL:-fcc_voce} --steps ${STEPS:-20} --warmup 1 --pcg-iters 10 --no-cpu-baseline"
+CMD="python bench.py --full --model ${MODEL:-fcc_voce} --steps ${STEPS:-20} --warmup 1 --pcg-iters 10 --no-cpu-baseline"
 for method in stochastic host_trap; do
   unit=cycles; intv=65536
   if [ $method = host_trap ]; then unit=time; intv=1; fi

@@ -2,7 +2,7 @@
 # run on the GPU box: instruction-cache counters of the constitutive kernel (kinematic state)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export EXA_BENCH_SOLVE_STEPS=0
-CMD="python bench.py --model ${MODEL:-fcc_voce} --steps 3 --warmup 1 --pcg-iters 10 --no-cpu-baseline"
+CMD="python bench.py --full --model ${MODEL:-fcc_voce} --steps 3 --warmup 1 --pcg-iters 10 --no-cpu-baseline"
 tag=${1:-pmc_icache}
 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_IFETCH --output-format csv -d gpurun_out/$tag -- $CMD > gpurun_out/$tag.log 2>&1
 python - <<PY

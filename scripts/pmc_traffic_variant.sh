@@ -1,5 +1,6 @@
 #!/bin/bash
 # run on the GPU box: rebuild the model kernel with TUNE flags and print its HBM traffic per point (raw FETCH_SIZE / WRITE_SIZE)
+export EXA_BENCH_FULL=1     # every bench.py run below is the --full one: the blocks and the dispatch sequence it reads come from it
 cd $GRAFT_REPO_ROOT/exaconstit_amd/csrc
 for cfg in "$@"; do
   rm -f model_kernels.o; make -s -j8 TUNE="$cfg" 2>&1 | grep -E "error"

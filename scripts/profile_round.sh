@@ -2,6 +2,7 @@
 # run on the GPU box: the judged profile set of a round -> gpurun_out/<tag>_*  (copy the summaries into profiles/ afterwards)
 #   1. rocprofv3 --kernel-trace --stats of the default bench command
 #   2. separate --pmc FETCH_SIZE and --pmc WRITE_SIZE passes (MI355X_MICROARCH.md: they do not fit in one pass)
+export EXA_BENCH_FULL=1     # every bench.py run below is the --full one: the blocks and the dispatch sequence it reads come from it
 tag=${1:-r02}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 CMD="python bench.py --steps ${STEPS:-100} --warmup 5 --pcg-iters 100 --no-cpu-baseline ${BENCH_ARGS}"

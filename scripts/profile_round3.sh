@@ -3,6 +3,7 @@
 #   1. scripts/profile_round.sh r03: kernel + marker trace of the default bench command, region summary, FETCH/WRITE passes (fcc_voce)
 #   2. FETCH/WRITE passes of the BCC Kocks-Mecking launch (BASELINE config 3) -> per-model traffic json
 #   3. SQ counters of both constitutive kernels, FP64 instruction counts of the Voce kernel
+export EXA_BENCH_FULL=1     # every bench.py run below is the --full one: the blocks and the dispatch sequence it reads come from it
 cd $GRAFT_REPO_ROOT
 STEPS=${STEPS:-100} bash scripts/profile_round.sh r03
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT

@@ -4,6 +4,7 @@
 #   2. FETCH_SIZE / WRITE_SIZE passes per crystal model (separate passes, kinematic state: the counters serialise every dispatch) -> per-model
 #      traffic json, stamped with the library's kernel build id (bench.py refuses a file of another build)
 #   3. SQ counters of the three constitutive kernels, FP64 instruction counts of the Voce kernel (stamped as well)
+export EXA_BENCH_FULL=1     # every bench.py run below is the --full one: the blocks and the dispatch sequence it reads come from it
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 T=r05
 KID=$(python -c "import exaconstit_amd.lib as L; print(L.exa_kernel_build_id().decode())")

@@ -5,6 +5,7 @@
 #   2. bench records: driver form (--steps 20 --warmup 5), BCC / FCC Kocks-Mecking at 128^3, 64^3 (identity and true Jacobi), 128^3 true Jacobi, config-5 rates
 #   3. FETCH_SIZE / WRITE_SIZE passes per crystal model (kinematic state) + the staged AOS launch of the adapter route + the p = 2 kernels -> traffic json
 #   4. SQ counters of the constitutive kernels (element-blocked record launch per model, staged AOS launch, p = 2 launch), FP64 instruction counts of the Voce kernel
+export EXA_BENCH_FULL=1     # every bench.py run below is the --full one: the blocks and the dispatch sequence it reads come from it
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 T=r06
 KID=$(python -c "import exaconstit_amd.lib as L; print(L.exa_kernel_build_id().decode())")

@@ -17,7 +17,7 @@ for n in (12800, 3 * 65 * 65, 3 * 129 * 129):      # ~100 kB, one 64^3 face (3 d
     assert L.exa_rccl_microbench(2000, n, o, err, 256) == 0, err.value
     out["rccl_n%d" % n] = {"us_allreduce_16B": o[0], "us_sendrecv_self": o[1], "bytes": 8 * n}
 def bench(N, **env):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(N), "--steps", "100", "--pcg-iters", "400", "--no-cpu-baseline", "--no-adapter-route", "--solve-steps", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", str(N), "--steps", "100", "--pcg-iters", "400", "--no-cpu-baseline", "--no-adapter-route", "--solve-steps", "0"],
                        capture_output=True, text=True, env=dict(os.environ, EXA_PCG_GRAPH="0", **env))
     line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert line, r.stderr[-2000:]

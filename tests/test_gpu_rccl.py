@@ -85,13 +85,14 @@ def test_bench_ranks_under_torchrun(tmp_path, nproc):
     decomposition, 3 neighbours per rank; at most 4 rank processes, so that the test and its ranks keep within 6 processes with the GPU open - the
     2 x 2 x 2 decomposition of the driver's N = 8 SCALE run is checked in one process, test_gpu_multirank.py): torch's process group and the library's own communicator
     side by side, max-over-ranks timing, one JSON line from rank 0 that names the transport, the rank count the transport itself reports
-    (ncclCommCount over RCCL; the shared-device transport on a one-GPU box) and every rank's share of the partition."""
+    (ncclCommCount over RCCL; the shared-device transport on a one-GPU box) and every rank's share of the partition.  --full: the continued solve
+    (roofline.in_solve) runs across the ranks too."""
     import torch
     root = os.path.dirname(HERE)
     ss = 3
     env = dict(os.environ, EXA_BENCH_N="32", EXA_BENCH_SOLVE_STEPS=str(ss), EXA_BENCH_SOLVE_STEPS_TOTAL=str(ss + 1)); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # (the driver's line carries no size flags)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1", "--master-port", str(29573 + nproc),
-           os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1"]
+           os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -103,6 +104,22 @@ def test_bench_ranks_under_torchrun(tmp_path, nproc):
     assert [p["rank"] for p in pr] == list(range(nproc)) and sum(p["elements"] for p in pr) == 32 ** 3
     assert all(p["neighbours"] == (1 if nproc == 2 else 3) and p["halo_bytes_per_exchange"] > 0 for p in pr)
     assert d["roofline"]["in_solve"]["solved_to_step"] == ss + 1 and os.path.basename(d["library"]["path"]).startswith("libexaconstit_hip")
+
+
+def test_bench_plain_line(tmp_path):
+    """A plain `python bench.py` (no --full) does what `value` needs: the real solve to the benchmark state, the warm-up and timed passes, the dump and
+    the line - none of the blocks that --full adds.  Small RVE, 3 solve steps."""
+    root = os.path.dirname(HERE)
+    env = dict(os.environ, EXA_BENCH_N="16", EXA_BENCH_SOLVE_STEPS="3")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["value"] > 0 and d["unit"] == "qpt-updates/s" and d["higher_is_better"] and d["dtype"] == "f64" and d["steps"] == 3 and d["warmup"] == 1
+    assert abs(d["ms_per_step"] - 8 * 16 ** 3 / d["value"] * 1e3) < 1e-9 * d["ms_per_step"] and d["nonconverged_points"] == 0
+    assert d["newton_pcg_solve"]["steps"] == 3 and d["roofline"]["avg_kernel_ms"] > 0 and "in_solve" not in d["roofline"]
+    assert not {"pcg_iters_per_s", "roofline_pcg_apply", "elastic_regime", "kinematic_state", "adapter_route", "cpu_baseline"} & set(d)
+    assert np.load(tmp_path / "stress.npy").shape == (8 * 16 ** 3, 6) and np.load(tmp_path / "state.npy").shape == (8 * 16 ** 3, 28)
 
 
 def test_bench_order2_line():
