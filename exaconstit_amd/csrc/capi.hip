@@ -40,6 +40,8 @@ int exa_launch_ea_diag_gen(exa_ctx*, double*, hipStream_t);
 int exa_launch_ea_export_gen(exa_ctx*, double*, hipStream_t);
 int exa_launch_pa_apply_gen(exa_ctx*, const double*, double*, hipStream_t);
 int exa_launch_pa_diag_gen(exa_ctx*, double*, hipStream_t);
+int exa_launch_tet_setup(exa_ctx*, double, const double*, const double*, hipStream_t);
+int exa_launch_tet_apply(exa_ctx*, const double*, double*, const uint8_t*, const double*, hipStream_t);
 
 namespace {
 constexpr int VOL_AVG_BLOCKS = 512;
@@ -49,19 +51,28 @@ int fail(exa_ctx* ctx, int code, const char* msg) { if (ctx) ctx->err = msg; ret
 
 extern "C" {
 
-exa_ctx* exa_create(const exa_config* cfg, int* err) {
+exa_ctx* exa_create(const exa_config* cfg, int* err) { return exa_create_geom(cfg, EXA_GEOM_HEX, err); }
+
+exa_ctx* exa_create_geom(const exa_config* cfg, int geometry, int* err) {
    auto set = [&](int e) { if (err) *err = e; };
    // p = 1 and p = 2 have tuned kernels for every entry point; orders 3 ... 6 (what the reference's own unit tests run at:
    // test/mechanics_test.cpp:54,187,313,471,630) go through the run-time-order kernels.  Point ids of the tail-split list are 32-bit
-   if (!cfg || cfg->nelems <= 0 || cfg->order < 1 || cfg->order > 6) { set(EXA_ERR_ARG); return nullptr; }
-   { const int64_t np1 = cfg->order + 1; if ((int64_t)cfg->nelems * np1 * np1 * np1 >= (int64_t)INT32_MAX) { set(EXA_ERR_ARG); return nullptr; } }
+   const bool tet = geometry == EXA_GEOM_TET;
+   if (!cfg || cfg->nelems <= 0 || cfg->order < 1 || cfg->order > 6 || (geometry != EXA_GEOM_HEX && !tet)) { set(EXA_ERR_ARG); return nullptr; }
+   if (tet && cfg->order > 2) { std::fprintf(stderr, "exa_create_geom: tetrahedra run at p = 1 and p = 2\n"); set(EXA_ERR_UNSUPPORTED); return nullptr; }
+   // (no B-bar integrator for tetrahedra; refused before any device call, so that a host without a GPU sees the message too)
+   if (tet && cfg->integ == EXA_INTEG_BBAR) { std::fprintf(stderr, "exa_create_geom: integ_model BBAR is built for hexahedra only\n"); set(EXA_ERR_UNSUPPORTED); return nullptr; }
+   { const int64_t np1 = cfg->order + 1, q = tet ? (cfg->order == 1 ? 5 : 14) : np1 * np1 * np1; if ((int64_t)cfg->nelems * q >= (int64_t)INT32_MAX) { set(EXA_ERR_ARG); return nullptr; } }
    exa_ctx* ctx = new exa_ctx();
+   ctx->geom = tet ? EXA_GEOM_TET : EXA_GEOM_HEX;
    ctx->cfg = *cfg; ctx->cfg.props = nullptr;
    if (!exa_fill_mat_params(*cfg, ctx->mp, ctx->hist_init, ctx->err)) { std::fprintf(stderr, "exa_create: %s\n", ctx->err.c_str()); delete ctx; set(EXA_ERR_ARG); return nullptr; }
    if (cfg->integ != EXA_INTEG_FULL && cfg->integ != EXA_INTEG_BBAR) { delete ctx; set(EXA_ERR_ARG); return nullptr; }
    // the reference has no partial-assembly gradient for B-bar (README.md:20; ICExaNLFIntegrator does not override AddMultGradPA)
    if (cfg->integ == EXA_INTEG_BBAR && cfg->assembly != EXA_ASSEMBLY_EA) { std::fprintf(stderr, "exa_create: integ_model BBAR requires element (or full) assembly\n"); delete ctx; set(EXA_ERR_UNSUPPORTED); return nullptr; }
-   ctx->p = cfg->order; const int np = ctx->p + 1; ctx->n = np * np * np; ctx->Q = ctx->n; ctx->E = cfg->nelems; ctx->P = (int64_t)ctx->E * ctx->Q;
+   ctx->p = cfg->order; const int np = ctx->p + 1; ctx->n = np * np * np; ctx->Q = ctx->n; ctx->E = cfg->nelems;
+   if (tet) { ctx->n = ctx->p == 1 ? 4 : 10; ctx->Q = ctx->p == 1 ? 5 : 14; }
+   ctx->P = (int64_t)ctx->E * ctx->Q;
    ctx->nstatev = ecmdev::NSTATEV;
    if (cfg->device >= 0) { if (hipSetDevice(cfg->device) != hipSuccess) { delete ctx; set(EXA_ERR_HIP); return nullptr; } }
    if (hipGetDevice(&ctx->device) != hipSuccess) { std::fprintf(stderr, "exa_create: no HIP device available\n"); delete ctx; set(EXA_ERR_HIP); return nullptr; }
@@ -71,7 +82,8 @@ exa_ctx* exa_create(const exa_config* cfg, int* err) {
       static bool told = false;
       if (!told) { told = true; std::fprintf(stderr, "exaconstit_hip: Kocks-Mecking kinetics with p = %g, q = %g: the regime p, q != 1 is not pinned to a reference vector (DESIGN.md section 5)\n", ctx->mp.p, ctx->mp.q); }
    }
-   exa_build_ref_elem(ctx->p, ctx->G_host, ctx->W_host);
+   if (tet) exa_build_ref_elem_tet(ctx->p, ctx->G_host, ctx->W_host, nullptr);
+   else exa_build_ref_elem(ctx->p, ctx->G_host, ctx->W_host);
    bool ok = true;
    ok = ok && hipMalloc(&ctx->G_dev, sizeof(double) * ctx->G_host.size()) == hipSuccess;
    ok = ok && hipMalloc(&ctx->W_dev, sizeof(double) * ctx->W_host.size()) == hipSuccess;
@@ -92,7 +104,7 @@ void exa_destroy(exa_ctx* ctx) {
    if (!ctx) return;
    (void)hipFree(ctx->n2e_off); (void)hipFree(ctx->n2e_idx); (void)hipFree(ctx->ev_det);
    (void)hipFree(ctx->G_dev); (void)hipFree(ctx->W_dev); (void)hipFree(ctx->fail_count_dev); (void)hipFree(ctx->tail_dev); (void)hipFree(ctx->tail2_dev); (void)hipFree(ctx->resume_dev[0]); (void)hipFree(ctx->resume_dev[1]); (void)hipFree(ctx->scratch_dev);
-   (void)hipFree(ctx->dmat); (void)hipFree(ctx->pa); (void)hipFree(ctx->emat); (void)hipFree(ctx->eDS); (void)hipFree(ctx->T1_dev); (void)hipFree(ctx->pa_c); (void)hipFree(ctx->tbuf); (void)hipFree(ctx->vgrad_ref);
+   (void)hipFree(ctx->dmat); (void)hipFree(ctx->pa); (void)hipFree(ctx->emat); (void)hipFree(ctx->eDS); (void)hipFree(ctx->T1_dev); (void)hipFree(ctx->pa_c); (void)hipFree(ctx->tbuf); (void)hipFree(ctx->vgrad_ref); (void)hipFree(ctx->tet_rec);
    delete ctx;
 }
 
@@ -100,6 +112,7 @@ const char* exa_last_error(const exa_ctx* ctx) { return ctx ? ctx->err.c_str() :
 int exa_num_state_vars(const exa_ctx* ctx) { return ctx ? ctx->nstatev : EXA_ERR_ARG; }
 int exa_nodes_per_elem(const exa_ctx* ctx) { return ctx ? ctx->n : EXA_ERR_ARG; }
 int exa_qpts_per_elem(const exa_ctx* ctx) { return ctx ? ctx->Q : EXA_ERR_ARG; }
+int exa_element_geometry(const exa_ctx* ctx) { return ctx ? ctx->geom : EXA_ERR_ARG; }
 
 int exa_shape_table(const exa_ctx* ctx, double* G_host, double* W_host) {
    if (!ctx) return EXA_ERR_ARG;
@@ -110,8 +123,8 @@ int exa_shape_table(const exa_ctx* ctx, double* G_host, double* W_host) {
 
 int exa_set_quadrature_layout(exa_ctx* ctx, int layout) {
    if (!ctx || (layout != EXA_QLAYOUT_AOS && layout != EXA_QLAYOUT_EB64)) return fail(ctx, EXA_ERR_ARG, "exa_set_quadrature_layout: bad argument");
-   if (layout == EXA_QLAYOUT_EB64 && !((ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL) || ctx->p == 2))
-      return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_set_quadrature_layout: the element-blocked layout is built for p = 1 full integration and for p = 2");
+   if (layout == EXA_QLAYOUT_EB64 && !(exa_is_hex(ctx) && ((ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL) || ctx->p == 2)))
+      return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_set_quadrature_layout: the element-blocked layout is built for hexahedra at p = 1 full integration and at p = 2");
    ctx->qblk = (layout == EXA_QLAYOUT_EB64); ctx->have_resid = false; ctx->have_grad = false;
    return EXA_OK;
 }
@@ -177,6 +190,7 @@ int exa_model_setup_lvec_records(exa_ctx* ctx, double dt, const double* x_lvec, 
    if (!ctx || !x_lvec || !v_lvec || !stress0 || !state0 || !stress1 || !state1) return fail(ctx, EXA_ERR_ARG, "exa_model_setup_lvec_records: null pointer");   // J_out may be null
    if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_model_setup_lvec_records: call exa_set_connectivity first");
    if (!(dt > 0.0)) return fail(ctx, EXA_ERR_ARG, "exa_model_setup_lvec_records: dt must be positive");
+   if (!exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_model_setup_lvec_records: the record-writing constitutive launches are built for hexahedra (tetrahedra: exa_model_setup_lvec + exa_grad_setup)");
    const bool p1 = ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL, p2 = ctx->p == 2;      // p = 2: plain or B-bar, behind the geometry pre-pass (a Jacobian field is part of it)
    if (!(p1 || p2) || (!ctx->qblk && !p1) || ctx->tangent_form != EXA_TANGENT_DEV5_BULK || !(ctx->cfg.assembly == EXA_ASSEMBLY_PA || ctx->ea_matfree))
       return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_model_setup_lvec_records: needs p = 1 full integration (either layout) or p = 2 (element-blocked layout), the compact tangent form and PA or matrix-free EA");
@@ -287,7 +301,7 @@ int exa_residual_apply(exa_ctx* ctx, double* y, exa_stream s) {
 
 // element-assembly contexts whose L-vector action is computed from the point records (exa_set_ea_matrix_free)
 static bool ea_from_records(const exa_ctx* ctx) {
-   return ctx->ea_matfree && (ctx->n == 27 || (ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL));
+   return exa_is_hex(ctx) && ctx->ea_matfree && (ctx->n == 27 || (ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL));
 }
 
 // element matrices from the point records (and eDS) of the last exa_grad_setup
@@ -302,6 +316,7 @@ static int assemble_ea(exa_ctx* ctx, hipStream_t s) {
 
 int exa_set_tangent_form(exa_ctx* ctx, int form) {
    if (!ctx || (form != EXA_TANGENT_FULL && form != EXA_TANGENT_DEV5_BULK && form != EXA_TANGENT_DEV5_BULK_GEO)) return fail(ctx, EXA_ERR_ARG, "exa_set_tangent_form: bad argument");
+   if (form != EXA_TANGENT_FULL && !exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_set_tangent_form: the compact records serve the hexahedron actions");
    if (form == EXA_TANGENT_DEV5_BULK_GEO && !(ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL && ctx->cfg.assembly == EXA_ASSEMBLY_PA))
       return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_set_tangent_form: the compact record with geometry serves the E-vector action of p = 1 partial assembly");
    if (form != ctx->tangent_form && ctx->pa_c) { (void)hipFree(ctx->pa_c); ctx->pa_c = nullptr; ctx->pac_pairs = 0; ctx->have_grad = false; }      // (records of another shape)
@@ -351,16 +366,24 @@ int exa_grad_setup(exa_ctx* ctx, double dt, const double* J, const double* C, ex
    ctx->grad_records_only = false;
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
       const bool bbar = ctx->cfg.integ == EXA_INTEG_BBAR;
-      ctx->ea_generic = bbar || ctx->p != 1;
+      ctx->ea_generic = bbar || ctx->p != 1 || !exa_is_hex(ctx);
       if (bbar) {
          if (!ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, sizeof(double) * 3 * ctx->n * PA_BLK * (size_t)((ctx->E + PA_BLK - 1) / PA_BLK)));
          rc = exa_launch_eds(ctx, J, S(s));
          if (rc) return rc;
       }
       ctx->emat_valid = false;
-      if (!ea_from_records(ctx)) rc = assemble_ea(ctx, S(s));   // matrix-free: assembled on demand only
-   } else if (ctx->p != 1) {
+      if (!ea_from_records(ctx) && !(ctx->ea_matfree && !exa_is_hex(ctx))) rc = assemble_ea(ctx, S(s));   // matrix-free: assembled on demand only
+   } else if (ctx->p != 1 || !exa_is_hex(ctx)) {
       if (!ctx->tbuf) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->tbuf, sizeof(double) * 9 * ctx->P));
+   }
+   if (rc == EXA_OK && !exa_is_hex(ctx) && ctx->p == 1) {
+      // element records of the fused p = 1 action: built here where that action runs (PA or matrix-free EA, atomic mode, not switched off),
+      // otherwise by the first exa_grad_apply_lvec that needs them (J and C must then stay as they are until the next exa_grad_setup)
+      ctx->tet_J = J; ctx->tet_C = C; ctx->tet_dt = dt;
+      const bool fused = ctx->tet_fused && !ctx->det && (ctx->cfg.assembly == EXA_ASSEMBLY_PA || ctx->ea_matfree);
+      ctx->tet_rec_stale = !fused;
+      if (fused) rc = exa_launch_tet_setup(ctx, dt, J, C, S(s));
    }
    ctx->have_grad = (rc == EXA_OK);
    return rc;
@@ -374,7 +397,7 @@ int exa_grad_apply(exa_ctx* ctx, const double* x, double* y, exa_stream s) {
       if (int rc = assemble_ea(ctx, S(s))) return rc;
       return ctx->ea_generic ? exa_launch_ea_apply_gen(ctx, x, y, false, nullptr, nullptr, S(s)) : exa_launch_ea_apply_p1(ctx, x, y, false, nullptr, nullptr, S(s));
    }
-   if (ctx->p != 1) return exa_launch_pa_apply_gen(ctx, x, y, S(s));
+   if (ctx->p != 1 || !exa_is_hex(ctx)) return exa_launch_pa_apply_gen(ctx, x, y, S(s));
    return exa_launch_grad_apply_p1(ctx, x, y, false, nullptr, nullptr, S(s));
 }
 
@@ -386,7 +409,7 @@ int exa_grad_diagonal(exa_ctx* ctx, double* d, exa_stream s) {
       if (int rc = assemble_ea(ctx, S(s))) return rc;
       return ctx->ea_generic ? exa_launch_ea_diag_gen(ctx, d, S(s)) : exa_launch_ea_diag_p1(ctx, d, S(s));
    }
-   if (ctx->p != 1) return exa_launch_pa_diag_gen(ctx, d, S(s));
+   if (ctx->p != 1 || !exa_is_hex(ctx)) return exa_launch_pa_diag_gen(ctx, d, S(s));
    return exa_launch_grad_diag_p1(ctx, d, S(s));
 }
 
@@ -448,6 +471,7 @@ int exa_grad_apply_lvec_blocks(exa_ctx* ctx, const double* x, double* y, const u
    if (!ctx || !x || !y) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_blocks: null pointer");
    if (!ctx->conn || !ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_blocks: connectivity / gradient data not set");
    if (ctx->grad_records_only && !ctx->coords_lvec) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_blocks: name the nodal coordinates with exa_grad_set_coords");
+   if (!exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_grad_apply_lvec_blocks: block ranges are built for the hexahedron p = 1 action");
    if (ctx->det || ctx->p != 1 || ctx->cfg.integ != EXA_INTEG_FULL) return EXA_ERR_UNSUPPORTED;
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
       if (!ea_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
@@ -461,6 +485,14 @@ int exa_grad_apply_lvec_gated(exa_ctx* ctx, const double* x, double* y, const ui
    if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec: connectivity not set");
    if (!ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec called before exa_grad_setup");
    if (ctx->grad_records_only && !ctx->coords_lvec) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec: name the nodal coordinates with exa_grad_set_coords (the compact records hold no geometry)");
+   if (!exa_is_hex(ctx)) {   // tetrahedra: the fused action of tet_kernels.hip (PA, and EA from the records); assembled EA matrices through the generic kernel
+      if (ctx->det) return fail(ctx, EXA_ERR_UNSUPPORTED, "deterministic mode: the fused tetrahedron action scatters with atomics; use exa_restrict + exa_grad_apply + exa_restrict_transpose_add");
+      if (ctx->cfg.assembly == EXA_ASSEMBLY_EA && !ctx->ea_matfree) {
+         if (int rc = assemble_ea(ctx, S(s))) return rc;
+         return exa_launch_ea_apply_gen(ctx, x, y, true, mask, gate, S(s));
+      }
+      return exa_launch_tet_apply(ctx, x, y, mask, gate, S(s));
+   }
    if (ctx->det && (ctx->p != 1 || ctx->cfg.integ != EXA_INTEG_FULL))
       return fail(ctx, EXA_ERR_UNSUPPORTED, "deterministic mode: the fused L-vector action is ordered for p = 1 full integration only; use exa_restrict + exa_grad_apply + exa_restrict_transpose_add");
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
@@ -489,6 +521,7 @@ int exa_residual_lvec(exa_ctx* ctx, const double* J, const double* stress1, doub
    if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_residual_lvec: connectivity not set");
    if (!J && !(ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL && ctx->coords_lvec))
       return fail(ctx, EXA_ERR_ARG, "exa_residual_lvec: a null Jacobian field needs p = 1 full integration and nodal coordinates (exa_grad_set_coords)");
+   if (!exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_residual_lvec: the fused residual is built for hexahedra; use exa_residual_setup/apply + exa_restrict_transpose_add");
    if (ctx->det && ctx->p == 2) return fail(ctx, EXA_ERR_UNSUPPORTED, "deterministic mode: the fused p = 2 residual scatters with atomics; use exa_residual_setup/apply + exa_restrict_transpose_add");
    if (ctx->p == 2) {
       if (ctx->cfg.integ == EXA_INTEG_BBAR && !ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, sizeof(double) * 3 * ctx->n * PA_BLK * (size_t)((ctx->E + PA_BLK - 1) / PA_BLK)));

@@ -29,6 +29,10 @@ struct exa_ctx {
    ecmdev::MatParams mp;
    int p, n, Q, E;
    int64_t P;               // E * Q
+   int geom = EXA_GEOM_HEX; // EXA_GEOM_*: tetrahedra take the table-driven kernels and the fused action of tet_kernels.hip, never a hexahedron fast path
+   double* tet_rec = nullptr;               // tetrahedra, p = 1: element records of the fused action (tet_kernels.hip)
+   bool tet_fused = true;                   // tetrahedra: exa_grad_setup builds the element records for the fused action (exa_tet_set_fused_action)
+   bool tet_rec_stale = false; const double* tet_J = nullptr; const double* tet_C = nullptr; double tet_dt = 0.0;   // records not built yet: built by the first action
    int nstatev;
    int device;
    std::string err;
@@ -71,6 +75,9 @@ struct exa_ctx {
 // host-side reference element (H1 hex of order p at (p+1)^3 Gauss-Legendre points), src/mechanics_operator.cpp:237-261
 int exa_ensure_p2_tables(struct exa_ctx* ctx);   // gen_kernels.hip
 void exa_build_ref_elem(int p, std::vector<double>& G, std::vector<double>& W);
+// reference tetrahedron of order p = 1, 2; false for other orders.  N (n, Q) shape values, may be null
+bool exa_build_ref_elem_tet(int p, std::vector<double>& G, std::vector<double>& W, std::vector<double>* N);
+static inline bool exa_is_hex(const exa_ctx* ctx) { return ctx->geom == EXA_GEOM_HEX; }
 // one-dimensional tables [1D Gauss point][B_0..B_p, D_0..D_p] of the order-p nodal basis and the lexicographic -> native node map
 void exa_build_1d_tables(int p, std::vector<double>& T1, std::vector<int>& nat);
 bool exa_fill_mat_params(const exa_config& cfg, ecmdev::MatParams& mp, double* hist_init, std::string& err);

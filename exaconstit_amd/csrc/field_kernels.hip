@@ -50,7 +50,8 @@ __device__ __forceinline__ double det3(const double* Jq, const int st) {
 constexpr int NACC = 25;
 __device__ __forceinline__ constexpr int acc_slot(int k) { return k < 2 ? k : k + 2; }
 
-template <bool QB, bool P1, bool HAVE_J>
+// TET: straight-sided tetrahedra: volume = sum_q W_q detJ from the Jacobian field, centroid = mean of the four vertices
+template <bool QB, bool P1, bool HAVE_J, bool TET = false>
 __global__ __launch_bounds__(64) void k_element_fields(const int64_t E, const int Q, const int n, const int np, const double* __restrict__ W,
                                                        const double* __restrict__ J, const double* __restrict__ S, const double* __restrict__ X,
                                                        const double* __restrict__ xe, double* __restrict__ out, const Basis1D basis) {
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(64) void k_element_fields(const int64_t E, const in
                }
             }
             if constexpr (!HAVE_J) detJ = det3(Jl, 1);
-         } else {
+         } else if constexpr (!TET) {
             // x(xi_q) = sum_a N_a(xi_q) x_a, lexicographic node walk
             const int qx = q % np, qy = (q / np) % np, qz = q / (np * np);
             const double* xel = xe + (int64_t)3 * n * e;
@@ -160,6 +161,11 @@ __global__ __launch_bounds__(64) void k_element_fields(const int64_t E, const in
       double* o = sh + t * NF;
       o[EXA_F_VOLUME] = vol;
       o[EXA_F_CENTROID] = cx * iv; o[EXA_F_CENTROID + 1] = cy * iv; o[EXA_F_CENTROID + 2] = cz * iv;
+      if constexpr (TET) {
+         const double* xel = xe + (int64_t)3 * n * e;
+#pragma unroll
+         for (int d = 0; d < 3; d++) o[EXA_F_CENTROID + d] = 0.25 * (xel[n * d] + xel[1 + n * d] + xel[2 + n * d] + xel[3 + n * d]);
+      }
 #pragma unroll
       for (int k = 0; k < 6; k++) s[k] *= iv;
 #pragma unroll
@@ -192,10 +198,10 @@ __global__ __launch_bounds__(64) void k_element_fields(const int64_t E, const in
    for (int i = t; i < NF * nvalid; i += 64) ob[i] = sh[i];
 }
 
-template <bool QB, bool P1, bool HAVE_J>
+template <bool QB, bool P1, bool HAVE_J, bool TET = false>
 void launch(const exa_ctx* ctx, const double* J, const double* S, const double* X, const double* xe, double* out, const Basis1D& b, hipStream_t s) {
    const unsigned nb = (unsigned)((ctx->E + 63) / 64);
-   hipLaunchKernelGGL((k_element_fields<QB, P1, HAVE_J>), dim3(nb), dim3(64), 0, s, (int64_t)ctx->E, ctx->Q, ctx->n, ctx->p + 1, ctx->W_dev, J, S, X, xe, out, b);
+   hipLaunchKernelGGL((k_element_fields<QB, P1, HAVE_J, TET>), dim3(nb), dim3(64), 0, s, (int64_t)ctx->E, ctx->Q, ctx->n, ctx->p + 1, ctx->W_dev, J, S, X, xe, out, b);
 }
 
 }  // namespace
@@ -203,11 +209,17 @@ void launch(const exa_ctx* ctx, const double* J, const double* S, const double* 
 extern "C" int exa_element_fields(exa_ctx* ctx, const double* J, const double* S, const double* X, const double* xe, double* out, exa_stream str) {
    if (!ctx) return EXA_ERR_ARG;
    if (!S || !X || !xe || !out) { ctx->err = "exa_element_fields: stress, state, coordinates and output are required"; return EXA_ERR_ARG; }
-   if (!J && ctx->p != 1) { ctx->err = "exa_element_fields: a Jacobian field is required at p > 1 (only p = 1 recomputes det J from the coordinates)"; return EXA_ERR_ARG; }
+   if (!J && (ctx->p != 1 || !exa_is_hex(ctx))) { ctx->err = "exa_element_fields: a Jacobian field is required at p > 1 and for tetrahedra (only the p = 1 hexahedron recomputes det J from the coordinates)"; return EXA_ERR_ARG; }
    if (ctx->nstatev != SV) { ctx->err = "exa_element_fields: the fields read a 28-variable state"; return EXA_ERR_UNSUPPORTED; }
    if (ctx->p < 1 || ctx->p > 6) { ctx->err = "exa_element_fields: order out of range"; return EXA_ERR_UNSUPPORTED; }
    if (ctx->E == 0) return EXA_OK;
    Basis1D b{};
+   hipStream_t s = reinterpret_cast<hipStream_t>(str);
+   if (!exa_is_hex(ctx)) {
+      if (ctx->qblk) launch<true, false, true, true>(ctx, J, S, X, xe, out, b, s); else launch<false, false, true, true>(ctx, J, S, X, xe, out, b, s);
+      EXA_HIP_CHECK(ctx, hipGetLastError());
+      return EXA_OK;
+   }
    if (ctx->p > 1) {
       std::vector<double> T1; std::vector<int> nat;
       exa_build_1d_tables(ctx->p, T1, nat);
@@ -215,7 +227,6 @@ extern "C" int exa_element_fields(exa_ctx* ctx, const double* J, const double* S
       for (int q = 0; q < np; q++) for (int i = 0; i < np; i++) b.B[q * np + i] = T1[2 * np * q + i];
       for (size_t i = 0; i < nat.size(); i++) b.nat[i] = (int16_t)nat[i];
    }
-   hipStream_t s = reinterpret_cast<hipStream_t>(str);
    const bool p1 = ctx->p == 1;
    if (ctx->qblk) {
       if (p1) { if (J) launch<true, true, true>(ctx, J, S, X, xe, out, b, s); else launch<true, true, false>(ctx, J, S, X, xe, out, b, s); }

@@ -27,6 +27,7 @@
 extern "C" const int* exa_model_fail_counter_dev(exa_ctx* ctx);
 extern "C" int exa_grad_apply_lvec_blocks(exa_ctx* ctx, const double* x, double* y, const uint8_t* mask, const double* gate, int blk0, int nblk, exa_stream s);
 int exa_grad_refresh_bbar(exa_ctx* ctx, const double* J, hipStream_t s);   // gen_kernels.hip (driver-internal)
+int exa_tet_set_fused_action(exa_ctx* ctx, int on);                        // tet_kernels.hip (driver-internal)
 extern "C" int exa_grad_apply_lvec_gated(exa_ctx* ctx, const double* x, double* y, const uint8_t* mask, const double* gate, exa_stream s);
 
 
@@ -462,14 +463,19 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
    : opt_(opt), part_(part), comm_(comm) {
    EXA_HC(hipStreamCreate(&stream_)); EXA_HC(hipEventCreate(&ev0_)); EXA_HC(hipEventCreate(&ev1_));
    const bool bbar = ExaOptions::lower(opt.integ_model) == "bbar";
+   const bool tet = part.geom == 1;   // tetrahedra: table-driven kernels + the fused action of tet_kernels.hip, never a hexahedron fast path
+   if (tet && bbar) throw std::runtime_error("integ_model = \"BBAR\" is built for hexahedral meshes only (this mesh has tetrahedra)");
    exa_config cfg; cfg.model = model_id(opt); cfg.nprops = (int)props.size(); cfg.props = props.data(); cfg.temp_k = opt.temp_k; cfg.order = part.p;
    cfg.nelems = part.E; cfg.assembly = opt.assembly == Assembly::PA ? EXA_ASSEMBLY_PA : EXA_ASSEMBLY_EA; cfg.integ = bbar ? EXA_INTEG_BBAR : EXA_INTEG_FULL; cfg.device = -1;
-   int err = 0; ctx_ = exa_create(&cfg, &err);
+   int err = 0; ctx_ = exa_create_geom(&cfg, tet ? EXA_GEOM_TET : EXA_GEOM_HEX, &err);
    if (!ctx_) throw std::runtime_error("exa_create failed (" + std::to_string(err) + ")");
    this->props = props; cfg_used = cfg; cfg_used.props = nullptr;
    nn_ = part.NN; nd_ = 3 * nn_; E_ = part.E; npe_ = part.n;
-   fast_p1_ = (part.p == 1 && !bbar);          // fused L-vector kernels exist for p = 1 full integration
-   lvec_grad_ = fast_p1_ || opt.assembly == Assembly::EA || part.p == 2;   // p = 2: matrix-free action from the point records (PA and EA)
+   fast_p1_ = (part.p == 1 && !bbar && !tet);          // fused L-vector kernels exist for p = 1 full integration
+   const bool hex_p2 = part.p == 2 && !tet;
+   // EXA_TET_ACTION=generic: tetrahedra keep the table-driven PA (E-vector) / EA action (A/B switch)
+   tet_fused_ = tet && !(std::getenv("EXA_TET_ACTION") && std::string(std::getenv("EXA_TET_ACTION")) == "generic");
+   lvec_grad_ = fast_p1_ || opt.assembly == Assembly::EA || hex_p2 || tet_fused_;   // p = 2: matrix-free action from the point records (PA and EA)
    // EXA_DETERMINISTIC=1: ordered E->L sums and halo additions instead of FP64 atomics: bit-reproducible residuals, CG iterates and results.
    // The fused kernels are ordered for p = 1 full integration; the other contexts take the E-vector entries + the ordered E->L sum.
    const bool det = std::getenv("EXA_DETERMINISTIC") && std::string(std::getenv("EXA_DETERMINISTIC")) == "1";
@@ -493,19 +499,26 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
    if (const char* tc = std::getenv("EXA_TAIL_COST")) { const double v = std::atof(tc); if (v > 0.0) tail_cost_ = v; }   // A/B switch of the controller's cost model
    // element assembly: the element matrices are 2x (p = 1) to 5x (p = 2) the bytes of the records they are built from, so the action is
    // computed from the records and the matrices only exist if somebody asks for them (diagonal, export); EXA_EA_ASSEMBLED=1 streams them instead
-   if (!det_unfused && opt.assembly == Assembly::EA && (part.p == 2 || fast_p1_) && !(std::getenv("EXA_EA_ASSEMBLED") && std::string(std::getenv("EXA_EA_ASSEMBLED")) == "1"))
-      abi_check(ctx_, exa_set_ea_matrix_free(ctx_, 1), "exa_set_ea_matrix_free");
+   const bool ea_matfree = !det_unfused && opt.assembly == Assembly::EA && (hex_p2 || fast_p1_ || tet_fused_) &&
+                           !(std::getenv("EXA_EA_ASSEMBLED") && std::string(std::getenv("EXA_EA_ASSEMBLED")) == "1");
+   if (ea_matfree) abi_check(ctx_, exa_set_ea_matrix_free(ctx_, 1), "exa_set_ea_matrix_free");
+   // tetrahedra: the fused kernel runs for PA and for matrix-free EA, in atomic mode; assembled EA matrices (EXA_EA_ASSEMBLED=1) take the
+   // table-driven L-vector kernel, and the records of the fused action are then not built per Newton iteration
+   if (tet_fused_ && (det_unfused || (opt.assembly == Assembly::EA && !ea_matfree))) tet_fused_ = false;
+   // p = 1 fused action: J^-1 recomputed from the current coordinates (EXA_TET_APPLY_GEO=off: read from the element record)
+   tet_geo_ = tet_fused_ && part.p == 1 && !env_is_off("EXA_TET_APPLY_GEO");
+   if (tet) abi_check(ctx_, exa_tet_set_fused_action(ctx_, tet_fused_ ? 1 : 0), "exa_tet_set_fused_action");
    {  // compact tangent records wherever a record-based action runs: p = 1 PA / matrix-free EA with the geometry recomputed, p = 2 matrix-free
       auto env_is = [](const char* k, const char* v) { const char* e = std::getenv(k); return e && std::string(e) == v; };
       const bool ea_streamed = opt.assembly == Assembly::EA && env_is("EXA_EA_ASSEMBLED", "1");
-      compact_tangent_ = !det_unfused && !env_is("EXA_TANGENT_FORM", "full") && !ea_streamed && ((fast_p1_ && !env_is("EXA_APPLY_GEO", "off")) || part.p == 2);
+      compact_tangent_ = !det_unfused && !env_is("EXA_TANGENT_FORM", "full") && !ea_streamed && ((fast_p1_ && !env_is("EXA_APPLY_GEO", "off")) || hex_p2);
    }
    if (compact_tangent_) abi_check(ctx_, exa_set_tangent_form(ctx_, EXA_TANGENT_DEV5_BULK), "exa_set_tangent_form");
    // Gradient records straight from the constitutive launch (p = 1, compact form, identity "Jacobi" of the reference): no tangent field, no
    // defect check, no AssembleGradPA pass per Newton iteration.  EXA_TANGENT_RECORDS=off keeps the tangent field + exa_grad_setup (A/B switch);
    // true Jacobi needs the 46-double records for the diagonal and takes that route as well (SetPrecond).
    // p = 2 (round 6): the same behind the geometry pre-pass - the launch writes the 18-pair records of the matrix-free action (plain or B-bar, PA or EA)
-   const bool p2_records = part.p == 2 && !det && (opt.assembly == Assembly::PA || !(std::getenv("EXA_EA_ASSEMBLED") && std::string(std::getenv("EXA_EA_ASSEMBLED")) == "1")) &&
+   const bool p2_records = hex_p2 && !det && (opt.assembly == Assembly::PA || !(std::getenv("EXA_EA_ASSEMBLED") && std::string(std::getenv("EXA_EA_ASSEMBLED")) == "1")) &&
                            !env_is_off("EXA_P2_PREPASS");
    // (p = 1: on either layout - the reference layout through the staged launch; p = 2: element-blocked only)
    records_setup_ = (fast_p1_ || p2_records) && compact_tangent_ && fused_setup_ && !det && !env_is_off("EXA_TANGENT_RECORDS") &&
@@ -515,7 +528,7 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
    abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, tail_resume_ ? 1 : 0), "exa_set_newton_caps");   // A/B switch for measurements; the fused launch is the product path
    // internal quadrature-function layout: element-blocked on the fused p = 1 and p = 2 paths (EXA_QLAYOUT=aos switches back for A/B runs)
    const char* ql = std::getenv("EXA_QLAYOUT");
-   lvec_resid_ = fast_p1_ || (part.p == 2 && !det);      // fused L-vector residual kernels (p = 1 full integration; p = 2 plain and B-bar)
+   lvec_resid_ = fast_p1_ || (hex_p2 && !det);      // fused L-vector residual kernels (p = 1 full integration; p = 2 plain and B-bar)
    if (lvec_resid_ && !(ql && std::string(ql) == "aos")) abi_check(ctx_, exa_set_quadrature_layout(ctx_, EXA_QLAYOUT_EB64), "exa_set_quadrature_layout");
    auto qf = [&](int vdim) { return (size_t)exa_qf_size(ctx_, vdim); };
    conn.upload(part.conn); abi_check(ctx_, exa_set_connectivity(ctx_, conn.p, nn_), "exa_set_connectivity");
@@ -651,7 +664,7 @@ void NonlinearMechOperator::Setup(const double* k) {
       jac_stale_ = false;
    }
    EXA_HC(hipEventRecord(ev.b, stream_)); ev.pending = true;
-   timers.qpt_updates += (int64_t)E_ * npe_; model_calls++;
+   timers.qpt_updates += (int64_t)E_ * exa_qpts_per_elem(ctx_); model_calls++;
    model_status_pending_ = true;
    static const bool log_hist = std::getenv("EXA_NFEV_LOG") != nullptr;      // measurement aid: evaluation-count histogram of every launch on stderr (synchronises)
    if (log_hist) {
@@ -743,7 +756,7 @@ void NonlinearMechOperator::GetGradient() {
    }
    abi_check(ctx_, exa_grad_setup(ctx_, dt_, el_jac.p, matGrad.p, stream_), "exa_grad_setup");
    // geometry of the action recomputed from x_cur (unchanged until the next residual evaluation); EXA_APPLY_GEO=off streams it instead
-   if (fast_p1_ && !(std::getenv("EXA_APPLY_GEO") && std::string(std::getenv("EXA_APPLY_GEO")) == "off"))
+   if ((fast_p1_ && !(std::getenv("EXA_APPLY_GEO") && std::string(std::getenv("EXA_APPLY_GEO")) == "off")) || tet_geo_)
       abi_check(ctx_, exa_grad_set_coords(ctx_, x_cur.p), "exa_grad_set_coords");   // read by the record-based actions (PA, matrix-free EA) only
    // The reference assembles the operator diagonal here on every call, but its Jacobi smoother never reads it (dinv is built once
    // from diag = 1).  With that default the assembly is skipped: no result depends on it, and for p = 2 element
@@ -1431,7 +1444,7 @@ void SystemDriver::ComputeElementFields() {
    DevBuf<double> xe((size_t)3 * part.n * part.E), jac;
    if (fields_dev_.n != (size_t)EXA_NFIELDS * part.E) fields_dev_.alloc((size_t)EXA_NFIELDS * part.E);
    abi_check(ctx, exa_restrict(ctx, op.x_cur.p, xe.p, s), "exa_restrict");
-   if (part.p != 1) {   // p = 1: det J comes from the node coordinates inside the launch
+   if (part.p != 1 || part.geom == 1) {   // p = 1 hexahedra: det J comes from the node coordinates inside the launch
       jac.alloc((size_t)exa_qf_size(ctx, 9));
       abi_check(ctx, exa_jacobians(ctx, xe.p, jac.p, s), "exa_jacobians");
    }
@@ -1687,7 +1700,7 @@ void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool 
    const std::vector<double> fields = fields_dev_.to_host(s);
    const std::vector<double> xc = op.x_cur.to_host(s), xr = op.x_ref.to_host(s), v = v_sol.to_host(s);
    vtu::Piece p;
-   p.E = part.E; p.NN = part.NN; p.n = part.n; p.conn = part.conn.data();
+   p.E = part.E; p.NN = part.NN; p.n = part.n; p.tet = part.geom == 1; p.conn = part.conn.data();
    p.x_cur = xc.data(); p.x_ref = xr.data(); p.vel = v.data(); p.fields = fields.data(); p.attr = elem_attr.data(); p.gid = part.elem_gid.data();
    vtu::save_cycle(dir, comm.rank, comm.nranks, cycle, t, opt_.light_up, p, pvd_cycles_[dir]);
 }

@@ -139,6 +139,8 @@ class NonlinearMechOperator {
    hipStream_t stream() const { return stream_; }
    const Partition& part() const { return part_; }
    Comm& comm() { return comm_; }
+   // route of the Krylov action (Driver.mesh_info): 0 hexahedron kernels, 1 fused tetrahedron action, 2 table-driven E-vector PA, 3 table-driven EA on L-vectors
+   int action_route() const { return part_.geom != 1 ? 0 : (lvec_grad_ && tet_fused_ ? 1 : (lvec_grad_ ? 3 : 2)); }
    bool halo_overlap() const { return overlap_; }      // the gradient action overlaps the halo exchange with its interior blocks
    // data (device)
    DevBuf<double> x_ref, x_beg, x_cur, el_x, el_v, el_jac, diag, dinv, weight;
@@ -176,6 +178,8 @@ class NonlinearMechOperator {
    void ensure_mat_grad();
    bool overlap_ = false; int nblk_bdr_ = 0;   // halo exchange overlapped with the interior element blocks (several ranks, atomic p = 1 record action)
    bool fast_p1_ = true, lvec_grad_ = true, fused_setup_ = true; bool lvec_resid_ = false; bool compact_tangent_ = false;
+   bool tet_fused_ = false;       // tetrahedra: the Krylov action is the fused kernel of tet_kernels.hip (EXA_TET_ACTION=generic: the table-driven PA / EA action)
+   bool tet_geo_ = false;         // tetrahedra, p = 1 fused action: J^-1 from the nodal coordinates (exa_grad_set_coords) instead of the element record
    bool cap_auto_ = true; int newton_cap_ = 0, newton_cap2_ = 0; bool tail_resume_ = true; double tail_cost_ = 4.0;
    DevBuf<double> tmp_l_, tmp_r_, el_y_, el_x2_;
 };

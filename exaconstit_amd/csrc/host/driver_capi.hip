@@ -286,7 +286,16 @@ int exa_driver_precond_apply(exa_driver* d, const double* r, double* z) {
 }
 
 int exa_driver_num_steps(exa_driver* d) { return d->sd->options().nsteps; }
-int64_t exa_driver_local_qpts(exa_driver* d) { return (int64_t)d->sd->part.E * d->sd->part.n; }
+int64_t exa_driver_local_qpts(exa_driver* d) { return (int64_t)d->sd->part.E * d->sd->part.qpts(); }
+// out8 = { geometry (EXA_GEOM_*), order, nodes per element, points per element, local elements, local nodes, action route
+//          (NonlinearMechOperator::action_route), 0 }
+int exa_driver_mesh_info(exa_driver* d, int64_t* out8) {
+   try {
+      const Partition& p = d->sd->part;
+      out8[0] = p.geom; out8[1] = p.p; out8[2] = p.n; out8[3] = p.qpts(); out8[4] = p.E; out8[5] = p.NN; out8[6] = d->sd->oper().action_route(); out8[7] = 0;
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mesh_info: %s\n", e.what()); return -1; }
+}
 int64_t exa_driver_local_dofs(exa_driver* d) { return (int64_t)d->sd->part.NN * 3; }
 
 int exa_driver_step(exa_driver* d, int ti, char* err, int errlen) {

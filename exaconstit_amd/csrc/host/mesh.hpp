@@ -27,7 +27,8 @@ struct Partition {
    int N[3] = { 1, 1, 1 }; double len[3] = { 1, 1, 1 };
    int pg[3] = { 1, 1, 1 }, rank = 0, nranks = 1, rc[3] = { 0, 0, 0 };
    int e0[3], ne[3], nn[3];
-   int p = 1, n = 8;                 // H1 order, nodes per element (p+1)^3
+   int p = 1, n = 8;                 // H1 order, nodes per element (p+1)^3 (tetrahedra: 4 or 10)
+   int geom = 0;                     // EXA_GEOM_HEX (0) or EXA_GEOM_TET (1, file meshes only: DESIGN 4.9)
    int E = 0, NN = 0;
    std::vector<int32_t> conn;        // (n, E), native node order
    std::vector<double> X;            // byNODES (NN, 3)
@@ -37,6 +38,7 @@ struct Partition {
    // meshes read from a file (Mesh.type = "other"): grain id = element attribute, boundary ids = boundary-element attributes
    bool from_file = false; std::vector<int> elem_attr; std::vector<std::vector<uint8_t>> bdr_nodes;   // [attribute - 1][node]
    int64_t E_global() const { return (int64_t)N[0] * N[1] * N[2]; }
+   int qpts() const { return geom == 1 ? (p == 1 ? 5 : 14) : n; }   // quadrature points per element (hexahedra: n)
 
    static void split(int n, int p, int r, int& start, int& cnt) { const int b = n / p, rem = n % p; cnt = b + (r < rem ? 1 : 0); start = r * b + (r < rem ? r : rem); }
 
@@ -153,6 +155,11 @@ struct Partition {
    // centroids (the reference uses METIS through ParMesh, src/mechanics_driver.cpp:312; any partition gives the same operator) and the
    // rank keeps its elements, the nodes they touch, and one Neighbor per rank it shares nodes with (dofs ordered by global node id on
    // both sides).
+   // Tetrahedra: elements of geometry 4 (v0..v3, MFEM's vertex order) with boundary triangles (geometry 2), in the same file
+   // format; a file that mixes hexahedra and tetrahedra is refused.  A Gmsh 2.2 ASCII file (what Neper writes and what the reference's Mesh
+   // constructor reads too) is recognised by its `$MeshFormat` header: 4-node tetrahedra (type 4) and 3-node triangles (type 2), the first
+   // tag (the physical one) as the attribute; points and lines are skipped, second-order elements are refused (straight-sided geometry only).
+   // An element of non-positive volume is refused with its index.
    void build_from_mfem_mesh(const std::string& path, int rank_, int nranks_, int order = 1) {
       std::ifstream f(path);
       if (!f) throw std::runtime_error("Cannot open mesh file: " + path);
@@ -161,28 +168,71 @@ struct Partition {
          return false;
       };
       std::string line;
-      if (!next_token_line(line) || line.rfind("MFEM mesh v1.0", 0) != 0) throw std::runtime_error("Not an MFEM mesh v1.0 file: " + path);
-      p = 1; n = 8; rank = rank_; nranks = nranks_; from_file = true;
+      if (!next_token_line(line)) throw std::runtime_error("Not an MFEM mesh v1.0 file: " + path);
+      p = 1; n = 8; geom = 0; rank = rank_; nranks = nranks_; from_file = true;
       for (int d = 0; d < 3; d++) { N[d] = 0; pg[d] = 1; rc[d] = 0; e0[d] = 0; ne[d] = 0; nn[d] = 0; }
-      int nv = -1; std::vector<std::array<int, 5>> bdr;
+      std::vector<std::array<int, 5>> bdr; std::vector<std::array<int, 4>> tri;
+      if (line.rfind("$MeshFormat", 0) == 0) read_gmsh22(next_token_line, tri);
+      else if (line.rfind("MFEM mesh v1.0", 0) == 0) read_mfem(next_token_line, bdr, tri);
+      else throw std::runtime_error("Not an MFEM mesh v1.0 file: " + path);
+      if (E <= 0 || NN <= 0) throw std::runtime_error("mesh: missing elements or vertices section");
+      for (int32_t v : conn) if (v < 0 || v >= NN) throw std::runtime_error("mesh: vertex index out of range");
+      if (geom == 1) {
+         if (!bdr.empty()) throw std::runtime_error("mesh: quadrilateral boundary elements on a tetrahedral mesh");
+         for (int e = 0; e < E; e++) {   // 6 x signed volume of (v1 - v0, v2 - v0, v3 - v0)
+            const int32_t* v = &conn[(size_t)4 * e];
+            double a[3][3];
+            for (int k = 0; k < 3; k++) for (int d = 0; d < 3; d++) a[k][d] = X[v[k + 1] + (size_t)NN * d] - X[v[0] + (size_t)NN * d];
+            const double det = a[0][0] * (a[1][1] * a[2][2] - a[1][2] * a[2][1]) - a[0][1] * (a[1][0] * a[2][2] - a[1][2] * a[2][0]) + a[0][2] * (a[1][0] * a[2][1] - a[1][1] * a[2][0]);
+            if (!(det > 0.0)) throw std::runtime_error("mesh: tetrahedron " + std::to_string(e) + " has non-positive volume (inverted or degenerate element)");
+         }
+      } else if (!tri.empty()) throw std::runtime_error("mesh: triangular boundary elements on a hexahedral mesh");
+      int maxattr = 0; for (auto& q : bdr) maxattr = std::max(maxattr, q[0]); for (auto& t : tri) maxattr = std::max(maxattr, t[0]);
+      for (auto& q : bdr) if (q[0] < 1) throw std::runtime_error("mesh: boundary attributes start at 1");
+      for (auto& t : tri) if (t[0] < 1) throw std::runtime_error("mesh: boundary attributes start at 1");
+      bdr_nodes.assign(maxattr, std::vector<uint8_t>(NN, 0));
+      for (auto& q : bdr) for (int a = 0; a < 4; a++) bdr_nodes[q[0] - 1][q[1 + a]] = 1;
+      for (auto& t : tri) for (int a = 0; a < 3; a++) { if (t[1 + a] < 0 || t[1 + a] >= NN) throw std::runtime_error("mesh: vertex index out of range"); bdr_nodes[t[0] - 1][t[1 + a]] = 1; }
+      if (geom == 1) {
+         if (order == 2) elevate_tet_to_p2(tri);
+         else if (order != 1) throw std::runtime_error("mesh: tetrahedral meshes run at p_refinement = 1 or 2");
+      }
+      else if (order == 2) elevate_to_p2(bdr);
+      else if (order >= 3 && order <= 6) elevate_to_order(order, bdr);
+      else if (order != 1) throw std::runtime_error("mesh: file meshes run at p_refinement = 1 ... 6");
+      weight.assign(NN, 1.0); nbrs.clear();
+      if (nranks > 1) localize(rcb_owner(nranks));
+   }
+
+   // MFEM mesh v1.0 sections after the header line (see above)
+   template <typename NextLine>
+   void read_mfem(NextLine& next_token_line, std::vector<std::array<int, 5>>& bdr, std::vector<std::array<int, 4>>& tri) {
+      std::string line;
+      int nv = -1;
       while (next_token_line(line)) {
          if (line == "dimension") { next_token_line(line); if (std::stoi(line) != 3) throw std::runtime_error("mesh: dimension must be 3"); }
          else if (line == "elements") {
             next_token_line(line); E = std::stoi(line);
-            conn.resize((size_t)8 * E); elem_attr.resize(E); elem_gid.resize(E);
+            conn.clear(); conn.reserve((size_t)8 * E); elem_attr.resize(E); elem_gid.resize(E);
+            int seen_hex = 0, seen_tet = 0;
             for (int e = 0; e < E; e++) {
-               next_token_line(line); std::istringstream is(line); int attr, geom; is >> attr >> geom;
-               if (geom != 5) throw std::runtime_error("mesh: only hexahedra (geometry 5) are supported");
+               next_token_line(line); std::istringstream is(line); int attr, g; is >> attr >> g;
+               int nvtx;
+               if (g == 5) { nvtx = 8; seen_hex = 1; }
+               else if (g == 4) { nvtx = 4; seen_tet = 1; }
+               else throw std::runtime_error("mesh: only hexahedra (geometry 5) and tetrahedra (geometry 4) are supported");
+               if (seen_hex && seen_tet) throw std::runtime_error("mesh: a file that mixes hexahedra and tetrahedra is not supported");
                elem_attr[e] = attr; elem_gid[e] = e;
-               for (int a = 0; a < 8; a++) { int v; if (!(is >> v)) throw std::runtime_error("mesh: short element line"); conn[a + (size_t)8 * e] = v; }
+               for (int a = 0; a < nvtx; a++) { int v; if (!(is >> v)) throw std::runtime_error("mesh: short element line"); conn.push_back(v); }
             }
+            if (seen_tet) { geom = 1; n = 4; }
          } else if (line == "boundary") {
             next_token_line(line); const int nbe = std::stoi(line);
             for (int b = 0; b < nbe; b++) {
-               next_token_line(line); std::istringstream is(line); int attr, geom; is >> attr >> geom;
-               if (geom != 3) throw std::runtime_error("mesh: only quadrilateral boundary elements (geometry 3) are supported");
-               std::array<int, 5> q; q[0] = attr; for (int a = 0; a < 4; a++) is >> q[1 + a];
-               bdr.push_back(q);
+               next_token_line(line); std::istringstream is(line); int attr, g; is >> attr >> g;
+               if (g == 3) { std::array<int, 5> q; q[0] = attr; for (int a = 0; a < 4; a++) is >> q[1 + a]; bdr.push_back(q); }
+               else if (g == 2) { std::array<int, 4> t; t[0] = attr; for (int a = 0; a < 3; a++) is >> t[1 + a]; tri.push_back(t); }
+               else throw std::runtime_error("mesh: only quadrilateral (geometry 3) and triangular (geometry 2) boundary elements are supported");
             }
          } else if (line == "vertices") {
             next_token_line(line); nv = std::stoi(line); NN = nv; X.assign((size_t)3 * NN, 0.0);
@@ -198,16 +248,76 @@ struct Partition {
             else for (int g = 0; g < NN; g++) { next_token_line(line); std::istringstream is(line); for (int d = 0; d < 3; d++) is >> X[g + (size_t)NN * d]; }
          }
       }
-      if (E <= 0 || nv <= 0) throw std::runtime_error("mesh: missing elements or vertices section");
-      for (int32_t v : conn) if (v < 0 || v >= NN) throw std::runtime_error("mesh: vertex index out of range");
-      int maxattr = 0; for (auto& q : bdr) maxattr = std::max(maxattr, q[0]);
-      bdr_nodes.assign(maxattr, std::vector<uint8_t>(NN, 0));
-      for (auto& q : bdr) for (int a = 0; a < 4; a++) bdr_nodes[q[0] - 1][q[1 + a]] = 1;
-      if (order == 2) elevate_to_p2(bdr);
-      else if (order >= 3 && order <= 6) elevate_to_order(order, bdr);
-      else if (order != 1) throw std::runtime_error("mesh: file meshes run at p_refinement = 1 ... 6");
-      weight.assign(NN, 1.0); nbrs.clear();
-      if (nranks > 1) localize(rcb_owner(nranks));
+      if (nv <= 0) NN = 0;
+   }
+
+   // Gmsh 2.2 ASCII after the `$MeshFormat` line: node ids may be any positive integers (mapped to 0 ... NN-1 in file order)
+   template <typename NextLine>
+   void read_gmsh22(NextLine& next_token_line, std::vector<std::array<int, 4>>& tri) {
+      std::string line;
+      next_token_line(line);
+      { std::istringstream is(line); double ver = 0; int ft = -1; is >> ver >> ft;
+        if (ver < 2.0 || ver >= 3.0 || ft != 0) throw std::runtime_error("mesh: only the Gmsh 2.2 ASCII format is supported ($MeshFormat 2.2 0 8)"); }
+      std::map<long, int> id;
+      std::vector<std::array<long, 5>> tets; std::vector<std::array<long, 4>> tris;
+      while (next_token_line(line)) {
+         if (line == "$Nodes") {
+            next_token_line(line); NN = std::stoi(line); X.assign((size_t)3 * NN, 0.0);
+            for (int g = 0; g < NN; g++) {
+               next_token_line(line); std::istringstream is(line); long k; is >> k;
+               for (int d = 0; d < 3; d++) is >> X[g + (size_t)NN * d];
+               id[k] = g;
+            }
+         } else if (line == "$Elements") {
+            next_token_line(line); const int ne_ = std::stoi(line);
+            for (int i = 0; i < ne_; i++) {
+               next_token_line(line); std::istringstream is(line); long k; int type, ntags; is >> k >> type >> ntags;
+               std::vector<long> tags(ntags > 0 ? ntags : 0); for (auto& t : tags) is >> t;
+               const long phys = tags.empty() ? 0 : tags[0];
+               if (type == 4) { std::array<long, 5> t; t[0] = phys; for (int a = 0; a < 4; a++) is >> t[1 + a]; tets.push_back(t); }
+               else if (type == 2) { std::array<long, 4> t; t[0] = phys; for (int a = 0; a < 3; a++) is >> t[1 + a]; tris.push_back(t); }
+               else if (type == 11 || type == 9 || type == 8) throw std::runtime_error("mesh: second-order Gmsh elements (type " + std::to_string(type) + ") are not supported: straight-sided 4-node tetrahedra only");
+               else if (type == 5) throw std::runtime_error("mesh: Gmsh hexahedra are not supported: tetrahedra (type 4) only");
+               else if (type != 15 && type != 1) throw std::runtime_error("mesh: unsupported Gmsh element type " + std::to_string(type));
+            }
+         }
+      }
+      auto node = [&](long k) { auto it = id.find(k); if (it == id.end()) throw std::runtime_error("mesh: element refers to an unknown Gmsh node " + std::to_string(k)); return it->second; };
+      E = (int)tets.size(); geom = 1; n = 4;
+      conn.resize((size_t)4 * E); elem_attr.resize(E); elem_gid.resize(E);
+      for (int e = 0; e < E; e++) { elem_attr[e] = (int)tets[e][0]; elem_gid[e] = e; for (int a = 0; a < 4; a++) conn[a + (size_t)4 * e] = node(tets[e][1 + a]); }
+      for (auto& t : tris) tri.push_back({ (int)t[0], node(t[1]), node(t[2]), node(t[3]) });
+   }
+
+   // p_refinement = 2 on a tetrahedral mesh: one node per edge at its midpoint, shared through the edge map; local numbering = MFEM's order-2
+   // tetrahedron (vertices, then edges (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)).  A boundary triangle constrains its three edge nodes.
+   void elevate_tet_to_p2(const std::vector<std::array<int, 4>>& tri) {
+      static const int Ed[6][2] = { { 0, 1 }, { 0, 2 }, { 0, 3 }, { 1, 2 }, { 1, 3 }, { 2, 3 } };
+      const int nv = NN;
+      std::map<std::array<int, 2>, int> edge_node;
+      std::vector<std::array<double, 3>> xnew;
+      auto edge_of = [&](int a, int b) {
+         std::array<int, 2> key{ std::min(a, b), std::max(a, b) };
+         auto it = edge_node.find(key); if (it != edge_node.end()) return it->second;
+         std::array<double, 3> c; for (int d = 0; d < 3; d++) c[d] = 0.5 * (X[a + (size_t)nv * d] + X[b + (size_t)nv * d]);
+         xnew.push_back(c); const int g = nv + (int)xnew.size() - 1; edge_node.emplace(key, g); return g;
+      };
+      std::vector<int32_t> c2((size_t)10 * E);
+      for (int e = 0; e < E; e++) {
+         const int32_t* v = &conn[(size_t)4 * e];
+         int32_t* w = &c2[(size_t)10 * e];
+         for (int a = 0; a < 4; a++) w[a] = v[a];
+         for (int k = 0; k < 6; k++) w[4 + k] = edge_of(v[Ed[k][0]], v[Ed[k][1]]);
+      }
+      const int NN2 = nv + (int)xnew.size();
+      std::vector<double> X2((size_t)3 * NN2);
+      for (int g = 0; g < NN2; g++) for (int d = 0; d < 3; d++) X2[g + (size_t)NN2 * d] = g < nv ? X[g + (size_t)nv * d] : xnew[g - nv][d];
+      for (auto& b : bdr_nodes) b.resize(NN2, 0);
+      for (auto& t : tri) for (int a = 0; a < 3; a++) {
+         auto it = edge_node.find({ std::min(t[1 + a], t[1 + (a + 1) % 3]), std::max(t[1 + a], t[1 + (a + 1) % 3]) });
+         if (it != edge_node.end()) bdr_nodes[t[0] - 1][it->second] = 1;
+      }
+      conn.swap(c2); X.swap(X2); NN = NN2; p = 2; n = 10;
    }
 
    // p_refinement = 2 on a file mesh (the reference raises the order of the nodal space of any mesh, src/mechanics_driver.cpp:300-306): one new

@@ -72,6 +72,7 @@ inline void write_array(std::ostream& o, const Array& a, int64_t ntuples) {
 // host view of one rank's fields (everything host memory)
 struct Piece {
    int64_t E = 0, NN = 0; int n = 8;
+   bool tet = false;                                              // tetrahedra: VTK_TETRA over the first 4 nodes (the vertices, MFEM's order = VTK's)
    const int32_t* conn = nullptr;                                 // (n, E), native node order: the first 8 are the vertices in VTK_HEXAHEDRON order
    const double* x_cur = nullptr; const double* x_ref = nullptr;  // byNODES (NN, 3)
    const double* vel = nullptr;                                   // byNODES (NN, 3)
@@ -121,10 +122,11 @@ inline void write_piece(const std::string& path, const Piece& p, bool light_up) 
    o << "      <Points>\n";
    write_array(o, Array{ "Points", T::F64, 3, p.x_cur, 8, 8 * p.NN }, p.NN);
    o << "      </Points>\n      <Cells>\n";
-   std::vector<int32_t> offs((size_t)p.E); for (int64_t e = 0; e < p.E; e++) offs[e] = (int32_t)(8 * (e + 1));
-   const std::vector<uint8_t> types((size_t)p.E, 12);   // VTK_HEXAHEDRON
-   if (8 * p.E > INT32_MAX) throw std::runtime_error("vtu: piece too large for Int32 offsets");
-   write_array(o, Array{ "connectivity", T::I32, 8, p.conn, 4 * (int64_t)p.n, 4 }, p.E);
+   const int nv = p.tet ? 4 : 8;
+   std::vector<int32_t> offs((size_t)p.E); for (int64_t e = 0; e < p.E; e++) offs[e] = (int32_t)(nv * (e + 1));
+   const std::vector<uint8_t> types((size_t)p.E, p.tet ? 10 : 12);   // VTK_TETRA / VTK_HEXAHEDRON
+   if (nv * p.E > INT32_MAX) throw std::runtime_error("vtu: piece too large for Int32 offsets");
+   write_array(o, Array{ "connectivity", T::I32, nv, p.conn, 4 * (int64_t)p.n, 4 }, p.E);
    write_array(o, Array{ "offsets", T::I32, 1, offs.data(), 4, 0 }, p.E);
    write_array(o, Array{ "types", T::U8, 1, types.data(), 1, 0 }, p.E);
    o << "      </Cells>\n      <PointData>\n";

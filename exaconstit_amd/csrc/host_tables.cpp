@@ -5,6 +5,7 @@
 //   material parameters: ECMechXtalModel ctor -> initFromParams (src/mechanics_ecmech.hpp:219-246), parameter order
 //     src/mechanics_ecmech.hpp:395-405 (Voce) / :444-458 (KM-DD), scripts/ecmech_prop_file.py:58-122.
 #include "exa_internal.hpp"
+#include <array>
 #include <cmath>
 
 namespace {
@@ -103,6 +104,69 @@ void exa_build_ref_elem(int p, std::vector<double>& G, std::vector<double>& W) {
          G[a + n * (2 + 3 * q)] = vx[i] * vy[j] * dz[k];
       }
    }
+}
+
+// Reference tetrahedron (0,0,0) (1,0,0) (0,1,0) (0,0,1): MFEM's H1 tetrahedron of order p = 1, 2 (vertices, then one node per edge at
+// its midpoint in the edge order (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)) at the points of IntRules.Get(TETRAHEDRON, 2p + 1) (reference
+// src/mechanics_integrators.cpp:59, src/mechanics_driver.cpp:433): degree 3 = the 5-point Strang-Fix rule with its negative centroid weight,
+// degree 5 = the 14-point rule.  Weights sum to the volume 1/6.  N (n, Q) = shape values.
+bool exa_build_ref_elem_tet(int p, std::vector<double>& G, std::vector<double>& W, std::vector<double>* N) {
+   if (p != 1 && p != 2) return false;
+   std::vector<std::array<double, 4>> bary;   // barycentrics (l0, l1, l2, l3): x = l1, y = l2, z = l3
+   if (p == 1) {
+      bary.push_back({ 0.25, 0.25, 0.25, 0.25 }); W.assign(1, -2.0 / 15.0);
+      for (int k = 0; k < 4; k++) { std::array<double, 4> b{ 1.0 / 6.0, 1.0 / 6.0, 1.0 / 6.0, 1.0 / 6.0 }; b[k] = 0.5; bary.push_back(b); W.push_back(3.0 / 40.0); }
+   } else {
+      W.clear();
+      const double a = 0.045503704125649649492, b = 0.5 - a;
+      static const int pr[6][2] = { { 0, 1 }, { 0, 2 }, { 0, 3 }, { 1, 2 }, { 1, 3 }, { 2, 3 } };   // the two barycentrics that take a
+      for (auto& ij : pr) { std::array<double, 4> l{ b, b, b, b }; l[ij[0]] = a; l[ij[1]] = a; bary.push_back(l); W.push_back(7.0910034628469110730e-3); }
+      const double as[2] = { 0.092735250310891226402, 0.31088591926330060980 }, ws[2] = { 0.012248840519393658257, 0.018781320953002641800 };
+      for (int s = 0; s < 2; s++) for (int k = 0; k < 4; k++) { std::array<double, 4> l{ as[s], as[s], as[s], as[s] }; l[k] = 1.0 - 3.0 * as[s]; bary.push_back(l); W.push_back(ws[s]); }
+   }
+   const int Q = (int)bary.size(), n = p == 1 ? 4 : 10;
+   static const double dL[4][3] = { { -1, -1, -1 }, { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 } };
+   static const int Ed[6][2] = { { 0, 1 }, { 0, 2 }, { 0, 3 }, { 1, 2 }, { 1, 3 }, { 2, 3 } };
+   G.assign((size_t)n * 3 * Q, 0.0);
+   if (N) N->assign((size_t)n * Q, 0.0);
+   for (int q = 0; q < Q; q++) {
+      const std::array<double, 4>& L = bary[q];
+      for (int a = 0; a < 4; a++) {
+         const double v = p == 1 ? L[a] : L[a] * (2.0 * L[a] - 1.0), f = p == 1 ? 1.0 : 4.0 * L[a] - 1.0;
+         for (int j = 0; j < 3; j++) G[a + n * (j + 3 * q)] = f * dL[a][j];
+         if (N) (*N)[a + (size_t)n * q] = v;
+      }
+      if (p == 2) for (int k = 0; k < 6; k++) {
+         const int i = Ed[k][0], m = Ed[k][1];
+         for (int j = 0; j < 3; j++) G[4 + k + n * (j + 3 * q)] = 4.0 * (L[m] * dL[i][j] + L[i] * dL[m][j]);
+         if (N) (*N)[4 + k + (size_t)n * q] = 4.0 * L[i] * L[m];
+      }
+   }
+   return true;
+}
+
+extern "C" int exa_ref_elem_tables(int geometry, int order, double* G, double* W, double* N) {
+   std::vector<double> g, w, nv;
+   int n = 0, Q = 0;
+   if (geometry == EXA_GEOM_TET) {
+      if (!exa_build_ref_elem_tet(order, g, w, &nv)) return EXA_ERR_ARG;
+      n = order == 1 ? 4 : 10; Q = (int)w.size();
+   } else if (geometry == EXA_GEOM_HEX) {
+      if (order < 1 || order > 6) return EXA_ERR_ARG;
+      exa_build_ref_elem(order, g, w);
+      const int np = order + 1; n = np * np * np; Q = n;
+      if (N) {   // shape values: tensor products of the one-dimensional values, native node order
+         std::vector<double> T1; std::vector<int> nat; exa_build_1d_tables(order, T1, nat);
+         nv.assign((size_t)n * Q, 0.0);
+         for (int qk = 0; qk < np; qk++) for (int qj = 0; qj < np; qj++) for (int qi = 0; qi < np; qi++)
+            for (int k = 0; k < np; k++) for (int j = 0; j < np; j++) for (int i = 0; i < np; i++)
+               nv[nat[i + np * (j + np * k)] + (size_t)n * (qi + np * (qj + np * qk))] = T1[2 * np * qi + i] * T1[2 * np * qj + j] * T1[2 * np * qk + k];
+      }
+   } else return EXA_ERR_ARG;
+   if (G) std::copy(g.begin(), g.end(), G);
+   if (W) std::copy(w.begin(), w.end(), W);
+   if (N) std::copy(nv.begin(), nv.end(), N);
+   return n * 1000 + Q;
 }
 
 void exa_build_1d_tables(int p, std::vector<double>& T1, std::vector<int>& nat) {

@@ -53,6 +53,10 @@ exa_num_state_vars = _sig("exa_num_state_vars", C.c_int, C.c_void_p)
 exa_nodes_per_elem = _sig("exa_nodes_per_elem", C.c_int, C.c_void_p)
 exa_qpts_per_elem = _sig("exa_qpts_per_elem", C.c_int, C.c_void_p)
 exa_shape_table = _sig("exa_shape_table", C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double))
+exa_create_geom = _sig("exa_create_geom", C.c_void_p, C.POINTER(ExaConfig), C.c_int, C.POINTER(C.c_int))
+exa_element_geometry = _sig("exa_element_geometry", C.c_int, C.c_void_p)
+exa_ref_elem_tables = _sig("exa_ref_elem_tables", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double))
+EXA_GEOM_HEX, EXA_GEOM_TET = 0, 1
 exa_set_quadrature_layout = _sig("exa_set_quadrature_layout", C.c_int, C.c_void_p, C.c_int)
 exa_get_quadrature_layout = _sig("exa_get_quadrature_layout", C.c_int, C.c_void_p)
 exa_set_aos_staging = _sig("exa_set_aos_staging", C.c_int, C.c_void_p, C.c_int)
@@ -126,13 +130,13 @@ MODEL_IDS = {("fcc", "powervoce"): EXA_FCC_VOCE, ("fcc", "powervocenl"): EXA_FCC
 class Context:
     """Owns one exa_ctx.  Mirrors how the reference's operator owns its model + integrator (mechanics_operator.cpp:49-225)."""
 
-    def __init__(self, model, props, temp_k, order, nelems, assembly=EXA_ASSEMBLY_PA, integ=EXA_INTEG_FULL, device=-1):
+    def __init__(self, model, props, temp_k, order, nelems, assembly=EXA_ASSEMBLY_PA, integ=EXA_INTEG_FULL, device=-1, geometry=EXA_GEOM_HEX):
         import numpy as np
         self._props = np.ascontiguousarray(props, dtype=np.float64)
         cfg = ExaConfig(model, len(self._props), self._props.ctypes.data_as(C.POINTER(C.c_double)), float(temp_k),
                         order, nelems, assembly, integ, device)
         err = C.c_int(0)
-        self.h = exa_create(C.byref(cfg), C.byref(err))
+        self.h = exa_create(C.byref(cfg), C.byref(err)) if geometry == EXA_GEOM_HEX else exa_create_geom(C.byref(cfg), geometry, C.byref(err))
         if not self.h:
             raise RuntimeError(f"exa_create failed with code {err.value} (is a HIP device present and the model/props valid?)")
         self.n = exa_nodes_per_elem(self.h)
@@ -164,6 +168,19 @@ class Context:
             pass
 
 
+def ref_elem_tables(geometry, order):
+    """Reference-element tables of (geometry, order), host only: G (n,3,Q) flat, W (Q), N (n,Q) flat shape values."""
+    import numpy as np
+    rc = exa_ref_elem_tables(geometry, order, None, None, None)
+    if rc < 0:
+        raise ValueError(f"no reference element for geometry {geometry}, order {order}")
+    n, Q = rc // 1000, rc % 1000
+    G, W, N = np.zeros(n * 3 * Q), np.zeros(Q), np.zeros(n * Q)
+    f = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
+    exa_ref_elem_tables(geometry, order, f(G), f(W), f(N))
+    return G, W, N
+
+
 # ---- stand-alone driver (include/exaconstit_driver.h) ---------------------------------------------------
 class ExaSynthConfig(C.Structure):
     _fields_ = [("N", C.c_int), ("bcc", C.c_int), ("slip", C.c_int), ("nprops", C.c_int), ("props", C.POINTER(C.c_double)),
@@ -186,6 +203,8 @@ exa_driver_create_synthetic = _sig("exa_driver_create_synthetic", C.c_void_p, C.
 exa_driver_destroy = _sig("exa_driver_destroy", None, C.c_void_p)
 exa_driver_num_steps = _sig("exa_driver_num_steps", C.c_int, C.c_void_p)
 exa_driver_local_qpts = _sig("exa_driver_local_qpts", C.c_int64, C.c_void_p)
+exa_driver_mesh_info = _sig("exa_driver_mesh_info", C.c_int, C.c_void_p, C.POINTER(C.c_int64))
+ACTION_ROUTES = ("hex", "tet_fused", "generic_evector", "generic_ea_lvec")
 exa_driver_local_dofs = _sig("exa_driver_local_dofs", C.c_int64, C.c_void_p)
 exa_driver_step = _sig("exa_driver_step", C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_int)
 exa_driver_step_nocommit = _sig("exa_driver_step_nocommit", C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_int)
@@ -533,6 +552,13 @@ class Driver:
         assert exa_driver_comm_details(self.h, out) == 0
         return {"elements": int(out[0]), "boundary_block_elements": int(out[1]), "neighbours": int(out[2]), "halo_bytes_per_exchange": 8 * int(out[3]),
                 "halo_overlap": bool(out[4])}
+
+    def mesh_info(self):
+        """Element geometry and order of this rank's mesh and the route its Krylov action takes (ACTION_ROUTES)."""
+        out = (C.c_int64 * 8)()
+        assert exa_driver_mesh_info(self.h, out) == 0
+        return {"geometry": ("hex", "tet")[out[0]], "order": int(out[1]), "nodes_per_elem": int(out[2]), "qpts_per_elem": int(out[3]),
+                "elements": int(out[4]), "nodes": int(out[5]), "action_route": ACTION_ROUTES[out[6]]}
 
     def reset_timers(self):
         exa_driver_reset_timers(self.h)

@@ -96,6 +96,10 @@ int exa_driver_mg_stencil(exa_driver* d, int level, double* out);
 int exa_driver_precond_apply(exa_driver* d, const double* r, double* z);
 int exa_driver_num_steps(exa_driver* d);
 int64_t exa_driver_local_qpts(exa_driver* d);
+/* out8 = { element geometry (EXA_GEOM_HEX 0 / EXA_GEOM_TET 1), H1 order, nodes per element, quadrature points per element, local elements,
+ *          local nodes, route of the Krylov action (0 hexahedron kernels, 1 fused tetrahedron action, 2 table-driven E-vector action,
+ *          3 table-driven element-assembly action on L-vectors), 0 } */
+int exa_driver_mesh_info(exa_driver* d, int64_t* out8);
 int64_t exa_driver_local_dofs(exa_driver* d);
 int exa_driver_step(exa_driver* d, int ti, char* err, int errlen);
 /* solve step ti but do not commit it (no begin/end swap, no coordinate update, no output row): the state bench.py times its passes on */

@@ -79,6 +79,17 @@ int exa_qpts_per_elem(const exa_ctx* ctx);
 /* reference-element tables built on the host once: src/mechanics_operator.cpp:237-261, src/mechanics_integrators.cpp:184-197 */
 int exa_shape_table(const exa_ctx* ctx, double* G_host /*(n,3,Q)*/, double* W_host /*(Q)*/);
 
+/* Element geometry.  exa_create makes hexahedron contexts; exa_create_geom takes the geometry explicitly (same config).
+ * Tetrahedra: straight-sided, p = 1 (n = 4, Q = 5) or p = 2 (n = 10, Q = 14), MFEM's node order (vertices, then the edge midpoints of
+ * edges (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)) and the rules of IntRules.Get(TETRAHEDRON, 2p + 1) on the unit tetrahedron.  A tetrahedron
+ * context refuses EXA_INTEG_BBAR (at creation), exa_model_setup_lvec_records and exa_grad_apply_lvec_blocks (EXA_ERR_UNSUPPORTED). */
+enum { EXA_GEOM_HEX = 0, EXA_GEOM_TET = 1 };
+exa_ctx* exa_create_geom(const exa_config* cfg, int geometry, int* err);
+int exa_element_geometry(const exa_ctx* ctx);                  /* EXA_GEOM_* */
+/* Host only (no device needed): the reference-element tables of (geometry, order): G (n,3,Q), W (Q), N (n,Q) shape values (may be NULL).
+ * Returns n * 1000 + Q, or EXA_ERR_ARG (hexahedra: order 1 ... 6, tetrahedra: 1 or 2). */
+int exa_ref_elem_tables(int geometry, int order, double* G, double* W, double* N);
+
 /* Layout of every quadrature function passed to this context (jacobian, stress, state, ddsdde, dp, any exa_vol_avg field):
  *   EXA_QLAYOUT_AOS  (default) the reference's QuadratureFunction layout (vdim, Q, E), first index fastest;
  *   EXA_QLAYOUT_EB64 [block of 64 elements][q][component][lane = element], exa_qf_size(ctx, vdim) doubles per field.  It is the
