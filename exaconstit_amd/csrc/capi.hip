@@ -10,6 +10,8 @@ int exa_launch_model_setup_p2(exa_ctx*, double, double*, const double*, const do
 int exa_launch_model_setup_aos_rec(exa_ctx*, double, double*, const double*, const double*, const double*, const double*, double*, double*, hipStream_t);
 int exa_launch_init_state(exa_ctx*, double*, const double*, const double*, hipStream_t);
 int exa_launch_state_normalize(exa_ctx*, double*, hipStream_t);
+int exa_launch_qf_pack(exa_ctx*, int, const double*, double*, unsigned long long*, hipStream_t);     // checkpoint_kernels.hip
+int exa_launch_qf_unpack(exa_ctx*, int, const double*, double*, unsigned long long*, hipStream_t);
 int exa_launch_nfev_hist(exa_ctx*, const double*, int*, hipStream_t);
 int exa_launch_selftest_km_math(const double*, double*, int, hipStream_t);
 int exa_launch_calc_dp(exa_ctx*, const double*, double*, hipStream_t);
@@ -143,6 +145,16 @@ int exa_init_state(exa_ctx* ctx, double* state0, const double* quats, exa_stream
 int exa_state_normalize(exa_ctx* ctx, double* state, exa_stream s) {
    if (!ctx || !state) return fail(ctx, EXA_ERR_ARG, "exa_state_normalize: null pointer");
    return exa_launch_state_normalize(ctx, state, S(s));
+}
+
+int exa_qf_pack(exa_ctx* ctx, int vdim, const double* src, double* dst, uint64_t* checksum, exa_stream s) {
+   if (!ctx || !src || !dst) return fail(ctx, EXA_ERR_ARG, "exa_qf_pack: null pointer");
+   return exa_launch_qf_pack(ctx, vdim, src, dst, reinterpret_cast<unsigned long long*>(checksum), S(s));
+}
+
+int exa_qf_unpack(exa_ctx* ctx, int vdim, const double* src, double* dst, uint64_t* checksum, exa_stream s) {
+   if (!ctx || !src || !dst) return fail(ctx, EXA_ERR_ARG, "exa_qf_unpack: null pointer");
+   return exa_launch_qf_unpack(ctx, vdim, src, dst, reinterpret_cast<unsigned long long*>(checksum), S(s));
 }
 
 // exa_set_newton_cap_auto: the cap of the NEXT launches from the evaluation counts this launch left in state1 (slot 3).  The distribution drifts slowly: the first

@@ -570,6 +570,12 @@ NonlinearMechOperator::~NonlinearMechOperator() {
    (void)hipStreamDestroy(stream_);
 }
 
+void NonlinearMechOperator::SetCapState(int cap, int cap2) {
+   if (!cap_auto_) return;   // a fixed cap (EXA_NEWTON_CAP) or none: nothing follows the run
+   newton_cap_ = cap; newton_cap2_ = cap2;
+   abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, tail_resume_ ? 1 : 0), "exa_set_newton_caps");
+}
+
 void NonlinearMechOperator::UpdateEssTDofs(const std::vector<uint8_t>& mask) { ess_mask.upload(mask); }
 
 // Cost model of the tail split in units of one residual evaluation per point.  A wave costs the largest evaluation count among its 64
@@ -1300,6 +1306,7 @@ bool SystemDriver::Solve(double* x) {
    }
    if (iter > 0) time = time - dt_old + dt_class;
    last_dt_ = dt_class;
+   if (ok) auto_dt_rows_.push_back(dt_class);
    if (ok && write_files && comm.rank == 0) { std::ofstream f(out_dir + "/" + opt_.auto_dt_fname, std::ios_base::app); f << std::setprecision(12) << dt_class << std::endl; }
    const double niter_scale = (double)opt_.newton_iter * opt_.dt_scale;
    const double nr_iter = std::max(1, st.newton_iters);
@@ -1307,7 +1314,7 @@ bool SystemDriver::Solve(double* x) {
    return ok;
 }
 
-static void append_row(const std::string& path, const double* v, int n) {
+void append_row(const std::string& path, const double* v, int n) {   // (also rewrites the files of a restarted run: host/checkpoint.hip)
    std::ofstream f(path, std::ios_base::app);
    for (int i = 0; i < n; i++) { f << v[i]; f << (i + 1 == n ? '\n' : ' '); }   // mfem::Vector::Print(out, width = n)
 }
@@ -1374,6 +1381,7 @@ bool SystemDriver::Step(int ti, bool commit) {
    hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s));
    for (const BCEntry& bc : opt_.bcs) if (bc.step == ti) {
       DevBuf<double> v_prev(nd); v_prev.copy_from(v_sol, s);
+      bc_index_ = (int)(&bc - opt_.bcs.data());
       UpdateEssBdr(bc);
       UpdateVelocity(v_sol.p);
       SolveInit(v_prev.p, v_sol.p);
@@ -1413,6 +1421,7 @@ bool SystemDriver::Step(int ti, bool commit) {
       const int H = (int)opt_.lightup_hkl.size() / 3;
       std::vector<double> strain(H), vf(H);
       LatticeStrains(opt_.lightup_hkl, opt_.lightup_s_dir, opt_.lightup_tol_deg, strain.data(), vf.data(), true);
+      lattice_rows_.insert(lattice_rows_.end(), strain.begin(), strain.end()); volume_rows_.insert(volume_rows_.end(), vf.begin(), vf.end());
       if (comm.rank == 0) { append_row(out_dir + "/" + opt_.lightup_strain_fname, strain.data(), H); append_row(out_dir + "/" + opt_.lightup_volume_fname, vf.data(), H); }
    }
    return true;
@@ -1426,12 +1435,17 @@ void SystemDriver::CommitStep() {
 }
 
 int SystemDriver::RunAll() {
-   for (int ti = 1; ti <= opt_.nsteps; ti++) {
+   // (a restarted run that already stands at the end of the schedule has nothing to do)
+   bool finished = false;
+   if (restarted_ && !opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; finished = std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
+   for (int ti = steps_done + 1; ti <= opt_.nsteps && !finished; ti++) {
       if (!Step(ti)) {
          if (comm.rank == 0) std::cerr << "Newton Solver did not converge" << (oper_->model_fail > 0 ? " (the constitutive update failed at quadrature points of the last evaluation)" : "") << ".\n";
          return -ti;
       }
-      if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; if (std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl)) break; }
+      if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; finished = std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
+      // [Checkpoint]: every Checkpoint.steps steps and after the last one; older files are removed once the new one is in place
+      if (opt_.ckpt_write && write_files && (finished || ti == opt_.nsteps || ti % opt_.ckpt_steps == 0)) { SaveCheckpoint(checkpoint_path(ti)); PruneCheckpoints(ti); }
    }
    WriteStepTimes();
    return steps_done;

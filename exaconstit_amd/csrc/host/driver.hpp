@@ -141,6 +141,9 @@ class NonlinearMechOperator {
    Comm& comm() { return comm_; }
    // route of the Krylov action (Driver.mesh_info): 0 hexahedron kernels, 1 fused tetrahedron action, 2 table-driven E-vector PA, 3 table-driven EA on L-vectors
    int action_route() const { return part_.geom != 1 ? 0 : (lvec_grad_ && tet_fused_ ? 1 : (lvec_grad_ ? 3 : 2)); }
+   // state of the automatic Newton cap (checkpoint files carry it: the cap in force decides how the next constitutive launch is split)
+   void GetCapState(int& cap, int& cap2) const { cap = newton_cap_; cap2 = newton_cap2_; }
+   void SetCapState(int cap, int cap2);
    bool halo_overlap() const { return overlap_; }      // the gradient action overlaps the halo exchange with its interior blocks
    // data (device)
    DevBuf<double> x_ref, x_beg, x_cur, el_x, el_v, el_jac, diag, dinv, weight;
@@ -220,6 +223,12 @@ class SystemDriver {
    bool write_files = true; std::string out_dir = ".";
    std::vector<double> step_wall_s;            // wall time of each step (solve part), written to time/time_solve.<rank>.txt by RunAll
    void WriteStepTimes();
+   // Checkpoint and restart.  SaveCheckpoint: everything that defines where the run is, into one file written as <path>.tmp and
+   // renamed (every rank calls it).  LoadCheckpoint: legal only on a freshly created driver before its first step; refuses a file that does not
+   // belong to this mesh / model / property set, naming the mismatch; rewrites the avg_* and light-up files from the stored rows.
+   void SaveCheckpoint(const std::string& path);
+   void LoadCheckpoint(const std::string& path);
+   std::string checkpoint_path(int step) const;   // <out_dir>/<Checkpoint.floc>_<step %06d>.ckpt
    // per-element output fields (reference SystemDriver::Project*, src/system_driver.cpp:560-870) of the begin-of-step state - after a completed
    // step the converged one - and the current coordinates: host [E][EXA_NFIELDS] in local element order
    void ElementFields(std::vector<double>& out);
@@ -268,6 +277,14 @@ class SystemDriver {
    std::vector<int32_t> grain_plan_; DevBuf<int32_t> grain_plan_dev_; DevBuf<double> grain_work_, grain_sums_, grain_quat_dev_; int grain_G_ = 0;
    void EnsureGrainPlan();
    bool texture0_written_ = false;
+   // rows that exist only in append-mode files otherwise (checkpoint host sections): light-up strains / volume fractions, accepted dt of Time.Auto
+   std::vector<double> lattice_rows_, volume_rows_, auto_dt_rows_;
+   int bc_index_ = -1;                          // index in opt_.bcs of the essential-boundary entry in force
+   bool restarted_ = false;
+   // shared-node copies of a checkpoint written on another rank count (host/checkpoint.hip): carried along untouched and written back as long as
+   // no constitutive launch has run since the load, so that load + save reproduces the file on any rank count
+   std::vector<unsigned char> ckpt_foreign_copies_[2]; long ckpt_foreign_calls_ = -1;
+   void PruneCheckpoints(int step);
    DevBuf<double> texture_vmax_; DevBuf<int64_t> texture_counts_;   // largest element volume; [set][n_alpha][n_beta] counts of exa_texture_weights
    void WriteTexture(int step, double t);
    std::map<std::string, std::vector<std::pair<int, double>>> pvd_cycles_;   // saved cycles of each output directory (rank 0 writes the .pvd)

@@ -6,6 +6,7 @@
 #include "multigrid.hpp"
 #include "roctx.hpp"
 #include "vtu.hpp"
+#include "checkpoint.hpp"
 #include "../../../include/exaconstit_driver.h"
 #include <unistd.h>
 #include <cmath>
@@ -140,18 +141,78 @@ int exa_loopback_group_create(int nranks, void* out128) { try { Comm::loopback_c
 void exa_loopback_group_destroy(const void* id128) { Comm::loopback_destroy(id128); }
 
 exa_driver* exa_driver_create(const char* toml_path, const char* out_dir, int rank, int nranks, const void* uid, int jacobi, int write_files, char* err, int errlen) {
+   return exa_driver_create_restart(toml_path, out_dir, rank, nranks, uid, jacobi, write_files, nullptr, err, errlen);
+}
+
+// restart_path: NULL = what Checkpoint.restart_from of the options file says (usually nothing), "" = no restart, otherwise the checkpoint to resume from
+exa_driver* exa_driver_create_restart(const char* toml_path, const char* out_dir, int rank, int nranks, const void* uid, int jacobi, int write_files,
+                                      const char* restart_path, char* err, int errlen) {
    try {
       ExaOptions opt; opt.parse_options(toml_path);
-      auto d = new exa_driver();
+      std::unique_ptr<exa_driver> d(new exa_driver());
       d->sd.reset(new SystemDriver(opt, rank, nranks, uid));
       d->sd->out_dir = out_dir ? out_dir : "."; d->sd->write_files = write_files != 0;
       d->sd->precond = jacobi ? Precond::JACOBI : Precond::IDENTITY; d->sd->oper().precond = d->sd->precond;
-      if (opt.precond != 0) {   // Solvers.Krylov.preconditioner decides when it is present
-         try { d->sd->SetPreconditioner(opt.precond, opt.mg_levels, opt.mg_degree); }
-         catch (...) { delete d; throw; }
-      }
-      return d;
+      if (opt.precond != 0) d->sd->SetPreconditioner(opt.precond, opt.mg_levels, opt.mg_degree);   // Solvers.Krylov.preconditioner decides when it is present
+      const std::string from = restart_path ? std::string(restart_path) : opt.resolve(opt.ckpt_restart_from);
+      if (!from.empty()) d->sd->LoadCheckpoint(from);
+      return d.release();
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return nullptr; }
+}
+
+int exa_driver_save_checkpoint(exa_driver* d, const char* path, char* err, int errlen) {
+   try { d->sd->SaveCheckpoint(path); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+int exa_driver_load_checkpoint(exa_driver* d, const char* path, char* err, int errlen) {
+   try { d->sd->LoadCheckpoint(path); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// header of a checkpoint file (no GPU needed): out[0..19] = version, E_global, NN_global, Q, geometry, order, model, nprops, nstatev, steps_done, bc_index,
+// nranks, flags, nsections, model_calls, newton_cap, newton_cap2, writer, 0, 0; outd[0..2] = time, dt_class, last_dt; hashes[0..2] = property, grain-map,
+// connectivity hash.  sec_names (nsections x 24 bytes) and sec_info (nsections x { offset, nbytes, checksum }) may be NULL; at most max_sections are copied.
+int exa_checkpoint_info(const char* path, int64_t* out, double* outd, uint64_t* hashes, char* sec_names, uint64_t* sec_info, int max_sections, char* err, int errlen) {
+   try {
+      exa_ckpt::Header h; std::vector<exa_ckpt::Section> sec;
+      exa_ckpt::read_info(path, h, sec);
+      const int64_t v[20] = { h.version, h.E_global, h.NN_global, h.Q, h.geom, h.order, h.model, h.nprops, h.nstatev, h.steps_done, h.bc_index, h.nranks, h.flags,
+                              h.nsections, h.model_calls, h.newton_cap, h.newton_cap2, h.writer, 0, 0 };
+      if (out) std::memcpy(out, v, sizeof(v));
+      if (outd) { outd[0] = h.time; outd[1] = h.dt_class; outd[2] = h.last_dt; }
+      if (hashes) { hashes[0] = h.props_hash; hashes[1] = h.grain_hash; hashes[2] = h.conn_hash; }
+      for (int i = 0; i < (int)sec.size() && i < max_sections; i++) {
+         if (sec_names) { std::memset(sec_names + 24 * (size_t)i, 0, 24); std::memcpy(sec_names + 24 * (size_t)i, sec[i].name.c_str(), std::min<size_t>(sec[i].name.size(), 23)); }
+         if (sec_info) { sec_info[3 * i] = sec[i].offset; sec_info[3 * i + 1] = sec[i].nbytes; sec_info[3 * i + 2] = sec[i].checksum; }
+      }
+      return (int)sec.size();
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// [Checkpoint] table of an options file: out3 = { write, steps, keep }
+int exa_options_query_checkpoint(const char* toml_path, int* out3, char* floc, int floclen, char* restart_from, int restartlen, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      if (out3) { out3[0] = o.ckpt_write ? 1 : 0; out3[1] = o.ckpt_steps; out3[2] = o.ckpt_keep; }
+      if (floc && floclen > 0) { if ((int)o.ckpt_floc.size() >= floclen) throw std::runtime_error("Checkpoint.floc longer than the buffer"); std::strcpy(floc, o.ckpt_floc.c_str()); }
+      if (restart_from && restartlen > 0) { if ((int)o.ckpt_restart_from.size() >= restartlen) throw std::runtime_error("Checkpoint.restart_from longer than the buffer"); std::strcpy(restart_from, o.ckpt_restart_from.c_str()); }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// local -> global node map of a rank's partition (Partition::node_gid): info2 = { local nodes, global nodes }; node_gid may be NULL
+int exa_partition_query_nodes(const int* N, int rank, int nranks, int order, int64_t* info2, int64_t* node_gid) {
+   Partition p; const double L[3] = { 1.0, 1.0, 1.0 };
+   p.build(N, L, rank, nranks, (order >= 1 && order <= 6) ? order : 1);
+   info2[0] = p.NN; info2[1] = p.NN_glob;
+   if (node_gid) std::memcpy(node_gid, p.node_gid.data(), sizeof(int64_t) * p.node_gid.size());
+   return 0;
+}
+int exa_mesh_partition_query_nodes(const char* mesh_path, int rank, int nranks, int order, int64_t* info2, int64_t* node_gid, char* err, int errlen) {
+   try {
+      Partition p; p.build_from_mfem_mesh(mesh_path, rank, nranks, order);
+      info2[0] = p.NN; info2[1] = p.NN_glob;
+      if (node_gid) std::memcpy(node_gid, p.node_gid.data(), sizeof(int64_t) * p.node_gid.size());
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
 exa_driver* exa_driver_create_synthetic(const exa_synth_config* c, int rank, int nranks, const void* uid, char* err, int errlen) {

@@ -2,6 +2,7 @@
 // for its hot-path subset.  One process per GPU, like the reference's one MPI rank per device:
 //    mechanics -opt case.toml                      one MI355X
 //    mpirun -np 8 mechanics -opt case.toml         eight ranks (any launcher that exports a rank number: host/bootstrap.cpp)
+//    mechanics -opt case.toml -restart file.ckpt   resume from a checkpoint (overrides Checkpoint.restart_from; any rank count)
 // The ranks find each other through exa_bootstrap (rank / size from the launcher's environment, RCCL unique id over a TCP rendez-vous);
 // every collective afterwards is RCCL over xGMI.  Rank 0 prints and writes the avg_* files, every rank writes time/time_solve.<rank>.txt.
 #include <chrono>
@@ -22,13 +23,16 @@ int main(int argc, char** argv) {
          if (r0 == 0) std::fprintf(stderr, "mechanics: %d ranks, HSA_ENABLE_IPC_MODE_LEGACY was unset: running with 0 (dmabuf IPC)\n", n0);
       }
    }
-   std::string opt = "options.toml";
-   for (int i = 1; i < argc; i++) if ((!std::strcmp(argv[i], "-opt") || !std::strcmp(argv[i], "--option")) && i + 1 < argc) opt = argv[++i];
+   std::string opt = "options.toml", restart; bool have_restart = false;
+   for (int i = 1; i < argc; i++) {
+      if ((!std::strcmp(argv[i], "-opt") || !std::strcmp(argv[i], "--option")) && i + 1 < argc) opt = argv[++i];
+      else if ((!std::strcmp(argv[i], "-restart") || !std::strcmp(argv[i], "--restart")) && i + 1 < argc) { restart = argv[++i]; have_restart = true; }
+   }
    char err[512] = { 0 };
    int rank = 0, nranks = 1; unsigned char uid[128];
    if (exa_bootstrap(&rank, &nranks, uid, err, sizeof(err)) != 0) { std::fprintf(stderr, "mechanics: %s\n", err); return 1; }
    const auto t0 = std::chrono::steady_clock::now();
-   exa_driver* d = exa_driver_create(opt.c_str(), ".", rank, nranks, nranks > 1 ? uid : nullptr, 0, 1, err, sizeof(err));
+   exa_driver* d = exa_driver_create_restart(opt.c_str(), ".", rank, nranks, nranks > 1 ? uid : nullptr, 0, 1, have_restart ? restart.c_str() : nullptr, err, sizeof(err));
    if (!d) { std::fprintf(stderr, "mechanics (rank %d): %s\n", rank, err); return 1; }
    const int rc = exa_driver_run(d, err, sizeof(err));
    if (rc < 0) { std::fprintf(stderr, "mechanics (rank %d): run failed (%d) %s\n", rank, rc, err); exa_driver_destroy(d); return 2; }

@@ -33,6 +33,10 @@ struct Partition {
    std::vector<int32_t> conn;        // (n, E), native node order
    std::vector<double> X;            // byNODES (NN, 3)
    std::vector<int64_t> elem_gid;    // global element index, x fastest
+   // global number of every local node: generated meshes number the (N p + 1)^3 node grid x fastest, file meshes keep the reader's numbering
+   // after the order elevation.  Ranks that hold the same node give it the same number (checkpoint files are written by it)
+   std::vector<int64_t> node_gid;
+   int64_t E_glob = 0, NN_glob = 0;  // elements / nodes of the whole mesh
    std::vector<double> weight;       // 1 / (number of ranks holding the node)
    std::vector<Neighbor> nbrs;
    // meshes read from a file (Mesh.type = "other"): grain id = element attribute, boundary ids = boundary-element attributes
@@ -83,7 +87,8 @@ struct Partition {
       rc[0] = rank % pg[0]; rc[1] = (rank / pg[0]) % pg[1]; rc[2] = rank / (pg[0] * pg[1]);
       for (int d = 0; d < 3; d++) { split(N[d], pg[d], rc[d], e0[d], ne[d]); nn[d] = ne[d] * p + 1; }
       E = ne[0] * ne[1] * ne[2]; NN = nn[0] * nn[1] * nn[2];
-      conn.resize((size_t)n * E); X.resize((size_t)3 * NN); elem_gid.resize(E); weight.resize(NN);
+      conn.resize((size_t)n * E); X.resize((size_t)3 * NN); elem_gid.resize(E); weight.resize(NN); node_gid.resize(NN);
+      E_glob = E_global(); NN_glob = (int64_t)(N[0] * p + 1) * (N[1] * p + 1) * (N[2] * p + 1);
       const std::vector<int> nat = native_order(p);
       const int np = p + 1;
       std::vector<double> gll; exa_gll_nodes_01(np, gll);
@@ -96,6 +101,7 @@ struct Partition {
       for (int k = 0; k < nn[2]; k++) for (int j = 0; j < nn[1]; j++) for (int i = 0; i < nn[0]; i++) {
          const int g = i + nn[0] * (j + nn[1] * k);
          const int gi[3] = { e0[0] * p + i, e0[1] * p + j, e0[2] * p + k };   // nodes of an element at the Gauss-Lobatto points of the H1 basis
+         node_gid[g] = gi[0] + (int64_t)(N[0] * p + 1) * (gi[1] + (int64_t)(N[1] * p + 1) * gi[2]);
          for (int d = 0; d < 3; d++) {
             const int ge = std::min(gi[d] / p, N[d] - 1), a = gi[d] - ge * p;
             X[g + (size_t)NN * d] = len[d] * (ge + gll[a]) / N[d];
@@ -201,6 +207,8 @@ struct Partition {
       else if (order >= 3 && order <= 6) elevate_to_order(order, bdr);
       else if (order != 1) throw std::runtime_error("mesh: file meshes run at p_refinement = 1 ... 6");
       weight.assign(NN, 1.0); nbrs.clear();
+      E_glob = E; NN_glob = NN; node_gid.resize(NN);
+      for (int g = 0; g < NN; g++) node_gid[g] = g;
       if (nranks > 1) localize(rcb_owner(nranks));
    }
 
@@ -488,6 +496,7 @@ struct Partition {
          nbrs.push_back(std::move(nb));
       }
       conn.swap(lconn); elem_attr.swap(lattr); elem_gid.swap(lgid); X.swap(lX); bdr_nodes.swap(lb);
+      node_gid.assign(l2g.begin(), l2g.end());
       E = (int)elem_gid.size(); NN = NNl;
       if (E == 0) throw std::runtime_error("mesh: a rank received no elements (more ranks than the partitioner can serve)");
    }

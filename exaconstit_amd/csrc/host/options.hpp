@@ -100,6 +100,9 @@ struct ExaOptions {
    double dt_min = 1.0, dt_scale = 0.25; int nsteps = 1; std::string auto_dt_fname = "auto_dt_out.txt";
    std::string avg_stress_fname = "avg_stress.txt", avg_def_grad_fname = "avg_def_grad.txt", avg_pl_work_fname = "avg_pl_work.txt", avg_dp_tensor_fname = "avg_dp_tensor.txt";
    bool additional_avgs = false;
+   // [Checkpoint], every key optional: write = true writes <floc>_<step %06d>.ckpt into the output directory every `steps` steps and
+   // after the last one, keeping the newest `keep` files; restart_from names a checkpoint to resume from (relative to the options file)
+   bool ckpt_write = false; int ckpt_steps = 1, ckpt_keep = 2; std::string ckpt_floc = "checkpoint", ckpt_restart_from;
    // ParaView output of the per-element fields (reference src/option_parser.cpp:540-570): Visualizations.paraview / steps / floc / light_up.
    // visit, conduit and adios2 are read by the reference too; nothing is written for them here.
    bool paraview = false, light_up = false; int vis_steps = 1; std::string vis_floc = "results/exaconstit";
@@ -296,6 +299,26 @@ struct ExaOptions {
          texture_fname = f->str;
       }
       check_texture(texture_hkl, texture_dirs, texture_res_deg);
+      if (const TomlValue* w = d.get("Checkpoint.write")) {
+         if (w->kind != TomlValue::BOOL) throw std::runtime_error("Checkpoint.write must be true or false");
+         ckpt_write = w->b;
+      }
+      if (const TomlValue* v = d.get("Checkpoint.steps")) {
+         if (v->kind != TomlValue::NUM || v->num != std::floor(v->num) || v->num < 1 || v->num > 1e9) throw std::runtime_error("Checkpoint.steps must be a whole number of at least 1");
+         ckpt_steps = (int)v->num;
+      }
+      if (const TomlValue* v = d.get("Checkpoint.keep")) {
+         if (v->kind != TomlValue::NUM || v->num != std::floor(v->num) || v->num < 1 || v->num > 1e6) throw std::runtime_error("Checkpoint.keep must be a whole number of at least 1");
+         ckpt_keep = (int)v->num;
+      }
+      if (const TomlValue* v = d.get("Checkpoint.floc")) {
+         if (v->kind != TomlValue::STR || v->str.empty() || v->str.find('/') != std::string::npos) throw std::runtime_error("Checkpoint.floc must be a non-empty file name without '/'");
+         ckpt_floc = v->str;
+      }
+      if (const TomlValue* v = d.get("Checkpoint.restart_from")) {
+         if (v->kind != TomlValue::STR || v->str.empty()) throw std::runtime_error("Checkpoint.restart_from must be a non-empty path");
+         ckpt_restart_from = v->str;
+      }
       avg_def_grad_fname = d.str("Visualizations.avg_def_grad_fname", "avg_def_grad.txt");
       avg_pl_work_fname = d.str("Visualizations.avg_pl_work_fname", "avg_pl_work.txt");
       avg_dp_tensor_fname = d.str("Visualizations.avg_dp_tensor_fname", "avg_dp_tensor.txt");

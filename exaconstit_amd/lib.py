@@ -66,6 +66,8 @@ EXA_QLAYOUT_AOS, EXA_QLAYOUT_EB64 = 0, 1
 EXA_OK, EXA_ERR_ARG, EXA_ERR_HIP, EXA_ERR_STATE, EXA_ERR_UNSUPPORTED = 0, -1, -2, -3, -4
 exa_init_state = _sig("exa_init_state", C.c_int, C.c_void_p, dptr, dptr, C.c_void_p)
 exa_state_normalize = _sig("exa_state_normalize", C.c_int, C.c_void_p, dptr, C.c_void_p)
+exa_qf_pack = _sig("exa_qf_pack", C.c_int, C.c_void_p, C.c_int, dptr, dptr, dptr, C.c_void_p)
+exa_qf_unpack = _sig("exa_qf_unpack", C.c_int, C.c_void_p, C.c_int, dptr, dptr, dptr, C.c_void_p)
 exa_model_setup = _sig("exa_model_setup", C.c_int, C.c_void_p, C.c_double, dptr, dptr, dptr, dptr, dptr, dptr, dptr, C.c_void_p)
 exa_model_setup_checked = _sig("exa_model_setup_checked", C.c_int, C.c_void_p, C.c_double, dptr, dptr, dptr, dptr, dptr, dptr, dptr, C.c_void_p)
 exa_model_setup_lvec_records = _sig("exa_model_setup_lvec_records", C.c_int, C.c_void_p, C.c_double, dptr, dptr, dptr, dptr, dptr, dptr, dptr, C.c_void_p)
@@ -245,6 +247,14 @@ exa_options_query_lightup = _sig("exa_options_query_lightup", C.c_int, C.c_char_
                                  C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
 exa_driver_grain_averages = _sig("exa_driver_grain_averages", C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, C.c_char_p, C.c_int)
 exa_driver_set_grains = _sig("exa_driver_set_grains", C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int, C.c_int64, C.c_char_p, C.c_int)
+exa_driver_create_restart = _sig("exa_driver_create_restart", C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_int)
+exa_driver_save_checkpoint = _sig("exa_driver_save_checkpoint", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int)
+exa_driver_load_checkpoint = _sig("exa_driver_load_checkpoint", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_int)
+exa_checkpoint_info = _sig("exa_checkpoint_info", C.c_int, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint64),
+                           C.c_int, C.c_char_p, C.c_int)
+exa_options_query_checkpoint = _sig("exa_options_query_checkpoint", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
+exa_partition_query_nodes = _sig("exa_partition_query_nodes", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p)
+exa_mesh_partition_query_nodes = _sig("exa_mesh_partition_query_nodes", C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_char_p, C.c_int)
 exa_options_query_grains = _sig("exa_options_query_grains", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int, C.c_char_p, C.c_int)
 exa_grain_avgs_write = _sig("exa_grain_avgs_write", C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, C.c_int)
 EXA_GRAIN_NVALS = 45
@@ -401,6 +411,125 @@ def mg_level_count(N, nranks=1, cap=0):
     return exa_mg_level_count(n, int(nranks), int(cap))
 
 
+def options_checkpoint(path):
+    """[Checkpoint] table of an options file: dict(write, steps, keep, floc, restart_from)."""
+    out = (C.c_int * 3)()
+    floc, rst = C.create_string_buffer(4096), C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_query_checkpoint(path.encode(), out, floc, 4096, rst, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(write=bool(out[0]), steps=out[1], keep=out[2], floc=floc.value.decode(), restart_from=rst.value.decode())
+
+
+def partition_nodes(N, rank, nranks, order=1, mesh=None):
+    """Global node number of every local node of a rank's partition (generated N^3 mesh, or the mesh file `mesh`): (node_gid, global node count)."""
+    import numpy as np
+    info = (C.c_int64 * 2)()
+    err = C.create_string_buffer(512)
+
+    def call(buf):
+        if mesh is None:
+            n = (C.c_int * 3)(*([int(N)] * 3 if isinstance(N, int) else [int(v) for v in N]))
+            return exa_partition_query_nodes(n, rank, nranks, order, info, buf)
+        return exa_mesh_partition_query_nodes(mesh.encode(), rank, nranks, order, info, buf, err, 512)
+    if call(None) != 0:
+        raise RuntimeError(err.value.decode())
+    gid = np.zeros(info[0], np.int64)
+    if call(gid.ctypes.data_as(C.c_void_p)) != 0:
+        raise RuntimeError(err.value.decode())
+    return gid, int(info[1])
+
+
+CHECKPOINT_INFO_KEYS = ("version", "elements", "nodes", "qpts_per_elem", "geometry", "order", "model", "nprops", "nstatev", "steps_done", "bc_index",
+                        "nranks", "flags", "nsections", "model_calls", "newton_cap", "newton_cap2", "writer")
+
+
+def checkpoint_info(path):
+    """Header and section table of a checkpoint file through the library (no GPU needed): dict of the header fields (CHECKPOINT_INFO_KEYS, time,
+    dt_class, last_dt, props_hash, grain_hash, conn_hash, cycle0_saved, texture0_written) and "sections": {name: (offset, nbytes, checksum)}."""
+    out, outd, hs = (C.c_int64 * 20)(), (C.c_double * 3)(), (C.c_uint64 * 3)()
+    names, info = C.create_string_buffer(24 * 64), (C.c_uint64 * (3 * 64))()
+    err = C.create_string_buffer(1024)
+    n = exa_checkpoint_info(path.encode(), out, outd, hs, names, info, 64, err, 1024)
+    if n < 0:
+        raise RuntimeError(err.value.decode())
+    d = {k: int(out[i]) for i, k in enumerate(CHECKPOINT_INFO_KEYS)}
+    d.update(time=outd[0], dt_class=outd[1], last_dt=outd[2], props_hash=int(hs[0]), grain_hash=int(hs[1]), conn_hash=int(hs[2]),
+             cycle0_saved=bool(out[12] & 1), texture0_written=bool(out[12] & 2))
+    d["sections"] = {names.raw[24 * i:24 * i + 24].split(b"\0")[0].decode(): (int(info[3 * i]), int(info[3 * i + 1]), int(info[3 * i + 2])) for i in range(min(n, 64))}
+    return d
+
+
+CHECKPOINT_MAGIC = b"EXACKPT\0"
+# (name, struct format, byte offset) of the 256-byte header, little-endian (DESIGN 4.10)
+CHECKPOINT_HEADER = (("version", "<I", 8), ("header_bytes", "<I", 12), ("elements", "<q", 16), ("nodes", "<q", 24), ("qpts_per_elem", "<i", 32), ("geometry", "<i", 36),
+                     ("order", "<i", 40), ("model", "<i", 44), ("nprops", "<i", 48), ("nstatev", "<i", 52), ("props_hash", "<Q", 56), ("grain_hash", "<Q", 64),
+                     ("conn_hash", "<Q", 72), ("steps_done", "<q", 80), ("time", "<d", 88), ("dt_class", "<d", 96), ("last_dt", "<d", 104), ("bc_index", "<i", 112),
+                     ("nranks", "<i", 116), ("flags", "<I", 120), ("nsections", "<i", 124), ("model_calls", "<q", 128), ("newton_cap", "<i", 136), ("newton_cap2", "<i", 140),
+                     ("writer", "<I", 144))
+CHECKPOINT_ROW_WIDTH = {"avg_stress": 6, "avg_def_grad": 9, "avg_pl_work": 1, "avg_dp_tensor": 6, "pvd_cycles": 2, "auto_dt": 1}
+
+
+def read_checkpoint(path, copy=True):
+    """Pure-numpy reader of a checkpoint file, following the documented format and independent of the library: dict with "header"
+    (field -> value), "sections" ({name: (offset, nbytes, checksum)}) and one array per section: x_beg / v_sol (nodes, 3) by global node number,
+    stress0 (elements, Q, 6) and matVars0 (elements, Q, nstatev) by global element id, avg_* rows, solver_stats (steps, 4) int32
+    (Newton iterations, Krylov iterations, constitutive launches, converged), pvd_cycles (n, 2), lattice_strains / lattice_volumes / auto_dt (flat),
+    x_beg_copies / v_sol_copies (n, 5) int64 (rank + 2^32 * rank count, global node, bit patterns of the rank's x, y, z).
+    Refuses a wrong magic or version, a truncated file and a section whose checksum does not match, naming it.  The file is memory-mapped;
+    copy=False returns read-only views of the mapping instead of arrays (a 128^3 checkpoint is 4.7 GB)."""
+    import struct
+    import numpy as np
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        b = f.read(256)                      # header, then the table; the sections are mapped, not read into a second buffer
+        n_ = struct.unpack_from("<i", b, 124)[0] if len(b) == 256 and b[:8] == CHECKPOINT_MAGIC else 0
+        b += f.read(48 * max(0, min(n_, 4096)))
+    if len(b) < 8 or b[:8] != CHECKPOINT_MAGIC:
+        raise ValueError(f"checkpoint: wrong magic ({path} is not a checkpoint file of this library)")
+    if len(b) < 256:
+        raise ValueError(f"checkpoint: truncated file (the header needs 256 bytes, the file has {size})")
+    h = {k: struct.unpack_from(f, b, o)[0] for k, f, o in CHECKPOINT_HEADER}
+    if h["version"] != 1 or h["header_bytes"] != 256:
+        raise ValueError(f"checkpoint: unsupported format version {h['version']} (this reader reads version 1)")
+    with np.errstate(over="ignore"):
+        if int(np.frombuffer(b, "<u8", 31, 0).sum(dtype=np.uint64)) != struct.unpack_from("<Q", b, 248)[0]:
+            raise ValueError("checkpoint: checksum mismatch in the header")
+    n = h["nsections"]
+    if len(b) < 256 + 48 * n:
+        raise ValueError(f"checkpoint: truncated file (the section table ends at byte {256 + 48 * n}, the file has {size})")
+    data = np.memmap(path, dtype=np.uint8, mode="r")
+    out = {"header": h, "sections": {}}
+    for i in range(n):
+        e = 256 + 48 * i
+        name = b[e:e + 24].split(b"\0")[0].decode()
+        off, nb, cs = struct.unpack_from("<QQQ", b, e + 24)
+        if nb and off + nb > size:         # (an empty section holds no bytes wherever its offset points)
+            raise ValueError(f"checkpoint: truncated file (section '{name}' ends at byte {off + nb}, the file has {size})")
+        words = data[off:off + nb].view("<u8") if nb else np.zeros(0, "<u8")
+        with np.errstate(over="ignore"):
+            if int(words.sum(dtype=np.uint64)) != cs:
+                raise ValueError(f"checkpoint: checksum mismatch in section '{name}'")
+        out["sections"][name] = (off, nb, cs)
+        E, Q, NN = h["elements"], h["qpts_per_elem"], h["nodes"]
+        if name in ("x_beg", "v_sol"):
+            a = words.view(np.float64).reshape(NN, 3)
+        elif name == "stress0":
+            a = words.view(np.float64).reshape(E, Q, 6)
+        elif name == "matVars0":
+            a = words.view(np.float64).reshape(E, Q, h["nstatev"])
+        elif name == "solver_stats":
+            a = words.view(np.int32)[:4 * h["steps_done"]].reshape(-1, 4)
+        elif name.endswith("_copies"):          # { rank + 2^32 * rank count of the writer, global node, bit patterns of x, y, z } per entry
+            a = words.view(np.int64).reshape(-1, 5)
+        elif name in CHECKPOINT_ROW_WIDTH:
+            a = words.view(np.float64).reshape(-1, CHECKPOINT_ROW_WIDTH[name])
+        else:
+            a = words.view(np.float64)
+        out[name] = np.array(a) if copy else a
+    return out
+
+
 def options_vis(path):
     """Visualizations table of an options file: dict(paraview, steps, light_up, floc)."""
     pv, st, lu = C.c_int(), C.c_int(), C.c_int()
@@ -459,9 +588,11 @@ class Driver:
         self._err = C.create_string_buffer(512)
 
     @classmethod
-    def from_toml(cls, path, out_dir=".", rank=0, nranks=1, uid=None, jacobi=False, write_files=True):
-        err = C.create_string_buffer(512)
-        h = exa_driver_create(path.encode(), out_dir.encode(), rank, nranks, uid, int(jacobi), int(write_files), err, 512)
+    def from_toml(cls, path, out_dir=".", rank=0, nranks=1, uid=None, jacobi=False, write_files=True, restart=None):
+        """restart: a checkpoint file to resume from (overrides Checkpoint.restart_from of the options file); None: what the options file says."""
+        err = C.create_string_buffer(1024)
+        h = exa_driver_create_restart(path.encode(), out_dir.encode(), rank, nranks, uid, int(jacobi), int(write_files),
+                                      None if restart is None else str(restart).encode(), err, 1024)
         return cls(h, err)
 
     @classmethod
@@ -489,6 +620,14 @@ class Driver:
         if rc < 0:
             raise RuntimeError(self._err.value.decode())
         return rc == 1
+
+    def save_checkpoint(self, path):
+        """Writes a checkpoint of the current begin-of-step state; every rank of the group calls it."""
+        self._chk(exa_driver_save_checkpoint(self.h, str(path).encode(), self._err, 512))
+
+    def load_checkpoint(self, path):
+        """Resumes from a checkpoint: legal only on a freshly created driver before its first step; run() continues at the step after the stored one."""
+        self._chk(exa_driver_load_checkpoint(self.h, str(path).encode(), self._err, 512))
 
     def commit_step(self):
         self._chk(exa_driver_commit_step(self.h, self._err, 512))

@@ -71,6 +71,27 @@ int exa_loopback_group_create(int nranks, void* out128);
 void exa_loopback_group_destroy(const void* id128);
 exa_driver* exa_driver_create(const char* toml_path, const char* out_dir, int rank, int nranks, const void* uid, int jacobi, int write_files, char* err, int errlen);
 exa_driver* exa_driver_create_synthetic(const exa_synth_config* c, int rank, int nranks, const void* uid, char* err, int errlen);
+/* Checkpoint and restart.  A checkpoint is one self-describing file that does not depend on the decomposition, the quadrature
+ * layout or the rank count: a run resumes from it on any number of ranks.  Every rank of the group calls save / load.
+ *   exa_driver_save_checkpoint  writes <path>.tmp and renames it, so an interrupted write leaves the previous checkpoint intact
+ *   exa_driver_load_checkpoint  legal only on a freshly created driver before its first step; a file of another mesh, order, geometry, model,
+ *                               property set or grain map, a truncated file and a checksum mismatch are refused with a message that names the
+ *                               mismatch; the avg_* and light-up files are rewritten from the stored rows; exa_driver_run continues at the
+ *                               step after the stored one.  Nothing of the driver is changed before every section's checksum has been
+ *                               verified: after a refused load (-1) the driver is still the freshly created one and may load another file
+ *                               or run from the start
+ *   exa_driver_create_restart   exa_driver_create + load: restart_path NULL = Checkpoint.restart_from of the options file (if any),
+ *                               "" = no restart, otherwise the checkpoint to resume from
+ *   exa_checkpoint_info         header and section table only, no GPU needed: out20 = { version, global elements, global nodes, points per element,
+ *                               geometry, order, model, nprops, nstatev, steps_done, BC entry in force, writer's rank count, flags, sections,
+ *                               model_calls, newton_cap, newton_cap2, writer, 0, 0 }, outd3 = { time, dt_class, last_dt }, hashes3 = { property,
+ *                               grain-map, connectivity hash }, sec_names = 24 bytes per section, sec_info = { offset, nbytes, checksum } per
+ *                               section (any of them may be NULL); returns the number of sections or -1 (err) */
+exa_driver* exa_driver_create_restart(const char* toml_path, const char* out_dir, int rank, int nranks, const void* uid, int jacobi, int write_files,
+                                      const char* restart_path, char* err, int errlen);
+int exa_driver_save_checkpoint(exa_driver* d, const char* path, char* err, int errlen);
+int exa_driver_load_checkpoint(exa_driver* d, const char* path, char* err, int errlen);
+int exa_checkpoint_info(const char* path, int64_t* out20, double* outd3, uint64_t* hashes3, char* sec_names, uint64_t* sec_info, int max_sections, char* err, int errlen);
 void exa_driver_destroy(exa_driver* d);
 /* Preconditioner of the PCG (Solvers.Krylov.preconditioner in an options file; this call overrides it), valid before the first step (so
  * synthetic and exa_driver_bench_prepare'd drivers can use it): kind 0 identity, 1 Jacobi, 2 geometric multigrid V-cycle (generated p = 1
@@ -191,6 +212,8 @@ int exa_options_query_lightup(const char* toml_path, int* enabled, int* nhkl, in
 int exa_options_query_texture(const char* toml_path, int* enabled, int* nhkl, int* hkl48, int* ndir, double* dirs9, double* res_deg, char* fname, int fnamelen,
                               char* err, int errlen);
 int exa_options_query_grains(const char* toml_path, int* enabled, char* fname, int fnamelen, char* err, int errlen);
+/* [Checkpoint] table (all keys optional): out3 = { write (default 0), steps (1), keep (2) }, floc (default "checkpoint"), restart_from (default "") */
+int exa_options_query_checkpoint(const char* toml_path, int* out3, char* floc, int floclen, char* restart_from, int restartlen, char* err, int errlen);
 /* the grain_avgs file writer (host only): a '#' header naming the 46 columns, then n rows of grain_ids[i] and vals[i][EXA_GRAIN_NVALS] (the
  * element count as an integer, the rest with 17 significant digits).  Returns 0 or -1 (err). */
 int exa_grain_avgs_write(const char* path, int n, const int32_t* grain_ids, const double* vals, char* err, int errlen);
@@ -215,6 +238,10 @@ int exa_partition_query(const int* N, int rank, int nranks, int64_t* info8, int3
 /* The element order the driver runs with on several ranks: elements touching a node shared with another rank first (their 64-element
  * blocks are computed before the halo exchange starts, the interior ones while it is on the wire).  out2 = { E, E_bdr }. */
 int exa_partition_query_boundary_first(const int* N, int rank, int nranks, int order, int64_t* out2, int32_t* conn, int64_t* elem_gid);
+/* local -> global node numbers of a rank's partition: info2 = { local nodes, global nodes }; node_gid (local nodes) may be NULL.  Ranks that hold
+ * the same node give it the same number (generated meshes: the (N p + 1)^3 grid, x fastest; file meshes: the reader's numbering after elevation) */
+int exa_partition_query_nodes(const int* N, int rank, int nranks, int order, int64_t* info2, int64_t* node_gid);
+int exa_mesh_partition_query_nodes(const char* mesh_path, int rank, int nranks, int order, int64_t* info2, int64_t* node_gid, char* err, int errlen);
 int exa_mesh_partition_query(const char* mesh_path, int rank, int nranks, int64_t* info8, int32_t* conn, double* X, int64_t* elem_gid, double* weight,
                              int32_t* nbr_rank, int32_t* nbr_count, int32_t* nbr_dofs, char* err, int errlen);
 /* ... at p_refinement = order: 1, or 2 = one node added per edge, face and element of the trilinear file mesh (what the reference's order

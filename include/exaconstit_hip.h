@@ -144,6 +144,14 @@ int exa_init_state(exa_ctx* ctx, double* state0_dev, const double* quats_per_ele
 /* state[0] = sum_a |state[14+a]| at every point of a state array in the context's layout (see above) */
 int exa_state_normalize(exa_ctx* ctx, double* state_dev, exa_stream s);
 
+/* Checkpoint support.  exa_qf_pack: a quadrature function of vdim values per point in the context's layout -> the canonical
+ * (vdim, Q, E) rows of a checkpoint file (EXA_QLAYOUT_AOS order, local element order, vdim Q E doubles); exa_qf_unpack: the reverse (the
+ * padding lanes of the last element block keep what they held).  1 <= vdim <= 96.  checksum_dev may be NULL; otherwise it receives, in the
+ * same pass, the sum of the bit patterns of the vdim Q E values as unsigned 64-bit integers modulo 2^64 - a value that does not depend on
+ * the layout, on the order of the elements or on how they are spread over ranks (partial sums of ranks simply add). */
+int exa_qf_pack(exa_ctx* ctx, int vdim, const double* src_dev, double* dst_dev, uint64_t* checksum_dev, exa_stream s);
+int exa_qf_unpack(exa_ctx* ctx, int vdim, const double* src_dev, double* dst_dev, uint64_t* checksum_dev, exa_stream s);
+
 /* ExaCMechModel::ModelSetup (src/mechanics_ecmech.cpp:192-258), i.e. StressSetup/StateVarsSetup, grad_calc,
  * kernel_setup, getResponseECM, kernel_postprocessing fused into one launch.  On return (stream order) stress1, state1
  * and the column-major tangent d sigma/d eps hold end-of-step values.  Points whose local solve did not converge are
