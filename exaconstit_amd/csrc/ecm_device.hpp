@@ -18,12 +18,8 @@
 namespace ecmdev {
 
 #define ECM_DI __device__ __forceinline__
-#ifndef ECM_SLIP_UNROLL
-#define ECM_SLIP_UNROLL 1   // slip-system loop unroll factor of the point problem (ILP vs registers; tuned on MI355X)
-#endif
 
 constexpr int NSLIP = 12;
-constexpr int kSlipUnroll = ECM_SLIP_UNROLL;
 constexpr double SQR2 = 1.4142135623730951, SQR3 = 1.7320508075688772;
 constexpr double SQR2I = 0.70710678118654752, SQR6I = 0.40824829046386302, SQR2B3 = 0.81649658092772603;
 constexpr double TINY_SQRT = 1.0e-90, EPS_SQRT = 1.0e-8;
@@ -33,45 +29,18 @@ constexpr double E_SCALE = 5.0e-4, R_SCALE = 0.01;
 // launch writes are next read by ANOTHER launch after gigabytes of other traffic (3.5 GB of records, 3.8 GB of state at 128^3), so keeping them out
 // of L2 leaves it to the node rows the gathers of neighbouring waves share.  History: round 2 measured the hint as a loss (plastic pass 7.28 -> 7.56 ms)
 // when the kernel still spilled - its scratch lines are what the hint displaced; round 5 (no scratch): stores 4.21 -> 4.18 ms, loads alone +-0, both
-// 4.21 / 4.23 -> 4.17 / 4.13 ms, elastic pass 2.76 -> 2.70 ms (profiles/r05_kernel_experiments.txt).  ECM_NT=0 restores plain accesses (A/B switch).
-#ifndef ECM_NT
-#define ECM_NT 1
-#endif
-#ifndef ECM_NT_LD
-#define ECM_NT_LD ECM_NT
-#endif
-#ifndef ECM_NT_ST
-#define ECM_NT_ST ECM_NT
-#endif
-#ifndef ECM_NT_REC
-#define ECM_NT_REC ECM_NT_ST   // the 13 16-byte pairs of the compact gradient record (read by the NEXT kernel, 3.5 GB at 128^3: never from cache)
-#endif
-__device__ __forceinline__ double ldg(const double* p) {
-#if ECM_NT_LD
-   return __builtin_nontemporal_load(p);
-#else
-   return *p;
-#endif
-}
-__device__ __forceinline__ void stg(double* p, double v) {
-#if ECM_NT_ST
-   __builtin_nontemporal_store(v, p);
-#else
-   *p = v;
-#endif
-}
+// 4.21 / 4.23 -> 4.17 / 4.13 ms, elastic pass 2.76 -> 2.70 ms (profiles/r05_kernel_experiments.txt).
+__device__ __forceinline__ double ldg(const double* p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ void stg(double* p, double v) { __builtin_nontemporal_store(v, p); }
 // output store of the point update: global memory (non-temporal), or - LO, the staged AOS launch (model_kernel.hpp, PointIO<.., STG>) - the lane's row of
 // the wave's LDS stage, from where the wave stores whole rows of 64 points coalesced
 template <bool LO>
 __device__ __forceinline__ void ost(double* p, double v) { if constexpr (LO) *p = v; else stg(p, v); }
+// a 16-byte pair, e.g. one of the 13 of the compact gradient record (read by the NEXT kernel, 3.5 GB at 128^3: never from cache)
 __device__ __forceinline__ void stg2(double2* p, double a, double b) {
-#if ECM_NT_REC
    typedef double vd2 __attribute__((ext_vector_type(2)));
    vd2 v; v.x = a; v.y = b;
    __builtin_nontemporal_store(v, reinterpret_cast<vd2*>(p));
-#else
-   *p = make_double2(a, b);
-#endif
 }
 
 // history layout (reference src/mechanics_ecmech.hpp:165-185)
@@ -170,29 +139,18 @@ ECM_DI double frcp(double x) {
 // exp for N arguments (Kocks-Mecking kinetics: three exponentials per slip system and evaluation).  Same algorithm as the library routine -
 // n = rint(x log2 e), r = x - n ln2 (two-term), polynomial, ldexp - without its overflow / underflow selects: arguments are clamped to
 // [-800, 720], where ldexp itself produces 0 / inf; Taylor degree 13 on |r| <= ln2 / 2 (truncation 4e-18), |error| <= 1.5 ulp.  22 FP64
-// instructions per value instead of 38.  The values are computed one after the other (ECM_KM_EXP == 1: the empty asm keeps the compiler
-// from interleaving them): at 128^3 the interleaved form costs FCC 24.1 ms against 21.2 - the kernel has no registers left for six
-// polynomial chains in flight, and two waves per SIMD hide the FMA latency of a single chain.
-#ifndef ECM_KM_EXP
-#define ECM_KM_EXP 1   // A/B switch: 0 = library exp(), 1 = this routine, 2 = this routine, interleaving left to the compiler
-#endif
+// instructions per value instead of 38.  The values are computed one after the other (the empty asm keeps the compiler from interleaving
+// them): at 128^3 the interleaved form cost FCC 24.1 ms against 21.2 - the kernel has no registers left for six polynomial chains in
+// flight, and two waves per SIMD hide the FMA latency of a single chain.
 // a double constant that is materialised in a scalar register pair where it is used.  Left alone, the compiler hoists the polynomial
 // coefficients of exp_n / log_near1 out of the Newton loop INTO VECTOR REGISTERS (v_fmac wants its addend in the destination register) - 28
 // VGPRs for the exp coefficients alone, the logarithm's went to scratch and were re-loaded, one dependent round trip each, inside the
 // slip-system loop of the Kocks-Mecking kernels.  The volatile asm pins the materialisation (two s_mov, no VALU work) to the point of use.
-#ifndef ECM_SCONST
-#define ECM_SCONST 1
-#endif
 ECM_DI double sconst(double c) {
-#if ECM_SCONST
    asm volatile("" : "+s"(c));
-#endif
    return c;
 }
-#ifndef ECM_SCONST_EXP
-#define ECM_SCONST_EXP 1   // ... in exp_n (A/B switch)
-#endif
-template <bool SC> ECM_DI double sconst_e(double c) { return (ECM_SCONST_EXP && SC) ? sconst(c) : c; }
+template <bool SC> ECM_DI double sconst_e(double c) { return SC ? sconst(c) : c; }   // ... in exp_n, where the kernel kind decides
 // sin and cos of a moderate angle (rotation increments: |x| below ~1e5): Cody-Waite reduction by pi/2 in two parts and the fdlibm kernel
 // polynomials on |r| <= pi/4, |error| ~ 1 ulp.  Takes the place of the library sincos in the large-angle branches of the exponential map,
 // which are rarely taken but whose 12 polynomial coefficients the compiler kept in vector registers - or in scratch - across the whole
@@ -222,23 +180,21 @@ ECM_DI void sincos_s(const double x, double& sn, double& cs) {
 // exponentials per evaluation there: the 28 scalar moves per value get in the way), so the kernel kind decides (kin_sc_exp)
 template <int N, bool FAST, bool SC = true>   // FAST = false: library routine (the general instantiations, whose register allocation the routine upsets)
 ECM_DI void exp_n(double v[N]) {
-   if constexpr (ECM_KM_EXP != 0 && FAST) {
-   constexpr double tab[14] = { 1.4426950408889634074, -6.93147180369123816490e-01, -1.90821492927058770002e-10,
-      1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0, 1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0, 1.0 / 120.0, 1.0 / 24.0, 1.0 / 6.0 };
+   if constexpr (FAST) {
+      constexpr double tab[14] = { 1.4426950408889634074, -6.93147180369123816490e-01, -1.90821492927058770002e-10,
+         1.0 / 6227020800.0, 1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0, 1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0, 1.0 / 120.0, 1.0 / 24.0, 1.0 / 6.0 };
 #pragma unroll
-   for (int a = 0; a < N; a++) {
-      const double x = fmin(fmax(v[a], -800.0), 720.0); const double n = rint(x * sconst_e<SC>(tab[0])); double r = fma(n, sconst_e<SC>(tab[1]), x); r = fma(n, sconst_e<SC>(tab[2]), r);
-      double p = fma(sconst_e<SC>(tab[3]), r, sconst_e<SC>(tab[4]));
+      for (int a = 0; a < N; a++) {
+         const double x = fmin(fmax(v[a], -800.0), 720.0); const double n = rint(x * sconst_e<SC>(tab[0])); double r = fma(n, sconst_e<SC>(tab[1]), x); r = fma(n, sconst_e<SC>(tab[2]), r);
+         double p = fma(sconst_e<SC>(tab[3]), r, sconst_e<SC>(tab[4]));
 #pragma unroll
-      for (int k = 5; k < 14; k++) p = fma(p, r, sconst_e<SC>(tab[k]));
-      p = fma(p, r, 0.5); p = fma(p, r, 1.0); p = fma(p, r, 1.0); v[a] = ldexp(p, (int)n);
-#if ECM_KM_EXP == 1
-      asm volatile("" : "+v"(v[a]));
-#endif
-   }
+         for (int k = 5; k < 14; k++) p = fma(p, r, sconst_e<SC>(tab[k]));
+         p = fma(p, r, 0.5); p = fma(p, r, 1.0); p = fma(p, r, 1.0); v[a] = ldexp(p, (int)n);
+         asm volatile("" : "+v"(v[a]));
+      }
    } else {
 #pragma unroll
-   for (int a = 0; a < N; a++) v[a] = exp(v[a]);
+      for (int a = 0; a < N; a++) v[a] = exp(v[a]);
    }
 }
 
@@ -426,31 +382,19 @@ ECM_DI void voce_gdot12(const MatParams& mp, double g_i, const double tau[NSLIP]
 // keeps a uniform branch a branch: without it the compiler speculates the (pure) pow() of the general case and selects afterwards,
 // i.e. every call pays two full pow() expansions (~400 instructions) even when p == q == 1
 #define ECM_NO_SPECULATE() asm volatile("" ::: "memory")
-#ifndef ECM_KM_LOG_NEAR1
-#define ECM_KM_LOG_NEAR1 1   // Kocks-Mecking power-law tail: short-series logarithm when (t_min, t_max] lies in [0.75, 1.25] (A/B switch)
-#endif
-#ifndef ECM_KM_ONE_RCP
-#define ECM_KM_ONE_RCP 1     // Kocks-Mecking: series combination of the thermal and drag branches with one reciprocal instead of three (A/B switch)
-#endif
-#ifndef ECM_EXP_PQ1
-#define ECM_EXP_PQ1 0   // timing experiment: p == q == 1 known at compile time (no pow() code in the kinetics at all)
-#endif
-#ifndef ECM_KM_SKIP_BACK
-#define ECM_KM_SKIP_BACK 1   // p == q == 1: backward-jump term dropped where it is below half an ulp of the forward term (A/B switch)
-#endif
 template <bool PQ1>
 ECM_DI void mts_dG(const MatParams& mp, double c_e, double t_frac, double& exp_arg, double& dfac) {
    exp_arg = 0.0; dfac = 0.0;
    if (t_frac >= 1.0) return;
    double p_func, dp_func;
    const double at = fabs(t_frac);
-   if (PQ1 || ECM_EXP_PQ1 || mp.p == 1.0) { p_func = t_frac; dp_func = 1.0; }
+   if (PQ1 || mp.p == 1.0) { p_func = t_frac; dp_func = 1.0; }
    else if (at < TINY_SQRT) { p_func = 0.0; dp_func = 0.0; }
    else { ECM_NO_SPECULATE(); const double pw = pow(at, mp.p); p_func = copysign(pw, t_frac); dp_func = mp.p * pw / at; }
    const double q_arg = 1.0 - p_func;
    if (q_arg <= TINY_SQRT) return;
    double q_func, dq_func;
-   if (PQ1 || ECM_EXP_PQ1 || mp.q == 1.0) { q_func = q_arg; dq_func = 1.0; }
+   if (PQ1 || mp.q == 1.0) { q_func = q_arg; dq_func = 1.0; }
    else { ECM_NO_SPECULATE(); q_func = pow(q_arg, mp.q); dq_func = mp.q * q_func / q_arg; }
    exp_arg = -c_e * q_func; dfac = c_e * dq_func * dp_func;
 }
@@ -468,9 +412,6 @@ ECM_DI void mts_dG(const MatParams& mp, double c_e, double t_frac, double& exp_a
 #define ECM_KD 2
 #endif
 constexpr int KD = ECM_KD;   // systems per group of the cheap classes in the deferred form (only one exp each: wider groups for ILP)
-#ifndef ECM_KM_DEFER
-#define ECM_KM_DEFER 1   // athermal-threshold (BCC) variant: window systems are treated one per lane after the group loop (eval_rj)
-#endif
 constexpr int KW = ECM_KW;   // slip systems evaluated together by the Kocks-Mecking kinetics (ILP vs registers; tuned on MI355X)
 template <bool WITHD, int KW = ECM_KW, bool PQ1 = false, bool SC = true>
 ECM_DI void kmbald_gdot4(const MatParams& mp, const KinVals& kv, const double tau[KW], double gdot[KW], double dg[KW]) {
@@ -515,7 +456,7 @@ ECM_DI void kmbald_gdot4(const MatParams& mp, const KinVals& kv, const double ta
          // in-window system has eaf >= ln(1e-60) = -138.2, so for c_e > 180 the backward term is below e^-41.8 = 7e-19 < 2^-54 of the forward
          // one in both gw = gam_w (ef - eb) and its derivative: dropping it leaves every bit as it was (the shipped material sets have
          // c_e ~ 300).  In general (and always for exp(x) == 0, x < -745.2) the call is skipped when no lane of the wave needs it.
-         const bool pq1 = ECM_KM_SKIP_BACK && (PQ1 || ECM_EXP_PQ1 || (mp.p == 1.0 && mp.q == 1.0));
+         const bool pq1 = PQ1 || (mp.p == 1.0 && mp.q == 1.0);
          bool any_b = false;
          if (pq1) {
 #pragma unroll
@@ -542,7 +483,7 @@ ECM_DI void kmbald_gdot4(const MatParams& mp, const KinVals& kv, const double ta
 #pragma unroll
          for (int a = 0; a < KW; a++) pw[a] = 0.0;
          if (any_tail) {   // power-law tail: only above t_min = (1e-60)^m (rare for large 1/m)
-            if constexpr (PQ1 && ECM_KM_LOG_NEAR1) {
+            if constexpr (PQ1) {
                // p == q == 1 instantiation: the host selects it only when the tail's window (t_min, t_max] lies in [0.75, 1.25] and 1/m is not an
                // integer (model_kernels.hip, km_pq1), so the short-series logarithm is the only form compiled in - the general log() brought
                // eight more coefficients into the register file of the whole Newton loop
@@ -563,7 +504,7 @@ ECM_DI void kmbald_gdot4(const MatParams& mp, const KinVals& kv, const double ta
 #pragma unroll
                   for (int a = 0; a < KW; a++) b[a] *= b[a];
                }
-            } else if (ECM_KM_LOG_NEAR1 && mp.t_min >= 0.75 && mp.t_max <= 1.25) {
+            } else if (mp.t_min >= 0.75 && mp.t_max <= 1.25) {
                // the tail is only used for t_min < at0 <= t_max, and with 1/m = 2 c_e p q of a few hundred both bounds are close to 1
                // (1e-60^m, 1e45^m): logarithm by the short series (other lanes compute a finite value that is not used)
 #pragma unroll
@@ -584,16 +525,10 @@ ECM_DI void kmbald_gdot4(const MatParams& mp, const KinVals& kv, const double ta
             gw += tail ? temp * at0[a] : 0.0;
             dgw += tail ? temp * mp.xnn * g_i : 0.0;
             const bool valid = inwin[a] && (gw > 0.0);
-#if ECM_KM_ONE_RCP
             // series combination of the two branches 1 / (1/gw + 1/gr) = gw gr / (gw + gr) with one reciprocal (lanes that are not `valid` may hold junk here)
             const double R = frcp(gw + gr[a]);
             const double gd = (gw * gr[a]) * R;
             if (valid) { gdot[a] = copysign(gd, tau[a]); if (WITHD) dg[a] = (dgw * (gr[a] * gr[a]) + dgr[a] * (gw * gw)) * (R * R); }
-#else
-            const double r1 = frcp(gw), r2 = frcp(gr[a]);   // series combination of the two branches; lanes that are not `valid` may hold junk here
-            const double gd = frcp(r1 + r2);
-            if (valid) { gdot[a] = copysign(gd, tau[a]); if (WITHD) dg[a] = gd * gd * (dgw * r1 * r1 + dgr[a] * r2 * r2); }
-#endif
          }
       }
    }
@@ -641,69 +576,25 @@ ECM_DI double kin_update_h(const MatParams& mp, double hs_o, double dt, double s
 
 // Register budget.  Two waves per SIMD need <= 256 VGPRs; the naive point update wants ~370.  What is not touched inside the
 // slip-system loop is therefore parked outside the register file:
-//   * per-thread LDS stash (slot s of thread t at stash[s * ECM_STASH_STRIDE + t], conflict-free), 38 doubles so that two 256-thread
+//   * per-thread LDS stash (slot s of lane l of a wave at region[s * STASH_STRIDE + l], conflict-free), 38 doubles so that two 256-thread
 //     blocks fit the 160 KB of a CU: the vectors an evaluation reads once (e_n, d_n, w_n), the restore copy of x, and 17 of the 20
 //     values only needed after the local solve (D', old stress, quaternion, volumes, energy);
 //   * the last 3 of those (dEff, bulk modulus, hardness) sit in the point's own tangent slot in global memory, which is written last.
 // The rotation data of an evaluation (Tr, d_lat, w_lat) is never live across one and stays in registers (struct Jac).  Rule measured
 // on MI355X: inside a thread's lifetime nothing written to global memory is still in L2 when it is read back, and a reload waits for
 // every earlier store of the wave (vmcnt), so anything that must survive the Newton loop belongs in LDS, not in global memory.
-#ifndef ECM_KM_GDOT_AT_END
-#define ECM_KM_GDOT_AT_END 1   // Kocks-Mecking: slip rates written once from the converged point (A/B switch)
-#endif
-#ifndef ECM_DEFER_REJECT
-#define ECM_DEFER_REJECT 1   // capped launch with resumed tail points: a rejected trial hands the point over instead of re-evaluating (A/B switch;
-                             // 2 = also in instantiations that keep the dog-leg data: FCC 20.1 ms against 17.2 / 18.0)
-#endif
-#ifndef ECM_KEEP_DOGLEG
-#define ECM_KEEP_DOGLEG 0   // Kocks-Mecking without athermal threshold: dog-leg data kept across a trial evaluation instead of a re-evaluation after a
-                            // rejection.  Worth 14 % (FCC 29.7 -> 25.6 ms) until ECM_DEFER_REJECT made the capped launch free of re-evaluations
-                            // without the 20 carried values (18.0 -> 17.2 ms); still the better choice for a launch WITHOUT tail split (A/B switch)
-#endif
-#ifndef ECM_KM_BATCH
-#define ECM_KM_BATCH 1   // p == q == 1 FCC Kocks-Mecking instantiation: batched straight-line slip loop (A/B switch)
-#endif
 #ifndef ECM_KB
-#define ECM_KB 4         // systems per batch of that form (3, 4, 6 within 1.5 % of each other; 12: +70 %)
+#define ECM_KB 4         // systems per batch of the straight-line slip loop of the p == q == 1 FCC Kocks-Mecking instantiation (3, 4, 6 within 1.5 % of each other; 12: +70 %)
 #endif
-#ifndef ECM_KM_FORMS_CSE
-#define ECM_KM_FORMS_CSE 2   // athermal-threshold Kocks-Mecking kernel: cheap classes through the factored slip forms: 0 never, 1 always, 2 in the
-                             // p == q == 1 instantiation only.  Measured at 128^3: general instantiation 12.7 ms against 12.3 (448 B of scratch
-                             // instead of 320: spill latency), p == q == 1 instantiation 9.6 ms against 10.4 (profiles/r03_kernel_experiments.txt)
-#endif
-#ifndef ECM_KM_PEND_INSERT
-#define ECM_KM_PEND_INSERT 1   // athermal-threshold Kocks-Mecking kernel, factored-forms path: window systems inserted into the per-system arrays (eval_rj; A/B switch)
-#endif
-#ifndef ECM_TANGENT_WX
-#define ECM_TANGENT_WX 1   // tangent block as (Q5 Kt)(S^-1 Q5^T) with the rotated coupling through the equivariance of M35 (point_update; A/B switch)
-#endif
-#ifndef ECM_TANGENT_FIRST
-#define ECM_TANGENT_FIRST 1   // epilogue order: tangent before the state / stress outputs (see point_update)
-#endif
-#ifndef ECM_DEFER_DIS
-#define ECM_DEFER_DIS 1   // Voce: dissipation / effective shear rate from the converged point only (voce_slip_rates)
-#endif
-#ifndef ECM_SWEEP_UNROLL
-#define ECM_SWEEP_UNROLL 0   // block Gauss-Seidel sweeps of the Newton step rolled (1: unrolled; A/B on MI355X)
-#endif
-#ifndef ECM_STASH_STRIDE
-#define ECM_STASH_STRIDE 64    // lanes per stash region: every WAVE owns ST_SLOTS x 64 contiguous doubles (slot s of lane l at region[s * 64 + l]), the regions of a
-                               // block's waves one behind the other (model_kernel.hpp, PointIO::stash).  All slots are within the reach of a ds_read / ds_write
-                               // immediate offset from ONE address register (rounds 3-5: stride = block size 128, slots interleaved across the two waves; with
-                               // 256 the slots from 32 up needed their own address registers, which the allocator spilled).  Per-wave regions are what lets the
-                               // staged AOS launch use the wave's region as a transposition buffer for its 64 contiguous point rows (round 6); 128 = the
-                               // interleaved form of rounds 3-5 (A/B switch; no staged launch then)
-#endif
-#ifndef ECM_EPI_NO_LOADS
-#define ECM_EPI_NO_LOADS 1   // no global or scratch load behind the first output store: on gfx9 loads and stores share the in-order vmcnt counter, so a load
-                             // issued after the record / state stores waits until every one of them has reached memory (a store-queue drain of a few
-                             // microseconds, twice per wave in the round-3 kernel).  The two begin-of-step values the outputs need are read with the other
-                             // inputs and parked in the stash, and the output addresses are re-derived from the thread index after the local solve
-                             // (PointIO::refresh) instead of being carried - and spilled - through it (A/B switch)
-#endif
+// lanes per stash region: every WAVE owns ST_SLOTS x 64 contiguous doubles (slot s of lane l at region[s * 64 + l]), the regions of a block's waves one
+// behind the other (model_kernel.hpp, PointIO::stash).  All slots are within the reach of a ds_read / ds_write immediate offset from ONE address
+// register (rounds 3-5 had stride = block size 128, slots interleaved across the two waves; with 256 the slots from 32 up needed their own address
+// registers, which the allocator spilled).  Per-wave regions are what lets the staged AOS launch use the wave's region as a transposition buffer for
+// its 64 contiguous point rows (round 6)
+constexpr int STASH_STRIDE = 64;
 constexpr int ST_EN = 0, ST_DN = 5, ST_WN = 10, ST_XS = 13, ST_CD = 21, ST_PB = 33, ST_SLOTS = 38;   // ST_XS: restore copy of the unknowns; ST_CD: parking slots; ST_PB: rarely used scalars of the point problem
 constexpr int PB_SCI = 0, PB_ESCI = 1, PB_DETVRI = 2;   // 1/sc, 1/esc, 1/detV: read once per Newton step / in the epilogue only
-constexpr int PB_SHR0 = 3, PB_FLOW0 = 4;               // begin-of-step accumulated shear / plastic work: only the outputs need them (see ECM_EPI_NO_LOADS)
+constexpr int PB_SHR0 = 3, PB_FLOW0 = 4;               // begin-of-step accumulated shear / plastic work: only the outputs need them (see the epilogue of point_update)
 static_assert(ST_PB + PB_FLOW0 < ST_SLOTS, "stash slots");
 constexpr int ST_NCD = ST_PB - ST_CD;
 // Staged AOS launch (point_update<.., STG>): its tangent rows only cover slots 0 .. 17 of the wave's region, so what the state / stress outputs need after the
@@ -717,7 +608,7 @@ static_assert(ST_EPI_E == 19 && ST_EPI_Q0 == ST_CD + 3, "epilogue parking slots:
 //  the first scalar is parked, the second uses the lattice-frame D' of the converged evaluation - 10 slots fewer than parking both vectors)
 constexpr int CD_QN = 0, CD_VOLD = 4, CD_VNEW = 5, CD_ENEW = 6, CD_DEFF = 7, CD_BULK = 8, CD_HU = 9, CD_TSC = 10, CD_WRKOLD = 11;
 static_assert(CD_WRKOLD < ST_NCD, "every parked value lives in the LDS stash");
-#define ECM_ST(p, slot) (p)[(slot) * ECM_STASH_STRIDE]
+#define ECM_ST(p, slot) (p)[(slot) * STASH_STRIDE]
 // compiler-only barrier: what was parked must be re-loaded later instead of being kept alive in registers
 #define ECM_PARK_BARRIER() asm volatile("" ::: "memory")
 // parking slot c (compile-time) of the LDS stash (every parked value lives there: static_assert above)
@@ -748,15 +639,12 @@ ECM_DI constexpr int sidx(int i, int j) { return i <= j ? (i * (11 - i)) / 2 + (
 
 // tau = P^T k, D^p / W^p sums and the Jacobian blocks A = P G P^T, B = Q G P^T over the integer slip tables, with the partial sums the
 // 12 systems share factored out: 104 instead of 320 additions per evaluation (generated: scripts/gen_slip_forms.py)
-#ifndef ECM_SLIP_FORMS_CSE
-#define ECM_SLIP_FORMS_CSE 1
-#endif
 #include "slip_forms_gen.hpp"
 
-// One evaluation of residual (+ Jacobian).  gdot_out: nullable pointer (global memory) receiving the 12 slip rates.
+// One evaluation of residual (+ Jacobian).  The 12 slip rates are no output of an evaluation: they are written once from the converged point
+// (voce_slip_rates, km_slip_rates; Kocks-Mecking at 128^3: BCC 11.88 -> 11.65 ms, FCC 42.3 -> 40.9 ms, profiles/r03_kernel_experiments.txt).
 template <int KIN, bool WITHJ>
-ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], double r[8], Jac& jac,
-                    double* __restrict__ gdot_out, double& dis_rate, double& shrate) {
+ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], double r[8], Jac& jac, double& dis_rate, double& shrate) {
    // resolved shear stress from the Kirchhoff stress K e'
    double k[5], e_f[5];
 #pragma unroll
@@ -770,67 +658,17 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
       // fully unrolled, integer-coefficient form (see SP/SQ): resolved shear stresses, batched kinetics, then the Jacobian blocks
       const double ks[5] = { mp.pk0 * e_f[0], mp.pk1 * e_f[1], mp.pk2 * e_f[2], mp.pk2 * e_f[3], mp.pk2 * e_f[4] };   // PSC[c] * Kirchhoff component c
       double tau[NSLIP], gd[NSLIP], dg[NSLIP];
-      if (ECM_SLIP_FORMS_CSE) slip_tau12(ks, tau);
-      else {
-#pragma unroll
-      for (int a = 0; a < NSLIP; a++) {
-         double t = 0.0;
-#pragma unroll
-         for (int c = 0; c < 5; c++) if (SP[c][a] != 0) t += (double)SP[c][a] * ks[c];
-         tau[a] = t;
-      }
-      }
+      slip_tau12(ks, tau);
       voce_gdot12<WITHJ, false, kin_xn_ct(KIN)>(mp, g_i, tau, gd, dg);
-      // the dissipation rate is an output of the converged point only: voce_slip_rates computes it there (12 FMAs fewer per evaluation)
-      if (!ECM_DEFER_DIS) {
+      // the dissipation rate is an output of the converged point only: voce_slip_rates computes it there (12 FMAs fewer per evaluation), and the
+      // caller tests the residual norm for finiteness (a non-finite rate poisons D^p and with it the residual)
+      double dps[5], wps[3];
+      slip_dpwp(gd, dps, wps);
 #pragma unroll
-         for (int a = 0; a < NSLIP; a++) { dis += tau[a] * gd[a]; shr += fabs(gd[a]); }
-         ok = isfinite(shr);   // any non-finite rate poisons the sum
-      }   // deferred: the caller tests the residual norm for finiteness (a non-finite rate poisons D^p and with it the residual)
-      if (ECM_SLIP_FORMS_CSE) {
-         double dps[5], wps[3];
-         slip_dpwp(gd, dps, wps);
+      for (int c = 0; c < 5; c++) dp[c] = PSC[c] * dps[c];
 #pragma unroll
-         for (int c = 0; c < 5; c++) dp[c] = PSC[c] * dps[c];
-#pragma unroll
-         for (int c = 0; c < 3; c++) wp[c] = PB * wps[c];
-         if (WITHJ) slip_jac_blocks(dg, jac.A, jac.B);
-      } else {
-#pragma unroll
-      for (int c = 0; c < 5; c++) {
-         double t = 0.0;
-#pragma unroll
-         for (int a = 0; a < NSLIP; a++) if (SP[c][a] != 0) t += (double)SP[c][a] * gd[a];
-         dp[c] = PSC[c] * t;
-      }
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-         double t = 0.0;
-#pragma unroll
-         for (int a = 0; a < NSLIP; a++) t += (double)SQ[c][a] * gd[a];
-         wp[c] = PB * t;
-      }
-      if (WITHJ) {
-#pragma unroll
-         for (int i = 0; i < 5; i++)
-#pragma unroll
-            for (int j = i; j < 5; j++) {
-               double t = 0.0;
-#pragma unroll
-               for (int a = 0; a < NSLIP; a++) if (SP[i][a] * SP[j][a] != 0) t += (double)(SP[i][a] * SP[j][a]) * dg[a];
-               jac.A[sidx(i, j)] = (PSC[i] * PSC[j]) * t;
-            }
-#pragma unroll
-         for (int i = 0; i < 3; i++)
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-               double t = 0.0;
-#pragma unroll
-               for (int a = 0; a < NSLIP; a++) if (SQ[i][a] * SP[j][a] != 0) t += (double)(SQ[i][a] * SP[j][a]) * dg[a];
-               jac.B[i][j] = (PB * PSC[j]) * t;
-            }
-      }
-      }
+      for (int c = 0; c < 3; c++) wp[c] = PB * wps[c];
+      if (WITHJ) slip_jac_blocks(dg, jac.A, jac.B);
    } else {
    if (WITHJ) {
 #pragma unroll
@@ -842,7 +680,7 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
    }
    // (the runtime flag is always set in the KIN_KMBALD_GA instantiation; with the test compiled away the register allocator of ROCm 7.2
    //  spills 850 B/lane instead of 330 and the kernel runs 2.5x slower, so the never-taken alternative stays in that instantiation)
-   if (ECM_KM_DEFER && kin_base(KIN) == KIN_KMBALD_GA && mp.with_g_athermal) {
+   if (kin_base(KIN) == KIN_KMBALD_GA && mp.with_g_athermal) {
       // Athermal-threshold variant (BCC): a system is dormant (|tau| <= g), drag-limited (at_0 > t_max: one exp) or - for |tau| - g inside
       // the narrow thermally activated window (0, t_max tau_a] - needs the full balanced kinetics (four more exp/log).  About 1 % of
       // the (point, system) pairs are in the window, but a wave of 64 points x KW systems nearly always holds one, so the grouped form
@@ -852,11 +690,11 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
       // sums changes (round-off).
       const double g_ia = 1.0 / mp.tau_a, gAth = pb.kv.g, wi = 1.0 / mp.wrD;
       unsigned pend = 0;
-      if constexpr (ECM_KM_FORMS_CSE == 1 || (ECM_KM_FORMS_CSE == 2 && kin_pq1(KIN))) {
-      // cheap classes of all 12 systems with static indices: resolved shear stresses through the shared partial sums (slip_tau12), one exp
-      // per drag-limited system, then D^p / W^p and the Jacobian blocks of these systems through the factored forms (slip_dpwp,
-      // slip_jac_blocks: 114 instead of ~540 multiply-adds per evaluation); the window systems are added by the pending loop below
-      {
+      if constexpr (kin_pq1(KIN)) {
+         // p == q == 1 instantiation only: cheap classes of all 12 systems with static indices: resolved shear stresses through the shared partial
+         // sums (slip_tau12), one exp per drag-limited system, then D^p / W^p and the Jacobian blocks through the factored forms (slip_dpwp,
+         // slip_jac_blocks: 114 instead of ~540 multiply-adds per evaluation).  Measured at 128^3: this instantiation 9.6 ms against 10.4, the general
+         // one 12.7 ms against 12.3 (448 B of scratch instead of 320: spill latency; profiles/r03_kernel_experiments.txt), so that one keeps the rolled groups
          double ks[5];
 #pragma unroll
          for (int c = 0; c < 5; c++) ks[c] = PSC[c] * k[c];
@@ -887,29 +725,24 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
                if (xr[a] >= 0.0) { gd[a] = copysign(gr, tau[a]); dg[a] = dgr; }
             }
          }
-         if (ECM_KM_PEND_INSERT) {
-            // window systems, one per lane and pass: the rate and its derivative are INSERTED into gd[] / dg[] (compare-and-select over the 12
-            // static slots) and the factored forms below then run once over all 12 systems.  The loop no longer carries the 38 accumulators of
-            // D^p, W^p and the two Jacobian blocks plus a table row (they were what the allocator spilled inside the Newton loop), only the 24
-            // per-system values
-            while (__ballot(pend != 0) != 0ull) {
-               if (pend != 0) {
-                  const int a = __ffs((int)pend) - 1; pend &= pend - 1;
-                  double t1 = 0.0;
+         // window systems, one per lane and pass: the rate and its derivative are INSERTED into gd[] / dg[] (compare-and-select over the 12
+         // static slots) and the factored forms below then run once over all 12 systems.  The loop no longer carries the 38 accumulators of
+         // D^p, W^p and the two Jacobian blocks plus a table row (they were what the allocator spilled inside the Newton loop), only the 24
+         // per-system values
+         while (__ballot(pend != 0) != 0ull) {
+            if (pend != 0) {
+               const int a = __ffs((int)pend) - 1; pend &= pend - 1;
+               double t1 = 0.0;
 #pragma unroll
-                  for (int s2 = 0; s2 < NSLIP; s2++) t1 = (a == s2) ? tau[s2] : t1;
-                  double tau1[1] = { t1 }, gd1[1], dg1[1] = { 0.0 };
-                  kmbald_gdot4<WITHJ, 1, kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb.kv, tau1, gd1, dg1);
+               for (int s2 = 0; s2 < NSLIP; s2++) t1 = (a == s2) ? tau[s2] : t1;
+               double tau1[1] = { t1 }, gd1[1], dg1[1] = { 0.0 };
+               kmbald_gdot4<WITHJ, 1, kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb.kv, tau1, gd1, dg1);
 #pragma unroll
-                  for (int s2 = 0; s2 < NSLIP; s2++) { gd[s2] = (a == s2) ? gd1[0] : gd[s2]; if (WITHJ) dg[s2] = (a == s2) ? dg1[0] : dg[s2]; }
-               }
+               for (int s2 = 0; s2 < NSLIP; s2++) { gd[s2] = (a == s2) ? gd1[0] : gd[s2]; if (WITHJ) dg[s2] = (a == s2) ? dg1[0] : dg[s2]; }
             }
          }
 #pragma unroll
-         for (int a = 0; a < NSLIP; a++) {
-            if (gdot_out) gdot_out[a * pb.gs] = gd[a];
-            dis += tau[a] * gd[a]; shr += fabs(gd[a]);
-         }
+         for (int a = 0; a < NSLIP; a++) { dis += tau[a] * gd[a]; shr += fabs(gd[a]); }
          double dps[5], wps[3];
          slip_dpwp(gd, dps, wps);
 #pragma unroll
@@ -917,94 +750,89 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
 #pragma unroll
          for (int c = 0; c < 3; c++) wp[c] = PB * wps[c];
          if (WITHJ) slip_jac_blocks(dg, jac.A, jac.B);
-      }
       } else {
 #pragma unroll 1
-      for (int a0 = 0; a0 < NSLIP; a0 += KD) {
-         double pq[KD][8], tau[KD], gd[KD], dg[KD], xr[KD];
-         bool live[KD], over[KD], any_live = false;
-#pragma unroll
-         for (int a = 0; a < KD; a++) {
-#pragma unroll
-            for (int c = 0; c < 8; c++) pq[a][c] = PQ_TAB[a0 + a][c];
-            tau[a] = pq[a][0] * k[0] + pq[a][1] * k[1] + pq[a][2] * k[2] + pq[a][3] * k[3] + pq[a][4] * k[4];
-            const double at = fabs(tau[a]);
-            xr[a] = (at - gAth) * wi;
-            live[a] = (tau[a] != 0.0) && (xr[a] > 0.0); over[a] = fmax(0.0, at - gAth) * g_ia > mp.t_max;
-            any_live = any_live || live[a];
-            gd[a] = 0.0; dg[a] = 0.0;
-            if (live[a] && !over[a]) pend |= 1u << (a0 + a);
-         }
-         if (any_live) {
-            double ex[KD];
-#pragma unroll
-            for (int a = 0; a < KD; a++) ex[a] = -fmax(xr[a], 0.0);
-            exp_n<KD, kin_pq1(KIN), kin_sc_exp(KIN)>(ex);
+         for (int a0 = 0; a0 < NSLIP; a0 += KD) {
+            double pq[KD][8], tau[KD], gd[KD], dg[KD], xr[KD];
+            bool live[KD], over[KD], any_live = false;
 #pragma unroll
             for (int a = 0; a < KD; a++) {
-               const bool small = xr[a] < EPS_SQRT;
-               const double gr = small ? pb.kv.gam_r * xr[a] : pb.kv.gam_r * (1.0 - ex[a]);
-               const double dgr = (small ? pb.kv.gam_r : pb.kv.gam_r * ex[a]) * wi;
-               if (live[a] && over[a]) { gd[a] = copysign(gr, tau[a]); dg[a] = dgr; }
+#pragma unroll
+               for (int c = 0; c < 8; c++) pq[a][c] = PQ_TAB[a0 + a][c];
+               tau[a] = pq[a][0] * k[0] + pq[a][1] * k[1] + pq[a][2] * k[2] + pq[a][3] * k[3] + pq[a][4] * k[4];
+               const double at = fabs(tau[a]);
+               xr[a] = (at - gAth) * wi;
+               live[a] = (tau[a] != 0.0) && (xr[a] > 0.0); over[a] = fmax(0.0, at - gAth) * g_ia > mp.t_max;
+               any_live = any_live || live[a];
+               gd[a] = 0.0; dg[a] = 0.0;
+               if (live[a] && !over[a]) pend |= 1u << (a0 + a);
+            }
+            if (any_live) {
+               double ex[KD];
+#pragma unroll
+               for (int a = 0; a < KD; a++) ex[a] = -fmax(xr[a], 0.0);
+               exp_n<KD, kin_pq1(KIN), kin_sc_exp(KIN)>(ex);
+#pragma unroll
+               for (int a = 0; a < KD; a++) {
+                  const bool small = xr[a] < EPS_SQRT;
+                  const double gr = small ? pb.kv.gam_r * xr[a] : pb.kv.gam_r * (1.0 - ex[a]);
+                  const double dgr = (small ? pb.kv.gam_r : pb.kv.gam_r * ex[a]) * wi;
+                  if (live[a] && over[a]) { gd[a] = copysign(gr, tau[a]); dg[a] = dgr; }
+               }
+            }
+#pragma unroll
+            for (int a = 0; a < KD; a++) {
+               dis += tau[a] * gd[a]; shr += fabs(gd[a]);
+#pragma unroll
+               for (int c = 0; c < 5; c++) dp[c] += pq[a][c] * gd[a];
+#pragma unroll
+               for (int c = 0; c < 3; c++) wp[c] += pq[a][5 + c] * gd[a];
+               if (WITHJ) {
+                  double gp[5];
+#pragma unroll
+                  for (int c = 0; c < 5; c++) gp[c] = dg[a] * pq[a][c];
+#pragma unroll
+                  for (int i = 0; i < 5; i++)
+#pragma unroll
+                     for (int j = i; j < 5; j++) jac.A[sidx(i, j)] += pq[a][i] * gp[j];
+#pragma unroll
+                  for (int i = 0; i < 3; i++)
+#pragma unroll
+                     for (int j = 0; j < 5; j++) jac.B[i][j] += pq[a][5 + i] * gp[j];
+               }
             }
          }
+         while (__ballot(pend != 0) != 0ull) {      // one pending window system per lane and pass
+            if (pend != 0) {
+               const int a = __ffs((int)pend) - 1; pend &= pend - 1;
+               double pq[8];
 #pragma unroll
-         for (int a = 0; a < KD; a++) {
-            if (gdot_out) gdot_out[(a0 + a) * pb.gs] = gd[a];
-            dis += tau[a] * gd[a]; shr += fabs(gd[a]);
+               for (int c = 0; c < 8; c++) pq[c] = pb.pqt ? pb.pqt[8 * a + c] : PQ_TAB[a][c];      // lane-varying row: LDS copy of the 768-byte table
+               double tau1[1] = { pq[0] * k[0] + pq[1] * k[1] + pq[2] * k[2] + pq[3] * k[3] + pq[4] * k[4] }, gd1[1], dg1[1];
+               kmbald_gdot4<WITHJ, 1, kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb.kv, tau1, gd1, dg1);
+               dis += tau1[0] * gd1[0]; shr += fabs(gd1[0]);
 #pragma unroll
-            for (int c = 0; c < 5; c++) dp[c] += pq[a][c] * gd[a];
+               for (int c = 0; c < 5; c++) dp[c] += pq[c] * gd1[0];
 #pragma unroll
-            for (int c = 0; c < 3; c++) wp[c] += pq[a][5 + c] * gd[a];
-            if (WITHJ) {
-               double gp[5];
+               for (int c = 0; c < 3; c++) wp[c] += pq[5 + c] * gd1[0];
+               if (WITHJ) {
+                  double gp[5];
 #pragma unroll
-               for (int c = 0; c < 5; c++) gp[c] = dg[a] * pq[a][c];
+                  for (int c = 0; c < 5; c++) gp[c] = dg1[0] * pq[c];
 #pragma unroll
-               for (int i = 0; i < 5; i++)
+                  for (int i = 0; i < 5; i++)
 #pragma unroll
-                  for (int j = i; j < 5; j++) jac.A[sidx(i, j)] += pq[a][i] * gp[j];
+                     for (int j = i; j < 5; j++) jac.A[sidx(i, j)] += pq[i] * gp[j];
 #pragma unroll
-               for (int i = 0; i < 3; i++)
+                  for (int i = 0; i < 3; i++)
 #pragma unroll
-                  for (int j = 0; j < 5; j++) jac.B[i][j] += pq[a][5 + i] * gp[j];
-            }
-         }
-      }
-      }
-      constexpr bool PEND_DONE = ECM_KM_PEND_INSERT && (ECM_KM_FORMS_CSE == 1 || (ECM_KM_FORMS_CSE == 2 && kin_pq1(KIN)));   // handled above
-      if constexpr (!PEND_DONE)
-      while (__ballot(pend != 0) != 0ull) {      // one pending window system per lane and pass
-         if (pend != 0) {
-            const int a = __ffs((int)pend) - 1; pend &= pend - 1;
-            double pq[8];
-#pragma unroll
-            for (int c = 0; c < 8; c++) pq[c] = pb.pqt ? pb.pqt[8 * a + c] : PQ_TAB[a][c];      // lane-varying row: LDS copy of the 768-byte table
-            double tau1[1] = { pq[0] * k[0] + pq[1] * k[1] + pq[2] * k[2] + pq[3] * k[3] + pq[4] * k[4] }, gd1[1], dg1[1];
-            kmbald_gdot4<WITHJ, 1, kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb.kv, tau1, gd1, dg1);
-            if (gdot_out) gdot_out[a * pb.gs] = gd1[0];
-            dis += tau1[0] * gd1[0]; shr += fabs(gd1[0]);
-#pragma unroll
-            for (int c = 0; c < 5; c++) dp[c] += pq[c] * gd1[0];
-#pragma unroll
-            for (int c = 0; c < 3; c++) wp[c] += pq[5 + c] * gd1[0];
-            if (WITHJ) {
-               double gp[5];
-#pragma unroll
-               for (int c = 0; c < 5; c++) gp[c] = dg1[0] * pq[c];
-#pragma unroll
-               for (int i = 0; i < 5; i++)
-#pragma unroll
-                  for (int j = i; j < 5; j++) jac.A[sidx(i, j)] += pq[i] * gp[j];
-#pragma unroll
-               for (int i = 0; i < 3; i++)
-#pragma unroll
-                  for (int j = 0; j < 5; j++) jac.B[i][j] += pq[5 + i] * gp[j];
+                     for (int j = 0; j < 5; j++) jac.B[i][j] += pq[5 + i] * gp[j];
+               }
             }
          }
       }
       ok = isfinite(shr);
-   } else if constexpr (ECM_KM_BATCH && kin_pq1(KIN) && kin_base(KIN) == KIN_KMBALD) {
+   } else if constexpr (kin_pq1(KIN) && kin_base(KIN) == KIN_KMBALD) {
       // p == q == 1 instantiation without an athermal threshold (FCC): with the pow() alternatives compiled out the kinetics of a system is
       // a short straight-line sequence (three exp), so the 12 systems go through it in batches of ECM_KB with static indices like the Voce
       // form: resolved shear stresses, D^p / W^p and the Jacobian blocks through the factored slip forms (slip_forms_gen.hpp: 104 instead of
@@ -1018,10 +846,7 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
 #pragma unroll
       for (int a0 = 0; a0 < NSLIP; a0 += ECM_KB) kmbald_gdot4<WITHJ, ECM_KB, true, kin_sc_exp(KIN)>(mp, pb.kv, tau + a0, gd + a0, dg + a0);
 #pragma unroll
-      for (int a = 0; a < NSLIP; a++) {
-         if (gdot_out) gdot_out[a * pb.gs] = gd[a];
-         dis += tau[a] * gd[a]; shr += fabs(gd[a]);
-      }
+      for (int a = 0; a < NSLIP; a++) { dis += tau[a] * gd[a]; shr += fabs(gd[a]); }
       double dps[5], wps[3];
       slip_dpwp(gd, dps, wps);
 #pragma unroll
@@ -1043,7 +868,6 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
          kmbald_gdot4<WITHJ, ECM_KW, kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb.kv, tau, gd, dg);
 #pragma unroll
          for (int a = 0; a < KW; a++) {
-            if (gdot_out) gdot_out[(a0 + a) * pb.gs] = gd[a];
             dis += tau[a] * gd[a]; shr += fabs(gd[a]);
 #pragma unroll
             for (int c = 0; c < 5; c++) dp[c] += pq[a][c] * gd[a];
@@ -1113,24 +937,15 @@ template <int XNCT, bool LO = false>
 ECM_DI void voce_slip_rates(const MatParams& mp, const Prob& pb, const double e_f[5], double* __restrict__ gdot_out, double& dis_rate, double& shrate, const double detv_lo = 0.0) {
    const double ks[5] = { mp.pk0 * e_f[0], mp.pk1 * e_f[1], mp.pk2 * e_f[2], mp.pk2 * e_f[3], mp.pk2 * e_f[4] };
    double tau[NSLIP], gd[NSLIP];
-   if (ECM_SLIP_FORMS_CSE) slip_tau12(ks, tau);
-   else {
-#pragma unroll
-   for (int a = 0; a < NSLIP; a++) {
-      double t = 0.0;
-#pragma unroll
-      for (int c = 0; c < 5; c++) if (SP[c][a] != 0) t += (double)SP[c][a] * ks[c];
-      tau[a] = t;
-   }
-   }
+   slip_tau12(ks, tau);
    voce_gdot12<false, true, XNCT>(mp, pb.g_i, tau, gd, nullptr);
    double dis = 0.0, shr = 0.0;
 #pragma unroll
    for (int a = 0; a < NSLIP; a++) { ost<LO>(&gdot_out[a * pb.gs], gd[a]); dis += tau[a] * gd[a]; shr += fabs(gd[a]); }
-   if (ECM_DEFER_DIS) { dis_rate = dis * (LO ? detv_lo : ECM_ST(pb.st, ST_PB + PB_DETVRI)); shrate = shr; }   // (rates below t_min = (1e-60)^m count as 0 here: below 1e-60 of the reference rate)
+   dis_rate = dis * (LO ? detv_lo : ECM_ST(pb.st, ST_PB + PB_DETVRI)); shrate = shr;   // (rates below t_min = (1e-60)^m count as 0 here: below 1e-60 of the reference rate)
 }
 
-// slip rates at the converged point (Kocks-Mecking family, ECM_KM_GDOT_AT_END): one more pass through the kinetics (no derivatives) instead
+// slip rates at the converged point (Kocks-Mecking family): one more pass through the kinetics (no derivatives) instead
 // of 12 global stores per evaluation - on gfx9 every scratch reload of the Newton loop otherwise waits for those stores (vmcnt)
 template <bool PQ1, bool SC, bool LO = false>
 ECM_DI void km_slip_rates(const MatParams& mp, const Prob& pb, const double e_f[5], double* __restrict__ gdot_out) {
@@ -1147,11 +962,8 @@ ECM_DI void km_slip_rates(const MatParams& mp, const Prob& pb, const double e_f[
 }
 
 // the same for the athermal-threshold (BCC) kernel, organised like its evaluation: cheap classes of all 12 systems with static indices (one
-// exponential per drag-limited system), then one window system per lane and pass, inserted into the 12 slots (ECM_KM_GDOT_GA; the grouped
-// form above pays the window phases in nearly every group of this variant)
-#ifndef ECM_KM_GDOT_GA
-#define ECM_KM_GDOT_GA 1
-#endif
+// exponential per drag-limited system), then one window system per lane and pass, inserted into the 12 slots (the grouped form above pays the
+// window phases in nearly every group of this variant)
 template <bool PQ1, bool SC, bool LO = false>
 ECM_DI void km_slip_rates_ga(const MatParams& mp, const Prob& pb, const double e_f[5], double* __restrict__ gdot_out) {
    const double ks[5] = { mp.pk0 * e_f[0], mp.pk1 * e_f[1], mp.pk2 * e_f[2], mp.pk2 * e_f[3], mp.pk2 * e_f[4] };
@@ -1346,20 +1158,15 @@ ECM_DI void jac_mult_T(const MatParams& mp, const Prob& pb, const Jac& J, const 
 }
 
 // solve J dx = rhs by block Gauss-Seidel on the exact diagonal-block inverses (rhs_r may be identically zero: ZERO_R)
-// ECM_GS_START0: the sweeps start from x_r = 0 instead of x_r = Jrr^-1 rhs_r.  The first sweep then has no coupling term in its strain
-// half (x_e = Jee^-1 rhs_e) and the start-up product disappears: 39 FP64 operations fewer per Newton step.  Both starts leave an error
-// of (contraction)^2 ~ 1e-8 of an O(1) quantity after two sweeps (x_r* itself here, Jrr^-1 Jre x_e* there).
-#ifndef ECM_GS_START0
-#define ECM_GS_START0 1   // measured at 128^3 (profiles/r04_kernel_experiments.txt): nothing while the launch waited on scratch and stores (4.85 ms either way), 4.43 -> 4.35 ms once it was issue-bound again
-#endif
-#ifndef ECM_EXP_NSWEEP
-#define ECM_EXP_NSWEEP 0   // timing experiment: number of sweeps of the Newton step (0 = the product's two)
-#endif
+// The sweeps start from x_r = 0 instead of x_r = Jrr^-1 rhs_r.  The first sweep then has no coupling term in its strain half (x_e = Jee^-1 rhs_e,
+// written out in front of the loop) and the start-up product disappears: 39 FP64 operations fewer per Newton step.  Both starts leave an error
+// of (contraction)^2 ~ 1e-8 of an O(1) quantity after two sweeps (x_r* itself here, Jrr^-1 Jre x_e* there).  Measured at 128^3
+// (profiles/r04_kernel_experiments.txt): nothing while the launch waited on scratch and stores (4.85 ms either way), 4.43 -> 4.35 ms once it was
+// issue-bound again.  The remaining sweeps stay rolled (unrolled: 5.574 against 5.576 ms, neutral; profiles/r03_kernel_experiments.txt).
 template <bool ZERO_R, int NSWEEP>
 ECM_DI void jac_solve(const MatParams& mp, const Prob& pb, const Jac& J, const Fact& F, const double rhs[8], double dx[8]) {
-   double xr[3] = { 0, 0, 0 };
-   double xe[5];
-   if (ECM_GS_START0) {
+   double xr[3], xe[5];
+   {
 #pragma unroll
       for (int i = 0; i < 5; i++) xe[i] = rhs[i];
       jee_solve(mp, J, xe);
@@ -1369,16 +1176,9 @@ ECM_DI void jac_solve(const MatParams& mp, const Prob& pb, const Jac& J, const F
       for (int i = 0; i < 3; i++) br[i] = (ZERO_R ? 0.0 : rhs[5 + i]) - c[i];
 #pragma unroll
       for (int i = 0; i < 3; i++) xr[i] = F.Ri[3 * i] * br[0] + F.Ri[3 * i + 1] * br[1] + F.Ri[3 * i + 2] * br[2];
-   } else if (!ZERO_R) {
-#pragma unroll
-      for (int i = 0; i < 3; i++) xr[i] = F.Ri[3 * i] * rhs[5] + F.Ri[3 * i + 1] * rhs[6] + F.Ri[3 * i + 2] * rhs[7];
    }
-#if ECM_SWEEP_UNROLL
-#pragma unroll
-#else
 #pragma unroll 1
-#endif
-   for (int sweep = (ECM_GS_START0 ? 1 : 0); sweep < NSWEEP; sweep++) {
+   for (int sweep = 1; sweep < NSWEEP; sweep++) {
       double t[5]; jer_mult(J, xr, t);
 #pragma unroll
       for (int i = 0; i < 5; i++) xe[i] = rhs[i] - t[i];
@@ -1405,7 +1205,7 @@ ECM_DI double norm8sq(const double v[8]) { double s = 0; for (int i = 0; i < 8; 
 //   sv0/s0 : begin-of-step state (28) / Voigt stress (6)
 //   sv1/s1 : end-of-step outputs;  cmat: 6x6 tangent d sigma / d eps (engineering shear), column-major (used as a parking
 //            area for cold values until it is written at the very end)
-//   st     : per-thread stash (LDS), ST_SLOTS slots of stride ECM_STASH_STRIDE
+//   st     : per-thread stash (LDS), ST_SLOTS slots of stride STASH_STRIDE
 // returns 0 on success, 1 if the local solve failed to converge, 2 if it was cut off after kcap evaluations (nothing written)
 // ------------------------------------------------------------------------------------------------------------
 // QS: distance (in doubles) between consecutive values of one point in the state / stress / tangent arrays: 1 for the reference's
@@ -1415,9 +1215,9 @@ ECM_DI double norm8sq(const double v[8]) { double s = 0; for (int i = 0; i < 8; 
 // k_grad_setup_pa<.., CMP> would produce from the 36 entries (reference src/mechanics_integrators.cpp:331-414), without the round trip.
 // cmat then points at the lane's first 16-byte pair of the record ([13 pairs][64 lanes][2]); trd stores D^T (element-assembly contexts).
 // IO: where the point's data lives (model_kernels.hip, PointIO): sv0() / s0() begin-of-step state / stress, sv1() / s1() / cm() outputs, stash()
-// the lane's LDS stash, ipt() the point id, refresh() re-derives all of them from the thread index (see ECM_EPI_NO_LOADS)
+// the lane's LDS stash, ipt() the point id, refresh() re-derives all of them from the thread index (see the epilogue)
 // The begin-of-step values a point reads of its old state and stress (21 of the 34: slip rates and evaluation count are not inputs, see
-// ECM_SHRATE_FROM_STATE).  The caller requests them BEFORE it gathers nodes and forms the velocity gradient, so that the state rows and the node
+// shrate_o below).  The caller requests them BEFORE it gathers nodes and forms the velocity gradient, so that the state rows and the node
 // rows travel together: as loads inside point_update they were issued behind the gathers' wait - one more memory round trip at the start of every
 // wave (round 5: the prologue of the fused launch went from five dependent round trips to two).
 struct PointIn { double shrate, shr, flow, e[5], q[4], h, vol, eint, s[6]; };
@@ -1457,10 +1257,9 @@ template <int KIN, int QS, bool REC = false, bool STG = false, class IO>
 ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io, const int kcap, const PointIn& pin,
                         const double* pq_lds = nullptr, const double tsc = 0.0, const bool trd = false, const TailIO tio = TailIO()) {
    // (STG with REC: state and stress rows staged, the compact record written by each lane straight to its slot of the element-blocked record array)
-   static_assert(!STG || (QS == 1 && ECM_STASH_STRIDE == 64 && ECM_EPI_NO_LOADS && ECM_TANGENT_FIRST && ECM_KM_GDOT_AT_END), "staged outputs: AOS rows, per-wave stash regions, tangent first");
+   static_assert(!STG || QS == 1, "staged outputs: AOS rows");
    bool cut = false;   // STG: handed over to the dense launch (the lane stays for the wave's stores; what it writes the dense launch overwrites)
    const bool resume = tio.rs_in != nullptr;
-   const double* __restrict__ sv0 = io.sv0();
    double* st = io.stash();
    Prob pb; pb.st = st; pb.gs = QS; pb.pqt = pq_lds;
    pb.dt_ri = 1.0 / dt;
@@ -1482,14 +1281,9 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
       const double tK = mp.tK0 + eNew * mp.dtde;
       const double bulkNew = mp.bulk * vNew + mp.gamma * pOld * vNew;
       // ---- hardness to end of step with begin-of-step slip rates
-#ifndef ECM_SHRATE_FROM_STATE
-#define ECM_SHRATE_FROM_STATE 1   // measured at 128^3: 4.83 -> 4.65 ms (profiles/r04_kernel_experiments.txt)
-#endif
       // begin-of-step effective shear rate sum_a |gdot_a|: state slot 0 holds exactly this sum (written below from the same 12 values), so one
-      // load can replace twelve (88 B of the 208 B a point reads of its old state)
-      double shrate_o = 0;
-      if (ECM_SHRATE_FROM_STATE) shrate_o = pin.shrate;
-      else for (int a = 0; a < NSLIP; a++) shrate_o += fabs(ldg(&sv0[(H_GDOT + a) * QS]));
+      // load replaces twelve (88 B of the 208 B a point read of its old state; measured at 128^3: 4.83 -> 4.65 ms, profiles/r04_kernel_experiments.txt)
+      const double shrate_o = pin.shrate;
       const double h_u = kin_update_h<KIN>(mp, pin.h, dt, shrate_o);
       // ---- point problem set-up
       // (reciprocals of well-scaled positive numbers through frcp / rsqrt: 5 instructions instead of the ~13 of an IEEE division)
@@ -1506,7 +1300,7 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
       for (int i = 0; i < 4; i++) ECM_CD(CD_QN + i) = qn[i];
       ECM_CD(CD_VOLD) = vOld; ECM_CD(CD_VNEW) = vNew; ECM_CD(CD_ENEW) = eNew; ECM_CD(CD_DEFF) = dEff; ECM_CD(CD_BULK) = bulkNew; ECM_CD(CD_HU) = h_u;
       if (REC) ECM_CD(CD_TSC) = tsc;
-      if (ECM_EPI_NO_LOADS) { ECM_ST(st, ST_PB + PB_SHR0) = pin.shr; ECM_ST(st, ST_PB + PB_FLOW0) = pin.flow; }
+      ECM_ST(st, ST_PB + PB_SHR0) = pin.shr; ECM_ST(st, ST_PB + PB_FLOW0) = pin.flow;   // (for the outputs: see the epilogue)
       double adots_ref;
       if (kin_is_km(KIN)) {
          const double sq = sqrt(h_u);
@@ -1524,7 +1318,7 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
 
 #ifdef ECM_EXP_IO_ONLY   // timing experiment only: the launch's memory traffic without the constitutive arithmetic
    {
-      double* sv1 = io.sv1(); double* s1 = io.s1(); double* cmat = io.cm();
+      const double* sv0 = io.sv0(); double* sv1 = io.sv1(); double* s1 = io.s1(); double* cmat = io.cm();
       double acc = 0.0;
       for (int i = 0; i < NSTATEV; i++) { const double v = ldg(&sv0[i * QS]); acc += v; stg(&sv1[i * QS], v + L[i % 9]); }
       for (int i = 0; i < 6; i++) stg(&s1[i * QS], pin.s[i] + acc);
@@ -1543,9 +1337,8 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
    if (resume) { for (int i = 0; i < 8; i++) x[i] = ldg(&tio.rs_in[i * tio.stride]); }
    double r[8], dis_rate, shrate;
    Jac J; Fact F;
-   double* gdot_out = (kin_is_km(KIN) && !ECM_KM_GDOT_AT_END) ? io.sv1() + H_GDOT * QS : nullptr;
    int nfev = 1; bool conv = false;
-   bool ok = eval_rj<KIN, true>(mp, pb, x, r, J, gdot_out, dis_rate, shrate);
+   bool ok = eval_rj<KIN, true>(mp, pb, x, r, J, dis_rate, shrate);
    // Norms are carried SQUARED: the common iteration (full Newton step inside the trust region) only compares them - |r| < tol, |dx| <= delta,
    // |r_new| > 0.65 |r_old| (SNLS: rho = actual / predicted < 0.35 with predicted = -|r_old|), |r_new| > |r_old| - and the two square roots per
    // iteration (~20 instructions each in FP64) are only taken on the dog-leg path, which needs the values.
@@ -1561,22 +1354,17 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
    if (ok && !conv) {
       double delta = 1.0;
       if (resume) { delta = ldg(&tio.rs_in[8 * tio.stride]); nfev = (int)ldg(&tio.rs_in[9 * tio.stride]); }
-      // Kocks-Mecking without athermal threshold (ECM_KEEP_DOGLEG): the dog-leg ingredients of the accepted point - Newton step, steepest-descent direction and its
-      // three scalars - are computed with every accepted evaluation and kept across the trial, like SNLS does (reject_prev), so a rejected
-      // trial only restores x and shrinks the trust region: no second evaluation at the old point.  With these kinetics nearly every wave
-      // holds a rejecting lane in every iteration, i.e. the re-evaluation of the Voce form below (rare per lane) was paid by all of them.
-      // (not the athermal-threshold variant: the 20 values carried through the evaluation cost 7 % there).  Off by default since the capped
-      // launch hands rejecting points over to the dense launch (ECM_DEFER_REJECT below), which removes the re-evaluations at no cost.
-      constexpr bool KEEP = ECM_KEEP_DOGLEG && kin_base(KIN) == KIN_KMBALD;
       double nr[8], grad[8], nr2sq = 0.0, norm2_grad = 0.0, Jg_2 = 0.0, s2 = 0.0;
-      bool reject_prev = false;
       // A rejected trial needs (r, J) of the accepted point again: one more evaluation, rare per lane but paid by the whole wave.  In a capped
-      // launch whose listed points resume from their saved state (ECM_DEFER_REJECT) such a point is handed over instead - x restored, trust
+      // launch whose listed points resume from their saved state (tio.defer_reject) such a point is handed over instead - x restored, trust
       // radius shrunk: exactly the state a resumed point starts from, and the evaluation that restores (r, J) there is the one saved here.
       // The points that reject are the ones with long iteration histories, i.e. the ones the cap would list a few evaluations later anyway.
       // Kocks-Mecking instantiations only: the Voce launches run uncapped (their controller never finds a paying cap), and the mere presence
       // of the extra exit costs their register allocation 4.7 % (5.13 against 4.90 ms at 128^3).
-      constexpr bool DEFER = ECM_DEFER_REJECT != 0 && kin_is_km(KIN);
+      // (Before, the Kocks-Mecking kernel without athermal threshold kept the dog-leg ingredients of the accepted point across the trial, like SNLS does,
+      // so that a rejection needed no second evaluation: worth 14 % - FCC 29.7 -> 25.6 ms - until the hand-over made the capped launch free of
+      // re-evaluations without the 20 carried values, 18.0 -> 17.2 ms.)
+      constexpr bool DEFER = kin_is_km(KIN);
       bool hand_over = false;
       auto dogleg_data = [&]() {   // grad = Js^T r, Jg = Js grad, s2 = |r + Js sd_opt|^2 (all in SNLS's scaled variables)
          double u[8], rs[8], tt[8];
@@ -1602,22 +1390,19 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
             if constexpr (STG) { cut = true; break; } else return 2;
          }
          // Newton step first; the steepest-descent data (grad = Js^T r, Jg = Js grad) only when the step leaves the trust region
-         if (!KEEP || !reject_prev) {
-            double t[8];
-            jac_factor(mp, pb, J, F);
-            if (F.ok) {
-               double rhs[8]; for (int i = 0; i < 8; i++) rhs[i] = -r[i];
-               jac_solve<false, (ECM_EXP_NSWEEP ? ECM_EXP_NSWEEP : 2)>(mp, pb, J, F, rhs, t);
-               const double esc_i = ECM_ST(st, ST_PB + PB_ESCI);
-               for (int i = 0; i < 8; i++) nr[i] = t[i] * ((i < 5) ? esc_i : (1.0 / R_SCALE));
-               nr2sq = norm8sq(nr);
-            } else { nr2sq = 1e300; for (int i = 0; i < 8; i++) nr[i] = 0; }
-            if (KEEP) dogleg_data();
-         }
+         double t[8];
+         jac_factor(mp, pb, J, F);
+         if (F.ok) {
+            double rhs[8]; for (int i = 0; i < 8; i++) rhs[i] = -r[i];
+            jac_solve<false, 2>(mp, pb, J, F, rhs, t);
+            const double esc_i = ECM_ST(st, ST_PB + PB_ESCI);
+            for (int i = 0; i < 8; i++) nr[i] = t[i] * ((i < 5) ? esc_i : (1.0 / R_SCALE));
+            nr2sq = norm8sq(nr);
+         } else { nr2sq = 1e300; for (int i = 0; i < 8; i++) nr[i] = 0; }
          double delx[8], pred_resid; bool use_nr = false;
          if (nr2sq <= delta * delta) { use_nr = true; for (int i = 0; i < 8; i++) delx[i] = nr[i]; pred_resid = 0.0; }
          else {
-            if (!KEEP) dogleg_data();
+            dogleg_data();
             const double res_0 = sqrt(res2_0);
             const double norm_grad = sqrt(norm2_grad);
             const double fac = (Jg_2 > 0) ? norm2_grad / Jg_2 : 0.0;
@@ -1638,7 +1423,7 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
          }
          for (int i = 0; i < 8; i++) { ECM_ST(st, ST_XS + i) = x[i]; x[i] += delx[i]; }
          ECM_PARK_BARRIER();
-         ok = eval_rj<KIN, true>(mp, pb, x, r, J, gdot_out, dis_rate, shrate); nfev++;
+         ok = eval_rj<KIN, true>(mp, pb, x, r, J, dis_rate, shrate); nfev++;
          const double res2 = sc2 * norm8sq(r);
          ok = ok && isfinite(res2);
          bool reject;
@@ -1664,19 +1449,22 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
             reject = (res2 > res2_0);
             if (!reject) res2_0 = res2;
          }
-         reject_prev = reject;
          if (reject) {
             for (int i = 0; i < 8; i++) x[i] = ECM_ST(st, ST_XS + i);
-            if (DEFER && (!KEEP || ECM_DEFER_REJECT == 2) && tio.defer_reject && delta > 1e-12) { hand_over = true; continue; }
-            if (!KEEP) ok = eval_rj<KIN, true>(mp, pb, x, r, J, gdot_out, dis_rate, shrate);   // restore (r, J) of the accepted point
-            else ok = true;   // (the accepted point evaluated fine; r and J hold the rejected trial until the next accepted evaluation)
+            if (DEFER && tio.defer_reject && delta > 1e-12) { hand_over = true; continue; }
+            ok = eval_rj<KIN, true>(mp, pb, x, r, J, dis_rate, shrate);   // restore (r, J) of the accepted point
             if (!ok || delta <= 1e-12) break;
          }
       }
    }
    // ---- converged state: stress, energy, history (getResponseSngl tail + reference kernel_postprocessing src/mechanics_ecmech.cpp:116-152)
-   if (ECM_EPI_NO_LOADS) { io.refresh(); st = io.stash(); pb.st = st; }
-   double* __restrict__ sv1 = io.sv1(); double* __restrict__ s1 = io.s1(); double* __restrict__ cmat = io.cm();
+   // No global or scratch load behind the first output store: on gfx9 loads and stores share the in-order vmcnt counter, so a load issued after the
+   // record / state stores waits until every one of them has reached memory (a store-queue drain of a few microseconds, twice per wave in the round-3
+   // kernel).  The two begin-of-step values the outputs need were read with the other inputs and parked in the stash (PB_SHR0, PB_FLOW0), and the
+   // output addresses are re-derived from the thread index here instead of being carried - and spilled - through the local solve.
+   io.refresh(); st = io.stash(); pb.st = st;
+   double* __restrict__ sv1 = io.sv1(); double* __restrict__ s1 = io.s1();
+   [[maybe_unused]] double* __restrict__ cmat = io.cm();   // (unused in a -DECM_NO_TANGENT timing build, like bulkNew below)
    double e_f[5], xi[3];
    for (int i = 0; i < 5; i++) e_f[i] = ECM_ST(st, ST_EN + i) + x[i] * pb.esc;
    for (int i = 0; i < 3; i++) xi[i] = x[5 + i] * R_SCALE;
@@ -1703,11 +1491,12 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
    const double kdj[5] = { mp.kd0 * detV_ri, mp.kd0 * detV_ri, mp.kd2 * detV_ri, mp.kd2 * detV_ri, mp.kd2 * detV_ri };
    double s_lat[5];
    for (int i = 0; i < 5; i++) s_lat[i] = kdj[i] * e_f[i];
-   const double bulkNew = ECM_CD(CD_BULK);
-   // The tangent goes FIRST (ECM_TANGENT_FIRST): it is the only consumer of the 47 Jacobian values of the converged evaluation, so they die
+   [[maybe_unused]] const double bulkNew = ECM_CD(CD_BULK);
+   // The tangent goes FIRST: it is the only consumer of the 47 Jacobian values of the converged evaluation, so they die
    // before the state / stress outputs are computed instead of being carried (and spilled) through them; and no scratch reload of the
    // tangent arithmetic has to wait behind the 34 output stores (on gfx9 a reload waits for every earlier store of the wave).  The two
-   // parked values the outputs need from the slot the tangent overwrites are read before.
+   // parked values the outputs need from the slot the tangent overwrites are read before.  (Measured at 128^3: 5.70 -> 5.20 ms, 29 VGPR spills
+   // instead of 76; profiles/r03_kernel_experiments.txt.)
    const double hu_keep = ECM_CD(CD_HU), deff_keep = ECM_CD(CD_DEFF);      // (STG: read again in write_state_staged, not carried)
    double wrk_new = 0.0;   // s_new . D' in the lattice frame of the converged evaluation (the inner product of the 5-vectors is frame-invariant)
    for (int k = 0; k < 5; k++) wrk_new += s_lat[k] * J.dl[k];
@@ -1727,14 +1516,14 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
       double eNew = ECM_CD(CD_ENEW);
       eNew += 0.25 * (ECM_CD(CD_VOLD) + vNew) * dt * (ECM_CD(CD_WRKOLD) + wrk_new);
       if constexpr (!kin_is_km(KIN)) voce_slip_rates<kin_xn_ct(KIN)>(mp, pb, e_f, sv1 + H_GDOT * QS, dis_rate, shrate);
-      else if (ECM_KM_GDOT_AT_END) {
+      else {
          // (the runtime flag is always set in this instantiation, see eval_rj; only the p == q == 1 kernel has the factored forms of the evaluation)
-         if (ECM_KM_GDOT_GA && kin_base(KIN) == KIN_KMBALD_GA && kin_pq1(KIN) && mp.with_g_athermal) km_slip_rates_ga<kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb, e_f, sv1 + H_GDOT * QS);
+         if (kin_base(KIN) == KIN_KMBALD_GA && kin_pq1(KIN) && mp.with_g_athermal) km_slip_rates_ga<kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb, e_f, sv1 + H_GDOT * QS);
          else km_slip_rates<kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb, e_f, sv1 + H_GDOT * QS);
       }
       stg(&sv1[(H_SHRATE) * QS], shrate);
-      stg(&sv1[(H_SHR) * QS], (ECM_EPI_NO_LOADS ? ECM_ST(st, ST_PB + PB_SHR0) : ldg(&sv0[(H_SHR) * QS])) + shrate * dt);
-      stg(&sv1[(H_FLOW) * QS], ((deff_keep > TINY_SQRT) ? dis_rate * dt : 0.0) + (ECM_EPI_NO_LOADS ? ECM_ST(st, ST_PB + PB_FLOW0) : ldg(&sv0[(H_FLOW) * QS])));   // accumulated plastic work
+      stg(&sv1[(H_SHR) * QS], ECM_ST(st, ST_PB + PB_SHR0) + shrate * dt);
+      stg(&sv1[(H_FLOW) * QS], ((deff_keep > TINY_SQRT) ? dis_rate * dt : 0.0) + ECM_ST(st, ST_PB + PB_FLOW0));   // accumulated plastic work
       stg(&sv1[(H_NFEV) * QS], (double)nfev);
       { const double a_V = E_SCALE * ECM_ST(st, ST_PB + PB_ESCI); for (int i = 0; i < 5; i++) stg(&sv1[(H_E + i) * QS], e_f[i] * a_V); }   // state e = a_V E
       stg(&sv1[(H_H) * QS], hu_keep);
@@ -1762,7 +1551,7 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
       eNew += 0.25 * (vOld + vNew) * dt * (wrkOld + wrkn);
       if constexpr (!kin_is_km(KIN)) voce_slip_rates<kin_xn_ct(KIN), true>(mp, pb, ef, sv1 + H_GDOT * QS, dis_rate, shrate, detV_ri);
       else {
-         if (ECM_KM_GDOT_GA && kin_base(KIN) == KIN_KMBALD_GA && kin_pq1(KIN) && mp.with_g_athermal) km_slip_rates_ga<kin_pq1(KIN), kin_sc_exp(KIN), true>(mp, pb, ef, sv1 + H_GDOT * QS);
+         if (kin_base(KIN) == KIN_KMBALD_GA && kin_pq1(KIN) && mp.with_g_athermal) km_slip_rates_ga<kin_pq1(KIN), kin_sc_exp(KIN), true>(mp, pb, ef, sv1 + H_GDOT * QS);
          else km_slip_rates<kin_pq1(KIN), kin_sc_exp(KIN), true>(mp, pb, ef, sv1 + H_GDOT * QS);
       }
       ost<true>(&sv1[(H_SHRATE) * QS], shrate);
@@ -1779,7 +1568,6 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
       ECM_PARK_BARRIER(); __builtin_amdgcn_wave_barrier();
       io.flush_state();
    };
-   if (!ECM_TANGENT_FIRST) write_state();
 #ifdef ECM_EXP_TAN_FAKE   // timing experiment: the 13 record stores without the tangent arithmetic
    if constexpr (REC) { double2* rc = reinterpret_cast<double2*>(cmat); for (int pr = 0; pr < 13; pr++) rc[pr * 64] = make_double2(J.A[pr] * detV_ri, bulkNew + J.B[pr % 3][pr % 5]); }
 #define ECM_NO_TANGENT 1
@@ -1787,9 +1575,9 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
 #ifndef ECM_NO_TANGENT
    // ---- tangent (last: it overwrites the parking area): lattice-frame d sigma'/d D' by implicit differentiation on the converged
    // factorisation, rotated to the sample frame, then to Voigt (engineering shear) + bulk term, column-major
-   // Two forms of the same arithmetic: the W X form (ECM_TANGENT_WX) for the Voce kinds - 170 multiply-adds fewer, 4.62 -> 4.30 ms at 128^3 - and the
-   // round-3 chain for the Kocks-Mecking kinds, whose register allocation the W X form upsets (BCC p = q = 1: 4 -> 37 spills)
-   if constexpr (ECM_TANGENT_WX != 0 && !kin_is_km(KIN))
+   // Two forms of the same arithmetic: the W X form for the Voce kinds - 170 multiply-adds fewer, 4.62 -> 4.30 ms at 128^3 - and the
+   // round-3 chain for the Kocks-Mecking kinds, whose register allocation the W X form upset (BCC p = q = 1: 4 -> 37 spills, elastic pass 3.4 -> 4.1 ms)
+   if constexpr (!kin_is_km(KIN))
    {
       // J [xe; xr] = [e_c; 0] with Jee = M Kd, Jre = B Kd, Jer = -E (E = M35(d_lat) Tr), xr eliminated exactly:
       //   y = Kd xe,  (M + E G) y = e_c,  G = Jrr^-1 B,  xr = -G y   =>   Llat = (I/J + M35(s') Tr G) (M + E G)^-1
@@ -1803,9 +1591,6 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
          for (int k = 0; k < 5; k++) Q5[k][l] = out[k];
       }
       double D55[5][5];   // sample-frame deviatoric tangent block (times dt)
-      // (Voce kinds only: in the Kocks-Mecking kernels the W X form costs registers they do not have - BCC 4 -> 37 spills, elastic pass 3.4 -> 4.1 ms)
-      constexpr bool WX = true;
-      double Llat[WX ? 1 : 5][5];
       bool okT;
       {
          double Ri[9]; okT = rot_block_inverse(pb, J, Ri);
@@ -1847,81 +1632,36 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
                for (int j = k + 1; j < 5; j++) S[i][j] -= l * S[k][j];
             }
          }
-         if constexpr (WX) {
          // D55 = Q5 Llat Q5^T = (Q5 Kt) (S^-1 Q5^T) =: W X.  W = detV_ri Q5 + M35(s_sm) (Cf G): the map w -> vecd(S W - W S) is equivariant under the
          // rotation (Q5 M35(s) w = M35(Q5 s) (Cf w)), so the rotated coupling costs 45 + 65 multiply-adds instead of 75 + 125; X is five
          // forward / backward substitutions with the columns of Q5^T as right-hand sides.  375 + 110 multiply-adds where the chain
          // S^-1 -> Kt S^-1 -> Q5 (.) -> (.) Q5^T took 555 (same numbers in another order of summation)
-         {
-            double CG[3][5];
+         double CG[3][5];
 #pragma unroll
-            for (int i = 0; i < 3; i++)
+         for (int i = 0; i < 3; i++)
 #pragma unroll
-               for (int j = 0; j < 5; j++) CG[i][j] = Cf[3 * i] * G[0][j] + Cf[3 * i + 1] * G[1][j] + Cf[3 * i + 2] * G[2][j];
-            double s_sm5[5]; rot_vecd(Cf, s_lat, s_sm5);
-            double Mr[5][3]; m35(s_sm5, Mr);
-            double Wm[5][5], X[5][5];
+            for (int j = 0; j < 5; j++) CG[i][j] = Cf[3 * i] * G[0][j] + Cf[3 * i + 1] * G[1][j] + Cf[3 * i + 2] * G[2][j];
+         double s_sm5[5]; rot_vecd(Cf, s_lat, s_sm5);
+         double Mr[5][3]; m35(s_sm5, Mr);
+         double Wm[5][5], X[5][5];
 #pragma unroll
-            for (int k = 0; k < 5; k++)
+         for (int k = 0; k < 5; k++)
 #pragma unroll
-               for (int j = 0; j < 5; j++) Wm[k][j] = fma(detV_ri, Q5[k][j], Mr[k][0] * CG[0][j] + Mr[k][1] * CG[1][j] + Mr[k][2] * CG[2][j]);
+            for (int j = 0; j < 5; j++) Wm[k][j] = fma(detV_ri, Q5[k][j], Mr[k][0] * CG[0][j] + Mr[k][1] * CG[1][j] + Mr[k][2] * CG[2][j]);
 #pragma unroll
-            for (int c = 0; c < 5; c++) {       // column c of X = S^-1 (row c of Q5)
-               double y[5];
-#pragma unroll
-               for (int i = 0; i < 5; i++) { double t = Q5[c][i]; for (int j = 0; j < i; j++) t -= S[i][j] * y[j]; y[i] = t; }
-#pragma unroll
-               for (int i = 4; i >= 0; i--) { double t = y[i]; for (int j = i + 1; j < 5; j++) t -= S[i][j] * y[j]; y[i] = t * S[i][i]; }
-#pragma unroll
-               for (int l = 0; l < 5; l++) X[l][c] = y[l];
-            }
-#pragma unroll
-            for (int k = 0; k < 5; k++)
-#pragma unroll
-               for (int c = 0; c < 5; c++) D55[k][c] = Wm[k][0] * X[0][c] + Wm[k][1] * X[1][c] + Wm[k][2] * X[2][c] + Wm[k][3] * X[3][c] + Wm[k][4] * X[4][c];
-         }
-         } else {
-         double Kt[5][5];   // detV_ri I + M35(s_lat) (Tr G)
-         {
-            double Ms[5][3]; m35(s_lat, Ms);
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-#pragma unroll
-               for (int j = 0; j < 5; j++) Kt[k][j] = ((k == j) ? detV_ri : 0.0) + Ms[k][0] * G[0][j] + Ms[k][1] * G[1][j] + Ms[k][2] * G[2][j];
-            }
-         }
-#pragma unroll
-         for (int c = 0; c < 5; c++) {
+         for (int c = 0; c < 5; c++) {       // column c of X = S^-1 (row c of Q5)
             double y[5];
 #pragma unroll
-            for (int i = 0; i < 5; i++) {       // forward: L y = e_c (entries above c stay zero)
-               double t = (i == c) ? 1.0 : 0.0;
+            for (int i = 0; i < 5; i++) { double t = Q5[c][i]; for (int j = 0; j < i; j++) t -= S[i][j] * y[j]; y[i] = t; }
 #pragma unroll
-               for (int j = c; j < i; j++) t -= S[i][j] * y[j];
-               y[i] = (i < c) ? 0.0 : t;
-            }
+            for (int i = 4; i >= 0; i--) { double t = y[i]; for (int j = i + 1; j < 5; j++) t -= S[i][j] * y[j]; y[i] = t * S[i][i]; }
 #pragma unroll
-            for (int i = 4; i >= 0; i--) {      // backward: U y = y
-               double t = y[i];
-#pragma unroll
-               for (int j = i + 1; j < 5; j++) t -= S[i][j] * y[j];
-               y[i] = t * S[i][i];
-            }
-#pragma unroll
-            for (int k = 0; k < 5; k++) Llat[k][c] = Kt[k][0] * y[0] + Kt[k][1] * y[1] + Kt[k][2] * y[2] + Kt[k][3] * y[3] + Kt[k][4] * y[4];
+            for (int l = 0; l < 5; l++) X[l][c] = y[l];
          }
-               }
-      }
-      if constexpr (!WX) {  // D55 = Q5 Llat Q5^T
-         double T1[5][5];
 #pragma unroll
          for (int k = 0; k < 5; k++)
 #pragma unroll
-            for (int c = 0; c < 5; c++) { double v = 0; for (int l = 0; l < 5; l++) v += Q5[k][l] * Llat[l][c]; T1[k][c] = v; }
-#pragma unroll
-         for (int k = 0; k < 5; k++)
-#pragma unroll
-            for (int c = 0; c < 5; c++) { double v = 0; for (int l = 0; l < 5; l++) v += T1[k][l] * Q5[c][l]; D55[k][c] = v; }
+            for (int c = 0; c < 5; c++) D55[k][c] = Wm[k][0] * X[0][c] + Wm[k][1] * X[1][c] + Wm[k][2] * X[2][c] + Wm[k][3] * X[3][c] + Wm[k][4] * X[4][c];
       }
       if constexpr (REC) {
          const double rsc = STG ? rsc_keep : ECM_CD(CD_TSC);
@@ -2121,7 +1861,7 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
    }
 #endif
    if constexpr (STG) { write_state_staged(); return cut ? 2 : ((conv && ok) ? 0 : 1); }
-   if (ECM_TANGENT_FIRST) write_state();
+   write_state();
    return (conv && ok) ? 0 : 1;
 }
 

@@ -14,39 +14,25 @@ using namespace ecmdev;
 #ifndef EXA_MODEL_BS
 #define EXA_MODEL_BS 128   // threads per block of the constitutive launch (4 blocks of 2 waves per CU: 38.9 KB of stash each; a block waits for 2 waves, not 4)
 #endif
-static_assert(EXA_MODEL_BS % ECM_STASH_STRIDE == 0 && ECM_STASH_STRIDE % 64 == 0, "a block is a whole number of stash regions, a region a whole number of waves");
+static_assert(EXA_MODEL_BS % ecmdev::STASH_STRIDE == 0, "a block is a whole number of per-wave stash regions");
 constexpr int EXA_STASH_DOUBLES = ecmdev::ST_SLOTS * EXA_MODEL_BS;   // LDS stash of a block
 
-#ifndef EXA_STG_NT_LD
-#define EXA_STG_NT_LD 1   // row pieces of the staged launch: non-temporal loads / stores like the per-lane accesses of the other launches (A/B switches)
-#endif
-#ifndef EXA_STG_NT_ST
-#define EXA_STG_NT_ST 1   // (every round stores whole 128-byte lines: with the tangent in 144-byte pieces - rounds of 3 columns - plain stores were the faster ones)
-#endif
+// row pieces of the staged launch: non-temporal loads / stores like the per-lane accesses of the other launches
+// (every round stores whole 128-byte lines: with the tangent in 144-byte pieces - rounds of 3 columns - plain stores were the faster ones)
 __device__ __forceinline__ double2 ldg2(const double* p) {
-#if EXA_STG_NT_LD
    typedef double vd2 __attribute__((ext_vector_type(2)));
    const vd2 v = __builtin_nontemporal_load(reinterpret_cast<const vd2*>(p));
    return make_double2(v.x, v.y);
-#else
-   return *reinterpret_cast<const double2*>(p);
-#endif
 }
 // Row strides (doubles) in the stage: the rows lie there as in memory.  (Measured: rows one double apart - odd strides 29 / 7, no LDS bank conflicts of the lanes'
 // 8-byte row accesses, two 8-byte LDS accesses per 16-byte piece - are slower, 4.87 against 4.83 ms at 128^3: the row accesses are not what the launch waits for.)
 constexpr int RS_SV = ecmdev::NSTATEV, RS_S = 6, RS_T = 36;
-__device__ __forceinline__ void stg2r(double* p, const double a, const double b) {
-#if EXA_STG_NT_ST
-   ecmdev::stg2(reinterpret_cast<double2*>(p), a, b);
-#else
-   *reinterpret_cast<double2*>(p) = make_double2(a, b);
-#endif
-}
+__device__ __forceinline__ void stg2r(double* p, const double a, const double b) { ecmdev::stg2(reinterpret_cast<double2*>(p), a, b); }
 // Where one thread's quadrature point lives.  Everything is a function of (block index, thread index) and kernel-uniform data, so nothing
 // per-lane has to survive the local Newton solve: locate() derives the point from the thread index, refresh() does it again behind a compiler
 // barrier after the solve, and the accessors form the addresses where they are used.  Before, five 64-bit row pointers and two LDS addresses
 // were live across the solve; the register allocator spilled some of them and re-loaded them from scratch BEHIND the first output stores,
-// where a load waits for the whole store queue of the wave (ecm_device.hpp, ECM_EPI_NO_LOADS).
+// where a load waits for the whole store queue of the wave (ecm_device.hpp, epilogue of point_update).
 // STG (staged AOS launch, QB = false): a wave owns the 64 CONSECUTIVE points pt0() ... pt0() + 63, whose rows are contiguous in every (vdim, Q, E) array.
 // The wave's stash region (ST_SLOTS x 64 doubles of LDS) doubles as its transposition buffer: rows come in through coalesced 16-byte loads and are
 // read back by their lanes (model_kernel.hpp, stage_in); outputs are written by their lanes as rows - sv1() / s1() / cm() point into the region - and
@@ -62,7 +48,7 @@ struct PointIO {
    int Q; int64_t bidx; int wpb;    // points per element, (remapped) block index, waves per block
    int q; int64_t e; int tid;       // this thread's point and its index in the block
    int64_t P; bool live;            // STG: points of the launch; this lane's point exists
-   static_assert(!STG || (!QB && ECM_STASH_STRIDE == 64), "staged rows: AOS layout, per-wave stash regions");
+   static_assert(!STG || !QB, "staged rows: AOS layout");
    __device__ __forceinline__ int wave() const { return STG ? __builtin_amdgcn_readfirstlane(tid >> 6) : (tid >> 6); }   // (STG: wave-uniform row addresses in scalar registers)
    __device__ __forceinline__ int64_t pt0() const { return (bidx * wpb + wave()) * 64; }
    __device__ __forceinline__ int nvalid() const { const int64_t r = P - pt0(); return r < 64 ? (int)r : 64; }   // points of this wave that exist (may be <= 0)
@@ -127,8 +113,8 @@ struct PointIO {
       if (STG && !REC) return wreg() + (tid & 31) * RS_T;      // (lanes l and l + 32 use the row one after the other)
       return REC ? cmat + pac_off<NPAIR>(e >> 6, Q, q, 0) + 2 * (e & 63) : cmat + qview<QB>(36, Q, e, q).base;
    }
-   // slot s of this thread at stash()[s * ECM_STASH_STRIDE]: regions of ECM_STASH_STRIDE lanes, one behind the other
-   __device__ __forceinline__ double* stash() const { return stash0 + (tid / ECM_STASH_STRIDE) * (ecmdev::ST_SLOTS * ECM_STASH_STRIDE) + (tid % ECM_STASH_STRIDE); }
+   // slot s of this thread at stash()[s * STASH_STRIDE]: the regions of the block's waves, one behind the other
+   __device__ __forceinline__ double* stash() const { return stash0 + (tid / ecmdev::STASH_STRIDE) * (ecmdev::ST_SLOTS * ecmdev::STASH_STRIDE) + (tid % ecmdev::STASH_STRIDE); }
    __device__ __forceinline__ int ipt() const { return (int)(e * Q + q); }
 };
 
@@ -198,16 +184,9 @@ __global__ __launch_bounds__(EXA_MODEL_BS, EXA_MODEL_OCC) void k_model_setup(con
    if (tail_mode && (int64_t)blockIdx.x * blockDim.x >= tail[0]) return;   // tail launch: its grid covers the worst case, blocks beyond the list leave before the table fill
    const int n = NFIX ? NFIX : n_rt;
    constexpr bool P2F = (NFIX == 27);   // triquadratic fused path: G holds the 3 x 6 one-dimensional tables, read through scalar loads
-#ifndef EXA_MODEL_XCD_REMAP
-#define EXA_MODEL_XCD_REMAP 0
-#endif
-   // workgroups are dealt round-robin to the 8 XCDs; remapped, an XCD works on one contiguous eighth of the element blocks (node gathers of
-   // neighbouring blocks then hit the same L2)
-   int64_t bidx = blockIdx.x;
-   if (EXA_MODEL_XCD_REMAP && !tail_mode) {
-      const unsigned nb = gridDim.x, qq = nb >> 3, r = nb & 7u, x = blockIdx.x & 7u, i = blockIdx.x >> 3;
-      bidx = x < r ? (int64_t)x * (qq + 1) + i : (int64_t)r * (qq + 1) + (int64_t)(x - r) * qq + i;
-   }
+   // workgroups are dealt round-robin to the 8 XCDs.  (Remapped, so that an XCD works on one contiguous eighth of the element blocks and the node
+   // gathers of neighbouring blocks hit the same L2, the launch ran 4.176 against 4.194 ms at 128^3: nothing, the kernel is issue-bound.)
+   const int64_t bidx = blockIdx.x;
    // LDS: shape-derivative rows (not for P2F), the per-thread stash, the slip table (Kocks-Mecking).  A wave of the element-blocked launch works
    // on ONE point index q, so only the rows of the block's waves are staged (row w = the (n,3) table of wave w's q: 192 B per wave instead of
    // the 1.5 KB table - what lets four 128-thread blocks of the Kocks-Mecking kernels fit the 160 KB of a CU); the dense tail launch and the

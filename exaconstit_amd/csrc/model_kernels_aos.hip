@@ -59,7 +59,7 @@ void launch_aos_rec(exa_ctx* ctx, const Args& a, hipStream_t s) {
 int exa_launch_model_setup_aos_rec(exa_ctx* ctx, double dt, double* J, const double* vel, const double* xl, const double* stress0, const double* state0,
                                    double* stress1, double* state1, hipStream_t s) {
    if (ctx->qblk || ctx->n != 8 || !xl) return EXA_ERR_UNSUPPORTED;
-   bool staged = ctx->aos_stage && ECM_STASH_STRIDE == 64;
+   bool staged = ctx->aos_stage;
    for (const void* p : { (const void*)J, (const void*)stress0, (const void*)state0, (const void*)stress1, (const void*)state1 })
       if (reinterpret_cast<uintptr_t>(p) & 15u) staged = false;
    if (!staged) { ctx->err = "exa_model_setup_lvec_records on the reference layout is the staged launch: exa_set_aos_staging must be on and the arrays 16-byte aligned"; return EXA_ERR_UNSUPPORTED; }
@@ -73,7 +73,7 @@ int exa_launch_model_setup_aos_rec(exa_ctx* ctx, double dt, double* J, const dou
       default: ctx->err = "variant build without Kocks-Mecking kernels"; return EXA_ERR_UNSUPPORTED;
 #else
       default:
-         if (ECM_KM_DEFER && ctx->mp.with_g_athermal) { if (km_pq1(ctx)) launch_aos_rec<KIN_KMBALD_GA | KIN_PQ1>(ctx, a, s); else launch_aos_rec<KIN_KMBALD_GA>(ctx, a, s); }
+         if (ctx->mp.with_g_athermal) { if (km_pq1(ctx)) launch_aos_rec<KIN_KMBALD_GA | KIN_PQ1>(ctx, a, s); else launch_aos_rec<KIN_KMBALD_GA>(ctx, a, s); }
          else { if (km_pq1(ctx)) launch_aos_rec<KIN_KMBALD | KIN_PQ1>(ctx, a, s); else launch_aos_rec<KIN_KMBALD>(ctx, a, s); }
          break;
 #endif
@@ -86,7 +86,7 @@ int exa_launch_model_setup_aos_rec(exa_ctx* ctx, double dt, double* J, const dou
 int exa_launch_model_setup_aos(exa_ctx* ctx, double dt, double* J, const double* vel, const double* xl, const double* stress0, const double* state0,
                                double* stress1, double* state1, double* cmat, hipStream_t s) {
    // 16-byte pieces need every array on a 16-byte boundary (hipMalloc gives 256; a caller's sub-array might not: per-lane accesses then)
-   bool staged = ctx->aos_stage && ECM_STASH_STRIDE == 64;
+   bool staged = ctx->aos_stage;
    for (const void* p : { (const void*)J, (const void*)stress0, (const void*)state0, (const void*)stress1, (const void*)state1, (const void*)cmat, (const void*)(xl ? nullptr : vel) })
       if (reinterpret_cast<uintptr_t>(p) & 15u) staged = false;
    EXA_HIP_CHECK(ctx, hipMemsetAsync(ctx->fail_count_dev, 0, sizeof(int), s));
@@ -100,7 +100,7 @@ int exa_launch_model_setup_aos(exa_ctx* ctx, double dt, double* J, const double*
       default: ctx->err = "variant build without Kocks-Mecking kernels"; return EXA_ERR_UNSUPPORTED;
 #else
       default:
-         if (ECM_KM_DEFER && ctx->mp.with_g_athermal) launch_kind<KIN_KMBALD_GA, KIN_KMBALD_GA | KIN_PQ1>(ctx, km_pq1(ctx), lv, a, staged, s);
+         if (ctx->mp.with_g_athermal) launch_kind<KIN_KMBALD_GA, KIN_KMBALD_GA | KIN_PQ1>(ctx, km_pq1(ctx), lv, a, staged, s);
          else launch_kind<KIN_KMBALD, KIN_KMBALD | KIN_PQ1>(ctx, km_pq1(ctx), lv, a, staged, s);
          break;
 #endif

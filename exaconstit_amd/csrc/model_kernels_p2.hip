@@ -52,7 +52,7 @@ int exa_launch_model_setup_p2(exa_ctx* ctx, double dt, double* J, const double* 
       default: ctx->err = "variant build without Kocks-Mecking kernels"; return EXA_ERR_UNSUPPORTED;
 #else
       default:
-         if (ECM_KM_DEFER && ctx->mp.with_g_athermal) launch_p2_kind<KIN_KMBALD_GA>(ctx, records, dt, J, Lx, stress0, state0, stress1, state1, cmat, s);
+         if (ctx->mp.with_g_athermal) launch_p2_kind<KIN_KMBALD_GA>(ctx, records, dt, J, Lx, stress0, state0, stress1, state1, cmat, s);
          else launch_p2_kind<KIN_KMBALD>(ctx, records, dt, J, Lx, stress0, state0, stress1, state1, cmat, s);
          break;
 #endif
