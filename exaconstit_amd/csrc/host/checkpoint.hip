@@ -104,6 +104,7 @@ void SystemDriver::PruneCheckpoints(int step) {
 namespace {
 // lowest rank holding a node owns it: skip[g] = 1 for the nodes a lower rank shares
 std::vector<uint8_t> nodes_of_lower_ranks(const Partition& part, int rank) {
+   if (part.periodic) return part.held_by_lower;   // (the periodic neighbour lists name images too: other nodes, which a lower rank does not write)
    std::vector<uint8_t> skip((size_t)part.NN, 0);
    for (const Neighbor& nb : part.nbrs) if (nb.rank < rank) for (int32_t d : nb.dofs) skip[(size_t)(d % part.NN)] = 1;
    return skip;

@@ -69,5 +69,13 @@ void vk_qf_eb64_to_aos(int W, int Q, int64_t E, const double* src_eb64, double* 
 void vk_max_abs_diff(int64_t n, const double* a, const double* b, double* out3_dev /* max |a-b|, max |a|, (u64) differing entries of the skipped component */, hipStream_t s, int W = 0, int skip = -1);
 void vk_pack(int64_t n, const int32_t* idx, const double* y, double* buf, hipStream_t s);
 void vk_unpack_add(int64_t n, const int32_t* idx, const double* buf, double* y, hipStream_t s);
+// periodic boundary conditions (periodic_kernels.hip).  Device table of the local periodic groups, passed by value: n2 / n4 / n8 groups
+// of 2 / 4 / 8 images, each size class member-major (image j of group g of a class of n groups at base + j n + g), first image = representative
+struct PeriodicTable { const int32_t* idx = nullptr; int n2 = 0, n4 = 0, n8 = 0; int groups() const { return n2 + n4 + n8; } };
+void vk_periodic_sum(const PeriodicTable& T, int64_t nn, double* y, const double* flag, bool bcast, hipStream_t s);   // y(image) <- group sum in table order (bcast: <- y(representative))
+void vk_periodic_jump(const PeriodicTable& T, int64_t nn, const double* x, const double* L9_host, double* v, hipStream_t s);   // v(image) = v(rep) + L (x(image) - x(rep))
+void vk_periodic_affine_add(int64_t nn, const double* x, const double* org3_dev, const double* L9_host, double* v, hipStream_t s);   // v += L (x - org) on every node
+void vk_periodic_fluct(int64_t nn, const double* rep_w, const double* x, const double* L9_host, const double* v, double* t, hipStream_t s);      // t = rep_w (v - L x)
+void vk_periodic_unfluct(int64_t nn, const uint8_t* surf, const double* x, const double* L9_host, const double* t, double* v, hipStream_t s);   // v = t + L x where surf
 
 }  // namespace exa_host

@@ -554,12 +554,62 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
       // two launches of the action and two cross-stream waits to hide a 24 us exchange.  A box with real xGMI neighbours has to show where the balance tips.
       const char* ho = std::getenv("EXA_HALO_OVERLAP");
       const bool want = ho ? std::string(ho) != "off" && std::string(ho) != "0" : std::string(comm.transport()) != "rccl";
-      overlap_ = fast_p1_ && lvec_grad_ && !det && part.E_bdr > 0 && !part.nbrs.empty() && (opt.assembly == Assembly::PA || ea_rec) && want;
+      // (periodic partitions keep the plain sequence: the elements at the box surface touch shared dofs too, and the boundary-first order does not know them)
+      overlap_ = fast_p1_ && lvec_grad_ && !det && part.E_bdr > 0 && !part.nbrs.empty() && (opt.assembly == Assembly::PA || ea_rec) && want && !part.periodic;
       // decided collectively: every rank runs the same form (a partition in which one rank has no boundary block would otherwise put its
       // exchange on another stream than its peers')
       if (comm.nranks > 1) overlap_ = comm.max_over_ranks(overlap_ ? 0.0 : 1.0) == 0.0;
       nblk_bdr_ = (part.E_bdr + 63) / 64;
    }
+   if (part.periodic) SetupPeriodic();
+}
+
+// Periodic partition (Partition::make_periodic): the weights and the halo lists of the partition as it is now, the group table in the layout of
+// periodic_kernels.hip and, for several ranks, the two nodal arrays of the jump through the fluctuation (PeriodicJump)
+void NonlinearMechOperator::SetupPeriodic() {
+   const Partition& part = part_;
+   weight.upload(part.weight);
+   comm_.setup_halo(part);
+   overlap_ = false;
+   const int n2 = part.grp_count[0], n4 = part.grp_count[1], n8 = part.grp_count[2];
+   std::vector<int32_t> idx(part.grp_nodes.size());
+   size_t base = 0; int g0 = 0;
+   for (int cls = 0; cls < 3; cls++) {   // CSR (group-major) -> member-major within each size class
+      const int m = 2 << cls, n = part.grp_count[cls];
+      for (int g = 0; g < n; g++) for (int j = 0; j < m; j++) idx[base + (size_t)j * n + g] = part.grp_nodes[(size_t)part.grp_off[g0 + g] + j];
+      base += (size_t)m * n; g0 += n;
+   }
+   per_idx_.release(); if (!idx.empty()) per_idx_.upload(idx);
+   per_tab_.idx = per_idx_.p; per_tab_.n2 = n2; per_tab_.n4 = n4; per_tab_.n8 = n8;
+   if (comm_.nranks > 1) {
+      std::vector<double> rw((size_t)nn_, 0.0); std::vector<uint8_t> surf((size_t)nn_, 0);
+      for (int g = 0; g < nn_; g++) { if (part.node_gid[g] == part.canon[g]) rw[g] = part.weight_node[g]; surf[g] = part.on_box_surface(g) ? 1 : 0; }
+      per_repw_.upload(rw); per_surf_.upload(surf);
+      // the owner of a canonical id: its representative on the lowest rank that holds the id (ResidualAction)
+      std::vector<uint8_t> notown((size_t)nd_, 1), lower((size_t)nn_, 0);
+      for (const Neighbor& nb : part.nbrs) if (nb.rank < comm_.rank) for (int32_t d : nb.dofs) lower[(size_t)(d % nn_)] = 1;
+      std::vector<uint8_t> image((size_t)nn_, 0);      // local images other than the representative
+      for (size_t g = 0; g + 1 < part.grp_off.size(); g++) for (int32_t k = part.grp_off[g] + 1; k < part.grp_off[g + 1]; k++) image[(size_t)part.grp_nodes[k]] = 1;
+      for (int g = 0; g < nn_; g++) if (!lower[g] && !image[g]) for (int c = 0; c < 3; c++) notown[g + (size_t)nn_ * c] = 0;
+      per_notown_.upload(notown);
+   }
+}
+
+void NonlinearMechOperator::SumLVector(double* y, const double* flag) {
+   if (!part_.periodic) { comm_.halo_sum(part_, y, stream_); return; }
+   vk_periodic_sum(per_tab_, nn_, y, flag, false, stream_);
+   if (comm_.nranks == 1 && !comm_.forced()) return;
+   // the exchange carries the representative of a group: its local sum out, the other ranks' sums added to it, then back to its local images
+   comm_.halo_sum(part_, y, stream_);
+   vk_periodic_sum(per_tab_, nn_, y, flag, true, stream_);
+}
+
+void NonlinearMechOperator::PeriodicJump(const double* L9, double* v) {
+   if (comm_.nranks == 1) { vk_periodic_jump(per_tab_, nn_, x_cur.p, L9, v, stream_); return; }
+   // several ranks: the images of a node sit on different ranks - the node that carries the canonical id hands its fluctuation v - L x to all of them
+   vk_periodic_fluct(nn_, per_repw_.p, x_cur.p, L9, v, tmp_l_.p, stream_);
+   SumLVector(tmp_l_.p);
+   vk_periodic_unfluct(nn_, per_surf_.p, x_cur.p, L9, tmp_l_.p, v, stream_);
 }
 
 void NonlinearMechOperator::ensure_mat_grad() { if (matGrad.n == 0) { matGrad.alloc((size_t)exa_qf_size(ctx_, 36)); matGrad.zero(stream_); } }
@@ -726,7 +776,12 @@ void NonlinearMechOperator::ResidualAction(double* y) {
       abi_check(ctx_, exa_residual_apply(ctx_, el_y_.p, stream_), "exa_residual_apply");
       abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
    }
-   comm_.halo_sum(part_, y, stream_);
+   SumLVector(y);
+   // Several ranks, periodic: three or more holders add their contributions in different orders, so their copies of a residual entry differ in
+   // the last bits of the element forces - which is far above the last bits of a residual near equilibrium, and a part of the right-hand side
+   // that differs between the copies of a dof is out of the PCG's reach (tight Krylov tolerances then stop at the cap).  Every holder takes the
+   // owner's bits: all other copies are zeroed and summed again - one non-zero term per dof, an exact sum.
+   if (part_.periodic && comm_.nranks > 1) { vk_mask_zero(nd_, per_notown_.p, y, stream_); SumLVector(y); }
    vk_mask_zero(nd_, ess_mask.p, y, stream_);
 }
 
@@ -772,7 +827,7 @@ void NonlinearMechOperator::GetGradient() {
       abi_check(ctx_, exa_grad_diagonal(ctx_, el_y_.p, stream_), "exa_grad_diagonal");
       diag.zero(stream_);
       abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, diag.p, stream_), "exa_restrict_transpose_add");
-      comm_.halo_sum(part_, diag.p, stream_);
+      SumLVector(diag.p);
       vk_mask_one(nd_, ess_mask.p, diag.p, stream_);
    }
    vk_jacobi_setup(nd_, ess_mask.p, diag.p, precond == Precond::JACOBI ? 0 : 1, dinv.p, stream_);
@@ -820,7 +875,7 @@ void NonlinearMechOperator::GradMult(const double* x, double* y, bool constraine
       abi_check(ctx_, exa_grad_apply(ctx_, el_x2_.p, el_y_.p, stream_), "exa_grad_apply");
       abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
    }
-   comm_.halo_sum(part_, y, stream_);
+   SumLVector(y, done_flag);
    if (constrained && !skip_out_mask) vk_mask_zero(nd_, ess_mask.p, y, stream_);
 }
 
@@ -917,6 +972,7 @@ SystemDriver::SystemDriver(const ExaOptions& opt, int rank, int nranks, const vo
    } else part.build_from_mfem_mesh(opt.resolve(opt.mesh_file), rank, nranks, opt.order);
    add_selftest_neighbour(part, comm);
    if (opt.order == 1) part.order_boundary_first();   // several ranks: elements at shared nodes first (exchange overlapped with the interior, GradMult)
+   if (opt.periodic) part.make_periodic();            // (after the element order: it rewrites weights, neighbour lists and the group table only)
    std::vector<double> props, quats; load_case_data(opt, part, props, quats, elem_attr, grain_qref_);
    grain_qref_.resize(grain_qref_.size() / 4 * 4);
    normalise_quats(grain_qref_);   // grain g: row g - 1 of the orientation file
@@ -956,7 +1012,16 @@ void SystemDriver::UpdateEssBdr(const BCEntry& bc) {
    std::vector<uint8_t> vel(ess_host_.size(), 0), vg(ess_host_.size(), 0);
    have_vel_ = have_vgrad_ = false;
    for (int k = 0; k < 9; k++) vgrad_[k] = bc.vgrad[k];
-   for (size_t b = 0; b < bc.ids.size(); b++) {
+   if (part.periodic) {   // the eight corners, all components, as velocity-gradient dofs: v = L (x - origin) pins the rigid translation
+      for (int g = 0; g < nn; g++) {
+         const int l[3] = { g % part.nn[0], (g / part.nn[0]) % part.nn[1], g / (part.nn[0] * part.nn[1]) };
+         bool corner = true;
+         for (int d = 0; d < 3; d++) { const int gi = part.e0[d] * part.p + l[d]; corner = corner && (gi == 0 || gi == part.N[d] * part.p); }
+         if (corner) for (int k = 0; k < 3; k++) { ess_host_[g + nn * k] = 1; vg[g + nn * k] = 1; }
+      }
+      have_vgrad_ = true;
+   }
+   for (size_t b = 0; b < bc.ids.size(); b++) {   // (periodic: no ids)
       bool c[3] = { false, false, false };
       const bool is_vg = bc.comps[b] < 0;
       if (bc.ids[b] < 1 || bc.ids[b] > part.num_bdr_attr())
@@ -986,6 +1051,25 @@ void SystemDriver::UpdateVelocity(double* v) {
       else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
       vk_vgrad_velocity(part.NN, vg_mask_.p, op.x_cur.p, org, vgrad_, v, s);
    }
+   if (part.periodic) op.PeriodicJump(vgrad_, v);
+}
+
+// A new velocity gradient under periodic conditions (the first step included, from L = 0).  The corrector of the prescribed-face model
+// (SolveInit) moves the essential dofs and solves for the rest; here the essential dofs are the eight corners only, while the change of L
+// changes the jump of every image - a corrector that knows the corners alone returns a field whose images no longer fit their
+// neighbours once the jump is imposed.  The periodic counterpart keeps the fluctuation and swaps the affine part:
+// v += (L_new - L_old) (x - origin) on every node, which satisfies the new jump and the new corner values where v satisfied the old ones.
+void SystemDriver::PeriodicBCChange(const BCEntry& bc) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   double dL[9];
+   for (int k = 0; k < 9; k++) dL[k] = bc.vgrad[k] - (bc_index_ >= 0 ? vgrad_[k] : 0.0);
+   bc_index_ = (int)(&bc - opt_.bcs.data());
+   UpdateEssBdr(bc);
+   double* org = op.scal.p + 12;
+   if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
+   else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
+   vk_periodic_affine_add(part.NN, op.x_cur.p, org, dL, v_sol.p, s);
 }
 
 // PCG on more than one rank: the Chronopoulos-Gear arrangement of the same recurrence needs ONE fused reduction per iteration - the pair
@@ -1228,12 +1312,26 @@ void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
    if (kind < 0 || kind > 2) throw std::runtime_error("preconditioner kind must be 0 (identity), 1 (jacobi) or 2 (multigrid)");
    NonlinearMechOperator& op = *oper_;
    if (kind == 2) {
+      if (part.periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
       if (ExaOptions::lower(opt_.integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
       op.mg.reset(new Multigrid(op, levels, degree));   // throws where no hierarchy can be built
    } else op.mg.reset();
    drop_cg_graph();
    precond = kind == 0 ? Precond::IDENTITY : (kind == 1 ? Precond::JACOBI : Precond::MULTIGRID);
    op.precond = precond;
+}
+
+void SystemDriver::SetPeriodic(const double* L9) {
+   if (steps_done > 0 || !stats.empty() || restarted_) throw std::runtime_error("set_periodic: periodic boundary conditions can only be set before the first step");
+   if (!L9) throw std::runtime_error("set_periodic: a 3 x 3 velocity gradient is required");
+   for (int k = 0; k < 9; k++) if (!std::isfinite(L9[k])) throw std::runtime_error("set_periodic: the velocity gradient must be finite");
+   if (part.from_file || part.geom != 0) throw std::runtime_error(ExaOptions::periodic_needs_generated_mesh());
+   if (precond == Precond::MULTIGRID) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
+   part.make_periodic();
+   oper_->SetupPeriodic();
+   drop_cg_graph();
+   BCEntry e; e.step = 1; for (int k = 0; k < 9; k++) e.vgrad[k] = L9[k];
+   opt_.bcs.assign(1, e); opt_.periodic = true;
 }
 
 // ExaNewtonSolver::Mult / ExaNewtonLSSolver::Mult with b = 0 (reference src/mechanics_solver.cpp:39-143,155-281)
@@ -1269,6 +1367,7 @@ bool SystemDriver::NewtonSolve(double* x, SolverStats& st) {
       if (opt_.nl_solver == NLSolver::NR) scale = (norm / norm_prev > 0.5) ? 0.5 : 1.0;
    }
    st.newton_iters = it; st.converged = converged; st.model_calls += op.model_calls - calls0;
+   last_newton_norm = norm; last_newton_bound = norm_max;
    return converged;
 }
 
@@ -1380,6 +1479,7 @@ bool SystemDriver::Step(int ti, bool commit) {
    const auto wall0 = std::chrono::steady_clock::now();   // reference: t1 = MPI_Wtime() ... times[ti - 1] = t2 - t1 (src/mechanics_driver.cpp:865,891-892)
    hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s));
    for (const BCEntry& bc : opt_.bcs) if (bc.step == ti) {
+      if (part.periodic) { PeriodicBCChange(bc); continue; }
       DevBuf<double> v_prev(nd); v_prev.copy_from(v_sol, s);
       bc_index_ = (int)(&bc - opt_.bcs.data());
       UpdateEssBdr(bc);

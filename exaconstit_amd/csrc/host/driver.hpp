@@ -132,6 +132,14 @@ class NonlinearMechOperator {
    // reference src/mechanics_operator.cpp:446-483
    void GetUpdateBCsAction(const double* k, const double* x, double* y);
    void ResidualAction(double* y);
+   // The one place where an L-vector of element contributions becomes the assembled vector: the sum over the local periodic images (periodic
+   // partitions, DESIGN 4.11: one launch), then the sum over the ranks.  flag: the PCG's done flag (the periodic launch is a no-op once it is set).
+   void SumLVector(double* y, const double* flag = nullptr);
+   // device tables, weights and halo lists of a partition that has (just) become periodic
+   void SetupPeriodic();
+   // v(image) - v(representative) = L (x_cur(image) - x_cur(representative)) on every periodic group (UpdateVelocity)
+   void PeriodicJump(const double* L9, double* v);
+   const PeriodicTable& periodic_table() const { return per_tab_; }
    void RefreshJacobians();                // el_jac of x_cur when the record route left it unwritten (volume averages)
    void UpdateModel();                     // swap begin/end state, x_beg <- x_cur
    void SwapCoords();
@@ -185,6 +193,8 @@ class NonlinearMechOperator {
    bool tet_geo_ = false;         // tetrahedra, p = 1 fused action: J^-1 from the nodal coordinates (exa_grad_set_coords) instead of the element record
    bool cap_auto_ = true; int newton_cap_ = 0, newton_cap2_ = 0; bool tail_resume_ = true; double tail_cost_ = 4.0;
    DevBuf<double> tmp_l_, tmp_r_, el_y_, el_x2_;
+   // periodic partitions: the group table, and for several ranks 1 / holders on the node that carries the canonical id and the box-surface mask
+   DevBuf<int32_t> per_idx_; PeriodicTable per_tab_; DevBuf<double> per_repw_; DevBuf<uint8_t> per_surf_, per_notown_;
 };
 
 class SystemDriver {
@@ -195,6 +205,7 @@ class SystemDriver {
    SystemDriver(const ExaOptions& opt, const std::vector<double>& props, const std::vector<double>& quats_per_global_elem, int rank, int nranks, const void* nccl_uid);
    void UpdateEssBdr(const BCEntry& bc);
    void UpdateVelocity(double* v);
+   void PeriodicBCChange(const BCEntry& bc);   // periodic counterpart of UpdateEssBdr + SolveInit when the velocity gradient changes
    void SolveInit(const double* xprev, double* x);
    bool Solve(double* x);
    void UpdateModel();
@@ -210,6 +221,12 @@ class SystemDriver {
    // preconditioner of the PCG (set before the first step; takes effect at the next gradient set-up): kind 0 identity, 1 Jacobi, 2 multigrid with at most `levels` coarse levels (0: as
    // many as the mesh allows) and a Chebyshev smoother of `degree`; refuses multigrid where no hierarchy can be built
    void SetPreconditioner(int kind, int levels, int degree);
+   // periodic boundary conditions under the macroscopic velocity gradient L9 (row by row) on a freshly created driver before its first step,
+   // like SetPreconditioner: rebuilds the partition tables, weights, essential set and halo lists (every rank calls it).  Refuses file meshes
+   // and the multigrid preconditioner with the messages of the options reader.  The boundary-condition schedule becomes one entry: L from step 1.
+   void SetPeriodic(const double* L9);
+   const double* vgrad_in_force() const { return bc_index_ >= 0 ? vgrad_ : opt_.bcs.front().vgrad; }
+   double last_newton_norm = 0.0, last_newton_bound = 0.0;   // final residual norm and max(rel |r0|, abs) of the last Newton solve
    void note_cg_reduction(const double* hS);
    double last_cg_reduction = 0.0, worst_capped_cg_reduction = 0.0;   // |r|_M / |r0|_M of the last PCG solve / the worst among the solves that stopped at max_iter
    void drop_cg_graph();                      // forget the captured PCG chunk (its solution buffer is about to go away)

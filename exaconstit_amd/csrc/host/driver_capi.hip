@@ -250,6 +250,43 @@ exa_driver* exa_driver_create_synthetic(const exa_synth_config* c, int rank, int
 
 void exa_driver_destroy(exa_driver* d) { delete d; }
 
+int exa_driver_set_periodic(exa_driver* d, const double* vel_grad9, char* err, int errlen) {
+   try { d->sd->SetPeriodic(vel_grad9); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// out8 = { periodic (0 / 1), local groups of 2 / 4 / 8 images, canonical ids exchanged with other ranks (summed over the neighbours), neighbours, 0, 0 };
+// vel_grad9 = the macroscopic velocity gradient in force (zeros when not periodic)
+int exa_driver_periodic_info(exa_driver* d, int64_t* out8, double* vel_grad9) {
+   try {
+      const SystemDriver& sd = *d->sd; const Partition& p = sd.part;
+      for (int k = 0; k < 8; k++) out8[k] = 0;
+      for (int k = 0; k < 9; k++) vel_grad9[k] = 0.0;
+      if (!p.periodic) return 0;
+      out8[0] = 1; out8[1] = p.grp_count[0]; out8[2] = p.grp_count[1]; out8[3] = p.grp_count[2];
+      for (const Neighbor& nb : p.nbrs) out8[4] += (int64_t)nb.dofs.size() / 3;
+      out8[5] = (int64_t)p.nbrs.size();
+      for (int k = 0; k < 9; k++) vel_grad9[k] = sd.vgrad_in_force()[k];
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_periodic_info: %s\n", e.what()); return -1; }
+}
+
+// which: 0 velocity, 1 current coordinates (after a completed step: its end), 2 reference coordinates; out [local nodes][3] or NULL; returns the local node count
+int exa_driver_get_nodal(exa_driver* d, int which, double* out, char* err, int errlen) {
+   try {
+      SystemDriver& sd = *d->sd; NonlinearMechOperator& op = sd.oper();
+      if (which < 0 || which > 2) throw std::runtime_error("exa_driver_get_nodal: field must be 0 (velocity), 1 (coords) or 2 (coords_ref)");
+      const int nn = sd.part.NN;
+      if (out) {
+         const std::vector<double> h = (which == 0 ? sd.v_sol : (which == 1 ? op.x_cur : op.x_ref)).to_host(op.stream());
+         for (int g = 0; g < nn; g++) for (int c = 0; c < 3; c++) out[3 * (size_t)g + c] = h[g + (size_t)nn * c];
+      }
+      return nn;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// out2 = { residual norm the last Newton solve ended with, its bound max(rel |r0|, abs) }
+int exa_driver_newton_info(exa_driver* d, double* out2) { out2[0] = d->sd->last_newton_norm; out2[1] = d->sd->last_newton_bound; return 0; }
+
 int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen) {
    try { d->sd->SetPreconditioner(kind, levels, degree); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
@@ -836,6 +873,41 @@ int exa_options_query(const char* toml_path, double* out, char* err, int errlen)
       std::memcpy(out, v, sizeof(v));
       return 0;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// [BCs] table: out2 = { periodic, boundary-condition entries (update steps) }; vel_grad = 9 values per entry, at most max_entries of them (may be NULL)
+int exa_options_query_bcs(const char* toml_path, int* out2, double* vel_grad, int max_entries, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      out2[0] = o.periodic ? 1 : 0; out2[1] = (int)o.bcs.size();
+      if (vel_grad) for (int b = 0; b < (int)o.bcs.size() && b < max_entries; b++) std::memcpy(vel_grad + 9 * b, o.bcs[b].vgrad, sizeof(double) * 9);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// the periodic view of a rank's block (Partition::make_periodic): info8 = { local nodes, neighbours, neighbour dofs in all, local groups, their members in
+// all, groups of 2, of 4, of 8 }; every array pointer may be NULL: canon / weight (local nodes), nbr_rank / nbr_count (neighbours), nbr_dofs (concatenated),
+// grp_off (local groups + 1), grp_nodes (members in all)
+int exa_partition_query_periodic(const int* N, int rank, int nranks, int order, int64_t* info8, int64_t* canon, double* weight, int32_t* nbr_rank, int32_t* nbr_count,
+                                 int32_t* nbr_dofs, int32_t* grp_off, int32_t* grp_nodes) {
+   Partition p; const double L[3] = { 1.0, 1.0, 1.0 };
+   p.build(N, L, rank, nranks, (order >= 1 && order <= 6) ? order : 1);
+   p.make_periodic();
+   int64_t shared = 0; for (auto& nb : p.nbrs) shared += (int64_t)nb.dofs.size();
+   info8[0] = p.NN; info8[1] = (int64_t)p.nbrs.size(); info8[2] = shared; info8[3] = (int64_t)p.grp_off.size() - 1; info8[4] = (int64_t)p.grp_nodes.size();
+   for (int k = 0; k < 3; k++) info8[5 + k] = p.grp_count[k];
+   if (canon) std::memcpy(canon, p.canon.data(), sizeof(int64_t) * p.canon.size());
+   if (weight) std::memcpy(weight, p.weight.data(), sizeof(double) * p.weight.size());
+   size_t off = 0;
+   for (size_t i = 0; i < p.nbrs.size(); i++) {
+      if (nbr_rank) nbr_rank[i] = p.nbrs[i].rank;
+      if (nbr_count) nbr_count[i] = (int32_t)p.nbrs[i].dofs.size();
+      if (nbr_dofs) std::memcpy(nbr_dofs + off, p.nbrs[i].dofs.data(), sizeof(int32_t) * p.nbrs[i].dofs.size());
+      off += p.nbrs[i].dofs.size();
+   }
+   if (grp_off) std::memcpy(grp_off, p.grp_off.data(), sizeof(int32_t) * p.grp_off.size());
+   if (grp_nodes) std::memcpy(grp_nodes, p.grp_nodes.data(), sizeof(int32_t) * p.grp_nodes.size());
+   return 0;
 }
 
 static void export_partition(const Partition& p, int64_t* info, int32_t* conn, double* X, int64_t* elem_gid, double* weight,

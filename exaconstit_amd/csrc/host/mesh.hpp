@@ -154,6 +154,83 @@ struct Partition {
       conn.swap(c2); elem_gid.swap(g2); elem_attr.swap(a2);
    }
 
+   // ---- periodic boundary conditions on a generated mesh, all three directions ---------------------------------------------
+   // A node on the box surface has images on the opposite faces: the same degree of freedom up to the affine jump of the velocity.  Images
+   // are handled like the copies of a node that several ranks hold.  canon[g] = canonical id of local node g: its global grid index with
+   // index N[d] p mapped to 0 in every direction, numbered on the (N p + 1)^3 grid like node_gid.  make_periodic() rewrites
+   //   weight     1 / (number of (rank, local node) pairs holding the node's canonical id),
+   //   nbrs       one Neighbor per rank that holds a canonical id this rank holds too (wrap-around relations included, at most 26); dofs
+   //              component by component, ascending canonical id within a component, identical on both sides; a rank that holds several
+   //              images of an id lists its representative, the image with the lowest local index,
+   //   grp_*      CSR table of the canonical ids with >= 2 local images (they exist where pg[d] == 1): groups ordered by size (2, 4, 8), then by
+   //              canonical id; members in ascending local index, so the first one is the representative.
+   // Elements, nodes, coordinates and node_gid stay what they are (checkpoint rows are keyed by node_gid: images are distinct nodes).
+   bool periodic = false;
+   std::vector<int64_t> canon;
+   std::vector<int32_t> grp_off{ 0 }, grp_nodes; int grp_count[3] = { 0, 0, 0 };   // groups of 2 / 4 / 8 local images
+   std::vector<double> weight_node;        // the weights before make_periodic: 1 / (number of ranks holding the node itself)
+   std::vector<uint8_t> held_by_lower;     // the node itself is held by a lower rank too (checkpoint files: the lowest rank writes a node)
+   bool on_box_surface(int g) const {      // local node g has images (generated meshes)
+      const int l[3] = { g % nn[0], (g / nn[0]) % nn[1], g / (nn[0] * nn[1]) };
+      for (int d = 0; d < 3; d++) { const int gi = e0[d] * p + l[d]; if (gi == 0 || gi == N[d] * p) return true; }
+      return false;
+   }
+   void make_periodic() {
+      if (from_file || geom != 0) throw std::runtime_error("make_periodic: generated hexahedral meshes only");   // (callers refuse with the options reader's message first)
+      int M[3]; for (int d = 0; d < 3; d++) M[d] = N[d] * p;
+      // per direction: holders of every canonical coordinate over the process grid, and the local indices of this rank that map to it
+      std::vector<int> hold[3]; std::vector<std::vector<int>> loc[3];
+      auto coords_of = [&](int d, int r) { int s0, c; split(N[d], pg[d], r, s0, c); std::vector<int> v; for (int i = 0; i <= c * p; i++) v.push_back((s0 * p + i) % M[d]); return v; };
+      for (int d = 0; d < 3; d++) {
+         hold[d].assign(M[d], 0); loc[d].assign(M[d], {});
+         for (int r = 0; r < pg[d]; r++) for (int c : coords_of(d, r)) hold[d][c]++;
+         const std::vector<int> mine = coords_of(d, rc[d]);
+         for (int i = 0; i < (int)mine.size(); i++) loc[d][mine[i]].push_back(i);
+      }
+      held_by_lower.assign((size_t)NN, 0);
+      for (const Neighbor& nb : nbrs) if (nb.rank < rank) for (int32_t dof : nb.dofs) held_by_lower[(size_t)(dof % NN)] = 1;
+      weight_node = weight;
+      canon.resize((size_t)NN);
+      struct Group { int size; int64_t id; std::vector<int32_t> nodes; };
+      std::vector<Group> groups;
+      for (int k = 0; k < nn[2]; k++) for (int j = 0; j < nn[1]; j++) for (int i = 0; i < nn[0]; i++) {
+         const int g = i + nn[0] * (j + nn[1] * k);
+         const int c[3] = { (e0[0] * p + i) % M[0], (e0[1] * p + j) % M[1], (e0[2] * p + k) % M[2] };
+         canon[g] = c[0] + (int64_t)(M[0] + 1) * (c[1] + (int64_t)(M[1] + 1) * c[2]);
+         weight[g] = 1.0 / ((double)hold[0][c[0]] * hold[1][c[1]] * hold[2][c[2]]);
+         const std::vector<int>&a = loc[0][c[0]], &b = loc[1][c[1]], &cc = loc[2][c[2]];
+         if (a.size() * b.size() * cc.size() < 2 || i != a[0] || j != b[0] || k != cc[0]) continue;   // (the representative lists its group)
+         Group gr; gr.size = (int)(a.size() * b.size() * cc.size()); gr.id = canon[g];
+         for (int kk : cc) for (int jj : b) for (int ii : a) gr.nodes.push_back(ii + nn[0] * (jj + nn[1] * kk));
+         groups.push_back(std::move(gr));
+      }
+      std::sort(groups.begin(), groups.end(), [](const Group& x, const Group& y) { return x.size != y.size ? x.size < y.size : x.id < y.id; });
+      grp_off.assign(1, 0); grp_nodes.clear(); grp_count[0] = grp_count[1] = grp_count[2] = 0;
+      for (const Group& gr : groups) {
+         grp_nodes.insert(grp_nodes.end(), gr.nodes.begin(), gr.nodes.end()); grp_off.push_back((int32_t)grp_nodes.size());
+         grp_count[gr.size == 2 ? 0 : (gr.size == 4 ? 1 : 2)]++;
+      }
+      // neighbours: the ranks one step away on the process grid with wrap-around, every rank once (pg[d] == 2: +d and -d are the same rank)
+      nbrs.clear();
+      for (int dz = -1; dz <= 1; dz++) for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) {
+         const int o[3] = { dx, dy, dz }; int r2[3];
+         for (int d = 0; d < 3; d++) r2[d] = (rc[d] + o[d] + pg[d]) % pg[d];
+         const int other = r2[0] + pg[0] * (r2[1] + pg[1] * r2[2]);
+         if (other == rank || std::any_of(nbrs.begin(), nbrs.end(), [&](const Neighbor& nb) { return nb.rank == other; })) continue;
+         std::vector<int> sh[3];      // canonical coordinates both ranks hold, ascending
+         for (int d = 0; d < 3; d++) {
+            std::vector<int> theirs = coords_of(d, r2[d]); std::sort(theirs.begin(), theirs.end());
+            for (int c = 0; c < M[d]; c++) if (!loc[d][c].empty() && std::binary_search(theirs.begin(), theirs.end(), c)) sh[d].push_back(c);
+         }
+         if (sh[0].empty() || sh[1].empty() || sh[2].empty()) continue;
+         Neighbor nb; nb.rank = other;
+         for (int c = 0; c < 3; c++) for (int c2 : sh[2]) for (int c1 : sh[1]) for (int c0 : sh[0])
+            nb.dofs.push_back(loc[0][c0][0] + nn[0] * (loc[1][c1][0] + nn[1] * loc[2][c2][0]) + NN * c);
+         nbrs.push_back(std::move(nb));
+      }
+      periodic = true;
+   }
+
    // MFEM mesh v1.0 reader for trilinear hexahedra (what the reference gets from `Mesh(mesh_file, 1, 1, true)`, src/mechanics_driver.cpp:239-241;
    // format of workflows/Stage3/main_simulations/simulation.mesh): sections `dimension`, `elements` (attr geom=5 v0..v7, MFEM vertex order =
    // this repo's native order), `boundary` (attr geom=3 v0..v3), `vertices` with inline coordinates or a `nodes` grid function (H1 order 1).

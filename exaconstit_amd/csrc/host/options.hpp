@@ -95,6 +95,11 @@ struct ExaOptions {
    std::string props_file; int nprops = 0;
    std::string ori_file, grain_file; int num_grains = 0; std::string ori_type = "quat";
    std::vector<BCEntry> bcs; bool vgrad_origin_flag = false; double vgrad_origin[3] = { 0, 0, 0 };
+   // [BCs] periodic = true (not a key of the reference): periodic in all three directions under the macroscopic velocity gradient
+   // essential_vel_grad (one 3 x 3 per update step with changing_ess_bcs); the entries of bcs then carry no ids, only vgrad
+   bool periodic = false;
+   static const char* periodic_needs_generated_mesh() { return "BCs.periodic = true needs a generated hexahedral mesh (Mesh.type = \"auto\"): file and tetrahedral meshes need node matching"; }
+   static const char* periodic_no_multigrid() { return "BCs.periodic = true is not built for Solvers.Krylov.preconditioner = \"multigrid\" (the coarse levels have no periodic transfer)"; }
    XtalType xtal = XtalType::FCC; SlipType slip = SlipType::POWERVOCE;
    bool dt_cust = false, dt_auto = false; std::vector<double> cust_dt; double dt = 1.0, t_final = 1.0;
    double dt_min = 1.0, dt_scale = 0.25; int nsteps = 1; std::string auto_dt_fname = "auto_dt_out.txt";
@@ -175,7 +180,16 @@ struct ExaOptions {
       const bool changing = d.boolean("BCs.changing_ess_bcs", false);
       const TomlValue* ids = d.get("BCs.essential_ids"); const TomlValue* comps = d.get("BCs.essential_comps"); const TomlValue* vals = d.get("BCs.essential_vals");
       const TomlValue* vgr = d.get("BCs.essential_vel_grad");
-      if (!ids || !comps) throw std::runtime_error("BCs.essential_ids / essential_comps are required");
+      if (const TomlValue* pv = d.get("BCs.periodic")) {
+         if (pv->kind != TomlValue::BOOL) throw std::runtime_error("BCs.periodic must be true or false");
+         periodic = pv->b;
+      }
+      if (periodic) {   // no faces are prescribed: the essential set is the eight corners (SystemDriver::UpdateEssBdr)
+         auto given = [](const TomlValue* v) { return v && !(v->kind == TomlValue::ARR && v->arr.empty()); };
+         if (given(ids) || given(comps) || given(vals))
+            throw std::runtime_error("BCs.periodic = true: the faces cannot be both periodic and prescribed (leave essential_ids, essential_comps and essential_vals out)");
+         if (!vgr) throw std::runtime_error("BCs.periodic = true needs the macroscopic velocity gradient BCs.essential_vel_grad (3 x 3)");
+      } else if (!ids || !comps) throw std::runtime_error("BCs.essential_ids / essential_comps are required");
       if (const TomlValue* vo = d.get("BCs.vgrad_origin")) {
          if (!vo->arr.empty()) { if (vo->arr.size() != 3) throw std::runtime_error("BCs.vgrad_origin when provided must contain 3 components."); vgrad_origin_flag = true; for (int k = 0; k < 3; k++) vgrad_origin[k] = vo->arr[k].num; }
       }
@@ -185,20 +199,34 @@ struct ExaOptions {
          for (auto& row : m->arr) for (auto& x : row.arr) { if (k < 9) e.vgrad[k] = x.num; k++; }
          if (k != 0 && k != 9) throw std::runtime_error("BCs.essential_vel_grad must be a 3 x 3 array");
       };
+      auto full_vgrad = [](const TomlValue& m) {   // periodic: exactly 3 rows of 3 numbers
+         if (m.kind != TomlValue::ARR || m.arr.size() != 3) return false;
+         for (auto& row : m.arr) { if (row.kind != TomlValue::ARR || row.arr.size() != 3) return false; for (auto& x : row.arr) if (x.kind != TomlValue::NUM) return false; }
+         return true;
+      };
       if (changing) {
          const TomlValue* us = d.get("BCs.update_steps"); if (!us) throw std::runtime_error("BCs.update_steps was not provided any values.");
          bool has1 = false; for (auto& u : us->arr) has1 = has1 || (int)u.num == 1;
          if (!has1) throw std::runtime_error("BCs.update_steps must contain 1 in the array");
-         if (ids->arr.size() != us->arr.size()) throw std::runtime_error("BCs.essential_ids did not contain the same number of arrays as number of update steps");
-         if (comps->arr.size() != us->arr.size()) throw std::runtime_error("BCs.essential_comps did not contain the same number of arrays as number of update steps");
+         if (periodic && (vgr->kind != TomlValue::ARR || vgr->arr.size() != us->arr.size())) throw std::runtime_error("BCs.periodic = true: essential_vel_grad must hold one 3 x 3 array per update step");
+         if (!periodic && ids->arr.size() != us->arr.size()) throw std::runtime_error("BCs.essential_ids did not contain the same number of arrays as number of update steps");
+         if (!periodic && comps->arr.size() != us->arr.size()) throw std::runtime_error("BCs.essential_comps did not contain the same number of arrays as number of update steps");
          for (size_t b = 0; b < us->arr.size(); b++) {
             BCEntry e; e.step = (int)us->arr[b].num;
+            if (periodic) {
+               if (!full_vgrad(vgr->arr[b])) throw std::runtime_error("BCs.periodic = true: essential_vel_grad must hold one 3 x 3 array per update step");
+               fill_vgrad(&vgr->arr[b], e); bcs.push_back(e);
+               continue;
+            }
             for (double v : flat(ids->arr[b])) e.ids.push_back((int)v);
             for (double v : flat(comps->arr[b])) e.comps.push_back((int)v);
             if (vals && b < vals->arr.size()) e.vals = flat(vals->arr[b]);
             if (vgr && b < vgr->arr.size()) fill_vgrad(&vgr->arr[b], e);
             bcs.push_back(e);
          }
+      } else if (periodic) {
+         if (!full_vgrad(*vgr)) throw std::runtime_error("BCs.periodic = true: essential_vel_grad must be a 3 x 3 array");
+         BCEntry e; e.step = 1; fill_vgrad(vgr, e); bcs.push_back(e);
       } else {
          BCEntry e; e.step = 1;
          for (double v : flat(*ids)) e.ids.push_back((int)v);
@@ -352,6 +380,7 @@ struct ExaOptions {
          for (int i = 0; i < 3; i++) { ncuts[i] = (int)nc->arr[i].num; length[i] = ln->arr[i].num; }
       } else throw std::runtime_error("Mesh.type must be \"auto\", \"other\" or \"cubit\"");
       if (order < 1 || order > 6) throw std::runtime_error("p_refinement must be between 1 and 6");
+      if (periodic && mesh_type != "auto") throw std::runtime_error(periodic_needs_generated_mesh());
       if (const TomlValue* pc = d.get("Solvers.Krylov.preconditioner")) {
          const std::string k = pc->kind == TomlValue::STR ? lower(pc->str) : std::string("?");
          if (k == "jacobi") precond = 1;
@@ -364,6 +393,7 @@ struct ExaOptions {
             if (order != 1) throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is built for p_refinement = 1 only");
             if (lower(integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
             if (mesh_type != "auto") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\"): file meshes need algebraic coarsening");
+            if (periodic) throw std::runtime_error(periodic_no_multigrid());
          } else throw std::runtime_error("Solvers.Krylov.preconditioner must be \"jacobi\" or \"multigrid\"");
       }
    }

@@ -393,7 +393,52 @@ exa_driver_precond_apply = _sig("exa_driver_precond_apply", C.c_int, C.c_void_p,
 exa_options_query_solver = _sig("exa_options_query_solver", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int)
 exa_mg_level_count = _sig("exa_mg_level_count", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int)
 
+exa_driver_set_periodic = _sig("exa_driver_set_periodic", C.c_int, C.c_void_p, _dp, C.c_char_p, C.c_int)
+exa_driver_periodic_info = _sig("exa_driver_periodic_info", C.c_int, C.c_void_p, C.POINTER(C.c_int64), _dp)
+exa_driver_get_nodal = _sig("exa_driver_get_nodal", C.c_int, C.c_void_p, C.c_int, _dp, C.c_char_p, C.c_int)
+exa_periodic_sum_scratch_bytes = _sig("exa_periodic_sum_scratch_bytes", C.c_int)
+exa_driver_newton_info = _sig("exa_driver_newton_info", C.c_int, C.c_void_p, _dp)
+exa_options_query_bcs = _sig("exa_options_query_bcs", C.c_int, C.c_char_p, C.POINTER(C.c_int), _dp, C.c_int, C.c_char_p, C.c_int)
+exa_partition_query_periodic = _sig("exa_partition_query_periodic", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+
 PRECOND_KINDS = {"identity": 0, "jacobi": 1, "multigrid": 2}
+NODAL_FIELDS = {"velocity": 0, "coords": 1, "coords_ref": 2}
+
+
+def options_bcs(path):
+    """[BCs] table of an options file: dict(periodic, vel_grad: (entries, 3, 3) essential_vel_grad of every boundary-condition entry)"""
+    import numpy as np
+    out = (C.c_int * 2)()
+    err = C.create_string_buffer(512)
+    if exa_options_query_bcs(path.encode(), out, None, 0, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    vg = np.zeros((out[1], 3, 3))
+    if exa_options_query_bcs(path.encode(), out, vg.ctypes.data_as(_dp), out[1], err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(periodic=bool(out[0]), vel_grad=vg)
+
+
+def partition_periodic(N, rank, nranks, order=1):
+    """The periodic view of a rank's block of the generated N0 x N1 x N2 mesh: dict(canon (NN,) canonical id of every local node,
+    weight (NN,) = 1 / holders of the canonical id, nbrs [(rank, dofs)], groups [local node indices of a canonical id with >= 2 local images;
+    the first one is the representative], group_sizes {2: n, 4: n, 8: n})."""
+    import numpy as np
+    n = (C.c_int * 3)(*([int(N)] * 3 if isinstance(N, int) else [int(v) for v in N]))
+    info = (C.c_int64 * 8)()
+    exa_partition_query_periodic(n, rank, nranks, order, info, None, None, None, None, None, None, None)
+    NN, nnb, shared, ng, nm = (int(info[k]) for k in range(5))
+    canon, w = np.zeros(NN, np.int64), np.zeros(NN)
+    nr, nc, nd = np.zeros(max(nnb, 1), np.int32), np.zeros(max(nnb, 1), np.int32), np.zeros(max(shared, 1), np.int32)
+    go, gn = np.zeros(ng + 1, np.int32), np.zeros(max(nm, 1), np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    exa_partition_query_periodic(n, rank, nranks, order, info, vp(canon), vp(w), vp(nr), vp(nc), vp(nd), vp(go), vp(gn))
+    nbrs, off = [], 0
+    for i in range(nnb):
+        nbrs.append((int(nr[i]), nd[off:off + nc[i]].copy()))
+        off += nc[i]
+    return dict(NN=NN, canon=canon, weight=w, nbrs=nbrs, groups=[gn[go[g]:go[g + 1]].copy() for g in range(ng)],
+                group_sizes={2: int(info[5]), 4: int(info[6]), 8: int(info[7])})
 
 
 def options_solver(path):
@@ -810,6 +855,38 @@ class Driver:
         """kind: "identity", "jacobi" or "multigrid" (or 0 / 1 / 2); levels: max coarse levels (0 = as many as the mesh allows); degree: Chebyshev degree"""
         k = PRECOND_KINDS[kind] if isinstance(kind, str) else int(kind)
         self._chk(exa_driver_set_preconditioner(self.h, k, int(levels), int(degree), self._err, 512))
+
+    def set_periodic(self, vel_grad):
+        """Periodic boundary conditions in all three directions under the macroscopic velocity gradient vel_grad (3, 3), before the
+        first step; every rank of the group calls it.  Replaces the prescribed faces of a synthetic driver."""
+        import numpy as np
+        L = np.ascontiguousarray(np.asarray(vel_grad, dtype=np.float64).reshape(9))
+        self._chk(exa_driver_set_periodic(self.h, L.ctypes.data_as(_dp), self._err, 512))
+
+    def periodic_info(self):
+        """dict(enabled, groups {2: n, 4: n, 8: n} local periodic groups by image count, shared: canonical ids exchanged with other ranks,
+        neighbours, vel_grad (3, 3) in force)"""
+        import numpy as np
+        o = (C.c_int64 * 8)()
+        L = np.zeros(9)
+        assert exa_driver_periodic_info(self.h, o, L.ctypes.data_as(_dp)) == 0
+        return dict(enabled=bool(o[0]), groups={2: int(o[1]), 4: int(o[2]), 8: int(o[3])}, shared=int(o[4]), neighbours=int(o[5]), vel_grad=L.reshape(3, 3))
+
+    def nodal_field(self, name):
+        """"velocity", "coords" (current; after a completed step: its end) or "coords_ref" of this rank's nodes: (NN_local, 3); row g belongs to the
+        node partition_nodes() numbers node_gid[g]"""
+        import numpy as np
+        which = NODAL_FIELDS[name]
+        nn = self._chk(exa_driver_get_nodal(self.h, which, None, self._err, 512))
+        out = np.zeros((nn, 3))
+        self._chk(exa_driver_get_nodal(self.h, which, out.ctypes.data_as(_dp), self._err, 512))
+        return out
+
+    def newton_info(self):
+        """dict(norm: residual norm the last Newton solve of the last step ended with, bound: max(rel_tol |r0|, abs_tol) it had to reach)"""
+        o = (C.c_double * 2)()
+        exa_driver_newton_info(self.h, o)
+        return dict(norm=float(o[0]), bound=float(o[1]))
 
     def mg_info(self):
         """dict(levels, setup_ms, vcycle_ms, degree, boxes (L+1, 3) local elements per direction, lmax (L+1,))"""

@@ -178,6 +178,22 @@ int exa_driver_set_grains(exa_driver* d, const int32_t* grain_of_global_element,
  * exa_texture_weights summed exactly over the ranks: the same bits for any rank count.  0 <= nhkl <= 16, 0 <= ndir <= 3, nhkl + ndir >= 1.
  * Returns 0 or -1 (err). */
 int exa_driver_pole_figures(exa_driver* d, int nhkl, const int* hkl3, int ndir, const double* dirs3, double res_deg, double* mrd_out, char* err, int errlen);
+/* Periodic boundary conditions in all three directions under the macroscopic velocity gradient vel_grad9 (row by row), on a freshly
+ * created driver before its first step - also one made by exa_driver_create_synthetic, whose prescribed faces it replaces: the velocity satisfies
+ * v(image) - v(node) = L (x(image) - x(node)) between the images of a surface node, the eight corners carry v = L (x - origin).  Rebuilds the
+ * partition tables, weights, essential set and halo lists; every rank of the group calls it.  Refuses meshes read from a file and the multigrid
+ * preconditioner, like the options reader ([BCs] periodic = true).  Returns 0 or -1 (err). */
+int exa_driver_set_periodic(exa_driver* d, const double* vel_grad9, char* err, int errlen);
+/* out8 = { periodic (0 / 1), local periodic groups of 2, of 4, of 8 images, canonical ids exchanged with other ranks, neighbours, 0, 0 };
+ * vel_grad9 = the macroscopic velocity gradient in force (zeros when the driver is not periodic).  Returns 0 or -1. */
+int exa_driver_periodic_info(exa_driver* d, int64_t* out8, double* vel_grad9);
+/* private (scratch) bytes per lane of k_periodic_sum in the loaded code object (the launch that follows every periodic operator action); -1 without a device */
+int exa_periodic_sum_scratch_bytes(void);
+/* A nodal field of this rank: which = 0 velocity, 1 current coordinates (after a completed step: its end), 2 reference coordinates; out
+ * [local nodes][3] or NULL.  Row g belongs to the node exa_partition_query_nodes numbers node_gid[g].  Returns the local node count or -1 (err). */
+int exa_driver_get_nodal(exa_driver* d, int which, double* out, char* err, int errlen);
+/* out2 = { residual norm the last Newton solve of the last step ended with, its bound max(rel_tol |r0|, abs_tol) }.  Returns 0. */
+int exa_driver_newton_info(exa_driver* d, double* out2);
 int exa_driver_bench_prepare(exa_driver* d, int nsteps, const double* dts, double perturb, char* err, int errlen);
 int exa_driver_bench_model(exa_driver* d, int steps, double* out3, char* err, int errlen);
 int exa_driver_bench_pcg(exa_driver* d, int iters, double* out3, char* err, int errlen);
@@ -191,6 +207,9 @@ int exa_driver_bench_adapter_route(exa_driver* d, int steps, int iters, double* 
  * {temp_k, nprops, num_grains, xtal, slip, dt_cust, dt_auto, nsteps, assembly(0 PA,1 EA), nl_solver(0 NR,1 NRLS), newton_iter, newton_rel,
  *  newton_abs, krylov_iter, krylov_rel, krylov_abs, ref_ser, ncuts0, additional_avgs, number of BC change steps}; returns 0 or -1 (err) */
 int exa_options_query(const char* toml_path, double* out20, char* err, int errlen);
+/* [BCs] table: out2 = { periodic (default 0), boundary-condition entries }, vel_grad = essential_vel_grad of every entry (9 values each, row by
+ * row; at most max_entries entries are copied; may be NULL); returns 0 or -1 (err) */
+int exa_options_query_bcs(const char* toml_path, int* out2, double* vel_grad, int max_entries, char* err, int errlen);
 /* Solvers.Krylov keys of the multigrid preconditioner: out3 = { 0 key absent (the jacobi flag of exa_driver_create decides), 1 "jacobi",
  * 2 "multigrid"; mg_levels (default 0 = as many as the mesh allows); mg_smoother_degree (default 2) }; returns 0 or -1 (err) */
 int exa_options_query_solver(const char* toml_path, int* out3, char* err, int errlen);
@@ -238,6 +257,13 @@ int exa_partition_query(const int* N, int rank, int nranks, int64_t* info8, int3
 /* The element order the driver runs with on several ranks: elements touching a node shared with another rank first (their 64-element
  * blocks are computed before the halo exchange starts, the interior ones while it is on the wire).  out2 = { E, E_bdr }. */
 int exa_partition_query_boundary_first(const int* N, int rank, int nranks, int order, int64_t* out2, int32_t* conn, int64_t* elem_gid);
+/* The periodic view of a rank's block of the generated mesh: info8 = { local nodes, neighbours, neighbour dofs in all, local
+ * groups, their members in all, groups of 2, of 4, of 8 images }, then the arrays whose pointers are non-null: canon (local nodes; the
+ * canonical id: global grid index with index N p mapped to 0 in every direction, numbered like node_gid), weight (local nodes; 1 / holders of the
+ * canonical id over all ranks), nbr_rank / nbr_count (neighbours), nbr_dofs (concatenated; component by component, ascending canonical id,
+ * identical on both sides), grp_off (local groups + 1) and grp_nodes: CSR of the canonical ids with >= 2 local images, by size, then by id. */
+int exa_partition_query_periodic(const int* N, int rank, int nranks, int order, int64_t* info8, int64_t* canon, double* weight, int32_t* nbr_rank,
+                                 int32_t* nbr_count, int32_t* nbr_dofs, int32_t* grp_off, int32_t* grp_nodes);
 /* local -> global node numbers of a rank's partition: info2 = { local nodes, global nodes }; node_gid (local nodes) may be NULL.  Ranks that hold
  * the same node give it the same number (generated meshes: the (N p + 1)^3 grid, x fastest; file meshes: the reader's numbering after elevation) */
 int exa_partition_query_nodes(const int* N, int rank, int nranks, int order, int64_t* info2, int64_t* node_gid);
