@@ -76,6 +76,17 @@ void vk_periodic_sum(const PeriodicTable& T, int64_t nn, double* y, const double
 void vk_periodic_jump(const PeriodicTable& T, int64_t nn, const double* x, const double* L9_host, double* v, hipStream_t s);   // v(image) = v(rep) + L (x(image) - x(rep))
 void vk_periodic_affine_add(int64_t nn, const double* x, const double* org3_dev, const double* L9_host, double* v, hipStream_t s);   // v += L (x - org) on every node
 void vk_periodic_fluct(int64_t nn, const double* rep_w, const double* x, const double* L9_host, const double* v, double* t, hipStream_t s);      // t = rep_w (v - L x)
+// mixed loading.  img / code: the nodes on the top faces with their offset codes (bit d: one period up in direction d, bit 3: a corner);
+// face: the three top-face node lists back to back, list d at [foff[d], foff[d + 1]), worked on by the blocks [fblk[d], fblk[d + 1]) of 256 nodes;
+// ctrl: local ids of c_0, c_1, c_2, c_3 (-1: another rank's); free_bits: bit 3 i + d = H_id is an unknown
+struct MixedTable { const int32_t* img = nullptr; const uint8_t* code = nullptr; int nimg = 0; const int32_t* face = nullptr; int foff[4] = { 0, 0, 0, 0 }, fblk[4] = { 0, 0, 0, 0 };
+                    int32_t ctrl[4] = { -1, -1, -1, -1 }; uint32_t free_bits = 0; };
+void vk_periodic_expand(const MixedTable& M, int64_t nn, const double* in, const double* h12, double* out, const double* flag, bool constrained, hipStream_t s);
+void vk_gather_slots(const int32_t* idx_host, int n /* <= 24 */, const double* src, double* out, hipStream_t s);   // out[k] = src[idx[k]], 0 where idx[k] < 0
+void vk_face_resultants(const MixedTable& M, int64_t nn, const double* y, const double* flag, double* part /* 3 fblk[3] */, hipStream_t s);
+void vk_periodic_sum_controls(const PeriodicTable& T, const MixedTable& M, int64_t nn, double* y, const double* flag, const double* part, double* f9, hipStream_t s);
+void vk_translate(int64_t nn, const double* t3_host, double* v, hipStream_t s);   // v += t on every node
+void vk_face_combine(const MixedTable& M, int64_t nn, const double* part, double* f9, double* y, const double* flag, hipStream_t s);
 void vk_periodic_unfluct(int64_t nn, const uint8_t* surf, const double* x, const double* L9_host, const double* t, double* v, hipStream_t s);   // v = t + L x where surf
 
 }  // namespace exa_host

@@ -134,7 +134,18 @@ class NonlinearMechOperator {
    void ResidualAction(double* y);
    // The one place where an L-vector of element contributions becomes the assembled vector: the sum over the local periodic images (periodic
    // partitions, DESIGN 4.11: one launch), then the sum over the ranks.  flag: the PCG's done flag (the periodic launch is a no-op once it is set).
-   void SumLVector(double* y, const double* flag = nullptr);
+   // Mixed loading, raw = true (y holds raw element contributions): the nine face resultants are taken first and the free ones are
+   // written to their control slots after the sums; raw = false: the sums alone.
+   void SumLVector(double* y, const double* flag = nullptr, bool raw = true);
+   bool mixed() const { return part_.periodic && part_.mixed; }
+   void SetMixedFree(uint32_t free_bits) { mix_tab_.free_bits = free_bits; }
+   // full nodal field of the stored vector x in the scratch L-vector (mixed loading): masked first when constrained
+   const double* MixedExpand(const double* x, const double* flag, bool constrained);
+   void ExpandCorrection(double* c);         // the same in place: the PCG solution before Newton adds it to the velocity
+   void UpdateEndCoords(const double* k);    // x_cur = x_beg + dt k, as the residual evaluation at k computes it
+   void ReadResultants(double* f9_host);     // face resultants of the last residual evaluation (all ranks' sum); waits for the stream
+   // values of an L-vector at the nodes c_0 .. c_3 (12 numbers, node by node), summed over the ranks; waits for the stream
+   void CornerValues(const double* v, double* out12_host);
    // device tables, weights and halo lists of a partition that has (just) become periodic
    void SetupPeriodic();
    // v(image) - v(representative) = L (x_cur(image) - x_cur(representative)) on every periodic group (UpdateVelocity)
@@ -195,6 +206,9 @@ class NonlinearMechOperator {
    DevBuf<double> tmp_l_, tmp_r_, el_y_, el_x2_;
    // periodic partitions: the group table, and for several ranks 1 / holders on the node that carries the canonical id and the box-surface mask
    DevBuf<int32_t> per_idx_; PeriodicTable per_tab_; DevBuf<double> per_repw_; DevBuf<uint8_t> per_surf_, per_notown_;
+   // mixed loading: tables, the scratch L-vector of the expanded input, block partials of the resultants, { v(c_0), H } of the input (several ranks),
+   // resultants of the last action / of the last residual
+   MixedTable mix_tab_; DevBuf<int32_t> mix_img_, mix_face_; DevBuf<uint8_t> mix_code_; DevBuf<double> mix_x_, mix_part_, mix_h_, mix_f_, mix_res_;
 };
 
 class SystemDriver {
@@ -224,8 +238,20 @@ class SystemDriver {
    // periodic boundary conditions under the macroscopic velocity gradient L9 (row by row) on a freshly created driver before its first step,
    // like SetPreconditioner: rebuilds the partition tables, weights, essential set and halo lists (every rank calls it).  Refuses file meshes
    // and the multigrid preconditioner with the messages of the options reader.  The boundary-condition schedule becomes one entry: L from step 1.
-   void SetPeriodic(const double* L9);
-   const double* vgrad_in_force() const { return bc_index_ >= 0 ? vgrad_ : opt_.bcs.front().vgrad; }
+   // free9 (row by row, may be null: all prescribed): the entries of L that are unknowns, their mean tractions zero (mixed loading)
+   void SetPeriodic(const double* L9, const uint8_t* free9 = nullptr);
+   // (mixed loading: the realised gradient H A^-1 of the last solved step, once there is one)
+   const double* vgrad_in_force() const { return mixed_ && mac_have_ ? mac_L_ : (bc_index_ >= 0 ? vgrad_ : opt_.bcs.front().vgrad); }
+   // Mixed loading, start of a step: period vectors A and corner differences H from the fields, the run-time check that "prescribed L_id" is a
+   // condition on H_id alone, the prescribed H_id = (L a_d)_i (step 1: all of them), the gradient L = H A^-1 that UpdateVelocity imposes; when the
+   // options' L has just changed, the affine part of the velocity is swapped for the prescribed entries
+   void MixedStepStart();
+   void MixedStepEnd();   // realised gradient and face resultants of the converged step
+   bool mixed() const { return mixed_; }
+   bool mac_solved() const { return mac_have_; }
+   const uint8_t* mac_free() const { return free_; }
+   const double* mac_period() const { return mac_A_; }       // A, column d = a_d (row by row), of the start of the last step
+   const double* mac_resultants() const { return mac_F_; }   // F_id, row by row
    double last_newton_norm = 0.0, last_newton_bound = 0.0;   // final residual norm and max(rel |r0|, abs) of the last Newton solve
    void note_cg_reduction(const double* hS);
    double last_cg_reduction = 0.0, worst_capped_cg_reduction = 0.0;   // |r|_M / |r0|_M of the last PCG solve / the worst among the solves that stopped at max_iter
@@ -296,6 +322,9 @@ class SystemDriver {
    bool texture0_written_ = false;
    // rows that exist only in append-mode files otherwise (checkpoint host sections): light-up strains / volume fractions, accepted dt of Time.Auto
    std::vector<double> lattice_rows_, volume_rows_, auto_dt_rows_;
+   bool mixed_ = false, mac_have_ = false, mix_bc_changed_ = false; uint8_t free_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+   double vgrad_eff_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_A_[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, mac_L_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_F_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_w0_[3] = { 0, 0, 0 };
+   void set_free(const uint8_t* f);
    int bc_index_ = -1;                          // index in opt_.bcs of the essential-boundary entry in force
    bool restarted_ = false;
    // shared-node copies of a checkpoint written on another rank count (host/checkpoint.hip): carried along untouched and written back as long as

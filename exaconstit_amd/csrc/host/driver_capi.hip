@@ -254,6 +254,27 @@ int exa_driver_set_periodic(exa_driver* d, const double* vel_grad9, char* err, i
    try { d->sd->SetPeriodic(vel_grad9); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+// mixed loading: free9[3 i + d] != 0 makes entry (i, d) of the velocity gradient an unknown with zero mean traction; NULL or all zero = exa_driver_set_periodic
+int exa_driver_set_periodic_mixed(exa_driver* d, const double* vel_grad9, const int* free9, char* err, int errlen) {
+   try {
+      uint8_t f[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+      if (free9) for (int k = 0; k < 9; k++) f[k] = free9[k] ? 1 : 0;
+      d->sd->SetPeriodic(vel_grad9, f); return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+// free9: the mask; vel_grad9: H A^-1 realised by the last solved step (zeros before it); period9: A of the start of that step, column d = a_d, row by
+// row; resultants9: F_id of the last converged residual, row by row.  Returns 1 when mixed loading is on (0: all outputs zero), -1 on error.
+int exa_driver_macro_info(exa_driver* d, int* free9, double* vel_grad9, double* period9, double* resultants9) {
+   try {
+      const SystemDriver& sd = *d->sd;
+      for (int k = 0; k < 9; k++) { free9[k] = 0; vel_grad9[k] = period9[k] = resultants9[k] = 0.0; }
+      if (!sd.mixed()) return 0;
+      for (int k = 0; k < 9; k++) { free9[k] = sd.mac_free()[k]; period9[k] = sd.mac_period()[k]; resultants9[k] = sd.mac_resultants()[k]; }
+      if (sd.mac_solved()) for (int k = 0; k < 9; k++) vel_grad9[k] = sd.vgrad_in_force()[k];
+      return 1;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_macro_info: %s\n", e.what()); return -1; }
+}
+
 // out8 = { periodic (0 / 1), local groups of 2 / 4 / 8 images, canonical ids exchanged with other ranks (summed over the neighbours), neighbours, 0, 0 };
 // vel_grad9 = the macroscopic velocity gradient in force (zeros when not periodic)
 int exa_driver_periodic_info(exa_driver* d, int64_t* out8, double* vel_grad9) {
@@ -883,6 +904,37 @@ int exa_options_query_bcs(const char* toml_path, int* out2, double* vel_grad, in
       if (vel_grad) for (int b = 0; b < (int)o.bcs.size() && b < max_entries; b++) std::memcpy(vel_grad + 9 * b, o.bcs[b].vgrad, sizeof(double) * 9);
       return 0;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// [BCs] periodic_free: out10 = { mixed loading on (0 / 1), the mask row by row }
+int exa_options_query_periodic_free(const char* toml_path, int* out10, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      out10[0] = o.periodic_mixed ? 1 : 0;
+      for (int k = 0; k < 9; k++) out10[1 + k] = o.periodic_free[k];
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// the tables of mixed loading (Partition::make_periodic(true)) of a rank's block: info8 = { local nodes, top-face nodes of direction 0, 1, 2,
+// image entries, neighbours, neighbour dofs in all, local groups }; arrays (may be NULL): weight (local nodes), face_nodes (the three lists back to
+// back), ctrl4 (local ids of c_0 .. c_3, -1 where not held), img_nodes / img_code (image entries), canon (local nodes), nbr_dofs (concatenated)
+int exa_partition_query_periodic_mixed(const int* N, int rank, int nranks, int order, int64_t* info8, double* weight, int32_t* face_nodes, int32_t* ctrl4,
+                                       int32_t* img_nodes, uint8_t* img_code, int64_t* canon, int32_t* nbr_dofs) {
+   Partition p; const double L[3] = { 1.0, 1.0, 1.0 };
+   p.build(N, L, rank, nranks, (order >= 1 && order <= 6) ? order : 1);
+   p.make_periodic(true);
+   int64_t shared = 0; for (auto& nb : p.nbrs) shared += (int64_t)nb.dofs.size();
+   info8[0] = p.NN; for (int d = 0; d < 3; d++) info8[1 + d] = (int64_t)p.face_nodes[d].size();
+   info8[4] = (int64_t)p.img_nodes.size(); info8[5] = (int64_t)p.nbrs.size(); info8[6] = shared; info8[7] = (int64_t)p.grp_off.size() - 1;
+   if (weight) std::memcpy(weight, p.weight.data(), sizeof(double) * p.weight.size());
+   if (face_nodes) { size_t off = 0; for (int d = 0; d < 3; d++) { std::memcpy(face_nodes + off, p.face_nodes[d].data(), sizeof(int32_t) * p.face_nodes[d].size()); off += p.face_nodes[d].size(); } }
+   if (ctrl4) for (int k = 0; k < 4; k++) ctrl4[k] = p.ctrl_node[k];
+   if (img_nodes) std::memcpy(img_nodes, p.img_nodes.data(), sizeof(int32_t) * p.img_nodes.size());
+   if (img_code) std::memcpy(img_code, p.img_code.data(), p.img_code.size());
+   if (canon) std::memcpy(canon, p.canon.data(), sizeof(int64_t) * p.canon.size());
+   if (nbr_dofs) { size_t off = 0; for (auto& nb : p.nbrs) { std::memcpy(nbr_dofs + off, nb.dofs.data(), sizeof(int32_t) * nb.dofs.size()); off += nb.dofs.size(); } }
+   return 0;
 }
 
 // the periodic view of a rank's block (Partition::make_periodic): info8 = { local nodes, neighbours, neighbour dofs in all, local groups, their members in

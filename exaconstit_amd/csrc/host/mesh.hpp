@@ -175,7 +175,22 @@ struct Partition {
       for (int d = 0; d < 3; d++) { const int gi = e0[d] * p + l[d]; if (gi == 0 || gi == N[d] * p) return true; }
       return false;
    }
-   void make_periodic() {
+   // Mixed loading (mixed = true): the corner differences v(c_d) - v(c_0) carry the macroscopic motion, so the eight corners leave the
+   // group table and the neighbour lists (the operator handles them) and the partition gains
+   //   face_nodes[d]   the local nodes whose grid index in direction d is N[d] p (the top face of pair d: every node one period up), ascending,
+   //   ctrl_node[0..3] the local ids of c_0 (box origin) and c_1, c_2, c_3 (one period along x, y, z), -1 where this rank does not hold the node,
+   //   img_nodes/code  the local nodes on any top face with the 3-bit code of the periods they sit above their representative (bit d: direction d);
+   //                   the corners carry bit 3 as well: their base value is c_0's, not their own slot's,
+   //   weight          1 on c_0, c_1, c_2, c_3 (each is held by one rank) and 0 on the other four corners: every reduced unknown counts once.
+   bool mixed = false;
+   std::vector<int32_t> face_nodes[3], img_nodes; std::vector<uint8_t> img_code; int32_t ctrl_node[4] = { -1, -1, -1, -1 };
+   bool is_corner(int g) const {
+      const int l[3] = { g % nn[0], (g / nn[0]) % nn[1], g / (nn[0] * nn[1]) };
+      for (int d = 0; d < 3; d++) { const int gi = e0[d] * p + l[d]; if (gi != 0 && gi != N[d] * p) return false; }
+      return true;
+   }
+   void make_periodic(bool mixed_ = false) {
+      mixed = mixed_;
       if (from_file || geom != 0) throw std::runtime_error("make_periodic: generated hexahedral meshes only");   // (callers refuse with the options reader's message first)
       int M[3]; for (int d = 0; d < 3; d++) M[d] = N[d] * p;
       // per direction: holders of every canonical coordinate over the process grid, and the local indices of this rank that map to it
@@ -200,6 +215,7 @@ struct Partition {
          weight[g] = 1.0 / ((double)hold[0][c[0]] * hold[1][c[1]] * hold[2][c[2]]);
          const std::vector<int>&a = loc[0][c[0]], &b = loc[1][c[1]], &cc = loc[2][c[2]];
          if (a.size() * b.size() * cc.size() < 2 || i != a[0] || j != b[0] || k != cc[0]) continue;   // (the representative lists its group)
+         if (mixed && canon[g] == 0) continue;   // (the corners: handled by the operator)
          Group gr; gr.size = (int)(a.size() * b.size() * cc.size()); gr.id = canon[g];
          for (int kk : cc) for (int jj : b) for (int ii : a) gr.nodes.push_back(ii + nn[0] * (jj + nn[1] * kk));
          groups.push_back(std::move(gr));
@@ -225,8 +241,21 @@ struct Partition {
          if (sh[0].empty() || sh[1].empty() || sh[2].empty()) continue;
          Neighbor nb; nb.rank = other;
          for (int c = 0; c < 3; c++) for (int c2 : sh[2]) for (int c1 : sh[1]) for (int c0 : sh[0])
-            nb.dofs.push_back(loc[0][c0][0] + nn[0] * (loc[1][c1][0] + nn[1] * loc[2][c2][0]) + NN * c);
-         nbrs.push_back(std::move(nb));
+            if (!(mixed && c0 == 0 && c1 == 0 && c2 == 0)) nb.dofs.push_back(loc[0][c0][0] + nn[0] * (loc[1][c1][0] + nn[1] * loc[2][c2][0]) + NN * c);
+         if (!nb.dofs.empty()) nbrs.push_back(std::move(nb));
+      }
+      for (int d = 0; d < 3; d++) face_nodes[d].clear();
+      img_nodes.clear(); img_code.clear(); for (int k = 0; k < 4; k++) ctrl_node[k] = -1;
+      if (mixed) for (int g = 0; g < NN; g++) {
+         const int l[3] = { g % nn[0], (g / nn[0]) % nn[1], g / (nn[0] * nn[1]) };
+         int code = 0;
+         for (int d = 0; d < 3; d++) if (e0[d] * p + l[d] == M[d]) { code |= 1 << d; face_nodes[d].push_back(g); }
+         const bool corner = is_corner(g);
+         if (corner) {
+            weight[g] = (code == 0 || code == 1 || code == 2 || code == 4) ? 1.0 : 0.0;
+            if (code == 0) ctrl_node[0] = g; else if (code == 1) ctrl_node[1] = g; else if (code == 2) ctrl_node[2] = g; else if (code == 4) ctrl_node[3] = g;
+         }
+         if (code) { img_nodes.push_back(g); img_code.push_back((uint8_t)(code | (corner ? 8 : 0))); }
       }
       periodic = true;
    }

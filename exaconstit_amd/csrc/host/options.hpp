@@ -98,6 +98,17 @@ struct ExaOptions {
    // [BCs] periodic = true (not a key of the reference): periodic in all three directions under the macroscopic velocity gradient
    // essential_vel_grad (one 3 x 3 per update step with changing_ess_bcs); the entries of bcs then carry no ids, only vgrad
    bool periodic = false;
+   // [BCs] periodic_free = 3 x 3 of 0 / 1: entry (i, d) free = the mean traction component i on face pair d is zero and the entry of
+   // the velocity gradient an unknown; the others stay prescribed at essential_vel_grad.  All zero (or no key): every entry prescribed, as in 4.11.
+   bool periodic_mixed = false; uint8_t periodic_free[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+   // the refusals of a mask, shared with SystemDriver::SetPeriodic: the message, or nullptr for a mask that can be run
+   static const char* periodic_free_refusal(const uint8_t* f) {
+      int n = 0; for (int k = 0; k < 9; k++) n += f[k] ? 1 : 0;
+      if (n == 9) return "BCs.periodic_free: all nine entries are free - at least one entry of the velocity gradient must stay prescribed";
+      for (int i = 0; i < 3; i++) for (int j = i + 1; j < 3; j++) if (f[3 * i + j] && f[3 * j + i])
+         return "BCs.periodic_free: both entries of an off-diagonal pair (i, j), (j, i) are free - the rigid rotation would be free";
+      return nullptr;
+   }
    static const char* periodic_needs_generated_mesh() { return "BCs.periodic = true needs a generated hexahedral mesh (Mesh.type = \"auto\"): file and tetrahedral meshes need node matching"; }
    static const char* periodic_no_multigrid() { return "BCs.periodic = true is not built for Solvers.Krylov.preconditioner = \"multigrid\" (the coarse levels have no periodic transfer)"; }
    XtalType xtal = XtalType::FCC; SlipType slip = SlipType::POWERVOCE;
@@ -183,6 +194,23 @@ struct ExaOptions {
       if (const TomlValue* pv = d.get("BCs.periodic")) {
          if (pv->kind != TomlValue::BOOL) throw std::runtime_error("BCs.periodic must be true or false");
          periodic = pv->b;
+      }
+      if (const TomlValue* pf = d.get("BCs.periodic_free")) {
+         if (!periodic) throw std::runtime_error("BCs.periodic_free needs BCs.periodic = true");
+         const char* bad = "BCs.periodic_free must be a 3 x 3 array of 0 / 1 (or true / false)";
+         if (pf->kind != TomlValue::ARR || pf->arr.size() != 3) throw std::runtime_error(bad);
+         for (int i = 0; i < 3; i++) {
+            const TomlValue& row = pf->arr[i];
+            if (row.kind != TomlValue::ARR || row.arr.size() != 3) throw std::runtime_error(bad);
+            for (int j = 0; j < 3; j++) {
+               const TomlValue& x = row.arr[j];
+               if (x.kind == TomlValue::BOOL) periodic_free[3 * i + j] = x.b ? 1 : 0;
+               else if (x.kind == TomlValue::NUM && (x.num == 0.0 || x.num == 1.0)) periodic_free[3 * i + j] = x.num == 1.0 ? 1 : 0;
+               else throw std::runtime_error(bad);
+            }
+         }
+         if (const char* why = periodic_free_refusal(periodic_free)) throw std::runtime_error(why);
+         for (int k = 0; k < 9; k++) periodic_mixed = periodic_mixed || periodic_free[k];
       }
       if (periodic) {   // no faces are prescribed: the essential set is the eight corners (SystemDriver::UpdateEssBdr)
          auto given = [](const TomlValue* v) { return v && !(v->kind == TomlValue::ARR && v->arr.empty()); };

@@ -401,6 +401,12 @@ exa_driver_newton_info = _sig("exa_driver_newton_info", C.c_int, C.c_void_p, _dp
 exa_options_query_bcs = _sig("exa_options_query_bcs", C.c_int, C.c_char_p, C.POINTER(C.c_int), _dp, C.c_int, C.c_char_p, C.c_int)
 exa_partition_query_periodic = _sig("exa_partition_query_periodic", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+exa_driver_set_periodic_mixed = _sig("exa_driver_set_periodic_mixed", C.c_int, C.c_void_p, _dp, C.POINTER(C.c_int), C.c_char_p, C.c_int)
+exa_driver_macro_info = _sig("exa_driver_macro_info", C.c_int, C.c_void_p, C.POINTER(C.c_int), _dp, _dp, _dp)
+exa_periodic_mixed_scratch_bytes = _sig("exa_periodic_mixed_scratch_bytes", C.c_int, C.POINTER(C.c_int))
+exa_options_query_periodic_free = _sig("exa_options_query_periodic_free", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int)
+exa_partition_query_periodic_mixed = _sig("exa_partition_query_periodic_mixed", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
 PRECOND_KINDS = {"identity": 0, "jacobi": 1, "multigrid": 2}
 NODAL_FIELDS = {"velocity": 0, "coords": 1, "coords_ref": 2}
@@ -417,6 +423,33 @@ def options_bcs(path):
     if exa_options_query_bcs(path.encode(), out, vg.ctypes.data_as(_dp), out[1], err, 512) != 0:
         raise RuntimeError(err.value.decode())
     return dict(periodic=bool(out[0]), vel_grad=vg)
+
+
+def options_periodic_free(path):
+    """[BCs] periodic_free of an options file: dict(mixed, free (3, 3) bool)"""
+    import numpy as np
+    out = (C.c_int * 10)()
+    err = C.create_string_buffer(512)
+    if exa_options_query_periodic_free(path.encode(), out, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(mixed=bool(out[0]), free=np.array(out[1:10], dtype=bool).reshape(3, 3))
+
+
+def partition_periodic_mixed(N, rank, nranks, order=1):
+    """The tables of mixed loading of a rank's block of the generated mesh: dict(NN, weight (NN,), faces [3 arrays of local nodes on
+    the top face of direction d], ctrl (4,) local ids of c_0 .. c_3 or -1, img_nodes, img_code, canon (NN,), nbr_dofs, groups: local group count)"""
+    import numpy as np
+    n = (C.c_int * 3)(*([int(N)] * 3 if isinstance(N, int) else [int(v) for v in N]))
+    info = (C.c_int64 * 8)()
+    exa_partition_query_periodic_mixed(n, rank, nranks, order, info, None, None, None, None, None, None, None)
+    NN, nf, ni, shared = int(info[0]), [int(info[1 + d]) for d in range(3)], int(info[4]), int(info[6])
+    w, face, ctrl = np.zeros(NN), np.zeros(max(sum(nf), 1), np.int32), np.zeros(4, np.int32)
+    im, ic, canon, nd = np.zeros(max(ni, 1), np.int32), np.zeros(max(ni, 1), np.uint8), np.zeros(NN, np.int64), np.zeros(max(shared, 1), np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    exa_partition_query_periodic_mixed(n, rank, nranks, order, info, vp(w), vp(face), vp(ctrl), vp(im), vp(ic), vp(canon), vp(nd))
+    off = np.concatenate([[0], np.cumsum(nf)])
+    return dict(NN=NN, weight=w, faces=[face[off[d]:off[d + 1]].copy() for d in range(3)], ctrl=ctrl, img_nodes=im[:ni], img_code=ic[:ni], canon=canon,
+                nbr_dofs=nd[:shared], groups=int(info[7]))
 
 
 def partition_periodic(N, rank, nranks, order=1):
@@ -856,12 +889,30 @@ class Driver:
         k = PRECOND_KINDS[kind] if isinstance(kind, str) else int(kind)
         self._chk(exa_driver_set_preconditioner(self.h, k, int(levels), int(degree), self._err, 512))
 
-    def set_periodic(self, vel_grad):
+    def set_periodic(self, vel_grad, free=None):
         """Periodic boundary conditions in all three directions under the macroscopic velocity gradient vel_grad (3, 3), before the
-        first step; every rank of the group calls it.  Replaces the prescribed faces of a synthetic driver."""
+        first step; every rank of the group calls it.  Replaces the prescribed faces of a synthetic driver.  free (3, 3) of 0 / 1: mixed loading
+         - a free entry (i, d) is an unknown with zero mean traction component i on face pair d and starts from vel_grad[i, d]."""
         import numpy as np
         L = np.ascontiguousarray(np.asarray(vel_grad, dtype=np.float64).reshape(9))
-        self._chk(exa_driver_set_periodic(self.h, L.ctypes.data_as(_dp), self._err, 512))
+        if free is None:
+            self._chk(exa_driver_set_periodic(self.h, L.ctypes.data_as(_dp), self._err, 512))
+            return
+        f = np.asarray(free)
+        if f.shape != (3, 3):
+            raise ValueError("free must be a 3 x 3 mask")
+        fm = (C.c_int * 9)(*[int(bool(x)) for x in f.ravel()])
+        self._chk(exa_driver_set_periodic_mixed(self.h, L.ctypes.data_as(_dp), fm, self._err, 512))
+
+    def macro_info(self):
+        """Mixed loading: dict(free (3, 3) bool, vel_grad (3, 3) the gradient H A^-1 the last solved step realised, period (3, 3) A
+        with column d the period vector a_d at the start of that step, resultants (3, 3) F_id of the last converged residual)"""
+        import numpy as np
+        f = (C.c_int * 9)()
+        L, A, F = np.zeros(9), np.zeros(9), np.zeros(9)
+        if exa_driver_macro_info(self.h, f, L.ctypes.data_as(_dp), A.ctypes.data_as(_dp), F.ctypes.data_as(_dp)) < 0:
+            raise RuntimeError("exa_driver_macro_info failed")
+        return dict(free=np.array(list(f), dtype=bool).reshape(3, 3), vel_grad=L.reshape(3, 3), period=A.reshape(3, 3), resultants=F.reshape(3, 3))
 
     def periodic_info(self):
         """dict(enabled, groups {2: n, 4: n, 8: n} local periodic groups by image count, shared: canonical ids exchanged with other ranks,

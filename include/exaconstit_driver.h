@@ -184,6 +184,17 @@ int exa_driver_pole_figures(exa_driver* d, int nhkl, const int* hkl3, int ndir, 
  * partition tables, weights, essential set and halo lists; every rank of the group calls it.  Refuses meshes read from a file and the multigrid
  * preconditioner, like the options reader ([BCs] periodic = true).  Returns 0 or -1 (err). */
 int exa_driver_set_periodic(exa_driver* d, const double* vel_grad9, char* err, int errlen);
+/* Mixed stress / velocity-gradient loading of a periodic cell: like exa_driver_set_periodic, with free9[3 i + d] != 0 making entry
+ * (i, d) of the velocity gradient an unknown whose conjugate mean traction (component i on face pair d) is zero; the other entries stay
+ * prescribed at vel_grad9, the free ones start from it.  Refused: both entries of an off-diagonal pair free, all nine free.  free9 NULL or all
+ * zero is exa_driver_set_periodic.  Returns 0 or -1 (err). */
+int exa_driver_set_periodic_mixed(exa_driver* d, const double* vel_grad9, const int* free9, char* err, int errlen);
+/* free9 = the mask; vel_grad9 = the gradient H A^-1 the last solved step realised (zeros before it); period9 = the period vectors at the start of
+ * that step (column d = a_d, row by row); resultants9 = the face resultants F_id of the last converged residual (row by row, summed over the
+ * ranks).  Returns 1 with mixed loading on, 0 without it (all outputs zero), -1 on error. */
+int exa_driver_macro_info(exa_driver* d, int* free9, double* vel_grad9, double* period9, double* resultants9);
+/* private (scratch) bytes per lane of k_periodic_expand and k_face_resultants in the loaded code object: out2; returns 0, or -1 without a device */
+int exa_periodic_mixed_scratch_bytes(int* out2);
 /* out8 = { periodic (0 / 1), local periodic groups of 2, of 4, of 8 images, canonical ids exchanged with other ranks, neighbours, 0, 0 };
  * vel_grad9 = the macroscopic velocity gradient in force (zeros when the driver is not periodic).  Returns 0 or -1. */
 int exa_driver_periodic_info(exa_driver* d, int64_t* out8, double* vel_grad9);
@@ -257,6 +268,14 @@ int exa_partition_query(const int* N, int rank, int nranks, int64_t* info8, int3
 /* The element order the driver runs with on several ranks: elements touching a node shared with another rank first (their 64-element
  * blocks are computed before the halo exchange starts, the interior ones while it is on the wire).  out2 = { E, E_bdr }. */
 int exa_partition_query_boundary_first(const int* N, int rank, int nranks, int order, int64_t* out2, int32_t* conn, int64_t* elem_gid);
+/* [BCs] periodic_free: out10 = { mixed loading on (0 / 1), the 3 x 3 mask row by row }; returns 0 or -1 (err) */
+int exa_options_query_periodic_free(const char* toml_path, int* out10, char* err, int errlen);
+/* The tables of mixed loading of a rank's block: info8 = { local nodes, top-face nodes of direction 0, 1, 2, image entries,
+ * neighbours, neighbour dofs in all, local groups }, then the arrays whose pointers are non-null: weight (local nodes), face_nodes (the three
+ * lists back to back), ctrl4 (local ids of c_0 .. c_3, -1 where another rank holds the node), img_nodes / img_code (image entries; bit d of the
+ * code: one period up in direction d, bit 3: a corner), canon (local nodes), nbr_dofs (concatenated) */
+int exa_partition_query_periodic_mixed(const int* N, int rank, int nranks, int order, int64_t* info8, double* weight, int32_t* face_nodes, int32_t* ctrl4,
+                                       int32_t* img_nodes, uint8_t* img_code, int64_t* canon, int32_t* nbr_dofs);
 /* The periodic view of a rank's block of the generated mesh: info8 = { local nodes, neighbours, neighbour dofs in all, local
  * groups, their members in all, groups of 2, of 4, of 8 images }, then the arrays whose pointers are non-null: canon (local nodes; the
  * canonical id: global grid index with index N p mapped to 0 in every direction, numbered like node_gid), weight (local nodes; 1 / holders of the
