@@ -23,6 +23,7 @@ int exa_launch_residual_apply(exa_ctx*, double*, hipStream_t);
 int exa_launch_residual_p1(exa_ctx*, const double*, const double*, double*, bool, hipStream_t);
 int exa_launch_grad_setup_pa(exa_ctx*, double, const double*, const double*, hipStream_t);
 int exa_launch_grad_apply_p1(exa_ctx*, const double*, double*, bool, const uint8_t*, const double*, hipStream_t, bool trans = false, int blk0 = 0, int nblk_range = -1);
+int exa_launch_grad_apply_p1_cols(exa_ctx*, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, bool trans, int nch, hipStream_t);   // tangent_kernels.hip
 int exa_launch_grad_diag_p1(exa_ctx*, double*, hipStream_t);
 int exa_launch_assemble_ea_p1(exa_ctx*, hipStream_t);
 int exa_launch_ea_apply_p1(exa_ctx*, const double*, double*, bool, const uint8_t*, const double*, hipStream_t);
@@ -517,6 +518,29 @@ int exa_grad_apply_lvec_gated(exa_ctx* ctx, const double* x, double* y, const ui
    if (ctx->n == 27) return exa_launch_mf_apply_p2(ctx, x, y, mask, gate, false, S(s));
    if (ctx->p != 1) return fail(ctx, EXA_ERR_UNSUPPORTED, "fused L-vector partial-assembly action is built for p = 1 and p = 2; use exa_restrict + exa_grad_apply");
    return exa_launch_grad_apply_p1(ctx, x, y, true, mask, gate, S(s));
+}
+
+// The p = 1 hexahedron L-vector record action on `ncols` column vectors at once (tangent_kernels.hip): column k reads x + k ldx and adds into
+// y + k ldy; gates[k] (the array and every entry nullable) is the device flag of column k.  Built for one configuration - the geometry-recomputing
+// record action with atomic scatter (partial assembly, or element assembly from the records); every other context gets EXA_ERR_UNSUPPORTED
+// and loops exa_grad_apply_lvec_gated.  nch: columns per pass over the record stream (1 .. 3; 0: EXA_GRAD_COLS_DEFAULT).
+int exa_grad_apply_lvec_cols_w(exa_ctx* ctx, int nch, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, exa_stream s) {
+   if (!ctx || !x || !y) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: null pointer");
+   if (ncols < 1 || ncols > EXA_GRAD_COLS_MAX) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: between 1 and 16 columns");
+   if (nch < 0 || nch > 3) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: 1, 2 or 3 columns per pass");
+   if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_cols: connectivity not set");
+   if (!ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_cols called before exa_grad_setup");
+   const int64_t nd = 3 * (int64_t)ctx->nnodes;
+   if (ncols > 1 && (ldx < nd || ldy < nd)) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: column stride shorter than an L-vector");
+   if (!exa_is_hex(ctx) || ctx->det || ctx->p != 1 || ctx->cfg.integ != EXA_INTEG_FULL || !ctx->coords_lvec) return EXA_ERR_UNSUPPORTED;
+   const bool ea = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
+   if (ea && !ea_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
+   const bool cmp = ctx->pa_c && ctx->pac_pairs == PAC_PAIRS;
+   if (!cmp && (ctx->grad_records_only || ctx->pa_lazy || !ctx->pa)) return EXA_ERR_UNSUPPORTED;   // (no 46-double records to read the tangent from)
+   return exa_launch_grad_apply_p1_cols(ctx, ncols, x, ldx, y, ldy, mask, gates, ea, nch ? nch : EXA_GRAD_COLS_DEFAULT, S(s));
+}
+int exa_grad_apply_lvec_cols(exa_ctx* ctx, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, exa_stream s) {
+   return exa_grad_apply_lvec_cols_w(ctx, 0, ncols, x, ldx, y, ldy, mask, gates, s);
 }
 
 int exa_grad_set_coords(exa_ctx* ctx, const double* coords_lvec) {

@@ -146,6 +146,7 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
    { std::vector<double> cyc; auto it = pvd_cycles_.find(vis_dir()); if (it != pvd_cycles_.end()) for (auto& c : it->second) { cyc.push_back((double)c.first); cyc.push_back(c.second); }
      hs.push_back(host_sec("pvd_cycles", cyc)); }
    hs.push_back(host_sec("lattice_strains", lattice_rows_)); hs.push_back(host_sec("lattice_volumes", volume_rows_)); hs.push_back(host_sec("auto_dt", auto_dt_rows_));
+   if (opt_.macro_tangent) hs.push_back(host_sec("macro_tangent", macro_tangent_rows));   // (only with the option on: every other checkpoint stays byte for byte what it was)
    // ---- layout
    std::vector<Section> sec;
    for (const HostSec& x : hs) { Section t; t.name = x.name; t.nbytes = x.bytes.size(); t.checksum = sum64(x.bytes.data(), x.bytes.size()); sec.push_back(t); }
@@ -315,6 +316,8 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    host_doubles("pvd_cycles", 2, r_cyc); host_doubles("auto_dt", 1, r_dt);
    const int H = std::max(1, (int)opt_.lightup_hkl.size() / 3);
    host_doubles("lattice_strains", H, r_ls); host_doubles("lattice_volumes", H, r_lv);
+   std::vector<double> r_mt;   // rows of the macroscopic tangent: only files written with Visualizations.macro_tangent on carry them
+   if (opt_.macro_tangent && find(sec, "macro_tangent")) host_doubles("macro_tangent", MACRO_TANGENT_ROW, r_mt);
    std::vector<int32_t> r_stats;
    { const Section& t = need("solver_stats", 0, false);
      std::vector<unsigned char> b(t.nbytes); if (t.nbytes) pread_all(fd, b.data(), t.nbytes, t.offset);
@@ -393,6 +396,7 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    for (size_t i = 0; i < stats.size(); i++) { stats[i].newton_iters = r_stats[4 * i]; stats[i].krylov_iters = r_stats[4 * i + 1]; stats[i].model_calls = r_stats[4 * i + 2]; stats[i].converged = r_stats[4 * i + 3] != 0; }
    avg_stress.swap(r_stress); avg_def_grad.swap(r_F); avg_pl_work.swap(r_pw); avg_dp_tensor.swap(r_dp);
    lattice_rows_.swap(r_ls); volume_rows_.swap(r_lv); auto_dt_rows_.swap(r_dt);
+   macro_tangent_rows.swap(r_mt);
    { auto& cyc = pvd_cycles_[vis_dir()]; cyc.clear(); for (size_t i = 0; i + 1 < r_cyc.size(); i += 2) cyc.emplace_back((int)r_cyc[i], r_cyc[i + 1]); if (cyc.empty()) pvd_cycles_.erase(vis_dir()); }
    op.model_calls = (int)h.model_calls; op.SetCapState(h.newton_cap, h.newton_cap2);
    // the essential-boundary set in force, without the SolveInit that belongs to the step where it changed
@@ -407,6 +411,7 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
          rewrite_rows(out_dir + "/" + opt_.avg_dp_tensor_fname, avg_dp_tensor, 6);
       }
       if (opt_.lightup()) { rewrite_rows(out_dir + "/" + opt_.lightup_strain_fname, lattice_rows_, H); rewrite_rows(out_dir + "/" + opt_.lightup_volume_fname, volume_rows_, H); }
+      if (opt_.macro_tangent) write_macro_tangent_rows(out_dir + "/" + opt_.macro_tangent_fname, macro_tangent_rows, false);
       if (opt_.dt_auto) { std::ofstream f(out_dir + "/" + opt_.auto_dt_fname, std::ios_base::trunc); for (double v : auto_dt_rows_) f << std::setprecision(12) << v << std::endl; }
    }
    restarted_ = true; ckpt_foreign_calls_ = (long)op.model_calls;

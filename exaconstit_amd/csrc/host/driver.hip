@@ -29,6 +29,7 @@ extern "C" int exa_grad_apply_lvec_blocks(exa_ctx* ctx, const double* x, double*
 int exa_grad_refresh_bbar(exa_ctx* ctx, const double* J, hipStream_t s);   // gen_kernels.hip (driver-internal)
 int exa_tet_set_fused_action(exa_ctx* ctx, int on);                        // tet_kernels.hip (driver-internal)
 extern "C" int exa_grad_apply_lvec_gated(exa_ctx* ctx, const double* x, double* y, const uint8_t* mask, const double* gate, exa_stream s);
+extern "C" int exa_grad_apply_lvec_cols_w(exa_ctx* ctx, int nch, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, exa_stream s);
 
 
 namespace exa_host {
@@ -914,6 +915,27 @@ void NonlinearMechOperator::GradMultLocal(const double* x, double* y) {
    vk_mask_zero(nd_, ess_mask.p, y, stream_);
 }
 
+// y = this rank's element contributions of K x as they stand: no expansion, no sum over images or ranks, no output mask
+void NonlinearMechOperator::GradMultRaw(const double* x, double* y, const uint8_t* in_mask) {
+   EXA_HC(hipMemsetAsync(y, 0, sizeof(double) * nd_, stream_));
+   if (lvec_grad_) { abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, in_mask, nullptr, stream_), "exa_grad_apply_lvec"); return; }
+   EXA_HC(hipMemcpyAsync(tmp_l_.p, x, sizeof(double) * nd_, hipMemcpyDeviceToDevice, stream_));
+   if (in_mask) vk_mask_zero(nd_, in_mask, tmp_l_.p, stream_);
+   abi_check(ctx_, exa_restrict(ctx_, tmp_l_.p, el_x2_.p, stream_), "exa_restrict");
+   el_y_.zero(stream_);
+   abi_check(ctx_, exa_grad_apply(ctx_, el_x2_.p, el_y_.p, stream_), "exa_grad_apply");
+   abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
+}
+
+// the raw action on nc columns in one call (exa_grad_apply_lvec_cols): false when the context has no such kernel - y is then untouched
+bool NonlinearMechOperator::GradMultRawCols(int nch, int nc, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* in_mask, const double* const* gates) {
+   if (!lvec_grad_) return false;
+   const int rc = exa_grad_apply_lvec_cols_w(ctx_, nch, nc, x, ldx, y, ldy, in_mask, gates, stream_);
+   if (rc == EXA_ERR_UNSUPPORTED) return false;
+   abi_check(ctx_, rc, "exa_grad_apply_lvec_cols");
+   return true;
+}
+
 void NonlinearMechOperator::GradMult(const double* x, double* y, bool constrained, const double* done_flag, bool y_prezeroed, bool skip_out_mask) {
    if (!y_prezeroed) vk_fill_if(nd_, done_flag, 0.0, y, stream_);
    if (lvec_grad_ && overlap_) {
@@ -1636,6 +1658,7 @@ bool SystemDriver::Step(int ti, bool commit) {
    time += dt_real; dt_class = dt_real;
    op.SetDt(dt_real);
    stats.emplace_back();
+   step_solved_ = false;
    const auto wall0 = std::chrono::steady_clock::now();   // reference: t1 = MPI_Wtime() ... times[ti - 1] = t2 - t1 (src/mechanics_driver.cpp:865,891-892)
    hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s));
    for (const BCEntry& bc : opt_.bcs) if (bc.step == ti) {
@@ -1655,12 +1678,13 @@ bool SystemDriver::Step(int ti, bool commit) {
    step_wall_s.push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count());
    if (!ok) return false;
    if (mixed_) MixedStepEnd();
+   step_solved_ = true;
    if (!commit) return true;   // the converged state stays the END-of-step state: the next constitutive pass repeats this step's last residual evaluation
    CommitStep();
    // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
    // per-grain averages and texture on the same cadence, whether or not ParaView output is on
    bool due = false;
-   if ((opt_.paraview || opt_.grain_avgs || opt_.texture) && write_files) {
+   if ((opt_.paraview || opt_.grain_avgs || opt_.texture || opt_.macro_tangent) && write_files) {
       bool last = ti >= opt_.nsteps;
       if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
       due = last || ti % opt_.vis_steps == 0;
@@ -1671,6 +1695,7 @@ bool SystemDriver::Step(int ti, bool commit) {
    if (save || lattice || grains || texture) ComputeElementFields();
    if (save) SaveFields(vis_dir(), ti, time, true);
    if (texture) WriteTexture(ti, time);
+   if (opt_.macro_tangent && due) WriteMacroTangent(ti);
    if (grains) {
       std::vector<int32_t> ids; std::vector<double> vals;
       GrainAverages(ids, vals, true);

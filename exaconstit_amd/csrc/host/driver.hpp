@@ -77,6 +77,21 @@ void write_texture(const std::string& path, int step, double t, double res_deg, 
 enum class Precond { IDENTITY, JACOBI, MULTIGRID };
 class Multigrid;
 
+// macroscopic tangent of a periodic cell: T[9 (3 k + l) + m] / V = d sigma_bar_kl / d L_bar_m, m = 3 i + j the entry (i, j) of L_bar
+struct MacroTangentResult {
+   double T[81]; double V = 0.0, dt = 0.0;
+   int iters[9]; int flag[9];                       // per column: PCG iterations, the solver's flag (1 converged, 2 max_iter, -1 breakdown)
+   double reduction[9], b_norm[9], res_norm[9];     // the solver's own reduction sqrt((r, M^-1 r) / (r0, M^-1 r0)); |b_m|, |b_m - K_uu w_m| recomputed by one more action
+   double w_over_a[9];                              // max |w_m| / max |a_m|: size of the fluctuation against the affine field
+   int batched = 0, nch = 0;                        // route taken: nine columns in lockstep through the multi-column action (nch columns per pass), or one by one
+};
+// C_pp - C_pf C_ff^-1 C_fp of the 9 x 9 c[9 (kl) + (mn)] for the free mask (row by row): out81 holds it in the prescribed rows / columns and zeros in
+// the free ones; false when C_ff is singular.  Host code.
+bool macro_tangent_condense(const double* c81, const uint8_t* free9, double* out81);
+// one row (step, time, dt, V, 81 values of d sigma_bar / d L_bar, 17 significant digits) per evaluation
+void write_macro_tangent_rows(const std::string& path, const std::vector<double>& rows, bool append);
+constexpr int MACRO_TANGENT_ROW = 85;
+
 struct SolverStats { int newton_iters = 0; int krylov_iters = 0; int model_calls = 0; bool converged = false; };
 
 struct Timers {
@@ -129,6 +144,14 @@ class NonlinearMechOperator {
    void GradMult(const double* x, double* y, bool constrained, const double* done_flag = nullptr, bool y_prezeroed = false, bool skip_out_mask = false);
    // this rank's part of the constrained action (no halo exchange): what the multigrid hierarchy probes (host/multigrid.hpp)
    void GradMultLocal(const double* x, double* y);
+   // macroscopic tangent (host/tangent.hip): the element contributions of K x as they stand - no expansion, no sum over images or
+   // ranks, no output mask; in_mask (nullable): entries of x read as zero
+   void GradMultRaw(const double* x, double* y, const uint8_t* in_mask = nullptr);
+   // ... of nc columns at once, ADDED into y, nch columns per pass over the records (0: the library's default); gates: one device flag per column
+   // (nullable).  false: the context has no multi-column kernel (y untouched) and the caller goes column by column
+   bool GradMultRawCols(int nch, int nc, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* in_mask, const double* const* gates);
+   uint32_t MixedFree() const { return mix_tab_.free_bits; }
+   bool deterministic() const { return comm_.deterministic; }
    // reference src/mechanics_operator.cpp:446-483
    void GetUpdateBCsAction(const double* k, const double* x, double* y);
    void ResidualAction(double* y);
@@ -257,6 +280,21 @@ class SystemDriver {
    double last_cg_reduction = 0.0, worst_capped_cg_reduction = 0.0;   // |r|_M / |r0|_M of the last PCG solve / the worst among the solves that stopped at max_iter
    void drop_cg_graph();                      // forget the captured PCG chunk (its solution buffer is about to go away)
    void report_cg(const double* hS, int iters) const;   // MFEM CGSolver::Mult diagnostics (verbose / EXA_VERBOSE)
+   // Homogenised tangent d sigma_bar / d L_bar of the last solved step of a periodic cell (host/tangent.hip), every rank calls it.
+   // rel_tol / max_iter <= 0: the Krylov options.  batched: -1 the automatic route, 0 column by column through CGSolve, 1 the nine columns in
+   // lockstep through the multi-column action (one rank, non-deterministic mode, a context exa_grad_apply_lvec_cols serves; refused elsewhere).
+   // Refuses a driver that is not periodic or has no step solved in this process.  Leaves the run as it found it.
+   void MacroTangent(double rel_tol, int max_iter, int batched, MacroTangentResult& out);
+   // nc <= 16 systems K_uu x_m = b_m in lockstep: recurrence and stopping test of CGSolve with one scalar block per column, the multi-column action
+   // in the middle; B, X: columns at stride ld.  No graph capture, no consumer-side reductions; touches neither scal nor the timers.
+   void CGSolveColumns(int nc, const double* B, double* X, int64_t ld, double rel_tol, int max_iter, int nch, int* iters, double* reduction, int* flag);
+   // probe of the operator (exa_driver_grad_apply_columns): y_m = K x_m for nc host columns of local dofs (byNODES).  assembled: the operator of the
+   // tangent's solves (periodic and rank sums, the run's essential set plus the control slots, input and output); otherwise the raw element action.
+   // gated (nullable): columns with a non-zero entry are left out - their y stays as passed in.
+   void GradApplyColumns(int nc, const double* x, double* y, bool assembled, bool batched, const int* gated);
+   int tangent_nch = 0;                 // columns per pass of the multi-column action (0: the library's default; EXA_TANGENT_NCH)
+   bool tangent_auto_batched = true;    // what batched = -1 picks where the batched route is available (EXA_TANGENT_BATCHED=0 | 1)
+   std::vector<double> macro_tangent_rows;   // Visualizations.macro_tangent: MACRO_TANGENT_ROW values per written evaluation
    NonlinearMechOperator& oper() { return *oper_; }
    const ExaOptions& options() const { return opt_; }
    std::vector<double> avg_stress, avg_def_grad, avg_pl_work, avg_dp_tensor;   // one row per completed step (rank 0 view, all ranks identical)
@@ -327,6 +365,10 @@ class SystemDriver {
    void set_free(const uint8_t* f);
    int bc_index_ = -1;                          // index in opt_.bcs of the essential-boundary entry in force
    bool restarted_ = false;
+   bool step_solved_ = false;                   // the last Step of this process converged and no constitutive launch has run since (MacroTangent)
+   DevBuf<double> tangent_x_;                   // the one solution buffer of the column-by-column tangent solves
+   struct TangentScope;                         // host/tangent.hip: the essential set of the tangent's solves and everything an evaluation puts back
+   void WriteMacroTangent(int step);
    // shared-node copies of a checkpoint written on another rank count (host/checkpoint.hip): carried along untouched and written back as long as
    // no constitutive launch has run since the load, so that load + save reproduces the file on any rank count
    std::vector<unsigned char> ckpt_foreign_copies_[2]; long ckpt_foreign_calls_ = -1;

@@ -275,6 +275,62 @@ int exa_driver_macro_info(exa_driver* d, int* free9, double* vel_grad9, double* 
    } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_macro_info: %s\n", e.what()); return -1; }
 }
 
+// Homogenised tangent of the last solved step of a periodic cell.  rel_tol / max_iter <= 0: the Krylov options; batched: -1 automatic
+// route, 0 column by column, 1 the batched multi-column route.  dsig81[9 (3 k + l) + (3 m + n)] = d sigma_bar_kl / d L_bar_mn; out2 = { V, dt };
+// info (9 x 6, may be NULL): per column { iterations, solver flag, the solver's own reduction, |b|, |b - K_uu w| recomputed, max |w| / max |a| };
+// route2 (may be NULL) = { batched (0 / 1), columns per pass }.  Every rank calls it.  Returns 0 or -1 (err).
+int exa_driver_macro_tangent(exa_driver* d, double rel_tol, int max_iter, int batched, double* dsig81, double* out2, double* info, int* route2, char* err, int errlen) {
+   try {
+      MacroTangentResult r;
+      d->sd->MacroTangent(rel_tol, max_iter, batched, r);
+      for (int k = 0; k < 81; k++) dsig81[k] = r.T[k] / r.V;
+      out2[0] = r.V; out2[1] = r.dt;
+      if (info) for (int m = 0; m < 9; m++) {
+         info[6 * m] = r.iters[m]; info[6 * m + 1] = r.flag[m]; info[6 * m + 2] = r.reduction[m]; info[6 * m + 3] = r.b_norm[m]; info[6 * m + 4] = r.res_norm[m]; info[6 * m + 5] = r.w_over_a[m];
+      }
+      if (route2) { route2[0] = r.batched; route2[1] = r.nch; }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// Probe of the operator behind the tangent, in the spirit of exa_driver_mg_apply: y_m = K x_m for ncols <= 16 host columns of local dofs (byNODES: dof =
+// node + local nodes * component, column m at m * local dofs).  flags bit 0: assembled and masked (the operator K_uu of the tangent's solves) instead of
+// the raw element action; bit 1: batched (exa_grad_apply_lvec_cols) instead of one by one.  gated (may be NULL): columns with a non-zero entry are left
+// out and keep the y passed in.  nch: columns per pass of the batched route for this and later calls (0: leave as is).  Needs a solved step.
+int exa_driver_grad_apply_columns(exa_driver* d, int ncols, const double* x, double* y, int flags, const int* gated, int nch, char* err, int errlen) {
+   try {
+      if (nch < 0 || nch > 3) throw std::runtime_error("grad_apply_columns: 1, 2 or 3 columns per pass");
+      if (nch > 0) d->sd->tangent_nch = nch;
+      d->sd->GradApplyColumns(ncols, x, y, (flags & 1) != 0, (flags & 2) != 0, gated);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+// columns per pass of the batched route (1 .. 3; 0: the library's default) and what the automatic route picks where both exist (batched != 0)
+int exa_driver_set_tangent_route(exa_driver* d, int nch, int auto_batched) {
+   if (nch < 0 || nch > 3) return -1;
+   d->sd->tangent_nch = nch; d->sd->tangent_auto_batched = auto_batched != 0;
+   return 0;
+}
+
+// host only: C_pp - C_pf C_ff^-1 C_fp of c81[9 (kl) + (mn)] for the free mask free9 (row by row); out81: the condensed tangent in the prescribed rows /
+// columns, zeros in the free ones.  Returns 0, or -1 when C_ff is singular.
+int exa_macro_tangent_condense(const double* c81, const int* free9, double* out81) {
+   uint8_t f[9]; for (int k = 0; k < 9; k++) f[k] = free9 && free9[k] ? 1 : 0;
+   return macro_tangent_condense(c81, f, out81) ? 0 : -1;
+}
+
+// [Visualizations] macro_tangent keys of an options file: out2 = { macro_tangent (0 / 1), macro_tangent_max_iter (0: the Krylov value) },
+// rel_tol (0: the Krylov value), fname
+int exa_options_macro_tangent(const char* toml_path, int* out2, double* rel_tol, char* fname, int fnamelen, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      out2[0] = o.macro_tangent ? 1 : 0; out2[1] = o.macro_tangent_max_iter; *rel_tol = o.macro_tangent_rel_tol;
+      if (fname && fnamelen > 0) { if ((int)o.macro_tangent_fname.size() >= fnamelen) throw std::runtime_error("Visualizations.macro_tangent_fname longer than the buffer"); std::strcpy(fname, o.macro_tangent_fname.c_str()); }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
 // out8 = { periodic (0 / 1), local groups of 2 / 4 / 8 images, canonical ids exchanged with other ranks (summed over the neighbours), neighbours, 0, 0 };
 // vel_grad9 = the macroscopic velocity gradient in force (zeros when not periodic)
 int exa_driver_periodic_info(exa_driver* d, int64_t* out8, double* vel_grad9) {

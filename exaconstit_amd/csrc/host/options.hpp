@@ -145,6 +145,11 @@ struct ExaOptions {
    // to <out_dir>/<texture_fname>_<step %06d>.txt
    bool texture = false; std::vector<int> texture_hkl = { 1, 1, 1, 2, 0, 0, 2, 2, 0 }; std::vector<double> texture_dirs = { 0, 0, 1 };
    double texture_res_deg = 5.0; std::string texture_fname = "texture";
+   // macroscopic tangent (host/tangent.hip, SystemDriver::MacroTangent): d sigma_bar / d L_bar of the converged step of a periodic cell,
+   // one row (step, time, dt, V, 81 values with 17 significant digits) appended to <out_dir>/<macro_tangent_fname> every Visualizations.steps steps
+   // and at the last step.  rel_tol / max_iter of its nine solves: 0 = the Solvers.Krylov values
+   bool macro_tangent = false; std::string macro_tangent_fname = "macro_tangent.txt"; double macro_tangent_rel_tol = 0.0; int macro_tangent_max_iter = 0;
+   static const char* macro_tangent_needs_periodic() { return "Visualizations.macro_tangent = true needs BCs.periodic = true: the homogenised tangent is that of a periodic cell"; }
    // the checks of the texture keys, shared with exa_driver_pole_figures (hkl: 3 integers per family, dirs: 3 components per direction,
    // normalised in place; the driver takes 0 families as long as there is a direction)
    static void check_texture(const std::vector<int>& hkl, std::vector<double>& dirs, double res_deg, bool need_hkl = true) {
@@ -355,6 +360,23 @@ struct ExaOptions {
          texture_fname = f->str;
       }
       check_texture(texture_hkl, texture_dirs, texture_res_deg);
+      if (const TomlValue* t = d.get("Visualizations.macro_tangent")) {
+         if (t->kind != TomlValue::BOOL) throw std::runtime_error("Visualizations.macro_tangent must be true or false");
+         macro_tangent = t->b;
+      }
+      if (const TomlValue* f = d.get("Visualizations.macro_tangent_fname")) {
+         if (f->kind != TomlValue::STR || f->str.empty() || f->str.find('/') != std::string::npos)
+            throw std::runtime_error("Visualizations.macro_tangent_fname must be a non-empty file name without '/'");
+         macro_tangent_fname = f->str;
+      }
+      if (const TomlValue* r = d.get("Visualizations.macro_tangent_rel_tol")) {
+         if (r->kind != TomlValue::NUM || !(r->num > 0.0) || !(r->num < 1.0)) throw std::runtime_error("Visualizations.macro_tangent_rel_tol must be a number in (0, 1)");
+         macro_tangent_rel_tol = r->num;
+      }
+      if (const TomlValue* v = d.get("Visualizations.macro_tangent_max_iter")) {
+         if (v->kind != TomlValue::NUM || v->num != std::floor(v->num) || v->num < 1 || v->num > 1e9) throw std::runtime_error("Visualizations.macro_tangent_max_iter must be a whole number of at least 1");
+         macro_tangent_max_iter = (int)v->num;
+      }
       if (const TomlValue* w = d.get("Checkpoint.write")) {
          if (w->kind != TomlValue::BOOL) throw std::runtime_error("Checkpoint.write must be true or false");
          ckpt_write = w->b;
@@ -409,6 +431,7 @@ struct ExaOptions {
       } else throw std::runtime_error("Mesh.type must be \"auto\", \"other\" or \"cubit\"");
       if (order < 1 || order > 6) throw std::runtime_error("p_refinement must be between 1 and 6");
       if (periodic && mesh_type != "auto") throw std::runtime_error(periodic_needs_generated_mesh());
+      if (macro_tangent && !periodic) throw std::runtime_error(macro_tangent_needs_periodic());
       if (const TomlValue* pc = d.get("Solvers.Krylov.preconditioner")) {
          const std::string k = pc->kind == TomlValue::STR ? lower(pc->str) : std::string("?");
          if (k == "jacobi") precond = 1;

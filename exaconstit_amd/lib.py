@@ -408,6 +408,14 @@ exa_options_query_periodic_free = _sig("exa_options_query_periodic_free", C.c_in
 exa_partition_query_periodic_mixed = _sig("exa_partition_query_periodic_mixed", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 
+exa_driver_macro_tangent = _sig("exa_driver_macro_tangent", C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int), C.c_char_p, C.c_int)
+exa_driver_grad_apply_columns = _sig("exa_driver_grad_apply_columns", C.c_int, C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_int)
+exa_driver_set_tangent_route = _sig("exa_driver_set_tangent_route", C.c_int, C.c_void_p, C.c_int, C.c_int)
+exa_macro_tangent_condense = _sig("exa_macro_tangent_condense", C.c_int, _dp, C.POINTER(C.c_int), _dp)
+exa_options_macro_tangent = _sig("exa_options_macro_tangent", C.c_int, C.c_char_p, C.POINTER(C.c_int), _dp, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
+exa_tangent_scratch_bytes = _sig("exa_tangent_scratch_bytes", C.c_int, C.POINTER(C.c_int))
+exa_grad_apply_lvec_cols = _sig("exa_grad_apply_lvec_cols", C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p)
+
 PRECOND_KINDS = {"identity": 0, "jacobi": 1, "multigrid": 2}
 NODAL_FIELDS = {"velocity": 0, "coords": 1, "coords_ref": 2}
 
@@ -472,6 +480,79 @@ def partition_periodic(N, rank, nranks, order=1):
         off += nc[i]
     return dict(NN=NN, canon=canon, weight=w, nbrs=nbrs, groups=[gn[go[g]:go[g + 1]].copy() for g in range(ng)],
                 group_sizes={2: int(info[5]), 4: int(info[6]), 8: int(info[7])})
+
+
+# ---- macroscopic tangent of a periodic cell ----------------------------------------------------------------------------------
+VOIGT_PAIRS = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))   # the driver's stress order 11, 22, 33, 23, 13, 12
+
+
+def macro_tangent_voigt(dsig_dL, dt):
+    """The 6 x 6 stiffness per strain increment of a (3, 3, 3, 3) tangent d sigma_kl / d L_mn: row I = stress component VOIGT_PAIRS[I], column J = the
+    symmetric unit strain of VOIGT_PAIRS[J] (a unit ENGINEERING shear for the off-diagonal pairs: L_mn = L_nm = 1/2), divided by the dt factor
+    the operator carries."""
+    import numpy as np
+    t = np.asarray(dsig_dL, dtype=np.float64).reshape(3, 3, 3, 3)
+    c = np.zeros((6, 6))
+    for i, (k, l) in enumerate(VOIGT_PAIRS):
+        for j, (m, n) in enumerate(VOIGT_PAIRS):
+            c[i, j] = 0.5 * (t[k, l, m, n] + t[k, l, n, m]) / dt
+    return c
+
+
+def condense_macro_tangent(dsig_dL, free):
+    """Host code: the condensed tangent C_pp - C_pf C_ff^-1 C_fp of the prescribed entries of a mixed run with the (3, 3) free mask, as a
+    (3, 3, 3, 3) array with zeros in the free rows and columns."""
+    import numpy as np
+    c = np.ascontiguousarray(np.asarray(dsig_dL, dtype=np.float64).reshape(81))
+    f = (C.c_int * 9)(*[int(bool(v)) for v in np.asarray(free).reshape(9)])
+    out = np.zeros(81)
+    if exa_macro_tangent_condense(c.ctypes.data_as(_dp), f, out.ctypes.data_as(_dp)) != 0:
+        raise RuntimeError("condense_macro_tangent: the block of the free entries is singular")
+    return out.reshape(3, 3, 3, 3)
+
+
+def options_macro_tangent(path):
+    """macro_tangent keys of the Visualizations table: dict(enabled, fname, rel_tol, max_iter); rel_tol / max_iter None = the Solvers.Krylov values"""
+    o = (C.c_int * 2)()
+    rel = C.c_double()
+    f = C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_macro_tangent(path.encode(), o, C.byref(rel), f, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(enabled=bool(o[0]), fname=f.value.decode(), rel_tol=rel.value if rel.value > 0 else None, max_iter=int(o[1]) if o[1] > 0 else None)
+
+
+def write_macro_tangent(path, rows, append=False):
+    """rows of (step, time, dt, V, dsig_dL (3, 3, 3, 3)) in the layout of the driver's macro_tangent file (17 significant digits)"""
+    import numpy as np
+    with open(path, "a" if append else "w") as f:
+        for step, t, dt, V, c in rows:
+            f.write(" ".join([str(int(step))] + ["%.17g" % v for v in (t, dt, V)] + ["%.17g" % v for v in np.asarray(c, dtype=np.float64).reshape(81)]) + "\n")
+
+
+def read_macro_tangent(path):
+    """a macro_tangent file of the driver: list of dict(step, time, dt, V, dsig_dL (3, 3, 3, 3), C_voigt (6, 6)), one per row"""
+    import numpy as np
+    out = []
+    with open(path) as f:
+        for ln in f:
+            if not ln.strip() or ln.startswith("#"):
+                continue
+            v = ln.split()
+            if len(v) != 85:
+                raise ValueError(f"{path}: a row holds step, time, dt, V and 81 values, not {len(v)} entries")
+            c = np.array([float(x) for x in v[4:]]).reshape(3, 3, 3, 3)
+            dt = float(v[2])
+            out.append(dict(step=int(v[0]), time=float(v[1]), dt=dt, V=float(v[3]), dsig_dL=c, C_voigt=macro_tangent_voigt(c, dt)))
+    return out
+
+
+def tangent_scratch_bytes():
+    """private (scratch) bytes per lane of the tangent's kernels in the loaded code object: dict(cols1, cols2, cols3, affine, contract9, contract1, combine)"""
+    o = (C.c_int * 8)()
+    if exa_tangent_scratch_bytes(o) != 0:
+        raise RuntimeError("exa_tangent_scratch_bytes: no device")
+    return dict(zip(("cols1", "cols2", "cols3", "affine", "contract9", "contract1", "combine"), [int(v) for v in o[:7]]))
 
 
 def options_solver(path):
@@ -913,6 +994,49 @@ class Driver:
         if exa_driver_macro_info(self.h, f, L.ctypes.data_as(_dp), A.ctypes.data_as(_dp), F.ctypes.data_as(_dp)) < 0:
             raise RuntimeError("exa_driver_macro_info failed")
         return dict(free=np.array(list(f), dtype=bool).reshape(3, 3), vel_grad=L.reshape(3, 3), period=A.reshape(3, 3), resultants=F.reshape(3, 3))
+
+    def macro_tangent(self, rel_tol=None, max_iter=None, batched=None):
+        """Homogenised tangent of the last solved step of a periodic cell; every rank calls it.  rel_tol / max_iter None: the Krylov
+        options; batched None: the automatic route, False: column by column, True: the nine columns in lockstep through the multi-column action.
+        dict(dsig_dL (3, 3, 3, 3) = d sigma_kl / d L_mn, C_voigt (6, 6) per strain increment in the order 11, 22, 33, 23, 13, 12 with engineering
+        shears, V, dt, iters (9,), flags (9,), reduction (9,) the solver's own, b_norm (9,), true_residual (9,) |b - K_uu w| recomputed by one more
+        action, true_rel (9,) their ratio, w_over_a (9,), batched, nch; on a mixed run also free (3, 3) and condensed (3, 3, 3, 3))"""
+        import numpy as np
+        c, o2, info = np.zeros(81), np.zeros(2), np.zeros((9, 6))
+        route = (C.c_int * 2)()
+        self._chk(exa_driver_macro_tangent(self.h, 0.0 if rel_tol is None else float(rel_tol), 0 if max_iter is None else int(max_iter),
+                                           -1 if batched is None else int(bool(batched)), c.ctypes.data_as(_dp), o2.ctypes.data_as(_dp), info.ctypes.data_as(_dp), route,
+                                           self._err, 512))
+        c = c.reshape(3, 3, 3, 3)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rel = np.where(info[:, 3] > 0, info[:, 4] / info[:, 3], 0.0)
+        out = dict(dsig_dL=c, C_voigt=macro_tangent_voigt(c, o2[1]), V=float(o2[0]), dt=float(o2[1]), iters=info[:, 0].astype(int), flags=info[:, 1].astype(int),
+                   reduction=info[:, 2].copy(), b_norm=info[:, 3].copy(), true_residual=info[:, 4].copy(), true_rel=rel, w_over_a=info[:, 5].copy(),
+                   batched=bool(route[0]), nch=int(route[1]))
+        mi = self.macro_info()
+        if mi["free"].any():
+            out["free"] = mi["free"]
+            out["condensed"] = condense_macro_tangent(c, mi["free"])
+        return out
+
+    def grad_apply_columns(self, x, assembled=False, batched=False, gated=None, y0=None, nch=0):
+        """Probe of the operator behind the tangent: x (ncols, local dofs) with dof = node + local nodes * component -> K x, same shape.  assembled:
+        the operator K_uu of the tangent's solves instead of the raw element action.  batched: the multi-column action instead of one column at a
+        time.  gated (ncols,) bool: those columns are left out and keep y0.  nch: columns per pass of the batched route from now on (0: unchanged)."""
+        import numpy as np
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        if x.shape[1] != exa_driver_local_dofs(self.h) or not 1 <= x.shape[0] <= 16:
+            raise RuntimeError("grad_apply_columns: x holds 1 to 16 columns of %d local dofs" % exa_driver_local_dofs(self.h))
+        y = np.zeros_like(x) if y0 is None else np.ascontiguousarray(y0, dtype=np.float64).copy()
+        if y.shape != x.shape:
+            raise ValueError("grad_apply_columns: y0 must have the shape of x")
+        g = None if gated is None else (C.c_int * x.shape[0])(*[int(bool(v)) for v in gated])
+        self._chk(exa_driver_grad_apply_columns(self.h, x.shape[0], x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), (1 if assembled else 0) | (2 if batched else 0), g, int(nch),
+                                                self._err, 512))
+        return y
+
+    def set_tangent_route(self, nch=0, auto_batched=True):
+        assert exa_driver_set_tangent_route(self.h, int(nch), int(bool(auto_batched))) == 0
 
     def periodic_info(self):
         """dict(enabled, groups {2: n, 4: n, 8: n} local periodic groups by image count, shared: canonical ids exchanged with other ranks,

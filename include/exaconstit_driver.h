@@ -193,6 +193,28 @@ int exa_driver_set_periodic_mixed(exa_driver* d, const double* vel_grad9, const 
  * that step (column d = a_d, row by row); resultants9 = the face resultants F_id of the last converged residual (row by row, summed over the
  * ranks).  Returns 1 with mixed loading on, 0 without it (all outputs zero), -1 on error. */
 int exa_driver_macro_info(exa_driver* d, int* free9, double* vel_grad9, double* period9, double* resultants9);
+/* Homogenised tangent d sigma_bar / d L_bar of the last solved step of a periodic cell: nine fluctuation solves with the operator, the
+ * periodic sum and the PCG of the step, then dsig81[9 (3 k + l) + (3 m + n)] = d sigma_bar_kl / d L_bar_mn by Hill-Mandel.  rel_tol / max_iter <= 0:
+ * the Krylov options.  batched: -1 the automatic route, 0 column by column, 1 the nine columns in lockstep through exa_grad_apply_lvec_cols (one
+ * rank, non-deterministic mode, p = 1 hexahedron L-vector record action; refused elsewhere).  out2 = { current cell volume V, dt }.  info (9 x 6,
+ * may be NULL): per column { PCG iterations, solver flag (1 converged, 2 max_iter, -1 breakdown), the solver's own reduction, |b_m|, the TRUE residual
+ * |b_m - K_uu w_m| recomputed by one more action, max |w_m| / max |a_m| }.  route2 (may be NULL) = { batched, columns per pass }.  Refused: a driver
+ * that is not periodic; a driver without a step solved in this process (a freshly restarted one included).  The run is left as it was: essential
+ * mask, PCG scalars and captured graph, records, timers, Newton cap state, statistics.  Every rank calls it.  Returns 0 or -1 (err). */
+int exa_driver_macro_tangent(exa_driver* d, double rel_tol, int max_iter, int batched, double* dsig81, double* out2, double* info, int* route2, char* err, int errlen);
+/* Probe of the operator behind the tangent (cf. exa_driver_mg_apply): y_m = K x_m for ncols <= 16 host columns of local dofs, byNODES (dof = node +
+ * local nodes * component), column m at m * local dofs.  flags bit 0: assembled and masked - the operator K_uu of the tangent's solves (periodic and
+ * rank sums; the run's essential set plus the control slots) - instead of the raw element action; bit 1: batched instead of one by one.  gated (may
+ * be NULL): columns with a non-zero entry are left out and keep the y passed in.  nch: 1 .. 3 columns per pass of the batched route from now on
+ * (0: unchanged).  Needs a solved step. */
+int exa_driver_grad_apply_columns(exa_driver* d, int ncols, const double* x, double* y, int flags, const int* gated, int nch, char* err, int errlen);
+/* columns per pass of the batched route (1 .. 3, 0: the default) and whether the automatic route takes it where it exists */
+int exa_driver_set_tangent_route(exa_driver* d, int nch, int auto_batched);
+/* host only: the condensed tangent of the prescribed entries, C_pp - C_pf C_ff^-1 C_fp, of the 9 x 9 c81[9 (kl) + (mn)] for the free mask of a mixed
+ * run (row by row); zeros in the free rows and columns.  0, or -1 when C_ff is singular. */
+int exa_macro_tangent_condense(const double* c81, const int* free9, double* out81);
+/* [Visualizations] macro_tangent, macro_tangent_max_iter -> out2; macro_tangent_rel_tol; macro_tangent_fname (0: the Solvers.Krylov value) */
+int exa_options_macro_tangent(const char* toml_path, int* out2, double* rel_tol, char* fname, int fnamelen, char* err, int errlen);
 /* private (scratch) bytes per lane of k_periodic_expand and k_face_resultants in the loaded code object: out2; returns 0, or -1 without a device */
 int exa_periodic_mixed_scratch_bytes(int* out2);
 /* out8 = { periodic (0 / 1), local periodic groups of 2, of 4, of 8 images, canonical ids exchanged with other ranks, neighbours, 0, 0 };

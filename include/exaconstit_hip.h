@@ -253,6 +253,20 @@ int exa_restrict_transpose_add(exa_ctx* ctx, const double* evec_dev, double* lve
 /* fused gather / apply / scatter-add of the gradient action on L-vectors (the PCG inner kernel): y_L += K x_L.
  * mask_dev (nullable, 3*nnodes bytes): essential dofs — x is read as 0 there (spec src/mechanics_operator_ext.cpp:143-146). */
 int exa_grad_apply_lvec(exa_ctx* ctx, const double* x_lvec_dev, double* y_lvec_dev, const uint8_t* mask_dev, exa_stream s);
+/* The same action on `ncols` (1 .. EXA_GRAD_COLS_MAX) column vectors in one call: column k reads x_dev + k ldx and adds into y_dev + k ldy
+ * (ldx, ldy in doubles, >= 3 nnodes).  The record of a point is loaded once per pass and applied to up to three columns, so the record
+ * stream - most of what the action moves - is shared among them; every column's result is what exa_grad_apply_lvec gives for it, up to the
+ * order of the atomic addends, whatever the other columns are.  mask_dev as above (one mask for all columns).  gates (host array of ncols
+ * device pointers; the array and every entry may be NULL): a non-zero double at gates[k] leaves column k out - it is neither read nor
+ * written.  Built for ONE configuration: hexahedra at p = 1 full integration with nodal coordinates named (exa_grad_set_coords), partial
+ * assembly or element assembly from the point records, atomic scatter.  Every other context - p >= 2, tetrahedra, B-bar, assembled element
+ * matrices, deterministic mode, no coordinates - returns EXA_ERR_UNSUPPORTED without touching y: loop exa_grad_apply_lvec there. */
+enum { EXA_GRAD_COLS_MAX = 16, EXA_GRAD_COLS_DEFAULT = 3 };
+int exa_grad_apply_lvec_cols(exa_ctx* ctx, int ncols, const double* x_dev, int64_t ldx, double* y_dev, int64_t ldy, const uint8_t* mask_dev,
+                             const double* const* gates, exa_stream s);
+/* private (scratch) bytes per lane of the kernels behind exa_grad_apply_lvec_cols and the macroscopic tangent in the loaded code object:
+ * out8 = { column action at 1, 2, 3 columns per pass, affine columns, contraction (9 columns, 1 column), its combine, 0 }; 0, or -1 without a device */
+int exa_tangent_scratch_bytes(int* out8);
 /* Optional (p = 1 partial assembly, L-vector action): the nodal coordinates (nnodes,3 byNODES) the Jacobians given to exa_grad_setup
  * were computed from.  When set, exa_grad_apply_lvec recomputes adj(J) from them instead of streaming it from its per-point record
  * (36 instead of 46 doubles per point from HBM); the array must stay unchanged until the next exa_grad_setup.  NULL switches it off. */
