@@ -1684,7 +1684,7 @@ bool SystemDriver::Step(int ti, bool commit) {
    // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
    // per-grain averages and texture on the same cadence, whether or not ParaView output is on
    bool due = false;
-   if ((opt_.paraview || opt_.grain_avgs || opt_.texture || opt_.macro_tangent) && write_files) {
+   if ((opt_.paraview || opt_.grain_avgs || opt_.texture || opt_.macro_tangent || opt_.lattice_curvature) && write_files) {
       bool last = ti >= opt_.nsteps;
       if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
       due = last || ti % opt_.vis_steps == 0;
@@ -1692,8 +1692,11 @@ bool SystemDriver::Step(int ti, bool commit) {
    const bool save = opt_.paraview && due, grains = opt_.grain_avgs && due, texture = opt_.texture && due;
    // light-up analysis: one row of lattice strains and one of fibre volume fractions per converged step, from the same element rows
    const bool lattice = opt_.lightup() && write_files;
-   if (save || lattice || grains || texture) ComputeElementFields();
-   if (save) SaveFields(vis_dir(), ti, time, true);
+   const bool curvature = opt_.lattice_curvature && due;
+   if (save || lattice || grains || texture || curvature) ComputeElementFields();
+   std::vector<double> curv_rows;
+   if (curvature) { double m[7]; LatticeCurvature(opt_.lattice_curvature_burgers, curv_rows, m, true, save); WriteLatticeCurvature(ti, m); }
+   if (save) SaveFields(vis_dir(), ti, time, true, curvature ? &curv_rows : nullptr);
    if (texture) WriteTexture(ti, time);
    if (opt_.macro_tangent && due) WriteMacroTangent(ti);
    if (grains) {
@@ -1812,8 +1815,32 @@ void SystemDriver::EnsureGrainPlan() {
    grain_work_.alloc((size_t)std::max<int64_t>(work, 1));
    grain_sums_.alloc((size_t)G * EXA_GRAIN_NSUMS);
    grain_quat_dev_.alloc((size_t)4 * G);
+   grain_attr_dev_.upload(elem_attr, s);   // the map itself, for the analyses that take it element by element (LatticeCurvature)
    grain_G_ = G;
    grain_plan_ = std::move(plan);
+}
+
+void SystemDriver::GrainMeans(std::vector<double>& h, std::vector<double>& qbar, double& vtot) {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   exa_ctx* ctx = op.GetModel()->ctx();
+   const int G = grain_G_; constexpr int K = EXA_GRAIN_NSUMS;
+   // pass 1: the 39 sums of every grain; elements are not shared across ranks, grains are
+   grain_quat_dev_.upload(grain_qref_.data(), (size_t)4 * G, s);
+   grain_sums_.zero(s);
+   abi_check(ctx, exa_grain_sums(ctx, 1, fields_dev_.p, grain_plan_.data(), grain_plan_dev_.p, G, grain_quat_dev_.p, grain_work_.p, grain_sums_.p, s), "exa_grain_sums");
+   comm.allreduce_sum(grain_sums_.p, G * K, s);
+   h.resize((size_t)G * K); grain_sums_.download(h.data(), h.size(), s);
+   // the grain means, identical on every rank
+   qbar.assign(grain_qref_.begin(), grain_qref_.begin() + 4 * (size_t)G);
+   vtot = 0.0;
+   for (int g = 0; g < G; g++) {
+      const double* r = &h[(size_t)g * K];
+      if (!(r[1] > 0.0)) continue;
+      vtot += r[0];
+      const double n = std::sqrt(r[35] * r[35] + r[36] * r[36] + r[37] * r[37] + r[38] * r[38]);
+      if (n > 0.0) for (int k = 0; k < 4; k++) qbar[4 * (size_t)g + k] = r[35 + k] / n;
+   }
 }
 
 void SystemDriver::GrainAverages(std::vector<int32_t>& ids, std::vector<double>& vals, bool fields_current) {
@@ -1823,22 +1850,8 @@ void SystemDriver::GrainAverages(std::vector<int32_t>& ids, std::vector<double>&
    EnsureGrainPlan();
    const int G = grain_G_; constexpr int K = EXA_GRAIN_NSUMS;
    if (!fields_current) ComputeElementFields();
-   // pass 1: the 39 sums of every grain; elements are not shared across ranks, grains are
-   grain_quat_dev_.upload(grain_qref_.data(), (size_t)4 * G, s);
-   grain_sums_.zero(s);
-   abi_check(ctx, exa_grain_sums(ctx, 1, fields_dev_.p, grain_plan_.data(), grain_plan_dev_.p, G, grain_quat_dev_.p, grain_work_.p, grain_sums_.p, s), "exa_grain_sums");
-   comm.allreduce_sum(grain_sums_.p, G * K, s);
-   std::vector<double> h((size_t)G * K); grain_sums_.download(h.data(), h.size(), s);
-   // the grain means, identical on every rank
-   std::vector<double> qbar(grain_qref_.begin(), grain_qref_.begin() + 4 * (size_t)G);
-   double vtot = 0.0;
-   for (int g = 0; g < G; g++) {
-      const double* r = &h[(size_t)g * K];
-      if (!(r[1] > 0.0)) continue;
-      vtot += r[0];
-      const double n = std::sqrt(r[35] * r[35] + r[36] * r[36] + r[37] * r[37] + r[38] * r[38]);
-      if (n > 0.0) for (int k = 0; k < 4; k++) qbar[4 * (size_t)g + k] = r[35 + k] / n;
-   }
+   std::vector<double> h, qbar; double vtot = 0.0;
+   GrainMeans(h, qbar, vtot);
    // pass 2: sum V theta and max theta about the means
    grain_quat_dev_.upload(qbar.data(), (size_t)4 * G, s);
    EXA_HC(hipMemsetAsync(grain_sums_.p, 0, sizeof(double) * 2 * G, s));
@@ -1866,6 +1879,58 @@ void SystemDriver::GrainAverages(std::vector<int32_t>& ids, std::vector<double>&
       ids.push_back(g + 1);
       vals.insert(vals.end(), o, o + GRAIN_NVALS);
    }
+}
+
+// element rows -> grain means (pass 1 of the grain sums) -> per-element rotation vectors and their nodal sums -> the sum over the
+// copies of a node, on the path every assembled L-vector takes (periodic images, then ranks; segment by segment in deterministic mode) ->
+// curvature rows -> summary
+void SystemDriver::LatticeCurvature(double burgers, std::vector<double>& rows, double* summary7, bool fields_current, bool want_rows) {
+   if (!(burgers > 0.0) || !std::isfinite(burgers)) throw std::runtime_error("lattice curvature: the Burgers vector length must be a finite number > 0");
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   exa_ctx* ctx = op.GetModel()->ctx();
+   EnsureGrainPlan();
+   const int G = grain_G_;
+   if (!fields_current) ComputeElementFields();
+   std::vector<double> h, qbar; double vtot = 0.0;
+   GrainMeans(h, qbar, vtot);
+   grain_quat_dev_.upload(qbar.data(), (size_t)4 * G, s);
+   int64_t work = 0; int planes = 0;
+   exa_curvature_sizes(part.E, &work, &planes);
+   const size_t nn = (size_t)part.NN;
+   if (curv_work_.n != (size_t)std::max<int64_t>(work, 1)) curv_work_.alloc((size_t)std::max<int64_t>(work, 1));
+   if (curv_nodal_.n != (size_t)planes * nn) curv_nodal_.alloc((size_t)planes * nn);
+   if (curv_rows_.n != (size_t)EXA_NCURV * part.E) curv_rows_.alloc((size_t)EXA_NCURV * part.E);
+   if (curv_sum_.n < 7) curv_sum_.alloc(7);
+   if (curv_xe_.n != (size_t)3 * part.n * part.E) curv_xe_.alloc((size_t)3 * part.n * part.E);
+   DevBuf<double>& xe = curv_xe_;
+   abi_check(ctx, exa_restrict(ctx, op.x_cur.p, xe.p, s), "exa_restrict");
+   abi_check(ctx, exa_curvature_nodal(ctx, fields_dev_.p, grain_attr_dev_.p, G, grain_quat_dev_.p, curv_work_.p, curv_nodal_.p, s), "exa_curvature_nodal");
+   for (int t = 0; t < planes / 3; t++) op.SumLVector(curv_nodal_.p + (size_t)3 * nn * t, nullptr, false);
+   abi_check(ctx, exa_curvature_elements(ctx, fields_dev_.p, grain_attr_dev_.p, G, grain_quat_dev_.p, curv_work_.p, curv_nodal_.p, xe.p, burgers, curv_rows_.p, s),
+             "exa_curvature_elements");
+   abi_check(ctx, exa_curvature_summary(ctx, fields_dev_.p, curv_rows_.p, curv_sum_.p, s), "exa_curvature_summary");
+   comm.allreduce_sum(curv_sum_.p, 4, s);   // elements are not shared across ranks
+   comm.allreduce_max(curv_sum_.p + 4, 3, s);
+   double t7[7]; curv_sum_.download(t7, 7, s);
+   rows.resize(want_rows ? (size_t)EXA_NCURV * part.E : 0);
+   if (!rows.empty()) curv_rows_.download(rows.data(), rows.size(), s);
+   const double iv = 1.0 / t7[0];
+   for (int k = 0; k < 3; k++) { summary7[2 * k] = t7[1 + k] * iv; summary7[2 * k + 1] = t7[4 + k]; }
+   summary7[6] = t7[0];
+}
+
+void SystemDriver::WriteLatticeCurvature(int step, const double* m) {
+   if (comm.rank != 0) return;
+   const std::string path = out_dir + "/" + opt_.lattice_curvature_fname;
+   bool fresh = true;
+   { std::ifstream g(path); fresh = !g || g.peek() == std::ifstream::traits_type::eof(); }
+   std::ofstream f(path, std::ios_base::app);   // a restarted run goes on in the file it finds
+   if (!f) throw std::runtime_error("lattice curvature: cannot write " + path);
+   if (fresh) f << "# step time grod_mean_deg grod_max_deg kam_mean_deg kam_max_deg gnd_density_mean gnd_density_max\n";
+   f << std::setprecision(17) << step << ' ' << time;
+   for (int k = 0; k < 6; k++) f << ' ' << m[k];
+   f << '\n';
 }
 
 void SystemDriver::SetGrains(const int32_t* grain, int64_t n_global, const double* grain_quats, int G) {
@@ -1994,15 +2059,18 @@ void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const 
    if (!f) throw std::runtime_error("grain averages: writing " + path + " failed");
 }
 
-void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool fields_current) {
+void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool fields_current, const std::vector<double>* curv) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
    if (!fields_current) ComputeElementFields();
+   std::vector<double> curv_own;
+   if (opt_.lattice_curvature && !curv) { double m[7]; LatticeCurvature(opt_.lattice_curvature_burgers, curv_own, m, true); curv = &curv_own; }
    const std::vector<double> fields = fields_dev_.to_host(s);
    const std::vector<double> xc = op.x_cur.to_host(s), xr = op.x_ref.to_host(s), v = v_sol.to_host(s);
    vtu::Piece p;
    p.E = part.E; p.NN = part.NN; p.n = part.n; p.tet = part.geom == 1; p.conn = part.conn.data();
    p.x_cur = xc.data(); p.x_ref = xr.data(); p.vel = v.data(); p.fields = fields.data(); p.attr = elem_attr.data(); p.gid = part.elem_gid.data();
+   if (opt_.lattice_curvature) { p.has_curv = true; p.curv = curv->data(); }
    vtu::save_cycle(dir, comm.rank, comm.nranks, cycle, t, opt_.light_up, p, pvd_cycles_[dir]);
 }
 

@@ -317,13 +317,19 @@ class SystemDriver {
    void ComputeElementFields();
    // ParaView save of those fields as cycle `cycle` at time t under dir (host/vtu.hpp); every rank calls it.  fields_current: fields_dev_
    // already holds the rows of this state (computed once for both the save and the lattice strains of a step)
-   void SaveFields(const std::string& dir, int cycle, double t, bool fields_current = false);
+   // curv ([E][EXA_NCURV], Visualizations.lattice_curvature only): the rows of LatticeCurvature of this state; computed here when null
+   void SaveFields(const std::string& dir, int cycle, double t, bool fields_current = false, const std::vector<double>* curv = nullptr);
    // lattice strains of the {hkl} families (3 integers each; options.hpp check_lightup) of the same state, summed over all ranks (every rank calls
    // it): strain[j] = volume-weighted mean of s^T eps s over the elements of fibre j (NaN when the fibre is empty), volfrac[j] = its volume fraction
    void LatticeStrains(const std::vector<int>& hkl, const double s_dir[3], double tol_deg, double* strain, double* volfrac, bool fields_current = false);
    // per-grain averages of the same state over all ranks (every rank calls it): ids = the ascending 1-based ids of the grains with
    // elements, vals = GRAIN_NVALS values per grain (the value columns of the grain_avgs files, write_grain_avgs)
    void GrainAverages(std::vector<int32_t>& ids, std::vector<double>& vals, bool fields_current = false);
+   // intragranular misorientation and lattice curvature of the same state (every rank calls it): rows = [E][EXA_NCURV] of the local
+   // elements (exa_curvature_elements; burgers: Burgers vector length in the mesh's length unit), summary7 = over all ranks the volume-weighted
+   // means of GROD, KAM and the GND density, their maxima and the total volume: { mean GROD, max GROD, mean KAM, max KAM, mean GND, max GND, V }
+   // want_rows = false: the summary alone (rows is left empty and the [E][EXA_NCURV] copy to the host is skipped)
+   void LatticeCurvature(double burgers, std::vector<double>& rows, double* summary7, bool fields_current = false, bool want_rows = true);
    // grain map of a synthetic driver before its first step: grain (1..G) of every global element and the orientation of every grain (normalised
    // here); the elements' initial orientations and states become their grain's
    void SetGrains(const int32_t* grain_of_global_elem, int64_t n_global, const double* grain_quats, int G);
@@ -357,6 +363,12 @@ class SystemDriver {
    // plan of exa_grain_sums for elem_attr (built on first use, dropped by SetGrains), its device copy and workspace; G = largest grain id over all ranks
    std::vector<int32_t> grain_plan_; DevBuf<int32_t> grain_plan_dev_; DevBuf<double> grain_work_, grain_sums_, grain_quat_dev_; int grain_G_ = 0;
    void EnsureGrainPlan();
+   // pass 1 of exa_grain_sums on fields_dev_, all-reduced: h = [G][EXA_GRAIN_NSUMS], qbar = the unit grain means (the reference orientation of a grain
+   // without elements), vtot = the volume of all grains
+   void GrainMeans(std::vector<double>& h, std::vector<double>& qbar, double& vtot);
+   DevBuf<int32_t> grain_attr_dev_;   // elem_attr on the device, uploaded with the grain plan
+   DevBuf<double> curv_work_, curv_nodal_, curv_rows_, curv_sum_, curv_xe_;   // LatticeCurvature: records, nodal planes, rows, 7 sums, current coordinates as an E-vector
+   void WriteLatticeCurvature(int step, const double* summary7);
    bool texture0_written_ = false;
    // rows that exist only in append-mode files otherwise (checkpoint host sections): light-up strains / volume fractions, accepted dt of Time.Auto
    std::vector<double> lattice_rows_, volume_rows_, auto_dt_rows_;

@@ -838,6 +838,34 @@ int exa_driver_grain_averages(exa_driver* d, int32_t* grain_ids, double* vals, i
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+int exa_driver_lattice_curvature(exa_driver* d, double burgers, double* out, int64_t* elem_gid, int32_t* attribute, double* summary7, char* err, int errlen) {
+   try {
+      SystemDriver& sd = *d->sd;
+      if (out || summary7) {
+         std::vector<double> rows; double m[7];
+         sd.LatticeCurvature(burgers, rows, m);
+         if (out) std::memcpy(out, rows.data(), sizeof(double) * rows.size());
+         if (summary7) std::memcpy(summary7, m, sizeof(m));
+      }
+      if (elem_gid) std::memcpy(elem_gid, sd.part.elem_gid.data(), sizeof(int64_t) * sd.part.E);
+      if (attribute) std::memcpy(attribute, sd.elem_attr.data(), sizeof(int32_t) * sd.part.E);
+      return sd.part.E;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_options_query_lattice_curvature(const char* toml_path, int* enabled, double* burgers, char* fname, int fnamelen, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      if (enabled) *enabled = o.lattice_curvature ? 1 : 0;
+      if (burgers) *burgers = o.lattice_curvature_burgers;
+      if (fname && fnamelen > 0) {
+         if ((int)o.lattice_curvature_fname.size() >= fnamelen) throw std::runtime_error("Visualizations.lattice_curvature_fname longer than the buffer");
+         std::strcpy(fname, o.lattice_curvature_fname.c_str());
+      }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
 int exa_driver_set_grains(exa_driver* d, const int32_t* grain_of_global_element, const double* grain_quats, int G, int64_t n_global, char* err, int errlen) {
    try {
       d->sd->SetGrains(grain_of_global_element, n_global, grain_quats, G);

@@ -149,6 +149,10 @@ struct ExaOptions {
    // one row (step, time, dt, V, 81 values with 17 significant digits) appended to <out_dir>/<macro_tangent_fname> every Visualizations.steps steps
    // and at the last step.  rel_tol / max_iter of its nine solves: 0 = the Solvers.Krylov values
    bool macro_tangent = false; std::string macro_tangent_fname = "macro_tangent.txt"; double macro_tangent_rel_tol = 0.0; int macro_tangent_max_iter = 0;
+   // intragranular misorientation and lattice curvature (driver.hip, SystemDriver::LatticeCurvature): one row (step, time, mean and
+   // max of GROD, KAM and the GND density, 17 significant digits) appended to <out_dir>/<lattice_curvature_fname> every Visualizations.steps steps and
+   // at the last step, and four more cell arrays in the ParaView pieces; lattice_curvature_burgers: Burgers vector length in the mesh's length unit
+   bool lattice_curvature = false; double lattice_curvature_burgers = 1.0; std::string lattice_curvature_fname = "lattice_curvature.txt";
    static const char* macro_tangent_needs_periodic() { return "Visualizations.macro_tangent = true needs BCs.periodic = true: the homogenised tangent is that of a periodic cell"; }
    // the checks of the texture keys, shared with exa_driver_pole_figures (hkl: 3 integers per family, dirs: 3 components per direction,
    // normalised in place; the driver takes 0 families as long as there is a direction)
@@ -368,6 +372,19 @@ struct ExaOptions {
          if (f->kind != TomlValue::STR || f->str.empty() || f->str.find('/') != std::string::npos)
             throw std::runtime_error("Visualizations.macro_tangent_fname must be a non-empty file name without '/'");
          macro_tangent_fname = f->str;
+      }
+      if (const TomlValue* t = d.get("Visualizations.lattice_curvature")) {
+         if (t->kind != TomlValue::BOOL) throw std::runtime_error("Visualizations.lattice_curvature must be true or false");
+         lattice_curvature = t->b;
+      }
+      if (const TomlValue* b = d.get("Visualizations.lattice_curvature_burgers")) {
+         if (b->kind != TomlValue::NUM || !(b->num > 0.0) || !std::isfinite(b->num)) throw std::runtime_error("Visualizations.lattice_curvature_burgers must be a number > 0");
+         lattice_curvature_burgers = b->num;
+      }
+      if (const TomlValue* f = d.get("Visualizations.lattice_curvature_fname")) {
+         if (f->kind != TomlValue::STR || f->str.empty() || f->str.find('/') != std::string::npos)
+            throw std::runtime_error("Visualizations.lattice_curvature_fname must be a non-empty file name without '/'");
+         lattice_curvature_fname = f->str;
       }
       if (const TomlValue* r = d.get("Visualizations.macro_tangent_rel_tol")) {
          if (r->kind != TomlValue::NUM || !(r->num > 0.0) || !(r->num < 1.0)) throw std::runtime_error("Visualizations.macro_tangent_rel_tol must be a number in (0, 1)");

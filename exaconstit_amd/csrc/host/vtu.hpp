@@ -78,6 +78,7 @@ struct Piece {
    const double* vel = nullptr;                                   // byNODES (NN, 3)
    const double* fields = nullptr;                                // [E][EXA_NFIELDS] (exa_element_fields)
    const int32_t* attr = nullptr; const int64_t* gid = nullptr;   // grain id (element attribute), global element index
+   bool has_curv = false; const double* curv = nullptr;           // Visualizations.lattice_curvature: [E][EXA_NCURV] (exa_curvature_elements)
 };
 
 // the cell arrays of a save, in the order of the reference's RegisterField calls (ElemCentroid and XtalElasticStrain only with light_up)
@@ -96,6 +97,11 @@ inline std::vector<Array> cell_arrays(const Piece& p, bool light_up) {
    a.push_back(col("Hardness", EXA_F_HARDNESS, 1));
    a.push_back(Array{ "attribute", T::I32, 1, p.attr, 4, 0 });
    a.push_back(Array{ "GlobalElementId", T::I64, 1, p.gid, 8, 0 });
+   if (p.has_curv) {
+      auto ccol = [&](const char* nm, int c0, int nc) { return Array{ nm, T::F64, nc, p.curv + c0, 8 * EXA_NCURV, 8 }; };
+      a.push_back(ccol("GROD", EXA_C_GROD, 1)); a.push_back(ccol("KAM", EXA_C_KAM, 1)); a.push_back(ccol("GNDDensity", EXA_C_GND, 1));
+      a.push_back(ccol("LatticeCurvature", EXA_C_CURVATURE, 9));
+   }
    return a;
 }
 
@@ -138,14 +144,14 @@ inline void write_piece(const std::string& path, const Piece& p, bool light_up) 
    if (!o) throw std::runtime_error("write failed: " + path);
 }
 
-inline void write_pvtu(const std::string& path, int nranks, bool light_up) {
+inline void write_pvtu(const std::string& path, int nranks, bool light_up, bool has_curv = false) {
    std::ofstream o(path);
    if (!o) throw std::runtime_error("cannot write " + path);
    o << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"" << (is_little() ? "LittleEndian" : "BigEndian") << "\" header_type=\"UInt32\">\n"
      << "  <PUnstructuredGrid GhostLevel=\"0\">\n    <PPoints>\n      <PDataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\"/>\n    </PPoints>\n"
      << "    <PPointData>\n      <PDataArray type=\"Float64\" Name=\"Displacement\" NumberOfComponents=\"3\"/>\n"
      << "      <PDataArray type=\"Float64\" Name=\"Velocity\" NumberOfComponents=\"3\"/>\n    </PPointData>\n    <PCellData>\n";
-   Piece none;
+   Piece none; none.has_curv = has_curv;
    for (const Array& a : cell_arrays(none, light_up)) {
       o << "      <PDataArray type=\"" << type_name(a.type) << "\" Name=\"" << a.name << "\"";
       if (a.ncomp > 1) o << " NumberOfComponents=\"" << a.ncomp << "\"";
@@ -180,7 +186,7 @@ inline void save_cycle(const std::string& floc, int rank, int nranks, int cycle,
    mkdir_p(dir);
    write_piece(dir + "/" + piece_name(rank), p, light_up);
    if (rank != 0) return;
-   write_pvtu(dir + "/data.pvtu", nranks, light_up);
+   write_pvtu(dir + "/data.pvtu", nranks, light_up, p.has_curv);
    bool found = false;
    for (auto& c : cycles) if (c.first == cycle) { c.second = t; found = true; }
    if (!found) cycles.emplace_back(cycle, t);

@@ -291,6 +291,55 @@ def read_grain_avgs(path):
     return grain_dict(np.rint(a[:, 0]).astype(np.int64), a[:, 1:])
 
 
+# intragranular misorientation and lattice curvature (include/exaconstit_hip.h)
+exa_curvature_nodal = _sig("exa_curvature_nodal", C.c_int, C.c_void_p, dptr, C.c_void_p, C.c_int, dptr, dptr, dptr, C.c_void_p)
+exa_curvature_elements = _sig("exa_curvature_elements", C.c_int, C.c_void_p, dptr, C.c_void_p, C.c_int, dptr, dptr, dptr, dptr, C.c_double, dptr, C.c_void_p)
+exa_curvature_summary = _sig("exa_curvature_summary", C.c_int, C.c_void_p, dptr, dptr, dptr, C.c_void_p)
+exa_curvature_sizes = _sig("exa_curvature_sizes", C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int))
+exa_driver_lattice_curvature = _sig("exa_driver_lattice_curvature", C.c_int, C.c_void_p, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_double), C.c_char_p, C.c_int)
+exa_options_query_lattice_curvature = _sig("exa_options_query_lattice_curvature", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_char_p, C.c_int,
+                                           C.c_char_p, C.c_int)
+EXA_NCURV = 16
+# columns of the rows of exa_curvature_elements / exa_driver_lattice_curvature: name -> (first, count)
+CURVATURE_COLUMNS = {"RotationVector": (0, 3), "GROD": (3, 1), "KAM": (4, 1), "LatticeCurvature": (5, 9), "NyeNorm": (14, 1), "GNDDensity": (15, 1)}
+# the values of "summary" (Driver.lattice_curvature) and, after step and time, the columns of the lattice_curvature file
+CURVATURE_SUMMARY = ("GROD_mean", "GROD_max", "KAM_mean", "KAM_max", "GNDDensity_mean", "GNDDensity_max")
+
+
+def curvature_sizes(E):
+    """(doubles of work_dev for E elements, planes of nodal_dev) of exa_curvature_nodal (host only)"""
+    w, pl = C.c_int64(), C.c_int()
+    if exa_curvature_sizes(int(E), C.byref(w), C.byref(pl)) != 0:
+        raise ValueError(f"E = {E} must not be negative")
+    return w.value, pl.value
+
+
+def options_lattice_curvature(path):
+    """lattice-curvature keys of the Visualizations table: dict(enabled, burgers, fname)"""
+    en, b = C.c_int(), C.c_double()
+    f = C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_query_lattice_curvature(path.encode(), C.byref(en), C.byref(b), f, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(enabled=bool(en.value), burgers=b.value, fname=f.value.decode())
+
+
+def read_lattice_curvature(path):
+    """a lattice_curvature file of the driver: dict(step (n,) int64, time (n,), and (n,) per CURVATURE_SUMMARY name), one entry per written step"""
+    import numpy as np
+    with open(path) as f:
+        head = f.readline().split()
+    names = ["step", "time", "grod_mean_deg", "grod_max_deg", "kam_mean_deg", "kam_max_deg", "gnd_density_mean", "gnd_density_max"]
+    if head != ["#"] + names:
+        raise ValueError(f"{path}: not a lattice_curvature file (header {head})")
+    a = np.loadtxt(path, ndmin=2).reshape(-1, len(names))
+    out = {"step": np.rint(a[:, 0]).astype(np.int64), "time": a[:, 1].copy()}
+    for k, nm in enumerate(CURVATURE_SUMMARY):
+        out[nm] = a[:, 2 + k].copy()
+    return out
+
+
 exa_driver_pole_figures = _sig("exa_driver_pole_figures", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.c_double,
                                C.POINTER(C.c_double), C.c_char_p, C.c_int)
 exa_options_query_texture = _sig("exa_options_query_texture", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -912,6 +961,26 @@ class Driver:
             if n <= cap:
                 return grain_dict(ids[:n], vals[:n])
             cap = self._grain_cap = n
+
+    def lattice_curvature(self, burgers=1.0):
+        """Intragranular misorientation and lattice curvature of the current begin-of-step state (after a completed step: the
+        converged one); every rank of the group calls it.  Rows of this rank in local element order: {"RotationVector": (E, 3) radians,
+        "GROD": (E,) degrees, "KAM": (E,) degrees, "LatticeCurvature": (E, 9) row-major kappa_ij in radians per length, "NyeNorm": (E,),
+        "GNDDensity": (E,) = NyeNorm / burgers, "GlobalElementId", "attribute"} and "summary": over all ranks the volume-weighted means and
+        the maxima named by CURVATURE_SUMMARY, plus "volume"."""
+        import numpy as np
+        E = self._chk(exa_driver_lattice_curvature(self.h, float(burgers), None, None, None, None, self._err, 512))
+        rows = np.zeros((E, EXA_NCURV))
+        gid = np.zeros(E, np.int64)
+        attr = np.zeros(E, np.int32)
+        m = np.zeros(7)
+        self._chk(exa_driver_lattice_curvature(self.h, float(burgers), rows.ctypes.data_as(C.POINTER(C.c_double)), gid.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               attr.ctypes.data_as(C.POINTER(C.c_int32)), m.ctypes.data_as(C.POINTER(C.c_double)), self._err, 512))
+        out = {k: (rows[:, c0].copy() if n == 1 else rows[:, c0:c0 + n].copy()) for k, (c0, n) in CURVATURE_COLUMNS.items()}
+        out["GlobalElementId"] = gid
+        out["attribute"] = attr
+        out["summary"] = dict(zip(CURVATURE_SUMMARY, m[:6].tolist()), volume=float(m[6]))
+        return out
 
     def set_grains(self, grain_ids, quats):
         """Grain map of a synthetic driver before its first step: grain_ids (N^3,) in 1..G by global element index (x fastest), quats (G, 4);

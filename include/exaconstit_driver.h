@@ -167,6 +167,14 @@ int exa_driver_lattice_strains(exa_driver* d, int nhkl, const int* hkl3, const d
  * MisorientationMean, MisorientationMax, GrainRotation (degrees).  Either pointer may be NULL.  Returns n or -1 (err). */
 enum { EXA_GRAIN_NVALS = 45 };
 int exa_driver_grain_averages(exa_driver* d, int32_t* grain_ids, double* vals, int64_t cap, char* err, int errlen);
+/* Intragranular misorientation and lattice curvature of the current begin-of-step state (after a completed step: the converged
+ * one); every rank of the group calls it.  Grains are the element attributes and their means the LatticeOrientation of exa_driver_grain_averages;
+ * the nodal recovery sums over the ranks and, on a periodic cell, over the periodic images of a node.  burgers > 0: Burgers vector length in the
+ * mesh's length unit.  out [E][EXA_NCURV] (column table at exa_curvature_elements, include/exaconstit_hip.h) in the local element order of the
+ * driver, elem_gid [E] and attribute [E] as exa_driver_element_fields; summary7 (all ranks) = { mean GROD, max GROD, mean KAM, max KAM (degrees),
+ * mean GNDDensity, max GNDDensity, total volume }, means weighted by element volume.  Every pointer may be NULL (all NULL: no launch, the row
+ * count only).  Returns E (>= 0) or -1 (err). */
+int exa_driver_lattice_curvature(exa_driver* d, double burgers, double* out, int64_t* elem_gid, int32_t* attribute, double* summary7, char* err, int errlen);
 /* Grain map of a synthetic driver (exa_driver_create_synthetic), before its first step: grain_of_global_element[n_global] in 1..G (n_global =
  * N^3, global element index x fastest) and grain_quats[G][4] (scalar first, normalised here).  Every element's initial orientation and state
  * become its grain's, and the grain's orientation is its reference q_ref.  Every rank of the group calls it with the same map.  Returns 0 or -1 (err). */
@@ -264,6 +272,10 @@ int exa_options_query_lightup(const char* toml_path, int* enabled, int* nhkl, in
 int exa_options_query_texture(const char* toml_path, int* enabled, int* nhkl, int* hkl48, int* ndir, double* dirs9, double* res_deg, char* fname, int fnamelen,
                               char* err, int errlen);
 int exa_options_query_grains(const char* toml_path, int* enabled, char* fname, int fnamelen, char* err, int errlen);
+/* lattice-curvature keys of the Visualizations table: enabled = lattice_curvature (default 0), burgers = lattice_curvature_burgers (1.0; refused
+ * unless > 0), lattice_curvature_fname ("lattice_curvature.txt"; refused if empty or with a '/') into a buffer of fnamelen bytes.  Every pointer
+ * may be NULL.  Returns 0 or -1 (err). */
+int exa_options_query_lattice_curvature(const char* toml_path, int* enabled, double* burgers, char* fname, int fnamelen, char* err, int errlen);
 /* [Checkpoint] table (all keys optional): out3 = { write (default 0), steps (1), keep (2) }, floc (default "checkpoint"), restart_from (default "") */
 int exa_options_query_checkpoint(const char* toml_path, int* out3, char* floc, int floclen, char* restart_from, int restartlen, char* err, int errlen);
 /* the grain_avgs file writer (host only): a '#' header naming the 46 columns, then n rows of grain_ids[i] and vals[i][EXA_GRAIN_NVALS] (the

@@ -394,6 +394,40 @@ int exa_texture_grid(double res_deg, int* n_alpha, int* n_beta);
  * p_y = 0 and p_x < 0); alpha = atan2(sqrt(p_x^2 + p_y^2), p_z), beta = atan2(p_y, p_x) in [0, 360) degrees (0 at the pole);
  * i = min(floor(alpha / res_deg), n_alpha - 1), k = floor(beta / res_deg) mod n_beta.  Returns 0, or -1 for a bad res_deg. */
 int exa_texture_bin(const double* p3, double res_deg, int* i, int* k);
+/* Intragranular misorientation and lattice curvature on the rows of exa_element_fields (fields_dev [E][EXA_NFIELDS], device), for
+ * any context with connectivity (exa_set_connectivity): hexahedra p = 1..6, tetrahedra p = 1, 2, both quadrature layouts.  grain_of_elem_dev [E]
+ * (device, int32) are 1-based grain ids and qbar_dev [G][4] (device) the unit grain means; an id outside 1 .. G takes the identity as its mean.
+ * Per element: delta = s q (x) conj(qbar_g) with s = +-1 so that delta_0 >= 0, omega = 2 atan2(|delta_vec|, delta_0) delta_vec / |delta_vec|
+ * (radians, sample frame; 0 when delta_vec = 0).  The recovery runs over the vertex nodes only (the first 8 / 4 entries of an element's
+ * connectivity).  Three calls, so that the caller can add up the copies of a shared node in between:
+ *   exa_curvature_nodal     writes the per-element record (omega (3), V, g) to work_dev and the sums over the holders of every node to nodal_dev,
+ *                           planar [planes][nnodes]: V omega (3) | V, holder count, sum g_lo | sum g_lo^2, sum g_hi, sum g_hi^2 (g_lo, g_hi the
+ *                           16-bit halves of the id).  Every triple of planes is a byNODES nodal 3-vector: sum it over ranks and periodic images
+ *                           like any assembled L-vector.  The last five planes are integers below 2^53, exact in any summation order.  One lane
+ *                           per node walks the node -> element table of the deterministic E->L sums in its stored order (built, with one
+ *                           device -> host copy of the connectivity, by the first call on a connectivity); no atomics.
+ *   exa_curvature_elements  reads work_dev as exa_curvature_nodal left it (same fields_dev, ids and means: they are not read again) and the summed
+ *                           nodal_dev.  A node is mixed when its holders do not all carry one id: count x sum g^2 != (sum g)^2 for either half.
+ *                           omega~_a = (sum V omega / sum V)_a at an unmixed vertex, the element's own omega at a mixed one;
+ *                           kappa_ij = sum_a omega~_a,i dN_a/dx_j at the centroid, N_a the trilinear / linear vertex functions on the vertex
+ *                           coordinates of xe_dev (current coordinates as an E-vector (n,3,E)); alpha_ij = kappa_ji - delta_ij kappa_kk
+ *                           (elastic-strain gradients neglected).  out_dev [E][EXA_NCURV]: EXA_C_ROTVEC omega (3, radians), EXA_C_GROD |omega|
+ *                           (degrees), EXA_C_KAM mean over the unmixed vertices of |Omega_a - omega| (degrees; 0 without one), EXA_C_CURVATURE
+ *                           kappa row-major (9, radians per length), EXA_C_NYENORM |alpha|_F, EXA_C_GND |alpha|_F / burgers (burgers > 0 in
+ *                           the mesh's length unit).
+ *   exa_curvature_summary   out_dev [7] (device) = local sum V, sum V GROD, sum V KAM, sum V GND, max GROD, max KAM, max GND over the rows curv_dev
+ *                           of exa_curvature_elements (V = EXA_F_VOLUME of fields_dev); partial sums per block in the context's scratch, then
+ *                           one block.
+ * No atomics, fixed summation orders: every call on the same data gives the same bits.  None of them synchronises. */
+enum { EXA_NCURV = 16, EXA_C_ROTVEC = 0, EXA_C_GROD = 3, EXA_C_KAM = 4, EXA_C_CURVATURE = 5 /* 9, row-major kappa_ij */, EXA_C_NYENORM = 14, EXA_C_GND = 15 };
+int exa_curvature_nodal(exa_ctx* ctx, const double* fields_dev, const int32_t* grain_of_elem_dev, int G, const double* qbar_dev, double* work_dev,
+                        double* nodal_dev, exa_stream s);
+int exa_curvature_elements(exa_ctx* ctx, const double* fields_dev, const int32_t* grain_of_elem_dev, int G, const double* qbar_dev, const double* work_dev,
+                           const double* nodal_dev, const double* xe_dev, double burgers, double* out_dev, exa_stream s);
+int exa_curvature_summary(exa_ctx* ctx, const double* fields_dev, const double* curv_dev, double* out_dev /* 7 */, exa_stream s);
+/* host only: doubles of work_dev for E elements and the plane count of nodal_dev (a multiple of 3; nodal_dev holds planes x nnodes doubles);
+ * either output may be NULL.  Returns 0, or EXA_ERR_ARG for E < 0. */
+int exa_curvature_sizes(int64_t E, int64_t* work_doubles, int* nodal_planes);
 /* volume average  sum_q W detJ val / sum_q W detJ  (src/mechanics_kernels.hpp:19-134); out_host[vdim] (+ volume in out_host[vdim]).
  * Synchronises the stream. */
 int exa_vol_avg(exa_ctx* ctx, const double* jacobian_dev, const double* qf_dev, int vdim, int normalise, double* out_host, exa_stream s);
