@@ -52,7 +52,6 @@ void vk_cg_den(double* S, hipStream_t s);
 void vk_cg_beta(double* S, int max_iter, hipStream_t s);
 void vk_cg_step1(int64_t n, int64_t nn, double* S, const double* w, const double* dinv, const double* d, double* x, double* r, double* z, double* partial, bool ident,
                  bool fuse_beta, int max_iter, hipStream_t s, const double* partialD = nullptr);   // partialD: consumer-side reduction of the denominator (vec_kernels.hip)
-void vk_cg_step2(int64_t n, const double* S, const double* z, double* d, hipStream_t s);
 // single-reduction PCG (more than one rank): see vec_kernels.hip
 void vk_cg2_init(double* S, double rel, double abs_, hipStream_t s);
 void vk_cg2_scalars(double* S, int max_iter, hipStream_t s);

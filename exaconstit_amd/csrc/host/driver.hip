@@ -540,7 +540,7 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
    if (!records_setup_) { matGrad.alloc(qf(36)); matGrad.zero(); }   // (allocated on demand if the records route is left, see SetPrecond)
    stress0.zero(); stress1.zero(); matVars1.zero();
    diag.alloc(nd_); dinv.alloc(nd_); tmp_l_.alloc(nd_); tmp_r_.alloc(nd_); el_x2_.alloc(3 * (size_t)npe_ * E_); ess_mask.alloc(nd_); ess_mask.zero();
-   partial.alloc(DOT_BLOCKS * 4); scal.alloc(32); scal.zero();
+   partial.alloc(DOT_BLOCKS * 4); scal.alloc(SCAL_LEN); scal.zero();
    { DevBuf<double> q; q.upload(quats_per_elem); abi_check(ctx_, exa_init_state(ctx_, matVars0.p, q.p, stream_), "exa_init_state"); EXA_HC(hipStreamSynchronize(stream_)); }
    model_.reset(new ExaCMechModel(ctx_, &stress0, &stress1, &matGrad, &matVars0, &matVars1));
    comm_.setup_halo(part);
@@ -982,20 +982,22 @@ void NonlinearMechOperator::GetUpdateBCsAction(const double* k, const double* x,
 }
 
 double NonlinearMechOperator::dot(const double* a, const double* b) {
-   vk_dot(nd_, nn_, weight.p, a, b, nullptr, partial.p, scal.p + 9, stream_);
-   comm_.allreduce_sum(scal.p + 9, 1, stream_);
-   double h; EXA_HC(hipMemcpyAsync(&h, scal.p + 9, sizeof(double), hipMemcpyDeviceToHost, stream_)); EXA_HC(hipStreamSynchronize(stream_));
+   double* sum = scal.p + SCAL_DOT;
+   vk_dot(nd_, nn_, weight.p, a, b, nullptr, partial.p, sum, stream_);
+   comm_.allreduce_sum(sum, 1, stream_);
+   double h; EXA_HC(hipMemcpyAsync(&h, sum, sizeof(double), hipMemcpyDeviceToHost, stream_)); EXA_HC(hipStreamSynchronize(stream_));
    return h;
 }
 
 // ||r|| over all ranks; +inf everywhere if any rank saw an unconverged constitutive point in the launch that produced r
 double NonlinearMechOperator::ResidualNorm(const double* r) {
-   vk_dot(nd_, nn_, weight.p, r, r, nullptr, partial.p, scal.p + 9, stream_);
-   // device side: fail count of the launch that produced r -> scal[15]; a non-zero count turns the local sum into +inf before the all-reduce
-   if (model_status_pending_) vk_poison_if_failed(exa_model_fail_counter_dev(ctx_), scal.p + 9, scal.p + 15, stream_);
-   comm_.allreduce_sum(scal.p + 9, 1, stream_);
-   double h[7]; EXA_HC(hipMemcpyAsync(h, scal.p + 9, sizeof(double) * 7, hipMemcpyDeviceToHost, stream_)); EXA_HC(hipStreamSynchronize(stream_));
-   if (model_status_pending_) { model_fail = (int)h[6]; model_fail_total += model_fail; model_status_pending_ = false; }
+   double* sum = scal.p + SCAL_DOT;
+   vk_dot(nd_, nn_, weight.p, r, r, nullptr, partial.p, sum, stream_);
+   // device side: fail count of the launch that produced r -> SCAL_FAILED; a non-zero count turns the local sum into +inf before the all-reduce
+   if (model_status_pending_) vk_poison_if_failed(exa_model_fail_counter_dev(ctx_), sum, scal.p + SCAL_FAILED, stream_);
+   comm_.allreduce_sum(sum, 1, stream_);
+   double h[SCAL_FAILED - SCAL_DOT + 1]; EXA_HC(hipMemcpyAsync(h, sum, sizeof(h), hipMemcpyDeviceToHost, stream_)); EXA_HC(hipStreamSynchronize(stream_));
+   if (model_status_pending_) { model_fail = (int)h[SCAL_FAILED - SCAL_DOT]; model_fail_total += model_fail; model_status_pending_ = false; }
    FlushModelTimers();   // everything on the stream has finished: no wait
    return std::sqrt(h[0]);
 }
@@ -1037,7 +1039,7 @@ static void load_case_data(const ExaOptions& opt, const Partition& part, std::ve
    }
 }
 
-SystemDriver::~SystemDriver() { drop_cg_graph(); }
+SystemDriver::~SystemDriver() = default;
 
 static void normalise_quats(std::vector<double>& q) {
    for (size_t i = 0; i + 3 < q.size(); i += 4) {
@@ -1092,10 +1094,13 @@ void SystemDriver::init(const std::vector<double>& props, const std::vector<doub
    if (opt_.periodic && opt_.periodic_mixed) set_free(opt_.periodic_free);
    oper_->precond = precond;
    const int nd = oper_->Height();
-   v_sol.alloc(nd); v_sol.zero(); r_.alloc(nd); c_.alloc(nd); xt_.alloc(nd); cg_r_.alloc(nd); cg_z_.alloc(nd); cg_d_.alloc(nd); ess_val_.alloc(nd);
+   v_sol.alloc(nd); v_sol.zero(); r_.alloc(nd); c_.alloc(nd); xt_.alloc(nd); ess_val_.alloc(nd);
    ess_host_.assign(nd, 0); ess_val_host_.assign(nd, 0.0);
    dt_class = opt_.dt;
-   if (const char* g = std::getenv("EXA_PCG_GRAPH")) { if (std::string(g) == "0") cg_graph_max_dofs = 0; else if (std::string(g) == "all") cg_graph_max_dofs = INT64_MAX; }
+   PCGSolver::Settings ks;
+   ks.rel_tol = opt_.krylov_rel; ks.abs_tol = opt_.krylov_abs; ks.max_iter = opt_.krylov_iter;
+   if (const char* g = std::getenv("EXA_PCG_GRAPH")) { if (std::string(g) == "0") ks.graph_max_dofs = 0; else if (std::string(g) == "all") ks.graph_max_dofs = INT64_MAX; }
+   krylov_.reset(new PCGSolver(*oper_, ks));
 }
 
 // BCManager::updateBCData + UpdateEssTDofs; component codes reference src/BCData.cpp:25-116
@@ -1141,7 +1146,7 @@ void SystemDriver::UpdateVelocity(double* v) {
    hipStream_t s = op.stream();
    if (have_vel_) vk_mask_set(op.Height(), vel_mask_.p, ess_val_.p, v, s);
    if (have_vgrad_) {
-      double* org = op.scal.p + 12;
+      double* org = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
       if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
       else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
       vk_vgrad_velocity(part.NN, vg_mask_.p, op.x_cur.p, org, mixed_ ? vgrad_eff_ : vgrad_, v, s);
@@ -1195,7 +1200,7 @@ void SystemDriver::MixedStepStart() {
       double Lold[9], dL[9];
       mul3(Hp, Ai, Lold);
       for (int k = 0; k < 9; k++) dL[k] = vgrad_eff_[k] - Lold[k];
-      double* org = op.scal.p + 12;
+      double* org = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
       if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
       else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
       vk_periodic_affine_add(part.NN, op.x_cur.p, org, dL, v_sol.p, s);
@@ -1206,8 +1211,9 @@ void SystemDriver::MixedStepStart() {
    double org[3];
    if (opt_.vgrad_origin_flag) for (int k = 0; k < 3; k++) org[k] = opt_.vgrad_origin[k];
    else {
-      vk_min3(part.NN, op.x_cur.p, op.partial.p, op.scal.p + 12, s); comm.allreduce_min(op.scal.p + 12, 3, s);
-      EXA_HC(hipMemcpyAsync(org, op.scal.p + 12, 3 * sizeof(double), hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
+      double* org_dev = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
+      vk_min3(part.NN, op.x_cur.p, op.partial.p, org_dev, s); comm.allreduce_min(org_dev, 3, s);
+      EXA_HC(hipMemcpyAsync(org, org_dev, 3 * sizeof(double), hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
    }
    for (int k = 0; k < 3; k++) mac_w0_[k] = cx[k] - org[k];
 }
@@ -1240,246 +1246,10 @@ void SystemDriver::PeriodicBCChange(const BCEntry& bc) {
    bc_index_ = (int)(&bc - opt_.bcs.data());
    UpdateEssBdr(bc);
    if (mixed_) { mix_bc_changed_ = true; return; }   // (MixedStepStart swaps the affine part of the prescribed entries)
-   double* org = op.scal.p + 12;
+   double* org = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
    if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
    else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
    vk_periodic_affine_add(part.NN, op.x_cur.p, org, dL, v_sol.p, s);
-}
-
-// PCG on more than one rank: the Chronopoulos-Gear arrangement of the same recurrence needs ONE fused reduction per iteration - the pair
-// gamma = (r, u), delta = (A u, u) in a single 16-byte all-reduce - instead of the two 8-byte ones of MFEM's loop:
-//    u = M^-1 r,  s = A u,  beta = gamma / gamma_old,  alpha = gamma / (delta - beta gamma / alpha_old),
-//    p = u + beta p,  q = s + beta q (= A p),  x += alpha p,  r -= alpha q.
-// Same iterates in exact arithmetic, same stopping test on (r, M^-1 r) after each update, same iteration cap.  EXA_PCG_TWO_REDUCTIONS=1
-// keeps the two-reduction loop on several ranks (A/B switch).
-int SystemDriver::CGSolveSingleReduction(const double* b, double* x) {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   const int64_t nd = op.Height(), nn = part.NN;
-   double* S = op.scal.p;
-   ProfRegion prof("krylov_solver");
-   if (cg_s_.n < (size_t)nd) { cg_s_.alloc(nd); cg_q_.alloc(nd); }
-   hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s));
-   const bool ident = op.precond == Precond::IDENTITY;
-   EXA_HC(hipMemsetAsync(x, 0, sizeof(double) * nd, s));
-   EXA_HC(hipMemcpyAsync(cg_r_.p, b, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
-   if (!ident) vk_pointwise(nd, op.dinv.p, cg_r_.p, cg_z_.p, s);
-   const double* u = ident ? cg_r_.p : cg_z_.p;
-   EXA_HC(hipMemsetAsync(cg_d_.p, 0, sizeof(double) * nd, s)); EXA_HC(hipMemsetAsync(cg_q_.p, 0, sizeof(double) * nd, s));
-   EXA_HC(hipMemsetAsync(cg_s_.p, 0, sizeof(double) * nd, s));
-   EXA_HC(hipMemsetAsync(S, 0, sizeof(double) * 11, s));
-   op.GradMult(u, cg_s_.p, true, S + 6, true, true);
-   vk_cg2_dots(nd, nn, op.weight.p, op.ess_mask.p, cg_r_.p, cg_z_.p, cg_s_.p, S + 6, op.partial.p, S + 8, ident, s);
-   comm.allreduce_sum(S + 8, 2, s);
-   vk_cg2_init(S, opt_.krylov_rel, opt_.krylov_abs, s);
-   double hS[12]; int launched = 0; bool done = false;
-   while (!done) {
-      for (int k = 0; k < cg_check_every && launched < opt_.krylov_iter; k++, launched++) {
-         vk_cg2_update(nd, S, op.dinv.p, x, cg_r_.p, cg_z_.p, cg_d_.p, cg_s_.p, cg_q_.p, ident, s);
-         op.GradMult(u, cg_s_.p, true, S + 6, true, true);
-         vk_cg2_dots(nd, nn, op.weight.p, op.ess_mask.p, cg_r_.p, cg_z_.p, cg_s_.p, S + 6, op.partial.p, S + 8, ident, s);
-         comm.allreduce_sum(S + 8, 2, s);
-         vk_cg2_scalars(S, opt_.krylov_iter, s);
-      }
-      EXA_HC(hipMemcpyAsync(hS, S, sizeof(double) * 12, hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
-      done = (hS[6] != 0.0) || launched >= opt_.krylov_iter;
-   }
-   EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1));
-   float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e0, e1)); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-   const int iters = (hS[6] == 1.0 && hS[7] == 0.0) ? 0 : (int)hS[7];
-   op.timers.t_krylov_ms += ms; op.timers.krylov_iters += iters;
-   last_cg_flag = (int)hS[6]; cg_indefinite_iters += (int64_t)hS[10];
-   if (hS[6] != 1.0) cg_not_converged++;
-   note_cg_reduction(hS);
-   report_cg(hS, iters);
-   return iters;
-}
-
-// what MFEM prints (CGSolver::Mult): breakdown, indefinite operator, no convergence within max_iter
-void SystemDriver::report_cg(const double* hS, int iters) const {
-   if (comm.rank == 0 && (verbose || std::getenv("EXA_VERBOSE"))) {
-      if (hS[10] > 0.0) std::cerr << "PCG: The operator is not positive definite. (Ad, d) < 0 in " << (int)hS[10] << " iteration(s)\n";
-      if (hS[6] == -1.0) std::cerr << "PCG: (Ad, d) = 0, stopping after " << iters << " iterations\n";
-      else if (hS[6] != 1.0) std::cerr << "PCG: No convergence! (" << iters << " iterations)\n";
-   }
-}
-
-// achieved reduction of the preconditioned residual, sqrt((r, M^-1 r) / (r0, M^-1 r0)): what a solve that stopped at max_iter reached
-void SystemDriver::note_cg_reduction(const double* hS) {
-   last_cg_reduction = (hS[11] > 0.0) ? std::sqrt(std::fmax(hS[2], 0.0) / hS[11]) : 0.0;
-   if (hS[6] != 1.0) worst_capped_cg_reduction = std::max(worst_capped_cg_reduction, last_cg_reduction);
-}
-
-void SystemDriver::drop_cg_graph() {
-   if (cg_graph_) { (void)hipGraphExecDestroy((hipGraphExec_t)cg_graph_); cg_graph_ = nullptr; }
-   cg_graph_x_ = nullptr; cg_graph_key_ = -1;
-}
-
-// device PCG (MFEM CGSolver::Mult with iterative_mode = false); all scalars stay on the device, the host only polls the
-// done-flag every cg_check_every iterations.
-#ifndef EXA_PCG_CONSUMER_REDUCE_MAX_DOFS
-#define EXA_PCG_CONSUMER_REDUCE_MAX_DOFS INT64_MAX   // consumer-side reductions of the PCG scalars up to this many local dofs (EXA_PCG_REDUCE_LAUNCH=1: never, =<n>: up to n)
-#endif
-int SystemDriver::CGSolve(const double* b, double* x) {
-   if (oper_->precond == Precond::MULTIGRID) return CGSolveMG(b, x);
-   if ((comm.nranks > 1 || comm.forced()) && std::getenv("EXA_PCG_TWO_REDUCTIONS") == nullptr) return CGSolveSingleReduction(b, x);
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   const int64_t nd = op.Height(), nn = part.NN;
-   double* S = op.scal.p;
-   ProfRegion prof("krylov_solver");
-   hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s));
-   EXA_HC(hipMemsetAsync(x, 0, sizeof(double) * nd, s));
-   EXA_HC(hipMemcpyAsync(cg_r_.p, b, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
-   vk_pointwise(nd, op.dinv.p, cg_r_.p, cg_z_.p, s);
-   EXA_HC(hipMemcpyAsync(cg_d_.p, cg_z_.p, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
-   EXA_HC(hipMemsetAsync(S, 0, sizeof(double) * 11, s));
-   vk_dot(nd, nn, op.weight.p, cg_d_.p, cg_r_.p, nullptr, op.partial.p, S + 8, s);
-   comm.allreduce_sum(S + 8, 1, s);
-   vk_cg_init(S, opt_.krylov_rel, opt_.krylov_abs, s);
-   const bool fused = std::getenv("EXA_PCG_UNFUSED") == nullptr;   // A/B switch for measurements
-   // Consumer-side reductions (vec_kernels.hip): one rank, fused loop.  An iteration is then four launches instead of six - update / direction / action / masked dot - and
-   // the blocks of the update and direction kernels sum the <= 1024 partial sums themselves.  Same bits as the one-block reduction launches (EXA_PCG_REDUCE_LAUNCH=1).
-   const char* red_env = std::getenv("EXA_PCG_REDUCE_LAUNCH");      // (read per solve: the tests switch it between drivers of one process)
-   const int64_t red_max_dofs = red_env ? (std::atoll(red_env) == 1 ? (int64_t)0 : (int64_t)std::atoll(red_env)) : (int64_t)EXA_PCG_CONSUMER_REDUCE_MAX_DOFS;
-   const bool red = fused && comm.nranks == 1 && !comm.forced() && nd <= red_max_dofs;
-   double* partD = op.partial.p + 2 * DOT_BLOCKS;      // partial sums of the denominator (the (r, z) ones use the front of the buffer)
-   op.GradMult(cg_d_.p, cg_z_.p, true, S + 6);
-   if (red) vk_dot_partial(nd, nn, op.weight.p, cg_z_.p, cg_d_.p, S + 6, partD, s);      // the first update kernel turns them into alpha
-   else {
-      vk_dot(nd, nn, op.weight.p, cg_z_.p, cg_d_.p, S + 6, op.partial.p, S + 8, s);
-      comm.allreduce_sum(S + 8, 1, s);
-      vk_cg_den(S, s);
-   }
-   double hS[18]; int launched = 0; bool done = false;
-   // One rank: the scalar updates ride in the reductions (no all-reduce in between).  (Summing the denominator d.(K d) element-wise
-   // inside the action, with its scatter skipping the essential rows, was measured too: the pass it saves costs what it adds to the
-   // action kernel, +0.8 %.)
-   const bool one = comm.nranks == 1;
-   auto iteration = [&]() {
-      // identity preconditioner + fused loop: z == r is never materialised (the un-fused path reads z in k_cg_step2)
-      const bool ident = fused && op.precond == Precond::IDENTITY;
-      if (red) {
-         vk_cg_step1(nd, nn, S, op.weight.p, op.dinv.p, cg_d_.p, x, cg_r_.p, cg_z_.p, op.partial.p, ident, false, opt_.krylov_iter, s, partD);      // alpha from partD; (r, z) partial sums
-         vk_cg_step2z(nd, S, cg_z_.p, cg_r_.p, cg_d_.p, ident, s, op.partial.p, opt_.krylov_iter);      // beta from them; d = z + beta d; z = 0
-         op.GradMult(cg_d_.p, cg_z_.p, true, S + 6, true, true);
-         vk_mask_dot(nd, nn, op.weight.p, op.ess_mask.p, cg_d_.p, cg_z_.p, S + 6, partD, nullptr, s, nullptr);
-         return;
-      }
-      vk_cg_step1(nd, nn, S, op.weight.p, op.dinv.p, cg_d_.p, x, cg_r_.p, cg_z_.p, op.partial.p, ident, fused && one, opt_.krylov_iter, s);
-      if (!(fused && one)) { comm.allreduce_sum(S + 8, 1, s); vk_cg_beta(S, opt_.krylov_iter, s); }
-      if (fused) {
-         vk_cg_step2z(nd, S, cg_z_.p, cg_r_.p, cg_d_.p, ident, s);      // d = z + beta d; z = 0
-         op.GradMult(cg_d_.p, cg_z_.p, true, S + 6, true, true);       // z += K d (input masked in the kernel, output mask folded into the dot)
-         vk_mask_dot(nd, nn, op.weight.p, op.ess_mask.p, cg_d_.p, cg_z_.p, S + 6, op.partial.p, S + 8, s, one ? S : nullptr);
-         if (!one) { comm.allreduce_sum(S + 8, 1, s); vk_cg_den(S, s); }
-      } else {
-         vk_cg_step2(nd, S, cg_z_.p, cg_d_.p, s);
-         op.GradMult(cg_d_.p, cg_z_.p, true, S + 6);
-         vk_dot(nd, nn, op.weight.p, cg_d_.p, cg_z_.p, S + 6, op.partial.p, S + 8, s);
-         comm.allreduce_sum(S + 8, 1, s);
-         vk_cg_den(S, s);
-      }
-   };
-   // Small systems are launch-bound (16^3: 6 kernels of 2-3 us per iteration): the cg_check_every iterations between two polls of the
-   // done-flag are captured once in a hipGraph and replayed.  Every kernel of an iteration takes its scalars from the device array and is
-   // a no-op once the flag is set or max_iter is reached, so the graph always holds the full chunk.  One rank, fused loop only (no
-   // collective inside the capture); above graph_max_dofs the kernels are long enough to hide their launches (measured).
-   // The capture bakes in every kernel argument: the solution pointer, the preconditioner variant, the iteration cap (an argument of
-   // k_cg_step1 / the reductions) and the chunk length - all of them are part of the key.
-   const int64_t graph_key = ((int64_t)op.precond << 48) ^ ((int64_t)red << 47) ^ ((int64_t)cg_check_every << 32) ^ (int64_t)opt_.krylov_iter;
-   bool use_graph = one && fused && !comm.forced() && nd <= cg_graph_max_dofs && cg_check_every > 1;
-   if (use_graph && (!cg_graph_ || cg_graph_x_ != x || cg_graph_key_ != graph_key)) {
-      drop_cg_graph();
-      // whatever happens between begin and end, the stream must leave capture mode and the graph must not leak
-      hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr; std::string cap_err;
-      EXA_HC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-      try { for (int k = 0; k < cg_check_every; k++) iteration(); } catch (const std::exception& e) { cap_err = e.what(); }
-      const hipError_t ec = hipStreamEndCapture(s, &g);
-      if (cap_err.empty() && ec == hipSuccess && g && hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess) {
-         cg_graph_ = ge; cg_graph_x_ = x; cg_graph_key_ = graph_key;
-      } else {
-         (void)hipGetLastError();   // clear the sticky capture error; the plain launch loop below does the work
-         use_graph = false; cg_graph_max_dofs = 0;
-         if (comm.rank == 0) std::cerr << "PCG: hipGraph capture failed (" << (cap_err.empty() ? "capture/instantiate" : cap_err) << "), using stream launches\n";
-      }
-      if (g) (void)hipGraphDestroy(g);
-   }
-   while (!done) {
-      if (use_graph) { EXA_HC(hipGraphLaunch((hipGraphExec_t)cg_graph_, s)); launched += cg_check_every; }
-      else for (int k = 0; k < cg_check_every && launched < opt_.krylov_iter; k++, launched++) iteration();
-      EXA_HC(hipMemcpyAsync(hS, S, sizeof(double) * 18, hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
-      if (red) hS[7] = hS[17];      // the iteration count travels in S[17] between the direction and the update kernel
-      done = (hS[6] != 0.0) || launched >= opt_.krylov_iter;
-   }
-   EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1));
-   float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e0, e1)); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-   const int iters = (hS[6] == 1.0 && hS[7] == 0.0) ? 0 : (int)hS[7];
-   op.timers.t_krylov_ms += ms; op.timers.krylov_iters += iters;
-   // what MFEM prints (CGSolver::Mult): breakdown, indefinite operator, no convergence within max_iter
-   last_cg_flag = (int)hS[6]; cg_indefinite_iters += (int64_t)hS[10];
-   if (hS[6] != 1.0) cg_not_converged++;
-   note_cg_reduction(hS);
-   report_cg(hS, iters);
-   return iters;
-}
-
-// PCG preconditioned by one multigrid V-cycle per iteration (host/multigrid.hpp): MFEM CGSolver::Mult with iterative_mode = false, its order of
-// operations and stopping test (r, z) <= max(rel^2 (r0, z0), abs^2), on one rank and on several.  The host reads every scalar (the V-cycle
-// synchronises for nothing else); no graph capture.  Fills the same diagnostics as the identity loops.
-int SystemDriver::CGSolveMG(const double* b, double* x) {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   const int64_t nd = op.Height();
-   ProfRegion prof("krylov_solver");
-   if (cg_s_.n < (size_t)nd) { cg_s_.alloc(nd); cg_q_.alloc(nd); }
-   hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s));
-   double* r = cg_r_.p; double* z = cg_z_.p; double* d = cg_d_.p;
-   EXA_HC(hipMemsetAsync(x, 0, sizeof(double) * nd, s));
-   EXA_HC(hipMemcpyAsync(r, b, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
-   op.mg->Apply(r, z);
-   EXA_HC(hipMemcpyAsync(d, z, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
-   double nom0 = op.dot(d, r), nom = nom0, betanom = nom0;
-   // hS: the slots of the device loops' scalar array that report_cg / note_cg_reduction read ([2] (r, z), [6] flag, [7] iterations, [10] (Ad, d) < 0, [11] (r0, z0))
-   double hS[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-   hS[11] = nom0; hS[2] = nom0;
-   int it = 0; double flag = 2.0;
-   const double r0 = std::max(nom0 * opt_.krylov_rel * opt_.krylov_rel, opt_.krylov_abs * opt_.krylov_abs);
-   if (nom0 < 0.0) flag = 2.0;                      // the preconditioner is not positive definite: MFEM stops, not converged
-   else if (nom0 <= r0) flag = 1.0;
-   else {
-      op.GradMult(d, z, true);
-      double den = op.dot(z, d);
-      if (den <= 0.0 && op.dot(d, d) > 0.0) hS[10] += 1.0;
-      if (den == 0.0) flag = -1.0;
-      else
-         for (it = 1; true; it++) {
-            const double alpha = nom / den;
-            vk_axpby(nd, alpha, d, 1.0, x, s);
-            vk_axpby(nd, -alpha, z, 1.0, r, s);
-            op.mg->Apply(r, z);
-            betanom = op.dot(r, z);
-            if (betanom < 0.0) { flag = 2.0; break; }
-            if (betanom <= r0) { flag = 1.0; break; }
-            if (it >= opt_.krylov_iter) { flag = 2.0; break; }
-            const double beta = betanom / nom;
-            vk_axpby(nd, 1.0, z, beta, d, s);      // d = z + beta d
-            op.GradMult(d, z, true);
-            den = op.dot(d, z);
-            if (den <= 0.0 && op.dot(d, d) > 0.0) hS[10] += 1.0;
-            if (den == 0.0) { flag = -1.0; break; }
-            nom = betanom;
-         }
-   }
-   hS[2] = betanom; hS[6] = flag; hS[7] = it;
-   EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1));
-   float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e0, e1)); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-   op.timers.t_krylov_ms += ms; op.timers.krylov_iters += it;
-   last_cg_flag = (int)flag; cg_indefinite_iters += (int64_t)hS[10];
-   if (flag != 1.0) cg_not_converged++;
-   note_cg_reduction(hS);
-   report_cg(hS, it);
-   return it;
 }
 
 void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
@@ -1490,7 +1260,7 @@ void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
       if (ExaOptions::lower(opt_.integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
       op.mg.reset(new Multigrid(op, levels, degree));   // throws where no hierarchy can be built
    } else op.mg.reset();
-   drop_cg_graph();
+   krylov_->DropGraph();
    precond = kind == 0 ? Precond::IDENTITY : (kind == 1 ? Precond::JACOBI : Precond::MULTIGRID);
    op.precond = precond;
 }
@@ -1512,7 +1282,7 @@ void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
    for (int k = 0; k < 9; k++) opt_.periodic_free[k] = any && free9[k] ? 1 : 0;
    set_free(opt_.periodic_free);
    oper_->SetupPeriodic();
-   drop_cg_graph();
+   krylov_->DropGraph();
 }
 
 // ExaNewtonSolver::Mult / ExaNewtonLSSolver::Mult with b = 0 (reference src/mechanics_solver.cpp:39-143,155-281)
@@ -1531,7 +1301,7 @@ bool SystemDriver::NewtonSolve(double* x, SolverStats& st) {
       if (norm <= norm_max) { converged = true; break; }
       if (it >= opt_.newton_iter) { converged = false; break; }
       op.GetGradient();
-      st.krylov_iters += CGSolve(r_.p, c_.p);
+      st.krylov_iters += krylov_->Solve(r_.p, c_.p);
       if (mixed_) op.ExpandCorrection(c_.p);   // the correction of the reduced unknowns -> of the nodal velocities
       if (opt_.nl_solver == NLSolver::NRLS) {
          const double q1 = norm;
@@ -1564,7 +1334,7 @@ void SystemDriver::SolveInit(const double* xprev, double* x) {
    vk_mask_set(nd, op.ess_mask.p, xt_.p, deltaF.p, s);
    op.GetUpdateBCsAction(xprev, deltaF.p, b.p);
    SolverStats dummy; (void)dummy;
-   const int it = CGSolve(b.p, x);
+   const int it = krylov_->Solve(b.p, x);
    if (!stats.empty()) stats.back().krylov_iters += it;
    vk_axpby(nd, 1.0, xprev, -1.0, x, s);   // x = -x + xprev
 }

@@ -6,6 +6,7 @@
 //   NonlinearMechOperator                reference src/mechanics_operator.hpp:18-100, src/mechanics_operator.cpp:288-483
 //   MechOperatorJacobiSmoother           reference src/mechanics_operator_ext.cpp:11-55
 //   ExaNewtonSolver / ExaNewtonLSSolver  reference src/mechanics_solver.cpp:39-281
+//   PCGSolver (host/krylov.hpp)          MFEM CGSolver, set up at reference src/system_driver.cpp:166-177
 //   SystemDriver                         reference src/system_driver.cpp:221-558
 //   time-step loop                       reference src/mechanics_driver.cpp:837-907
 #pragma once
@@ -15,6 +16,7 @@
 #include <vector>
 #include "../../../include/exaconstit_hip.h"
 #include "device_utils.hpp"
+#include "krylov.hpp"
 #include "mesh.hpp"
 #include "options.hpp"
 
@@ -74,7 +76,6 @@ void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const 
 void write_texture(const std::string& path, int step, double t, double res_deg, const std::vector<int>& hkl, const std::vector<double>& dirs,
                    const std::vector<double>& mrd);
 
-enum class Precond { IDENTITY, JACOBI, MULTIGRID };
 class Multigrid;
 
 // macroscopic tangent of a periodic cell: T[9 (3 k + l) + m] / V = d sigma_bar_kl / d L_bar_m, m = 3 i + j the entry (i, j) of L_bar
@@ -94,9 +95,7 @@ constexpr int MACRO_TANGENT_ROW = 85;
 
 struct SolverStats { int newton_iters = 0; int krylov_iters = 0; int model_calls = 0; bool converged = false; };
 
-struct Timers {
-   double t_model_ms = 0, t_krylov_ms = 0, t_solve_ms = 0; int64_t qpt_updates = 0; int64_t krylov_iters = 0;
-};
+struct Timers { double t_model_ms = 0, t_solve_ms = 0; int64_t qpt_updates = 0; };   // (the Krylov totals are the solver's: host/krylov.hpp)
 
 // Per-quadrature-point model seam (ExaModel): owns nothing but scratch; the driver owns the quadrature functions.
 class ExaCMechModel {
@@ -209,6 +208,9 @@ class NonlinearMechOperator {
    EvPair& NextModelTimer(); void FlushModelTimers(); void ReadModelStatus();
    double ResidualNorm(const double* r);
    double dot(const double* a, const double* b);   // weighted, all-reduced, synchronising
+   // scal: the operator's own device scalars - the sum of dot / ResidualNorm, the origin of the velocity-gradient conditions (3 doubles), the failed-point
+   // count of the constitutive launch behind a residual (ResidualNorm reads SCAL_DOT .. SCAL_FAILED back in one copy)
+   enum { SCAL_DOT = 9, SCAL_ORIGIN = 12, SCAL_FAILED = 15, SCAL_LEN = 32 };
    DevBuf<double> partial, scal;
  private:
    ExaOptions opt_; const Partition& part_; Comm& comm_;
@@ -252,9 +254,6 @@ class SystemDriver {
    void CommitStep();                      // end-of-step update of a step solved with commit = false
    int RunAll();
    bool NewtonSolve(double* x, SolverStats& st);
-   int CGSolve(const double* b, double* x);   // device PCG, returns iterations
-   int CGSolveSingleReduction(const double* b, double* x);   // more than one rank: one fused 16-byte all-reduce per iteration
-   int CGSolveMG(const double* b, double* x);   // multigrid-preconditioned CG (MFEM CGSolver::Mult order of operations), any rank count
    // preconditioner of the PCG (set before the first step; takes effect at the next gradient set-up): kind 0 identity, 1 Jacobi, 2 multigrid with at most `levels` coarse levels (0: as
    // many as the mesh allows) and a Chebyshev smoother of `degree`; refuses multigrid where no hierarchy can be built
    void SetPreconditioner(int kind, int levels, int degree);
@@ -276,18 +275,12 @@ class SystemDriver {
    const double* mac_period() const { return mac_A_; }       // A, column d = a_d (row by row), of the start of the last step
    const double* mac_resultants() const { return mac_F_; }   // F_id, row by row
    double last_newton_norm = 0.0, last_newton_bound = 0.0;   // final residual norm and max(rel |r0|, abs) of the last Newton solve
-   void note_cg_reduction(const double* hS);
-   double last_cg_reduction = 0.0, worst_capped_cg_reduction = 0.0;   // |r|_M / |r0|_M of the last PCG solve / the worst among the solves that stopped at max_iter
-   void drop_cg_graph();                      // forget the captured PCG chunk (its solution buffer is about to go away)
-   void report_cg(const double* hS, int iters) const;   // MFEM CGSolver::Mult diagnostics (verbose / EXA_VERBOSE)
+   PCGSolver& krylov() { return *krylov_; }   // the run's linear solver
    // Homogenised tangent d sigma_bar / d L_bar of the last solved step of a periodic cell (host/tangent.hip), every rank calls it.
-   // rel_tol / max_iter <= 0: the Krylov options.  batched: -1 the automatic route, 0 column by column through CGSolve, 1 the nine columns in
+   // rel_tol / max_iter <= 0: the Krylov options.  batched: -1 the automatic route, 0 column by column through PCGSolver::Solve, 1 the nine columns in
    // lockstep through the multi-column action (one rank, non-deterministic mode, a context exa_grad_apply_lvec_cols serves; refused elsewhere).
    // Refuses a driver that is not periodic or has no step solved in this process.  Leaves the run as it found it.
    void MacroTangent(double rel_tol, int max_iter, int batched, MacroTangentResult& out);
-   // nc <= 16 systems K_uu x_m = b_m in lockstep: recurrence and stopping test of CGSolve with one scalar block per column, the multi-column action
-   // in the middle; B, X: columns at stride ld.  No graph capture, no consumer-side reductions; touches neither scal nor the timers.
-   void CGSolveColumns(int nc, const double* B, double* X, int64_t ld, double rel_tol, int max_iter, int nch, int* iters, double* reduction, int* flag);
    // probe of the operator (exa_driver_grad_apply_columns): y_m = K x_m for nc host columns of local dofs (byNODES).  assembled: the operator of the
    // tangent's solves (periodic and rank sums, the run's essential set plus the control slots, input and output); otherwise the raw element action.
    // gated (nullable): columns with a non-zero entry are left out - their y stays as passed in.
@@ -340,19 +333,14 @@ class SystemDriver {
    std::string vis_dir() const { return (opt_.vis_floc.empty() || opt_.vis_floc[0] == '/') ? opt_.vis_floc : out_dir + "/" + opt_.vis_floc; }
    std::vector<int32_t> elem_attr;             // grain id (element attribute) of every local element
    Precond precond = Precond::IDENTITY;
-   int cg_check_every = 16;
-   int64_t cg_graph_max_dofs = 3 * 33 * 33 * 33;   // PCG iterations replayed from a hipGraph up to this many local dofs (32^3 elements at p = 1: +9 % at 16^3, +3 % at 32^3, a loss from 48^3 on); EXA_PCG_GRAPH=0 | all
-   // linear-solver diagnostics (MFEM's CGSolver prints these): flag of the last solve (1 converged, 2 max_iter, -1 den == 0),
-   // number of solves that did not converge, iterations that saw (Ad, d) < 0
-   int last_cg_flag = 1; int64_t cg_not_converged = 0, cg_indefinite_iters = 0;
-   bool verbose = false;
    Partition part;
    Comm comm;
  private:
    void init(const std::vector<double>& props, const std::vector<double>& quats_local);
    ExaOptions opt_;
    std::unique_ptr<NonlinearMechOperator> oper_;
-   DevBuf<double> r_, c_, xt_, cg_r_, cg_z_, cg_d_, cg_s_, cg_q_, ess_val_;
+   std::unique_ptr<PCGSolver> krylov_;
+   DevBuf<double> r_, c_, xt_, ess_val_;
    std::vector<uint8_t> ess_host_; std::vector<double> ess_val_host_;
    DevBuf<uint8_t> vel_mask_, vg_mask_; bool have_vel_ = false, have_vgrad_ = false; double vgrad_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
    double last_dt_ = 0.0;
@@ -378,8 +366,7 @@ class SystemDriver {
    int bc_index_ = -1;                          // index in opt_.bcs of the essential-boundary entry in force
    bool restarted_ = false;
    bool step_solved_ = false;                   // the last Step of this process converged and no constitutive launch has run since (MacroTangent)
-   DevBuf<double> tangent_x_;                   // the one solution buffer of the column-by-column tangent solves
-   struct TangentScope;                         // host/tangent.hip: the essential set of the tangent's solves and everything an evaluation puts back
+   struct TangentScope;                         // host/tangent.hip: the essential set of the tangent's solves and what an evaluation puts back
    void WriteMacroTangent(int step);
    // shared-node copies of a checkpoint written on another rank count (host/checkpoint.hip): carried along untouched and written back as long as
    // no constitutive launch has run since the load, so that load + save reproduces the file on any rank count
@@ -388,7 +375,6 @@ class SystemDriver {
    DevBuf<double> texture_vmax_; DevBuf<int64_t> texture_counts_;   // largest element volume; [set][n_alpha][n_beta] counts of exa_texture_weights
    void WriteTexture(int step, double t);
    std::map<std::string, std::vector<std::pair<int, double>>> pvd_cycles_;   // saved cycles of each output directory (rank 0 writes the .pvd)
-   void* cg_graph_ = nullptr; const double* cg_graph_x_ = nullptr; int64_t cg_graph_key_ = -1;   // captured PCG chunk (hipGraphExec_t) and what it was captured for
 };
 
 }  // namespace exa_host

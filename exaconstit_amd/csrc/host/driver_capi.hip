@@ -509,19 +509,20 @@ int exa_driver_get_stats(exa_driver* d, int* newton, int* krylov, int* model_cal
 // out[0] ms in the fused constitutive kernel, out[1] ms in PCG, out[2] ms in Solve (+SolveInit), out[3] qpt updates, out[4] PCG iterations
 void exa_driver_get_timers(exa_driver* d, double* out) {
    d->sd->oper().FlushModelTimers();
-   const Timers& t = d->sd->oper().timers;
-   out[0] = t.t_model_ms; out[1] = t.t_krylov_ms; out[2] = t.t_solve_ms; out[3] = (double)t.qpt_updates; out[4] = (double)t.krylov_iters;
+   const Timers& t = d->sd->oper().timers; const PCGSolver& k = d->sd->krylov();
+   out[0] = t.t_model_ms; out[1] = k.krylov_ms; out[2] = t.t_solve_ms; out[3] = (double)t.qpt_updates; out[4] = (double)k.krylov_iters;
 }
-void exa_driver_reset_timers(exa_driver* d) { d->sd->oper().FlushModelTimers(); d->sd->oper().timers = Timers(); }   // pending event pairs belong to the old totals
+void exa_driver_reset_timers(exa_driver* d) { d->sd->oper().FlushModelTimers(); d->sd->oper().timers = Timers(); d->sd->krylov().ResetTotals(); }   // pending event pairs belong to the old totals
 // out[0] quadrature points whose local solve failed (sum over all constitutive launches, this rank), out[1] linear solves that
 // did not converge, out[2] PCG iterations that saw (Ad, d) < 0, out[3] flag of the last PCG solve (1 converged, 2 max_iter, -1 den == 0)
 void exa_driver_get_diagnostics(exa_driver* d, int64_t* out) {
    d->sd->oper().ReadModelStatus();
-   out[0] = d->sd->oper().model_fail_total; out[1] = d->sd->cg_not_converged; out[2] = d->sd->cg_indefinite_iters; out[3] = d->sd->last_cg_flag;
+   const PCGSolver::Diagnostics& k = d->sd->krylov().diag;
+   out[0] = d->sd->oper().model_fail_total; out[1] = k.not_converged; out[2] = k.indefinite_iters; out[3] = k.last_flag;
 }
 
 // out[0] = sqrt((r, M^-1 r) / (r0, M^-1 r0)) reached by the last PCG solve, out[1] = the worst value among the solves that stopped at max_iter
-void exa_driver_get_pcg_reduction(exa_driver* d, double* out2) { out2[0] = d->sd->last_cg_reduction; out2[1] = d->sd->worst_capped_cg_reduction; }
+void exa_driver_get_pcg_reduction(exa_driver* d, double* out2) { out2[0] = d->sd->krylov().diag.last_reduction; out2[1] = d->sd->krylov().diag.worst_capped_reduction; }
 
 // which: 1 = end-of-step state of the last constitutive launch, 0 = begin-of-step state (after a completed step: that step's converged launch)
 int exa_driver_nfev_hist_of(exa_driver* d, int which, int* hist64, char* err, int errlen) {
@@ -613,16 +614,15 @@ int exa_driver_bench_pcg(exa_driver* d, int iters, double* out, char* err, int e
       DevBuf<double> r(nd), c(nd);
       op.Mult(sd.v_sol.p, r.p);
       op.GetGradient();
-      ExaOptions& o = const_cast<ExaOptions&>(sd.options());
-      const double rel = o.krylov_rel, ab = o.krylov_abs; const int mi = o.krylov_iter;
-      o.krylov_rel = 0.0; o.krylov_abs = 0.0; o.krylov_iter = iters;
-      const double t0 = op.timers.t_krylov_ms;
+      // a solver of the hook's own (the run's chunk length and graph limit): its captured chunk, which refers to the local solution buffer c, goes
+      // with it, and the run's diagnostics and totals do not see the capped solve
+      PCGSolver::Settings ks = sd.krylov().set;
+      ks.rel_tol = 0.0; ks.abs_tol = 0.0; ks.max_iter = iters;
+      PCGSolver k(op, ks);
       const std::string rname = "timed_region_pcg[iters=" + std::to_string(iters) + "]";
       ProfRegion prof(rname.c_str());
-      const int it = sd.CGSolve(r.p, c.p);
-      out[0] = op.timers.t_krylov_ms - t0; out[1] = it;
-      o.krylov_rel = rel; o.krylov_abs = ab; o.krylov_iter = mi;
-      sd.drop_cg_graph();   // the captured chunk refers to the local solution buffer c
+      const int it = k.Solve(r.p, c.p);
+      out[0] = k.krylov_ms; out[1] = it;
       hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1));
       EXA_HC(hipEventRecord(e0, s));
       for (int i = 0; i < iters; i++) exa_grad_apply_lvec(op.GetModel()->ctx(), r.p, c.p, op.ess_mask.p, s);

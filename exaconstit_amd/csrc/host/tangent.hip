@@ -11,9 +11,10 @@
 //   T        T_(kl),m = sum over the local nodes of (K_raw (a_m + w_m))_k (x_l - o_l), summed over the ranks;  T / V = d sigma_bar_kl / d L_bar_m
 //            by Hill-Mandel (V the current cell volume).  Every column of a raw action sums to zero over the nodes, so the origin drops out.
 //
-// Two routes for the nine solves.  Batched (one rank, non-deterministic mode, a context exa_grad_apply_lvec_cols serves): CGSolveColumns runs
-// the columns in lockstep around the multi-column action of tangent_kernels.hip.  Everywhere else - several ranks, EXA_DETERMINISTIC=1, p >= 2,
-// assembled element matrices, B-bar - the columns go one by one through CGSolve into one fixed solution buffer.
+// Two routes for the nine solves, both through a PCGSolver (host/krylov.hpp) built for the evaluation with its tolerance and cap.  Batched (one rank,
+// non-deterministic mode, a context exa_grad_apply_lvec_cols serves): SolveColumns runs the columns in lockstep around the multi-column action of
+// tangent_kernels.hip.  Everywhere else - several ranks, EXA_DETERMINISTIC=1, p >= 2, assembled element matrices, B-bar - the columns go one by one
+// through Solve into one fixed solution buffer.
 #include "driver.hpp"
 #include <cmath>
 #include <cstring>
@@ -26,27 +27,19 @@ int exa_launch_macro_contract(exa_ctx* ctx, int nn, int ncols, const double* y, 
 namespace exa_host {
 
 namespace {
-constexpr int SB = 24;                 // doubles per scalar block of a column (the PCG scalars of vec_kernels.hip use 18)
 constexpr int MACRO_WORK = 256 * 81;   // block partials of the contraction (tangent_kernels.hip, EXA_MACRO_BLOCKS)
 void abi(exa_ctx* ctx, int rc, const char* what) { if (rc < 0) throw std::runtime_error(std::string(what) + ": " + exa_last_error(ctx)); }
 int env_int(const char* k, int dflt) { const char* e = std::getenv(k); return e ? std::atoi(e) : dflt; }
 }
 
-// Everything an evaluation changes and puts back: the essential mask and the free bits (mixed partitions: the solves fix all nine control slots),
-// the Krylov options CGSolve reads, scal, the timers, the PCG diagnostics and the captured PCG chunk of the run (set aside, so that the solves
-// of the tangent capture and drop their own).  The records, the Newton cap state and stats are never written: no constitutive launch runs.
+// What an evaluation shares with the run and puts back: the essential mask and the free bits (mixed partitions: the solves fix all nine control
+// slots) and the operator's own scalars.  The solves run in a PCGSolver of the evaluation's own, so the run's Krylov settings, diagnostics, totals
+// and captured chunk are never touched; the records, the Newton cap state, stats and the model timers are never written: no constitutive launch runs.
 struct SystemDriver::TangentScope {
    SystemDriver& sd; NonlinearMechOperator& op;
-   double krylov_rel; int krylov_iter; Timers timers; int last_flag; int64_t not_conv, indef; double last_red, worst_red;
-   void* graph; const double* graph_x; int64_t graph_key;
-   double scal[32]; uint32_t free_bits; bool mask_changed = false; bool closed = false;
+   double scal[NonlinearMechOperator::SCAL_LEN]; uint32_t free_bits; bool mask_changed = false; bool closed = false;
    TangentScope(SystemDriver& d) : sd(d), op(*d.oper_) {
-      hipStream_t s = op.stream();
-      krylov_rel = sd.opt_.krylov_rel; krylov_iter = sd.opt_.krylov_iter; timers = op.timers;
-      last_flag = sd.last_cg_flag; not_conv = sd.cg_not_converged; indef = sd.cg_indefinite_iters; last_red = sd.last_cg_reduction; worst_red = sd.worst_capped_cg_reduction;
-      graph = sd.cg_graph_; graph_x = sd.cg_graph_x_; graph_key = sd.cg_graph_key_;
-      sd.cg_graph_ = nullptr; sd.cg_graph_x_ = nullptr; sd.cg_graph_key_ = -1;
-      op.scal.download(scal, 32, s);
+      op.scal.download(scal, NonlinearMechOperator::SCAL_LEN, op.stream());
       free_bits = op.MixedFree();
       if (sd.mixed_) {
          std::vector<uint8_t> m = sd.ess_host_;
@@ -61,79 +54,14 @@ struct SystemDriver::TangentScope {
       closed = true;
       hipStream_t s = op.stream();
       (void)hipStreamSynchronize(s);
-      sd.drop_cg_graph();
-      sd.cg_graph_ = graph; sd.cg_graph_x_ = graph_x; sd.cg_graph_key_ = graph_key;
-      sd.opt_.krylov_rel = krylov_rel; sd.opt_.krylov_iter = krylov_iter; op.timers = timers;
-      sd.last_cg_flag = last_flag; sd.cg_not_converged = not_conv; sd.cg_indefinite_iters = indef; sd.last_cg_reduction = last_red; sd.worst_capped_cg_reduction = worst_red;
       if (mask_changed) {
          op.UpdateEssTDofs(sd.ess_host_); op.SetMixedFree(free_bits);
          op.GetGradient();   // (the inverse diagonal follows the mask: back to the run's)
       }
-      op.scal.upload(scal, 32, s);
+      op.scal.upload(scal, NonlinearMechOperator::SCAL_LEN, s);
    }
    ~TangentScope() { try { close(); } catch (...) {} }
 };
-
-void SystemDriver::CGSolveColumns(int nc, const double* B, double* X, int64_t ld, double rel_tol, int max_iter, int nch, int* iters, double* reduction, int* flag) {
-   if (nc < 1 || nc > EXA_GRAD_COLS_MAX) throw std::runtime_error("CGSolveColumns: between 1 and 16 columns");
-   if (comm.nranks > 1 || comm.forced() || oper_->deterministic() || oper_->precond == Precond::MULTIGRID)
-      throw std::runtime_error("the batched tangent solve is built for one rank in non-deterministic mode with the identity or Jacobi preconditioner");
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   const int64_t nd = op.Height(), nn = part.NN;
-   if (ld < nd) throw std::runtime_error("CGSolveColumns: column stride shorter than the vectors");
-   DevBuf<double> R((size_t)nc * nd), Z((size_t)nc * nd), D((size_t)nc * nd), Sb((size_t)nc * SB);
-   Sb.zero(s);
-   const bool ident = op.precond == Precond::IDENTITY;
-   std::vector<const double*> gates(nc);
-   for (int m = 0; m < nc; m++) {
-      double* S = Sb.p + (size_t)m * SB; gates[m] = S + 6;
-      double* r = R.p + (size_t)m * nd; double* z = Z.p + (size_t)m * nd; double* d = D.p + (size_t)m * nd;
-      EXA_HC(hipMemsetAsync(X + (size_t)m * ld, 0, sizeof(double) * nd, s));
-      EXA_HC(hipMemcpyAsync(r, B + (size_t)m * ld, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
-      vk_pointwise(nd, op.dinv.p, r, z, s);
-      EXA_HC(hipMemcpyAsync(d, z, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
-      vk_dot(nd, nn, op.weight.p, d, r, nullptr, op.partial.p, S + 8, s);
-      vk_cg_init(S, rel_tol, opt_.krylov_abs, s);
-   }
-   // Z += K_uu D on the columns still running: one pass over the records per nch columns, then the periodic sum of every column (the control
-   // slots are essential in every solve of the tangent, so the masked direction is its own expansion: no MixedExpand); the output mask rides
-   // in the dot product that follows
-   auto action = [&]() {
-      if (!op.GradMultRawCols(nch, nc, D.p, nd, Z.p, nd, op.ess_mask.p, gates.data()))
-         throw std::runtime_error("the batched tangent solve needs the p = 1 hexahedron L-vector record action with atomic scatter (exa_grad_apply_lvec_cols)");
-      for (int m = 0; m < nc; m++) op.SumLVector(Z.p + (size_t)m * nd, gates[m], false);
-   };
-   for (int m = 0; m < nc; m++) vk_fill_if(nd, gates[m], 0.0, Z.p + (size_t)m * nd, s);
-   action();
-   for (int m = 0; m < nc; m++) { double* S = Sb.p + (size_t)m * SB; vk_mask_dot(nd, nn, op.weight.p, op.ess_mask.p, D.p + (size_t)m * nd, Z.p + (size_t)m * nd, S + 6, op.partial.p, S + 8, s, S); }
-   auto iteration = [&]() {
-      for (int m = 0; m < nc; m++) {
-         double* S = Sb.p + (size_t)m * SB;
-         double* r = R.p + (size_t)m * nd; double* z = Z.p + (size_t)m * nd; double* d = D.p + (size_t)m * nd;
-         vk_cg_step1(nd, nn, S, op.weight.p, op.dinv.p, d, X + (size_t)m * ld, r, z, op.partial.p, ident, true, max_iter, s);
-         vk_cg_step2z(nd, S, z, r, d, ident, s);
-      }
-      action();
-      for (int m = 0; m < nc; m++) { double* S = Sb.p + (size_t)m * SB; vk_mask_dot(nd, nn, op.weight.p, op.ess_mask.p, D.p + (size_t)m * nd, Z.p + (size_t)m * nd, S + 6, op.partial.p, S + 8, s, S); }
-   };
-   std::vector<double> hS((size_t)nc * SB);
-   int launched = 0; bool done = false;
-   while (!done) {
-      for (int k = 0; k < cg_check_every && launched < max_iter; k++, launched++) iteration();
-      Sb.download(hS.data(), hS.size(), s);
-      done = launched >= max_iter;
-      bool all = true;
-      for (int m = 0; m < nc; m++) all = all && hS[(size_t)m * SB + 6] != 0.0;
-      done = done || all;
-   }
-   for (int m = 0; m < nc; m++) {
-      const double* S = &hS[(size_t)m * SB];
-      iters[m] = (S[6] == 1.0 && S[7] == 0.0) ? 0 : (int)S[7];
-      reduction[m] = S[11] > 0.0 ? std::sqrt(std::fmax(S[2], 0.0) / S[11]) : 0.0;
-      flag[m] = S[6] == 0.0 ? 2 : (int)S[6];
-   }
-}
 
 void SystemDriver::MacroTangent(double rel_tol, int max_iter, int batched, MacroTangentResult& out) {
    if (!part.periodic) throw std::runtime_error("macro_tangent: the driver is not periodic (set_periodic / BCs.periodic = true) - the homogenised tangent is that of a periodic cell");
@@ -153,6 +81,9 @@ void SystemDriver::MacroTangent(double rel_tol, int max_iter, int batched, Macro
    const int nch = tangent_nch > 0 ? tangent_nch : env_int("EXA_TANGENT_NCH", 0);
    if (nch < 0 || nch > 3) throw std::runtime_error("macro_tangent: 1, 2 or 3 columns per pass");
    TangentScope scope(*this);
+   PCGSolver::Settings ks = krylov_->set;   // (chunk length and graph limit as the run has them: a capture that failed is not tried again)
+   ks.rel_tol = rel; ks.max_iter = mi;
+   PCGSolver pcg(op, ks);
    op.GetGradient();
    DevBuf<double> A((size_t)9 * nd), W((size_t)9 * nd), Bv((size_t)9 * nd), tmp((size_t)nd), small(3 + 81), work((size_t)MACRO_WORK);
    double org[3];
@@ -177,15 +108,13 @@ void SystemDriver::MacroTangent(double rel_tol, int max_iter, int batched, Macro
       vk_mask_zero(nd, op.ess_mask.p, b, s);
       out.b_norm[m] = std::sqrt(std::fmax(op.dot(b, b), 0.0));
    }
-   if (want) CGSolveColumns(9, Bv.p, W.p, nd, rel, mi, nch, out.iters, out.reduction, out.flag);
+   if (want) pcg.SolveColumns(9, Bv.p, W.p, nd, nch, out.iters, out.reduction, out.flag);
    else {
-      // one fixed solution buffer: the PCG chunk is captured once for it and replayed by all nine solves
-      if (tangent_x_.n != (size_t)nd) tangent_x_.alloc((size_t)nd);
-      opt_.krylov_rel = rel; opt_.krylov_iter = mi;
+      // one fixed solution buffer (tmp): the PCG chunk is captured once for it and replayed by all nine solves
       for (int m = 0; m < 9; m++) {
-         out.iters[m] = CGSolve(Bv.p + (size_t)m * nd, tangent_x_.p);
-         out.reduction[m] = last_cg_reduction; out.flag[m] = last_cg_flag;
-         EXA_HC(hipMemcpyAsync(W.p + (size_t)m * nd, tangent_x_.p, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
+         out.iters[m] = pcg.Solve(Bv.p + (size_t)m * nd, tmp.p);
+         out.reduction[m] = pcg.diag.last_reduction; out.flag[m] = pcg.diag.last_flag;
+         EXA_HC(hipMemcpyAsync(W.p + (size_t)m * nd, tmp.p, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
       }
    }
    out.batched = want ? 1 : 0; out.nch = want ? (nch ? nch : EXA_GRAD_COLS_DEFAULT) : 0;

@@ -6,6 +6,7 @@
 //   ExaModel::UpdateEndCoords         (reference src/mechanics_model.cpp:472-474)
 // Dot products are weighted by 1/multiplicity of a node across ranks so that duplicated interface nodes count once.
 #include "host/device_utils.hpp"
+#include "pcg_slots.hpp"
 
 namespace {
 
@@ -74,41 +75,40 @@ __global__ void k_reduce(int nb, const double* __restrict__ partial, const doubl
    if (threadIdx.x == 0) out[0] = s;
 }
 
-// PCG scalars: S[0]=nom S[1]=den S[2]=betanom S[3]=r0 S[4]=alpha S[5]=beta S[6]=done flag (0 run, 1 converged, -1 breakdown) S[7]=iterations
-// S[8]=scratch for reductions  S[9]=scratch of the operator's dot  S[10]=number of iterations with (Ad, d) < 0  S[16], S[17]=nom / iterations in flight (consumer-side reductions)
-__global__ void k_cg_init(double* S, double rel, double abs_) {       // after nom was reduced into S[8]
-   const double nom = S[8];
-   S[0] = nom; S[3] = fmax(nom * rel * rel, abs_ * abs_); S[7] = 0.0; S[2] = nom; S[11] = nom;   // S[11]: (r0, z0), S[2]: latest (r, z) - the achieved reduction is reported
-   S[16] = nom; S[17] = 0.0;   // (nom, iterations) as the consumer-side reductions hand them from k_cg_step2z to k_cg_step1 (below)
-   S[6] = (nom < 0.0) ? -1.0 : ((nom <= S[3]) ? 1.0 : 0.0);
+// PCG scalars: S is one record of pcg_slots.hpp
+__global__ void k_cg_init(double* S, double rel, double abs_) {       // after nom was reduced into S[pcg::RED0]
+   const double nom = S[pcg::RED0];
+   S[pcg::NOM] = nom; S[pcg::THRESHOLD] = fmax(nom * rel * rel, abs_ * abs_); S[pcg::ITERS] = 0.0; S[pcg::BETANOM] = nom; S[pcg::R0Z0] = nom;   // S[pcg::R0Z0]: (r0, z0), S[pcg::BETANOM]: latest (r, z) - the achieved reduction is reported
+   S[pcg::NOM_NEXT] = nom; S[pcg::ITERS_NEXT] = 0.0;   // (nom, iterations) as the consumer-side reductions hand them from k_cg_step2z to k_cg_step1 (below)
+   S[pcg::FLAG] = (nom < 0.0) ? pcg::BREAKDOWN : ((nom <= S[pcg::THRESHOLD]) ? pcg::CONVERGED : pcg::RUNNING);
 }
-__device__ __forceinline__ void cg_den_update(double* S) {            // den reduced into S[8]
-   const double den = S[8];
-   S[1] = den;
+__device__ __forceinline__ void cg_den_update(double* S) {            // den reduced into S[pcg::RED0]
+   const double den = S[pcg::RED0];
+   S[pcg::DEN] = den;
    // MFEM's CGSolver only warns when (Ad, d) < 0 ("The operator is not positive definite") and keeps iterating; it stops on den == 0
-   if (den == 0.0) { S[6] = -1.0; return; }
-   if (den < 0.0) S[10] += 1.0;      // S[10]: iterations with a negative denominator (reported by the driver)
-   S[4] = S[0] / den;
+   if (den == 0.0) { S[pcg::FLAG] = pcg::BREAKDOWN; return; }
+   if (den < 0.0) S[pcg::INDEFINITE] += 1.0;      // S[pcg::INDEFINITE]: iterations with a negative denominator (reported by the driver)
+   S[pcg::ALPHA] = S[pcg::NOM] / den;
 }
-__device__ __forceinline__ void cg_beta_update(double* S, double max_iter) {   // betanom reduced into S[8]
-   const double bn = S[8];
-   S[2] = bn; S[7] += 1.0;
-   if (bn <= S[3]) { S[6] = 1.0; return; }
-   if (S[7] >= max_iter) { S[6] = 2.0; return; }
-   S[5] = bn / S[0]; S[0] = bn;
+__device__ __forceinline__ void cg_beta_update(double* S, double max_iter) {   // betanom reduced into S[pcg::RED0]
+   const double bn = S[pcg::RED0];
+   S[pcg::BETANOM] = bn; S[pcg::ITERS] += 1.0;
+   if (bn <= S[pcg::THRESHOLD]) { S[pcg::FLAG] = pcg::CONVERGED; return; }
+   if (S[pcg::ITERS] >= max_iter) { S[pcg::FLAG] = pcg::MAX_ITER; return; }
+   S[pcg::BETA] = bn / S[pcg::NOM]; S[pcg::NOM] = bn;
 }
-__global__ void k_cg_den(double* S) { if (S[6] == 0.0) cg_den_update(S); }
-__global__ void k_cg_beta(double* S, double max_iter) { if (S[6] == 0.0) cg_beta_update(S, max_iter); }
+__global__ void k_cg_den(double* S) { if (S[pcg::FLAG] == pcg::RUNNING) cg_den_update(S); }
+__global__ void k_cg_beta(double* S, double max_iter) { if (S[pcg::FLAG] == pcg::RUNNING) cg_beta_update(S, max_iter); }
 // one rank: no all-reduce between the reduction of the partial sums and the scalar update, so they are one launch
 // (MODE 1: betanom -> beta, MODE 2: den -> alpha)
 template <int MODE>
 __global__ void k_reduce_cg(int nb, const double* __restrict__ partial, double* __restrict__ S, double max_iter) {
    __shared__ double sm[RBLK];
-   if (S[6] != 0.0) return;
+   if (S[pcg::FLAG] != pcg::RUNNING) return;
    double acc = 0;
    for (int i = threadIdx.x; i < nb; i += RBLK) acc += partial[i];
    const double s = block_sum(acc, sm);
-   if (threadIdx.x == 0) { S[8] = s; if (MODE == 1) cg_beta_update(S, max_iter); else cg_den_update(S); }
+   if (threadIdx.x == 0) { S[pcg::RED0] = s; if (MODE == 1) cg_beta_update(S, max_iter); else cg_den_update(S); }
 }
 
 // x += alpha d; r -= alpha z; z = dinv r; partial of (r, z)_w
@@ -119,8 +119,8 @@ __global__ void k_reduce_cg(int nb, const double* __restrict__ partial, double* 
 #endif
 // Consumer-side reductions (one rank, fused loop, small systems): the two one-block launches that turned partial sums into alpha / beta (k_reduce_cg) are gone;
 // every block of the NEXT kernel sums the partial sums itself - same order as k_reduce_cg, so the same bits in every block and as before - and block 0 keeps the
-// scalar record.  What all blocks read in a kernel is never written in that kernel: k_cg_step2z reads (nom, iterations) from S[0], S[7] and leaves the new pair in
-// S[16], S[17]; k_cg_step1 reads S[16] and commits both.  The done flag S[6] may be set by block 0 while other blocks start: a block takes it through one thread
+// scalar record.  What all blocks read in a kernel is never written in that kernel: k_cg_step2z reads (nom, iterations) from S[pcg::NOM], S[pcg::ITERS] and leaves the new pair in
+// S[pcg::NOM_NEXT], S[pcg::ITERS_NEXT]; k_cg_step1 reads S[pcg::NOM_NEXT] and commits both.  The done flag S[pcg::FLAG] may be set by block 0 while other blocks start: a block takes it through one thread
 // (no divergence across a barrier), and a block that still reads 0 reaches the same decision from the sum it computes.
 // block_sum's tree with fewer barriers: the steps 128 and 64 through LDS, the steps 32 ... 1 inside the first wave (the same pairs are added: the same bits)
 __device__ __forceinline__ double block_sum_w(double v, double* sm) {
@@ -143,9 +143,9 @@ __device__ __forceinline__ double block_sum_w(double v, double* sm) {
 __device__ __forceinline__ double sum_partials(int nb, const double* __restrict__ partial, const double* S, double* sm, double* sflag, bool& done) {
    double acc = 0;
    for (int i = threadIdx.x; i < nb; i += RBLK) acc += partial[i];
-   if (threadIdx.x == 0) *sflag = S[6];
+   if (threadIdx.x == 0) *sflag = S[pcg::FLAG];
    const double r = block_sum_w(acc, sm);
-   done = *sflag != 0.0;
+   done = *sflag != pcg::RUNNING;
    return r;
 }
 // RED: alpha from the partial sums of the denominator (k_mask_dot_partial / k_dot_partial wrote partialD[0 .. nbD))
@@ -157,17 +157,17 @@ __global__ void k_cg_step1(int64_t n, int64_t nn, double* S, const double* __res
    double alpha;
    if constexpr (RED) {
       __shared__ double sflag;
-      const double nom = S[16], its = S[17];      // (requested before the reduction: nothing below waits for them alone)
+      const double nom = S[pcg::NOM_NEXT], its = S[pcg::ITERS_NEXT];      // (requested before the reduction: nothing below waits for them alone)
       bool done;
       const double den = sum_partials(nbD, partialD, S, sm, &sflag, done);      // cg_den_update, in every block
       if (done) return;
       const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
-      if (den == 0.0) { if (lead) { S[8] = den; S[1] = den; S[6] = -1.0; } return; }
+      if (den == 0.0) { if (lead) { S[pcg::RED0] = den; S[pcg::DEN] = den; S[pcg::FLAG] = pcg::BREAKDOWN; } return; }
       alpha = nom / den;
-      if (lead) { S[8] = den; S[1] = den; if (den < 0.0) S[10] += 1.0; S[4] = alpha; S[0] = nom; S[7] = its; }
+      if (lead) { S[pcg::RED0] = den; S[pcg::DEN] = den; if (den < 0.0) S[pcg::INDEFINITE] += 1.0; S[pcg::ALPHA] = alpha; S[pcg::NOM] = nom; S[pcg::ITERS] = its; }
    } else {
-      if (S[6] != 0.0) return;
-      alpha = S[4];
+      if (S[pcg::FLAG] != pcg::RUNNING) return;
+      alpha = S[pcg::ALPHA];
    }
    double acc = 0;
    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -183,13 +183,6 @@ __global__ void k_cg_step1(int64_t n, int64_t nn, double* S, const double* __res
    if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
-// d = z + beta d
-__global__ void k_cg_step2(int64_t n, const double* __restrict__ S, const double* __restrict__ z, double* __restrict__ d) {
-   if (S[6] != 0.0) return;
-   const double beta = S[5];
-   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = z[i] + beta * d[i];
-}
-
 // d = z + beta d, then z = 0: the operator action that follows accumulates into z with atomics, so the separate fill pass is folded in
 // RED: beta from the partial sums of (r, z) (k_cg_step1 wrote partialN[0 .. nbN)); cg_beta_update in every block
 template <bool IDENT, bool RED = false>
@@ -198,51 +191,51 @@ __global__ void k_cg_step2z(int64_t n, double* S, double* __restrict__ z, const 
    double beta;
    if constexpr (RED) {
       __shared__ double sm[RBLK]; __shared__ double sflag;
-      const double nom = S[0], thr = S[3], it = S[7] + 1.0;
+      const double nom = S[pcg::NOM], thr = S[pcg::THRESHOLD], it = S[pcg::ITERS] + 1.0;
       bool done;
       const double bn = sum_partials(nbN, partialN, S, sm, &sflag, done);
       if (done) return;
       const bool conv = bn <= thr, capped = !conv && it >= max_iter;
       if (blockIdx.x == 0 && threadIdx.x == 0) {
-         S[8] = bn; S[2] = bn; S[17] = it;
-         if (conv) S[6] = 1.0; else if (capped) S[6] = 2.0; else { S[5] = bn / nom; S[16] = bn; }
+         S[pcg::RED0] = bn; S[pcg::BETANOM] = bn; S[pcg::ITERS_NEXT] = it;
+         if (conv) S[pcg::FLAG] = pcg::CONVERGED; else if (capped) S[pcg::FLAG] = pcg::MAX_ITER; else { S[pcg::BETA] = bn / nom; S[pcg::NOM_NEXT] = bn; }
       }
       if (conv || capped) return;
       beta = bn / nom;
    } else {
-      if (S[6] != 0.0) return;
-      beta = S[5];
+      if (S[pcg::FLAG] != pcg::RUNNING) return;
+      beta = S[pcg::BETA];
    }
    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) { d[i] = (IDENT ? r[i] : z[i]) + beta * d[i]; z[i] = 0.0; }
 }
 
 // ---- single-reduction PCG (Chronopoulos & Gear), used on more than one rank: one 16-byte all-reduce per iteration instead of two 8-byte ones
-// scalars as above; S[8], S[9] hold the reduced pair gamma = (r, u), delta = (A u, u)
-__global__ void k_cg2_init(double* S, double rel, double abs_) {          // after (gamma, delta) were reduced into S[8], S[9]
-   const double g = S[8], dl = S[9];
-   S[0] = g; S[1] = dl; S[3] = fmax(g * rel * rel, abs_ * abs_); S[7] = 0.0; S[5] = 0.0; S[2] = g; S[11] = g;
-   S[6] = (g < 0.0) ? -1.0 : ((g <= S[3]) ? 1.0 : 0.0);
-   if (S[6] == 0.0) { if (dl == 0.0) S[6] = -1.0; else { if (dl < 0.0) S[10] += 1.0; S[4] = g / dl; } }
+// scalars as above; S[pcg::RED0], S[pcg::RED1] hold the reduced pair gamma = (r, u), delta = (A u, u)
+__global__ void k_cg2_init(double* S, double rel, double abs_) {          // after (gamma, delta) were reduced into S[pcg::RED0], S[pcg::RED1]
+   const double g = S[pcg::RED0], dl = S[pcg::RED1];
+   S[pcg::NOM] = g; S[pcg::DEN] = dl; S[pcg::THRESHOLD] = fmax(g * rel * rel, abs_ * abs_); S[pcg::ITERS] = 0.0; S[pcg::BETA] = 0.0; S[pcg::BETANOM] = g; S[pcg::R0Z0] = g;
+   S[pcg::FLAG] = (g < 0.0) ? pcg::BREAKDOWN : ((g <= S[pcg::THRESHOLD]) ? pcg::CONVERGED : pcg::RUNNING);
+   if (S[pcg::FLAG] == pcg::RUNNING) { if (dl == 0.0) S[pcg::FLAG] = pcg::BREAKDOWN; else { if (dl < 0.0) S[pcg::INDEFINITE] += 1.0; S[pcg::ALPHA] = g / dl; } }
 }
-__global__ void k_cg2_scalars(double* S, double max_iter) {               // new (gamma, delta) in S[8], S[9]
-   if (S[6] != 0.0) return;
-   const double gn = S[8], dl = S[9];
-   S[2] = gn; S[7] += 1.0;
-   if (gn <= S[3]) { S[6] = 1.0; return; }
-   if (S[7] >= max_iter) { S[6] = 2.0; return; }
-   const double beta = gn / S[0];
-   const double den = dl - beta * gn / S[4];                              // = (A p, p) of the next direction
-   S[1] = den;
-   if (den == 0.0) { S[6] = -1.0; return; }
-   if (den < 0.0) S[10] += 1.0;
-   S[5] = beta; S[4] = gn / den; S[0] = gn;
+__global__ void k_cg2_scalars(double* S, double max_iter) {               // new (gamma, delta) in S[pcg::RED0], S[pcg::RED1]
+   if (S[pcg::FLAG] != pcg::RUNNING) return;
+   const double gn = S[pcg::RED0], dl = S[pcg::RED1];
+   S[pcg::BETANOM] = gn; S[pcg::ITERS] += 1.0;
+   if (gn <= S[pcg::THRESHOLD]) { S[pcg::FLAG] = pcg::CONVERGED; return; }
+   if (S[pcg::ITERS] >= max_iter) { S[pcg::FLAG] = pcg::MAX_ITER; return; }
+   const double beta = gn / S[pcg::NOM];
+   const double den = dl - beta * gn / S[pcg::ALPHA];                              // = (A p, p) of the next direction
+   S[pcg::DEN] = den;
+   if (den == 0.0) { S[pcg::FLAG] = pcg::BREAKDOWN; return; }
+   if (den < 0.0) S[pcg::INDEFINITE] += 1.0;
+   S[pcg::BETA] = beta; S[pcg::ALPHA] = gn / den; S[pcg::NOM] = gn;
 }
 // p = u + beta p; q = s + beta q; x += alpha p; r -= alpha q; u = dinv r; s = 0 (the operator action that follows accumulates into it)
 template <bool IDENT, bool XNT = (EXA_CG_X_NT != 0)>
 __global__ void k_cg2_update(int64_t n, const double* __restrict__ S, const double* __restrict__ dinv, double* __restrict__ x, double* __restrict__ r,
                              double* __restrict__ u, double* __restrict__ p, double* __restrict__ sv, double* __restrict__ q) {
-   if (S[6] != 0.0) return;
-   const double alpha = S[4], beta = S[5];
+   if (S[pcg::FLAG] != pcg::RUNNING) return;
+   const double alpha = S[pcg::ALPHA], beta = S[pcg::BETA];
    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
       const double ui = IDENT ? r[i] : u[i];
       const double pi = ui + beta * p[i], qi = sv[i] + beta * q[i];
@@ -429,7 +422,7 @@ void vk_vgrad_velocity(int64_t nn, const uint8_t* m, const double* x, const doub
 #ifndef EXA_CG_RED_GRID
 #define EXA_CG_RED_GRID 1
 #endif
-// partialN != nullptr: consumer-side reduction of the (r, z) partial sums k_cg_step1 left there (one rank; S[6] / S[5] / S[16..17] updated by the launch itself)
+// partialN != nullptr: consumer-side reduction of the (r, z) partial sums k_cg_step1 left there (one rank; FLAG / BETA / NOM_NEXT / ITERS_NEXT updated by the launch itself)
 void vk_cg_step2z(int64_t n, double* S, double* z, const double* r, double* d, bool ident, hipStream_t s, const double* partialN, int max_iter) {
    const unsigned nb = gblk(n);
    if (partialN) {
@@ -476,7 +469,7 @@ void vk_cg_step1(int64_t n, int64_t nn, double* S, const double* w, const double
    if (ident) { if (xnt) STEP1(true, true, false); else STEP1(true, false, false); } else { if (xnt) STEP1(false, true, false); else STEP1(false, false, false); }
 #undef STEP1
    if (fuse_beta) hipLaunchKernelGGL(k_reduce_cg<1>, dim3(1), dim3(RBLK), 0, s, (int)nb, partial, S, (double)max_iter);
-   else hipLaunchKernelGGL(k_reduce, dim3(1), dim3(RBLK), 0, s, (int)nb, partial, S + 6, S + 8);
+   else hipLaunchKernelGGL(k_reduce, dim3(1), dim3(RBLK), 0, s, (int)nb, partial, S + pcg::FLAG, S + pcg::RED0);
 }
 void vk_cg2_init(double* S, double rel, double abs_, hipStream_t s) { hipLaunchKernelGGL(k_cg2_init, dim3(1), dim3(1), 0, s, S, rel, abs_); }
 void vk_cg2_scalars(double* S, int max_iter, hipStream_t s) { hipLaunchKernelGGL(k_cg2_scalars, dim3(1), dim3(1), 0, s, S, (double)max_iter); }
@@ -494,7 +487,6 @@ void vk_cg2_dots(int64_t n, int64_t nn, const double* w, const uint8_t* m, const
    else hipLaunchKernelGGL(k_cg2_dots<false>, dim3(nb), dim3(RBLK), 0, s, n, nn, w, m, r, u, sv, flag, partial);
    hipLaunchKernelGGL(k_reduce2, dim3(1), dim3(RBLK), 0, s, (int)nb, partial, flag, out2);
 }
-void vk_cg_step2(int64_t n, const double* S, const double* z, double* d, hipStream_t s) { hipLaunchKernelGGL(k_cg_step2, dim3(gblk(n) * 4), dim3(RBLK), 0, s, n, S, z, d); }
 void vk_qf_eb64_to_aos(int W, int Q, int64_t E, const double* src, double* dst, hipStream_t s) {
    const int64_t n = (int64_t)W * Q * E;
    hipLaunchKernelGGL(k_qf_eb64_to_aos, dim3(gblk(n) * 8), dim3(RBLK), 0, s, W, Q, n, src, dst);

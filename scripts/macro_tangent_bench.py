@@ -1,5 +1,5 @@
 """Cost of the nine fluctuation solves of the homogenised tangent: the batched route at 1, 2, 3 columns per pass over the record
-stream against the columns one by one through CGSolve, at 64^3 and 128^3 (Voce FCC, one orientation per element, periodic under the velocity
+stream against the columns one by one through PCGSolver::Solve, at 64^3 and 128^3 (Voce FCC, one orientation per element, periodic under the velocity
 gradient of tests/test_gpu_periodic.py, after one solved step).
 
 A solve is cut off at a fixed iteration count (rel_tol far below reach), once at `--lo` and once at `--hi` iterations; the difference of the two
