@@ -6,6 +6,7 @@
 
 int exa_launch_model_setup(exa_ctx*, double, double*, const double*, const double*, const double*, const double*, double*, double*, double*, hipStream_t);
 int exa_launch_model_setup_rec(exa_ctx*, double, double*, const double*, const double*, const double*, const double*, double*, double*, hipStream_t);
+int exa_launch_slip_rates_from_state(exa_ctx*, double*, hipStream_t);
 int exa_launch_model_setup_p2(exa_ctx*, double, double*, const double*, const double*, const double*, const double*, double*, double*, double*, bool, hipStream_t);
 int exa_launch_model_setup_aos_rec(exa_ctx*, double, double*, const double*, const double*, const double*, const double*, double*, double*, hipStream_t);
 int exa_launch_init_state(exa_ctx*, double*, const double*, const double*, hipStream_t);
@@ -238,6 +239,18 @@ int exa_model_setup_checked(exa_ctx* ctx, double dt, const double* J, const doub
                             double* stress1, double* state1, double* ddsdde, exa_stream s) {
    const int rc = exa_model_setup(ctx, dt, J, vel, stress0, state0, stress1, state1, ddsdde, s);
    return rc != EXA_OK ? rc : exa_model_status(ctx, s);
+}
+
+// lean end-of-step state of the element-blocked record launches (include/exaconstit_hip.h, exa_set_lean_state)
+int exa_set_lean_state(exa_ctx* ctx, int on) { if (!ctx) return EXA_ERR_ARG; ctx->lean_state = on != 0; return EXA_OK; }
+int exa_get_lean_state(exa_ctx* ctx) {
+   if (!ctx) return EXA_ERR_ARG;
+   return ctx->lean_state && ctx->qblk && exa_is_hex(ctx) && ((ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL) || ctx->p == 2) ? 1 : 0;
+}
+int exa_slip_rates_from_state(exa_ctx* ctx, double* state, exa_stream s) {
+   if (!ctx || !state) return fail(ctx, EXA_ERR_ARG, "exa_slip_rates_from_state: null pointer");
+   if (!ctx->qblk) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_slip_rates_from_state: lean states exist in the element-blocked layout only");
+   return exa_launch_slip_rates_from_state(ctx, state, S(s));
 }
 
 int exa_set_newton_cap(exa_ctx* ctx, int max_evals) {

@@ -933,7 +933,8 @@ ECM_DI bool eval_rj(const MatParams& mp, const Prob& pb, const double x[8], doub
 
 // slip rates at the converged point (Voce family): written once, instead of one global store per system and evaluation
 // LO: gdot_out is the lane's row in the LDS stage (see ost); the stash may then no longer be read, 1/detV comes in through detv_lo
-template <int XNCT, bool LO = false>
+// ST = false (lean end-of-step state, point_update<.., LEAN>): shear rate and dissipation only, the 12 rates are not stored
+template <int XNCT, bool LO = false, bool ST = true>
 ECM_DI void voce_slip_rates(const MatParams& mp, const Prob& pb, const double e_f[5], double* __restrict__ gdot_out, double& dis_rate, double& shrate, const double detv_lo = 0.0) {
    const double ks[5] = { mp.pk0 * e_f[0], mp.pk1 * e_f[1], mp.pk2 * e_f[2], mp.pk2 * e_f[3], mp.pk2 * e_f[4] };
    double tau[NSLIP], gd[NSLIP];
@@ -941,7 +942,7 @@ ECM_DI void voce_slip_rates(const MatParams& mp, const Prob& pb, const double e_
    voce_gdot12<false, true, XNCT>(mp, pb.g_i, tau, gd, nullptr);
    double dis = 0.0, shr = 0.0;
 #pragma unroll
-   for (int a = 0; a < NSLIP; a++) { ost<LO>(&gdot_out[a * pb.gs], gd[a]); dis += tau[a] * gd[a]; shr += fabs(gd[a]); }
+   for (int a = 0; a < NSLIP; a++) { if constexpr (ST) ost<LO>(&gdot_out[a * pb.gs], gd[a]); dis += tau[a] * gd[a]; shr += fabs(gd[a]); }
    dis_rate = dis * (LO ? detv_lo : ECM_ST(pb.st, ST_PB + PB_DETVRI)); shrate = shr;   // (rates below t_min = (1e-60)^m count as 0 here: below 1e-60 of the reference rate)
 }
 
@@ -1253,11 +1254,15 @@ ECM_DI void staged_tangent(const IO& io, double* cmat, Emit&& emit) {
 // STG (staged AOS launch): the outputs go to the lane's rows of the wave's LDS stage - which is the wave's stash region - and the wave stores them
 // coalesced in three rounds (staged_tangent: io.flush_tangent(0 | 1); io.flush_state()): every lane must stay in the wave until the last round (a point that is cut off by the
 // tail split only marks itself), and nothing may be read from the stash once the first row of a round has been written.
-template <int KIN, int QS, bool REC = false, bool STG = false, class IO>
+// LEAN (record launches of the stand-alone driver, element-blocked): the end-of-step state carries, instead of the 12 slip rates (slots 14..25), what
+// they are a function of besides the hardness in slot 13 - the lattice strain e_f in slots 14..18 and, for the Kocks-Mecking kinds, the thermal
+// factor c_e in slot 19 - and k_slip_rates_from_state (model_kernels.hip) writes the rates when somebody reads them; slots 20..25 are not written
+template <int KIN, int QS, bool REC = false, bool STG = false, bool LEAN = false, class IO>
 ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io, const int kcap, const PointIn& pin,
                         const double* pq_lds = nullptr, const double tsc = 0.0, const bool trd = false, const TailIO tio = TailIO()) {
    // (STG with REC: state and stress rows staged, the compact record written by each lane straight to its slot of the element-blocked record array)
    static_assert(!STG || QS == 1, "staged outputs: AOS rows");
+   static_assert(!LEAN || (!STG && REC), "lean end-of-step state: the per-lane record launches");
    bool cut = false;   // STG: handed over to the dense launch (the lane stays for the wave's stores; what it writes the dense launch overwrites)
    const bool resume = tio.rs_in != nullptr;
    double* st = io.stash();
@@ -1515,7 +1520,12 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
       const double vNew = ECM_CD(CD_VNEW);
       double eNew = ECM_CD(CD_ENEW);
       eNew += 0.25 * (ECM_CD(CD_VOLD) + vNew) * dt * (ECM_CD(CD_WRKOLD) + wrk_new);
-      if constexpr (!kin_is_km(KIN)) voce_slip_rates<kin_xn_ct(KIN)>(mp, pb, e_f, sv1 + H_GDOT * QS, dis_rate, shrate);
+      if constexpr (LEAN) {
+         // (Kocks-Mecking: shear rate and dissipation are those of the converged evaluation, the kinetics pass below only ever produced the 12 stores)
+         if constexpr (!kin_is_km(KIN)) voce_slip_rates<kin_xn_ct(KIN), false, false>(mp, pb, e_f, nullptr, dis_rate, shrate);
+         for (int i = 0; i < 5; i++) stg(&sv1[(H_GDOT + i) * QS], e_f[i]);
+         if constexpr (kin_is_km(KIN)) stg(&sv1[(H_GDOT + 5) * QS], pb.kv.c_e);
+      } else if constexpr (!kin_is_km(KIN)) voce_slip_rates<kin_xn_ct(KIN)>(mp, pb, e_f, sv1 + H_GDOT * QS, dis_rate, shrate);
       else {
          // (the runtime flag is always set in this instantiation, see eval_rj; only the p == q == 1 kernel has the factored forms of the evaluation)
          if (kin_base(KIN) == KIN_KMBALD_GA && kin_pq1(KIN) && mp.with_g_athermal) km_slip_rates_ga<kin_pq1(KIN), kin_sc_exp(KIN)>(mp, pb, e_f, sv1 + H_GDOT * QS);

@@ -224,6 +224,7 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
       }
       // quadrature functions: one pack launch each (layout -> canonical rows in local element order + checksum), one copy to the host
       DevBuf<uint64_t> cks(1);
+      op.EnsureSlipRates(op.matVars0);   // the file holds the full state, slip rates included
       const DevBuf<double>* qb[2] = { &op.stress0, &op.matVars0 }; const int W[2] = { 6, nsv };
       for (int f = 0; f < 2; f++) {
          const size_t n = (size_t)W[f] * Q * part.E;
@@ -384,7 +385,7 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    for (int f = 0; f < 4; f++) if (sums[f] != fs[f]->checksum) throw std::runtime_error("checkpoint: checksum mismatch in section '" + fs[f]->name + "' (" + path + ")");
    // ---- verified: from here on the driver takes the state over
    op.x_beg.upload(nodes[0].data(), nodes[0].size(), s); op.x_cur.upload(nodes[0].data(), nodes[0].size(), s); v_sol.upload(nodes[1].data(), nodes[1].size(), s);
-   op.stress0.swap(scratch[0]); op.matVars0.swap(scratch[1]);
+   op.stress0.swap(scratch[0]); op.matVars0.swap(scratch[1]); op.ForgetPendingRates();   // (a full state from the file; the old arrays are freed)
    // a state written by another code is brought into the form the constitutive kernels expect (slot 0 = sum of |slip rates|); this library's own
    // files satisfy it as stored and come back bit for bit
    if (h.writer != WRITER_THIS_LIBRARY) ck(ctx, exa_state_normalize(ctx, op.matVars0.p, s), "exa_state_normalize");

@@ -527,6 +527,8 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
    geo_resid_ = !(std::getenv("EXA_JAC_FIELD") && std::string(std::getenv("EXA_JAC_FIELD")) == "on");   // A/B switch: the record route writes and reads the Jacobian field as before
    if (det) { abi_check(ctx_, exa_set_deterministic(ctx_, 1), "exa_set_deterministic"); comm_.deterministic = true; }
    abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, tail_resume_ ? 1 : 0), "exa_set_newton_caps");   // A/B switch for measurements; the fused launch is the product path
+   // slip rates on demand (EnsureSlipRates): the element-blocked record launches write 56 B per point less (Kocks-Mecking: 48); EXA_LEAN_STATE=off is the A/B switch
+   abi_check(ctx_, exa_set_lean_state(ctx_, env_is_off("EXA_LEAN_STATE") ? 0 : 1), "exa_set_lean_state");
    // internal quadrature-function layout: element-blocked on the fused p = 1 and p = 2 paths (EXA_QLAYOUT=aos switches back for A/B runs)
    const char* ql = std::getenv("EXA_QLAYOUT");
    lvec_resid_ = fast_p1_ || (hex_p2 && !det);      // fused L-vector residual kernels (p = 1 full integration; p = 2 plain and B-bar)
@@ -775,15 +777,15 @@ void NonlinearMechOperator::Setup(const double* k) {
    EXA_HC(hipEventRecord(ev.a, stream_));
    // ... and AssembleGradPA: the launch writes the action's point records.  With the L-vector residual both integrator actions take the geometry
    // from x_cur, so no Jacobian field is written (72 of 848 B per point); UpdateModel refreshes it once per step for the volume averages
-   if (use_records()) { model_->ModelSetupLVecRecords(x_cur.p, k, geo_resid() ? nullptr : el_jac.p, stream_); jac_stale_ = geo_resid(); }
-   else if (fused_setup_) { ensure_mat_grad(); model_->ModelSetupLVec(x_cur.p, k, el_jac.p, stream_); jac_stale_ = false; }   // L->E of x and v + SetupJacobianTerms inside the constitutive launch
+   if (use_records()) { model_->ModelSetupLVecRecords(x_cur.p, k, geo_resid() ? nullptr : el_jac.p, stream_); jac_stale_ = geo_resid(); MarkRates(matVars1.p, exa_get_lean_state(ctx_) == 1); }
+   else if (fused_setup_) { ensure_mat_grad(); model_->ModelSetupLVec(x_cur.p, k, el_jac.p, stream_); jac_stale_ = false; MarkRates(matVars1.p, false); }   // L->E of x and v + SetupJacobianTerms inside the constitutive launch
    else {
       ensure_mat_grad();
       abi_check(ctx_, exa_restrict(ctx_, x_cur.p, el_x.p, stream_), "exa_restrict");
       abi_check(ctx_, exa_jacobians(ctx_, el_x.p, el_jac.p, stream_), "exa_jacobians");   // SetupJacobianTerms
       abi_check(ctx_, exa_restrict(ctx_, k, el_v.p, stream_), "exa_restrict");
       model_->ModelSetup(el_jac.p, el_v.p, stream_);
-      jac_stale_ = false;
+      jac_stale_ = false; MarkRates(matVars1.p, false);
    }
    EXA_HC(hipEventRecord(ev.b, stream_)); ev.pending = true;
    timers.qpt_updates += (int64_t)E_ * exa_qpts_per_elem(ctx_); model_calls++;
@@ -805,6 +807,18 @@ void NonlinearMechOperator::Setup(const double* k) {
 }
 template void NonlinearMechOperator::Setup<true>(const double*);
 template void NonlinearMechOperator::Setup<false>(const double*);
+
+void NonlinearMechOperator::MarkRates(const double* p, bool pending) {
+   for (const double*& r : rates_pending_) if (r == p) r = nullptr;
+   if (!pending) return;
+   for (const double*& r : rates_pending_) if (!r) { r = p; return; }
+   throw std::runtime_error("lean state: more than two state arrays wait for their slip rates");
+}
+void NonlinearMechOperator::EnsureSlipRates(const DevBuf<double>& buf) {
+   if (!RatesPending(buf)) return;
+   abi_check(ctx_, exa_slip_rates_from_state(ctx_, buf.p, stream_), "exa_slip_rates_from_state");
+   MarkRates(buf.p, false); rate_launches++;
+}
 
 NonlinearMechOperator::EvPair& NonlinearMechOperator::NextModelTimer() {
    if (ev_ring_.empty()) { ev_ring_.resize(64); for (EvPair& e : ev_ring_) { EXA_HC(hipEventCreate(&e.a)); EXA_HC(hipEventCreate(&e.b)); } }
@@ -1389,6 +1403,7 @@ void SystemDriver::UpdateModel() {
    const bool root = comm.rank == 0 && write_files;
    if (root) append_row(out_dir + "/" + opt_.avg_stress_fname, a, 6);
    if (opt_.additional_avgs) {
+      op.EnsureSlipRates(op.matVars0);
       vol_avg(op.matVars0.p, 28, false, a);
       avg_pl_work.push_back(a[2]);
       if (root) append_row(out_dir + "/" + opt_.avg_pl_work_fname, a + 2, 1);
@@ -1402,6 +1417,7 @@ void SystemDriver::UpdateModel() {
       vol_avg(F.p, 9, true, a);
       avg_def_grad.insert(avg_def_grad.end(), a, a + 9);
       if (root) append_row(out_dir + "/" + opt_.avg_def_grad_fname, a, 9);
+      op.EnsureSlipRates(op.matVars1);
       op.GetModel()->calcDpMat(F.p, s);
       vol_avg(F.p, 9, true, a);
       const double dpv[6] = { a[0], a[4], a[8], a[5], a[2], a[1] };
@@ -1522,6 +1538,7 @@ void SystemDriver::ComputeElementFields() {
       jac.alloc((size_t)exa_qf_size(ctx, 9));
       abi_check(ctx, exa_jacobians(ctx, xe.p, jac.p, s), "exa_jacobians");
    }
+   op.EnsureSlipRates(op.matVars0);   // (the rows average slots 14..25)
    abi_check(ctx, exa_element_fields(ctx, jac.p, op.stress0.p, op.matVars0.p, xe.p, fields_dev_.p, s), "exa_element_fields");
    EXA_HC(hipStreamSynchronize(s));   // xe and jac leave scope
 }

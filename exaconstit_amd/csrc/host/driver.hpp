@@ -186,6 +186,14 @@ class NonlinearMechOperator {
    void GetCapState(int& cap, int& cap2) const { cap = newton_cap_; cap2 = newton_cap2_; }
    void SetCapState(int cap, int cap2);
    bool halo_overlap() const { return overlap_; }      // the gradient action overlaps the halo exchange with its interior blocks
+   // Lean end-of-step state (include/exaconstit_hip.h exa_set_lean_state): the element-blocked record launches leave the inputs of the 12
+   // slip rates in state slots 14..19 instead of the rates, and the buffer they wrote is marked "rates pending".  The mark belongs to the device
+   // array, so it follows matVars0 / matVars1 through their swaps.  Every reader of slots 14..25 calls EnsureSlipRates on its buffer first: one
+   // bandwidth-bound launch (exa_slip_rates_from_state) when the mark is set, nothing otherwise.  EXA_LEAN_STATE=off: full state from every launch.
+   void EnsureSlipRates(const DevBuf<double>& buf);
+   bool RatesPending(const DevBuf<double>& buf) const { return buf.p && (rates_pending_[0] == buf.p || rates_pending_[1] == buf.p); }
+   void ForgetPendingRates() { rates_pending_[0] = rates_pending_[1] = nullptr; }   // the state arrays have been replaced (checkpoint load)
+   int64_t rate_launches = 0;                          // materialisation launches so far (Driver.diagnostics)
    // data (device)
    DevBuf<double> x_ref, x_beg, x_cur, el_x, el_v, el_jac, diag, dinv, weight;
    DevBuf<double> stress0, stress1, matVars0, matVars1, matGrad;
@@ -227,6 +235,8 @@ class NonlinearMechOperator {
    bool fast_p1_ = true, lvec_grad_ = true, fused_setup_ = true; bool lvec_resid_ = false; bool compact_tangent_ = false;
    bool tet_fused_ = false;       // tetrahedra: the Krylov action is the fused kernel of tet_kernels.hip (EXA_TET_ACTION=generic: the table-driven PA / EA action)
    bool tet_geo_ = false;         // tetrahedra, p = 1 fused action: J^-1 from the nodal coordinates (exa_grad_set_coords) instead of the element record
+   const double* rates_pending_[2] = { nullptr, nullptr };   // state arrays whose slots 14..25 wait for EnsureSlipRates
+   void MarkRates(const double* p, bool pending);
    bool cap_auto_ = true; int newton_cap_ = 0, newton_cap2_ = 0; bool tail_resume_ = true; double tail_cost_ = 4.0;
    DevBuf<double> tmp_l_, tmp_r_, el_y_, el_x2_;
    // periodic partitions: the group table, and for several ranks 1 / holders on the node that carries the canonical id and the box-surface mask

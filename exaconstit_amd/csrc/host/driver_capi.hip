@@ -520,6 +520,8 @@ void exa_driver_get_diagnostics(exa_driver* d, int64_t* out) {
    const PCGSolver::Diagnostics& k = d->sd->krylov().diag;
    out[0] = d->sd->oper().model_fail_total; out[1] = k.not_converged; out[2] = k.indefinite_iters; out[3] = k.last_flag;
 }
+// launches of exa_slip_rates_from_state so far (lean end-of-step state: NonlinearMechOperator::EnsureSlipRates)
+int64_t exa_driver_get_rate_launches(exa_driver* d) { return d->sd->oper().rate_launches; }
 
 // out[0] = sqrt((r, M^-1 r) / (r0, M^-1 r0)) reached by the last PCG solve, out[1] = the worst value among the solves that stopped at max_iter
 void exa_driver_get_pcg_reduction(exa_driver* d, double* out2) { out2[0] = d->sd->krylov().diag.last_reduction; out2[1] = d->sd->krylov().diag.worst_capped_reduction; }
@@ -541,6 +543,7 @@ int exa_driver_get_qf_component(exa_driver* d, int which, int comp, double* out,
       const DevBuf<double>* b = which == 0 ? &op.matVars0 : (which == 1 ? &op.matVars1 : (which == 2 ? &op.stress0 : &op.stress1));
       const int W = which < 2 ? 28 : 6;
       if (comp < 0 || comp >= W) throw std::runtime_error("exa_driver_get_qf_component: component out of range");
+      if (which < 2 && comp >= 14 && comp < 26) op.EnsureSlipRates(*b);   // slip rates of a lean state: written now
       EXA_HC(hipStreamSynchronize(op.stream()));
       const std::vector<double> h = b->to_host();
       const exa_ctx* ctx = op.GetModel()->ctx();
@@ -696,6 +699,7 @@ int exa_driver_bench_adapter_route(exa_driver* d, int steps, int iters, double* 
          if (blocked) vk_qf_eb64_to_aos(W, Q, E, src.p, dst.p, s);
          else EXA_HC(hipMemcpyAsync(dst.p, src.p, sizeof(double) * W * P, hipMemcpyDeviceToDevice, s));
       };
+      op.EnsureSlipRates(op.matVars0); op.EnsureSlipRates(op.matVars1);   // (the reference launches are compared on all 28 slots)
       to_aos(28, op.matVars0, sv0); to_aos(6, op.stress0, s0);
       const double dt = op.dt();
       // geometric factors of the end-of-step configuration (MFEM: GetGeometricFactors + the re-layout of exa_jacobians_from_geom)

@@ -158,7 +158,9 @@ __device__ __forceinline__ void rows_to_stage(double* lds, const int lane, const
 }
 constexpr int STG_J = 0, STG_V = 576, STG_G = 768;   // stage offsets (doubles) of the prologue: 64 Jacobian rows, 8 velocity E-vector rows, the trilinear shape table
 
-template <int KIN, bool LVEC, int NFIX, bool QB, bool REC = false, bool STG = false>
+// LEAN (element-blocked record launches, exa_set_lean_state): state slots 14..19 carry the inputs of k_slip_rates_from_state instead of the 12 slip
+// rates (ecm_device.hpp, point_update<.., LEAN>); the dense launches of a tail split run the same instantiation, so a listed point parks the same values
+template <int KIN, bool LVEC, int NFIX, bool QB, bool REC = false, bool STG = false, bool LEAN = false>
 __global__ __launch_bounds__(EXA_MODEL_BS, EXA_MODEL_OCC) void k_model_setup(const MatParams mp, const int Q, const int n_rt, const int64_t P, const double dt,
                                                      double* __restrict__ Jio, const double* __restrict__ G,
                                                      const double* __restrict__ vel, const double* __restrict__ xl, const int32_t* __restrict__ conn, const int nnodes,
@@ -180,6 +182,7 @@ __global__ __launch_bounds__(EXA_MODEL_BS, EXA_MODEL_OCC) void k_model_setup(con
    // 8 consecutive elements of a wave store 8 whole 128-byte lines of the record array ([block][q][pair][lane = element])
    static_assert(!REC || (LVEC && NFIX == 8 && (QB || STG)) || (QB && VG), "record output: the fused p = 1 launches (element-blocked, or staged reference layout) and the p = 2 launch behind its geometry pre-pass");
    static_assert(!STG || (!QB && NFIX != 27), "staged rows: reference layout, generic or trilinear node loops");
+   static_assert(!LEAN || (QB && REC), "lean end-of-step state: the element-blocked record launches");
    const int tail_mode = tail_mode_rt;
    if (tail_mode && (int64_t)blockIdx.x * blockDim.x >= tail[0]) return;   // tail launch: its grid covers the worst case, blocks beyond the list leave before the table fill
    const int n = NFIX ? NFIX : n_rt;
@@ -431,7 +434,7 @@ __global__ __launch_bounds__(EXA_MODEL_BS, EXA_MODEL_OCC) void k_model_setup(con
    // per-thread stash behind the shape table in LDS (PointIO::stash)
    // (STG: a lane beyond the last point repeats the last point to the end - it is neither listed nor counted)
    const bool mine = !STG || io.live;
-   const int rc = point_update<KIN, QS, REC, STG>(mp, dt, L, io, mine ? kcap : (1 << 30), pin, sG + pqo, tsc, trd != 0,
+   const int rc = point_update<KIN, QS, REC, STG, LEAN>(mp, dt, L, io, mine ? kcap : (1 << 30), pin, sG + pqo, tsc, trd != 0,
                                                   TailIO{ tail_out, rs_out, tail_mode ? rs_in : nullptr, P, !tail_mode && rs_out != nullptr && mine });
    if (rc == 1 && mine) atomicAdd(fail, 1);
 }

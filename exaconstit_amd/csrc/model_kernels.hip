@@ -118,16 +118,67 @@ static void launch_model_q(exa_ctx* ctx, double dt, double* J, const double* vel
 }
 
 // fused p = 1 launch that writes the compact gradient records (exa_model_setup_lvec_records)
-template <int KIN>
-static void launch_model_rec(exa_ctx* ctx, double dt, double* J, const double* vel, const double* xl, const double* stress0, const double* state0,
-                             double* stress1, double* state1, hipStream_t s) {
+template <int KIN, bool LEAN>
+static void launch_model_rec_l(exa_ctx* ctx, double dt, double* J, const double* vel, const double* xl, const double* stress0, const double* state0,
+                               double* stress1, double* state1, hipStream_t s) {
    const int bs = EXA_MODEL_BS;
    const int64_t nb = (((int64_t)((ctx->E + 63) / 64) * ctx->Q) + (bs / 64) - 1) / (bs / 64);
    const int trd = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
    launch_levels(ctx, nb, [&](int64_t blocks, int kcap, int* list, int mode, int* list_out, const double* rs_in, double* rs_out) {
-      hipLaunchKernelGGL((k_model_setup<KIN, true, 8, true, true>), dim3((unsigned)blocks), dim3(bs), model_lds_bytes(ctx, ecmdev::kin_is_km(KIN), false, true, mode, true), s, ctx->mp, ctx->Q, ctx->n, ctx->P, dt, J, ctx->G_dev, vel, xl, ctx->conn,
+      hipLaunchKernelGGL((k_model_setup<KIN, true, 8, true, true, false, LEAN>), dim3((unsigned)blocks), dim3(bs), model_lds_bytes(ctx, ecmdev::kin_is_km(KIN), false, true, mode, true), s, ctx->mp, ctx->Q, ctx->n, ctx->P, dt, J, ctx->G_dev, vel, xl, ctx->conn,
                          ctx->nnodes, stress0, state0, stress1, state1, ctx->pa_c, ctx->fail_count_dev, kcap, list, mode, ctx->W_dev, trd, list_out, rs_in, rs_out);
    });
+}
+
+// (a context with exa_set_lean_state on: slip rates on demand, exa_slip_rates_from_state)
+template <int KIN>
+static void launch_model_rec(exa_ctx* ctx, double dt, double* J, const double* vel, const double* xl, const double* stress0, const double* state0,
+                             double* stress1, double* state1, hipStream_t s) {
+   if (ctx->lean_state) { ctx->lean_kin = KIN; launch_model_rec_l<KIN, true>(ctx, dt, J, vel, xl, stress0, state0, stress1, state1, s); }
+   else launch_model_rec_l<KIN, false>(ctx, dt, J, vel, xl, stress0, state0, stress1, state1, s);
+}
+
+// The 12 slip rates of a lean end-of-step state (point_update<.., LEAN>), written in place: one lane per point of the element-blocked layout reads the
+// hardness (slot 13), the lattice strain (14..18) and, Kocks-Mecking, the thermal factor (19), forms the kinetics' per-point values as point_update
+// does and runs the function the full launch runs in its epilogue - the same instantiation, so the same bits.  Bandwidth-bound: 6 - 7 doubles in, 12 out.
+template <int KIN>
+__global__ __launch_bounds__(256) void k_slip_rates_from_state(const MatParams mp, const int Q, const int64_t E, double* __restrict__ state) {
+   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   const int64_t w = t >> 6, e = (w / Q) * 64 + (t & 63);   // wave = (block of 64 elements, q); lane = element
+   if (e >= E) return;
+   double* sv = state + qview<true>(NSTATEV, Q, e, (int)(w % Q)).base;
+   const double h_u = sv[H_H * 64];
+   double e_f[5];
+#pragma unroll
+   for (int i = 0; i < 5; i++) e_f[i] = sv[(H_GDOT + i) * 64];
+   Prob pb; pb.st = nullptr; pb.pqt = nullptr; pb.gs = 64;
+   if (kin_is_km(KIN)) {
+      const double sq = sqrt(h_u);
+      pb.kv.g = mp.go + mp.s * sq; pb.kv.gam_w = mp.gam_wo / sq; pb.kv.gam_r = mp.gam_ro * sq * sq; pb.kv.c_e = sv[(H_GDOT + 5) * 64];
+   } else { pb.kv.g = h_u; pb.kv.gam_w = mp.gam_w; pb.kv.gam_r = 0; pb.kv.c_e = 0; }
+   pb.g_i = frcp(pb.kv.g);
+   double* out = sv + H_GDOT * 64;
+   if constexpr (!kin_is_km(KIN)) { double dis, shr; voce_slip_rates<kin_xn_ct(KIN), true>(mp, pb, e_f, out, dis, shr); }
+   else {
+      if (kin_base(KIN) == KIN_KMBALD_GA && kin_pq1(KIN) && mp.with_g_athermal) km_slip_rates_ga<kin_pq1(KIN), kin_sc_exp(KIN), true>(mp, pb, e_f, out);
+      else km_slip_rates<kin_pq1(KIN), kin_sc_exp(KIN), true>(mp, pb, e_f, out);
+   }
+}
+
+int exa_launch_slip_rates_from_state(exa_ctx* ctx, double* state, hipStream_t s) {
+   const int bs = 256;
+   const dim3 grid((unsigned)((((int64_t)((ctx->E + 63) / 64) * ctx->Q * 64) + bs - 1) / bs));
+#define EXA_RATES_CASE(K) case (K): hipLaunchKernelGGL(k_slip_rates_from_state<(K)>, grid, dim3(bs), 0, s, ctx->mp, ctx->Q, ctx->E, state); break;
+   switch (ctx->lean_kin) {
+      EXA_RATES_CASE(KIN_VOCE) EXA_RATES_CASE(KIN_VOCE | KIN_XN49) EXA_RATES_CASE(KIN_VOCE_NL) EXA_RATES_CASE(KIN_VOCE_NL | KIN_XN49)
+#ifndef EXA_VARIANT_VOCE_ONLY
+      EXA_RATES_CASE(KIN_KMBALD) EXA_RATES_CASE(KIN_KMBALD | KIN_PQ1) EXA_RATES_CASE(KIN_KMBALD_GA) EXA_RATES_CASE(KIN_KMBALD_GA | KIN_PQ1)
+#endif
+      default: ctx->err = "exa_slip_rates_from_state: no lean constitutive launch has run on this context"; return EXA_ERR_STATE;
+   }
+#undef EXA_RATES_CASE
+   EXA_HIP_CHECK(ctx, hipGetLastError());
+   return EXA_OK;
 }
 
 // lists and solver-state buffers of the tail split, allocated on first use; the list counters are cleared for the coming launch sequence

@@ -10,13 +10,13 @@ int exa_launch_geom_p2(exa_ctx*, const double*, const double*, double*, double*,
 
 namespace {
 
-template <int KIN, bool REC>
+template <int KIN, bool REC, bool LEAN = false>
 void launch_p2(exa_ctx* ctx, double dt, double* J, const double* Lx, const double* stress0, const double* state0, double* stress1, double* state1, double* cmat, hipStream_t s) {
    const int bs = EXA_MODEL_BS;
    const int64_t nb = (((int64_t)((ctx->E + 63) / 64) * ctx->Q) + (bs / 64) - 1) / (bs / 64);      // one wave per (64-element block, q)
    const int trd = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
    launch_levels(ctx, nb, [&](int64_t blocks, int kcap, int* list, int mode, int* list_out, const double* rs_in, double* rs_out) {
-      hipLaunchKernelGGL((k_model_setup<KIN, false, 27, true, REC>), dim3((unsigned)blocks), dim3(bs), model_lds_bytes(ctx, ecmdev::kin_is_km(KIN), true, true, mode, false), s,
+      hipLaunchKernelGGL((k_model_setup<KIN, false, 27, true, REC, false, LEAN>), dim3((unsigned)blocks), dim3(bs), model_lds_bytes(ctx, ecmdev::kin_is_km(KIN), true, true, mode, false), s,
                          ctx->mp, ctx->Q, ctx->n, ctx->P, dt, J, (const double*)nullptr, Lx, (const double*)nullptr, ctx->conn, ctx->nnodes, stress0, state0, stress1, state1,
                          REC ? ctx->pa_c : cmat, ctx->fail_count_dev, kcap, list, mode, ctx->W_dev, trd, list_out, rs_in, rs_out);
    });
@@ -24,7 +24,9 @@ void launch_p2(exa_ctx* ctx, double dt, double* J, const double* Lx, const doubl
 
 template <int KIN>
 void launch_p2_kind(exa_ctx* ctx, bool rec, double dt, double* J, const double* Lx, const double* stress0, const double* state0, double* stress1, double* state1, double* cmat, hipStream_t s) {
-   if (rec) launch_p2<KIN, true>(ctx, dt, J, Lx, stress0, state0, stress1, state1, cmat, s);
+   // (the record launch of a context with exa_set_lean_state on: slip rates on demand, exa_slip_rates_from_state)
+   if (rec && ctx->lean_state) { ctx->lean_kin = KIN; launch_p2<KIN, true, true>(ctx, dt, J, Lx, stress0, state0, stress1, state1, cmat, s); }
+   else if (rec) launch_p2<KIN, true>(ctx, dt, J, Lx, stress0, state0, stress1, state1, cmat, s);
    else launch_p2<KIN, false>(ctx, dt, J, Lx, stress0, state0, stress1, state1, cmat, s);
 }
 

@@ -78,6 +78,9 @@ exa_set_newton_caps = _sig("exa_set_newton_caps", C.c_int, C.c_void_p, C.c_int, 
 exa_model_tail_count = _sig("exa_model_tail_count", C.c_int, C.c_void_p, C.c_void_p)
 exa_set_newton_cap_auto = _sig("exa_set_newton_cap_auto", C.c_int, C.c_void_p, C.c_int, C.c_double)
 exa_get_newton_cap = _sig("exa_get_newton_cap", C.c_int, C.c_void_p)
+exa_set_lean_state = _sig("exa_set_lean_state", C.c_int, C.c_void_p, C.c_int)
+exa_get_lean_state = _sig("exa_get_lean_state", C.c_int, C.c_void_p)
+exa_slip_rates_from_state = _sig("exa_slip_rates_from_state", C.c_int, C.c_void_p, dptr, C.c_void_p)
 exa_model_nfev_hist = _sig("exa_model_nfev_hist", C.c_int, C.c_void_p, dptr, C.POINTER(C.c_int), C.c_void_p)
 exa_model_status = _sig("exa_model_status", C.c_int, C.c_void_p, C.c_void_p)
 exa_calc_dp = _sig("exa_calc_dp", C.c_int, C.c_void_p, dptr, dptr, C.c_void_p)
@@ -220,6 +223,7 @@ exa_driver_nfev_hist = _sig("exa_driver_nfev_hist", C.c_int, C.c_void_p, C.POINT
 exa_driver_get_qf_component = _sig("exa_driver_get_qf_component", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_int)
 exa_driver_nfev_hist_of = _sig("exa_driver_nfev_hist_of", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int)
 exa_driver_get_diagnostics = _sig("exa_driver_get_diagnostics", None, C.c_void_p, C.POINTER(C.c_int64))
+exa_driver_get_rate_launches = _sig("exa_driver_get_rate_launches", C.c_int64, C.c_void_p)
 exa_rccl_microbench = _sig("exa_rccl_microbench", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_char_p, C.c_int)
 exa_bootstrap_env = _sig("exa_bootstrap_env", C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
 exa_bootstrap_reply_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p)
@@ -872,7 +876,8 @@ class Driver:
         r = np.zeros(2)
         exa_driver_get_pcg_reduction(self.h, r.ctypes.data_as(C.POINTER(C.c_double)))
         return dict(model_failed_points=int(o[0]), pcg_not_converged=int(o[1]), pcg_indefinite_iters=int(o[2]), pcg_last_flag=int(o[3]),
-                    pcg_last_reduction=float(r[0]), pcg_worst_capped_reduction=float(r[1]))
+                    pcg_last_reduction=float(r[0]), pcg_worst_capped_reduction=float(r[1]),
+                    slip_rate_launches=int(exa_driver_get_rate_launches(self.h)))
 
     def bench_prepare(self, dts, perturb=1.0, advance=True):
         """Kinematic drive to the state the timed passes start from; advance=False keeps the virgin state (elastic first step, dt = dts[0])."""

@@ -137,6 +137,10 @@ void exa_driver_reset_timers(exa_driver* d);
  * library's ECMECH_FAIL; here Newton reports non-convergence), [1] PCG solves without convergence, [2] PCG iterations with
  * (Ad, d) < 0 (MFEM: "The operator is not positive definite"), [3] flag of the last PCG solve (1 ok, 2 max_iter, -1 (Ad, d) = 0). */
 void exa_driver_get_diagnostics(exa_driver* d, int64_t* out4);
+/* Launches of exa_slip_rates_from_state so far.  The driver's element-blocked record launches leave a lean end-of-step state (include/exaconstit_hip.h,
+ * exa_set_lean_state; EXA_LEAN_STATE=off at creation: the full state) and the 12 slip rates are written when a reader of state slots 14..25 asks:
+ * the additional averages, the element fields, a checkpoint, exa_driver_get_qf_component of those slots.  A run that asks for none of them stays at 0. */
+int64_t exa_driver_get_rate_launches(exa_driver* d);
 /* Residual reduction |r|_M / |r0|_M the PCG reached: out2[0] last solve, out2[1] the worst among the solves that stopped at max_iter
  * (MFEM's CGSolver prints "No convergence!" with the final norms, linalg/solvers.cpp; the reference's Newton loop goes on regardless). */
 void exa_driver_get_pcg_reduction(exa_driver* d, double* out2);

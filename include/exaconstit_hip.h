@@ -184,6 +184,18 @@ int exa_model_setup_lvec(exa_ctx* ctx, double dt, const double* coords_lvec_dev 
 int exa_model_setup_lvec_records(exa_ctx* ctx, double dt, const double* coords_lvec_dev, const double* vel_lvec_dev,
                                  const double* stress0_dev, const double* state0_dev,
                                  double* stress1_dev, double* state1_dev, double* jacobian_out_dev, exa_stream s);
+/* Lean end-of-step state (0 = off, the default).  With it on, exa_model_setup_lvec_records on an EXA_QLAYOUT_EB64 context - p = 1 and p = 2, the dense
+ * launches of a tail split included - does not write the 12 slip rates into state1 slots 14..25.  It leaves what they are a function of instead: the
+ * hardness is in slot 13 anyway, the lattice-frame elastic strain of the converged point goes to slots 14..18 and, for the Kocks-Mecking kinds, the
+ * thermal factor of the kinetics to slot 19 (40 / 48 B per point instead of 96, and no extra kinetics pass for the Kocks-Mecking kinds); slots
+ * 20..25 are not written.  Nothing in a constitutive launch reads slots 14..25 of state0.  exa_slip_rates_from_state turns such an array into the
+ * full state in place, with the bits the full launch writes; it must run before anything reads slots 14..25 of it (exa_calc_dp, exa_element_fields,
+ * a 28-wide exa_vol_avg, a copy for a checkpoint).  The caller keeps track of which arrays are lean: running it on a full state destroys the rates.
+ * The kinetics are those of the LAST lean launch of the context.  Every other launch writes all 28 slots, whatever the switch says.
+ * The stand-alone driver turns it on for its own record launches (EXA_LEAN_STATE=off keeps the full state) and materialises on demand. */
+int exa_set_lean_state(exa_ctx* ctx, int on);
+int exa_get_lean_state(exa_ctx* ctx);   /* 1: the next exa_model_setup_lvec_records of this context leaves a lean state1 */
+int exa_slip_rates_from_state(exa_ctx* ctx, double* state_dev, exa_stream s);
 /* Tail split of the constitutive launch (0 = off, the default).  The local Newton solve needs 3-6 evaluations at most points and
  * 10-19 at a few per cent of them, and a wave waits for its slowest lane (measured wave max / mean = 1.2 ... 2.7).  With max_evals = K
  * the launch stops a point after K residual evaluations and a second, dense launch of the same kernel redoes exactly those points from
