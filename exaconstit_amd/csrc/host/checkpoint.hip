@@ -147,9 +147,18 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
      hs.push_back(host_sec("pvd_cycles", cyc)); }
    hs.push_back(host_sec("lattice_strains", lattice_rows_)); hs.push_back(host_sec("lattice_volumes", volume_rows_)); hs.push_back(host_sec("auto_dt", auto_dt_rows_));
    if (opt_.macro_tangent) hs.push_back(host_sec("macro_tangent", macro_tangent_rows));   // (only with the option on: every other checkpoint stays byte for byte what it was)
+   // slip activity (only with the feature on, like the tangent's rows): window start step and pending reset, the rows of the fatigue file
+   if (fatigue_on_) {
+      if (!fatigue_init_) EnsureFatigueInit();
+      const int64_t w[2] = { fatigue_window_start_, fatigue_pending_ ? 1 : 0 };
+      hs.push_back(host_sec("fatigue_window", w, sizeof(w))); hs.push_back(host_sec("fatigue_rows", fatigue_rows));
+   }
    // ---- layout
    std::vector<Section> sec;
    for (const HostSec& x : hs) { Section t; t.name = x.name; t.nbytes = x.bytes.size(); t.checksum = sum64(x.bytes.data(), x.bytes.size()); sec.push_back(t); }
+   // ... and its accumulators (60, global element), ahead of the field sections every file has
+   const size_t slip_sec = sec.size();
+   if (fatigue_on_) { Section t; t.name = "slip_activity"; t.nbytes = 8ull * EXA_NSLIPACC * (uint64_t)part.E_glob; sec.push_back(t); }
    const size_t first_field = sec.size();
    { Section t; t.name = "x_beg"; t.nbytes = 24 * (uint64_t)part.NN_glob; sec.push_back(t); t.name = "v_sol"; sec.push_back(t);
      t.name = "stress0"; t.nbytes = 8ull * 6 * Q * (uint64_t)part.E_glob; sec.push_back(t); t.name = "matVars0"; t.nbytes = 8ull * nsv * Q * (uint64_t)part.E_glob; sec.push_back(t);
@@ -169,7 +178,7 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
    all_ok(comm, comm.rank != 0 || fd >= 0, "checkpoint: cannot create " + tmp);
    if (comm.rank != 0) fd = ::open(tmp.c_str(), O_RDWR);
    all_ok(comm, fd >= 0, "checkpoint: cannot open " + tmp);
-   std::vector<uint64_t> sums(6, 0);
+   std::vector<uint64_t> sums(7, 0);
    bool ok = true; std::string why;
    const std::vector<uint8_t> skip = nodes_of_lower_ranks(part, comm.rank);
    std::vector<double> rows[2];
@@ -233,11 +242,20 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
          std::vector<double> hv(n); can.download(hv.data(), n, s); cks.download(&sums[2 + f], 1, s);
          move_rows<true>(fd, sec[first_field + 2 + f].offset, sizeof(double) * W[f] * Q, part.elem_gid, nullptr, (char*)hv.data());
       }
+      if (fatigue_on_ && part.E > 0) {   // planar [60][E_pad] on the device -> rows of 60 by global element (480 B per element: transposed on the host)
+         const std::vector<double> pl = fat_acc_.to_host(s);
+         const size_t Ep = pl.size() / EXA_NSLIPACC, El = (size_t)part.E;
+         std::vector<double> hv(EXA_NSLIPACC * El);
+         for (int k = 0; k < EXA_NSLIPACC; k++) for (size_t e = 0; e < El; e++) hv[EXA_NSLIPACC * e + k] = pl[k * Ep + e];
+         sums[6] = sum64(hv.data(), sizeof(double) * hv.size());
+         move_rows<true>(fd, sec[slip_sec].offset, sizeof(double) * EXA_NSLIPACC, part.elem_gid, nullptr, (char*)hv.data());
+      }
       if (comm.rank != 0) { const bool synced = ::fsync(fd) == 0; const bool closed = ::close(fd) == 0; fd = -1; if (!synced || !closed) throw std::runtime_error("checkpoint: cannot flush " + tmp); }
    } catch (const std::exception& e) { ok = false; why = e.what(); }
    all_ok(comm, ok, why.empty() ? "checkpoint: write failed" : why);
    allreduce_u64(comm, sums, s);   // (also the barrier after which every rank's rows are in the file)
    for (int f = 0; f < 6; f++) sec[first_field + f].checksum = sums[f];
+   if (fatigue_on_) sec[slip_sec].checksum = sums[6];
    ok = true; why.clear();
    if (comm.rank == 0) {
       try {
@@ -319,6 +337,16 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    host_doubles("lattice_strains", H, r_ls); host_doubles("lattice_volumes", H, r_lv);
    std::vector<double> r_mt;   // rows of the macroscopic tangent: only files written with Visualizations.macro_tangent on carry them
    if (opt_.macro_tangent && find(sec, "macro_tangent")) host_doubles("macro_tangent", MACRO_TANGENT_ROW, r_mt);
+   // slip activity: a run with the feature on continues the accumulators of the file; with it off the sections are ignored
+   std::vector<double> r_fat; int64_t fat_window[2] = { 0, 0 }; const Section* fat_sec = nullptr;
+   if (fatigue_on_) {
+      if (!find(sec, "slip_activity")) throw std::runtime_error("checkpoint: section 'slip_activity' is missing: the file was written without Visualizations.fatigue / enable_slip_activity and cannot continue the accumulators of this run (" + path + ")");
+      fat_sec = &need("slip_activity", 8ull * EXA_NSLIPACC * (uint64_t)part.E_glob, true);
+      const Section& w = need("fatigue_window", 16, true);
+      pread_all(fd, fat_window, 16, w.offset);
+      if (sum64(fat_window, 16) != w.checksum) throw std::runtime_error("checkpoint: checksum mismatch in section 'fatigue_window' (" + path + ")");
+      host_doubles("fatigue_rows", FATIGUE_ROW, r_fat);
+   }
    std::vector<int32_t> r_stats;
    { const Section& t = need("solver_stats", 0, false);
      std::vector<unsigned char> b(t.nbytes); if (t.nbytes) pread_all(fd, b.data(), t.nbytes, t.offset);
@@ -348,10 +376,11 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    // Nothing of the driver is touched before every checksum has been verified: the node fields wait on the host, the quadrature functions are
    // unpacked into copies of the driver's buffers (copies, so that the padding lanes of the last element block keep what they held), which
    // replace the originals afterwards.  A load that fails leaves the driver as it was created.
-   std::vector<uint64_t> sums(4, 0);
+   std::vector<uint64_t> sums(5, 0);
    bool ok = true; std::string why;
    std::vector<double> nodes[2];
    DevBuf<double> scratch[2];
+   std::vector<double> fat_planar;
    try {
       const std::vector<uint8_t> skip = nodes_of_lower_ranks(part, comm.rank);
       std::unordered_map<int64_t, int> local_of;
@@ -379,9 +408,19 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
          ck(ctx, exa_qf_unpack(ctx, W[f], can.p, scratch[f].p, cks.p, s), "exa_qf_unpack");
          cks.download(&sums[2 + f], 1, s);
       }
+      if (fat_sec) {
+         int64_t n = 0; exa_slip_activity_sizes(part.E, &n);
+         const size_t El = (size_t)part.E, Ep = (size_t)n / EXA_NSLIPACC;
+         std::vector<double> hv(EXA_NSLIPACC * El);
+         move_rows<false>(fd, fat_sec->offset, sizeof(double) * EXA_NSLIPACC, part.elem_gid, nullptr, (char*)hv.data());
+         sums[4] = sum64(hv.data(), sizeof(double) * hv.size());
+         fat_planar.assign((size_t)std::max<int64_t>(n, 1), 0.0);
+         for (int k = 0; k < EXA_NSLIPACC; k++) for (size_t e = 0; e < El; e++) fat_planar[k * Ep + e] = hv[EXA_NSLIPACC * e + k];
+      }
    } catch (const std::exception& e) { ok = false; why = e.what(); }
    all_ok(comm, ok, why.empty() ? "checkpoint: read failed" : why);
    allreduce_u64(comm, sums, s);
+   if (fat_sec && sums[4] != fat_sec->checksum) throw std::runtime_error("checkpoint: checksum mismatch in section 'slip_activity' (" + path + ")");
    for (int f = 0; f < 4; f++) if (sums[f] != fs[f]->checksum) throw std::runtime_error("checkpoint: checksum mismatch in section '" + fs[f]->name + "' (" + path + ")");
    // ---- verified: from here on the driver takes the state over
    op.x_beg.upload(nodes[0].data(), nodes[0].size(), s); op.x_cur.upload(nodes[0].data(), nodes[0].size(), s); v_sol.upload(nodes[1].data(), nodes[1].size(), s);
@@ -398,6 +437,10 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    avg_stress.swap(r_stress); avg_def_grad.swap(r_F); avg_pl_work.swap(r_pw); avg_dp_tensor.swap(r_dp);
    lattice_rows_.swap(r_ls); volume_rows_.swap(r_lv); auto_dt_rows_.swap(r_dt);
    macro_tangent_rows.swap(r_mt);
+   if (fat_sec) {
+      fat_acc_.upload(fat_planar, s); fat_gid_.upload(part.elem_gid, s);
+      fatigue_window_start_ = fat_window[0]; fatigue_pending_ = fat_window[1] != 0; fatigue_init_ = true; fatigue_rows.swap(r_fat);
+   }
    { auto& cyc = pvd_cycles_[vis_dir()]; cyc.clear(); for (size_t i = 0; i + 1 < r_cyc.size(); i += 2) cyc.emplace_back((int)r_cyc[i], r_cyc[i + 1]); if (cyc.empty()) pvd_cycles_.erase(vis_dir()); }
    op.model_calls = (int)h.model_calls; op.SetCapState(h.newton_cap, h.newton_cap2);
    // the essential-boundary set in force, without the SolveInit that belongs to the step where it changed
@@ -413,6 +456,7 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
       }
       if (opt_.lightup()) { rewrite_rows(out_dir + "/" + opt_.lightup_strain_fname, lattice_rows_, H); rewrite_rows(out_dir + "/" + opt_.lightup_volume_fname, volume_rows_, H); }
       if (opt_.macro_tangent) write_macro_tangent_rows(out_dir + "/" + opt_.macro_tangent_fname, macro_tangent_rows, false);
+      if (opt_.fatigue) write_fatigue_rows(out_dir + "/" + opt_.fatigue_fname, fatigue_rows, false);
       if (opt_.dt_auto) { std::ofstream f(out_dir + "/" + opt_.auto_dt_fname, std::ios_base::trunc); for (double v : auto_dt_rows_) f << std::setprecision(12) << v << std::endl; }
    }
    restarted_ = true; ckpt_foreign_calls_ = (long)op.model_calls;

@@ -1115,6 +1115,7 @@ void SystemDriver::init(const std::vector<double>& props, const std::vector<doub
    ks.rel_tol = opt_.krylov_rel; ks.abs_tol = opt_.krylov_abs; ks.max_iter = opt_.krylov_iter;
    if (const char* g = std::getenv("EXA_PCG_GRAPH")) { if (std::string(g) == "0") ks.graph_max_dofs = 0; else if (std::string(g) == "all") ks.graph_max_dofs = INT64_MAX; }
    krylov_.reset(new PCGSolver(*oper_, ks));
+   if (opt_.fatigue) EnableSlipActivity();
 }
 
 // BCManager::updateBCData + UpdateEssTDofs; component codes reference src/BCData.cpp:25-116
@@ -1370,7 +1371,7 @@ bool SystemDriver::Solve(double* x) {
       ok = NewtonSolve(x, st); iter++;
    }
    if (iter > 0) time = time - dt_old + dt_class;
-   last_dt_ = dt_class;
+   last_dt_ = dt_class; step_dt_ = dt_class;   // (the size the step was solved with, after any cut-back: dt_class becomes the next step's proposal below)
    if (ok) auto_dt_rows_.push_back(dt_class);
    if (ok && write_files && comm.rank == 0) { std::ofstream f(out_dir + "/" + opt_.auto_dt_fname, std::ios_base::app); f << std::setprecision(12) << dt_class << std::endl; }
    const double niter_scale = (double)opt_.newton_iter * opt_.dt_scale;
@@ -1434,14 +1435,15 @@ bool SystemDriver::Step(int ti, bool commit) {
    // texture file of step 0 (the initial texture) at the same point; the two share the element rows
    const bool cycle0 = opt_.paraview && write_files && commit && steps_done == 0 && !cycle0_saved_;
    const bool texture0 = opt_.texture && write_files && commit && steps_done == 0 && !texture0_written_;
-   if (cycle0 || texture0) ComputeElementFields();
+   if (fatigue_on_ && !fatigue_init_) EnsureFatigueInit();   // (leaves the rows of the initial state in fields_dev_)
+   else if (cycle0 || texture0) ComputeElementFields();
    if (cycle0) { SaveFields(vis_dir(), 0, 0.0, true); cycle0_saved_ = true; }
    if (texture0) { WriteTexture(0, time); texture0_written_ = true; }
    double dt_real;
    if (opt_.dt_cust) dt_real = opt_.cust_dt[ti - 1];
    else if (opt_.dt_auto) dt_real = std::min(dt_class, opt_.t_final - time);
    else dt_real = std::min(opt_.dt, opt_.t_final - time);
-   time += dt_real; dt_class = dt_real;
+   time += dt_real; dt_class = dt_real; step_dt_ = dt_real;
    op.SetDt(dt_real);
    stats.emplace_back();
    step_solved_ = false;
@@ -1470,19 +1472,28 @@ bool SystemDriver::Step(int ti, bool commit) {
    // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
    // per-grain averages and texture on the same cadence, whether or not ParaView output is on
    bool due = false;
-   if ((opt_.paraview || opt_.grain_avgs || opt_.texture || opt_.macro_tangent || opt_.lattice_curvature) && write_files) {
+   bool last_step = false;
+   if ((opt_.paraview || opt_.grain_avgs || opt_.texture || opt_.macro_tangent || opt_.lattice_curvature || opt_.fatigue) && write_files) {
       bool last = ti >= opt_.nsteps;
       if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
-      due = last || ti % opt_.vis_steps == 0;
+      due = last || ti % opt_.vis_steps == 0; last_step = last;
    }
    const bool save = opt_.paraview && due, grains = opt_.grain_avgs && due, texture = opt_.texture && due;
    // light-up analysis: one row of lattice strains and one of fibre volume fractions per converged step, from the same element rows
    const bool lattice = opt_.lightup() && write_files;
    const bool curvature = opt_.lattice_curvature && due;
-   if (save || lattice || grains || texture || curvature) ComputeElementFields();
+   // slip activity: a file row every fatigue_cycle_steps steps, followed by the request to restart the window, and at the last step (0: on the cadence above)
+   const bool cycle_end = opt_.fatigue && write_files && opt_.fatigue_cycle_steps > 0 && ti % opt_.fatigue_cycle_steps == 0;
+   const bool fatigue = opt_.fatigue && write_files && (opt_.fatigue_cycle_steps > 0 ? (cycle_end || last_step) : due);
+   // (slip activity on: CommitStep left the rows of this state there - checked, not assumed: the stamp of the last element-field launch)
+   if ((save || lattice || grains || texture || curvature || fatigue) && !(fatigue_on_ && fields_are_current())) ComputeElementFields();
+   SlipActivityResult fat;
+   if (fatigue || (save && opt_.fatigue)) SlipActivity(opt_.fatigue_k, opt_.fatigue_sigma_y, fat, true, save);
+   if (fatigue) WriteFatigue(ti, fat);
+   if (cycle_end && !last_step) ResetFatigueWindow();
    std::vector<double> curv_rows;
    if (curvature) { double m[7]; LatticeCurvature(opt_.lattice_curvature_burgers, curv_rows, m, true, save); WriteLatticeCurvature(ti, m); }
-   if (save) SaveFields(vis_dir(), ti, time, true, curvature ? &curv_rows : nullptr);
+   if (save) SaveFields(vis_dir(), ti, time, true, curvature ? &curv_rows : nullptr, opt_.fatigue ? &fat : nullptr);
    if (texture) WriteTexture(ti, time);
    if (opt_.macro_tangent && due) WriteMacroTangent(ti);
    if (grains) {
@@ -1508,6 +1519,7 @@ void SystemDriver::CommitStep() {
    UpdateModel();
    oper_->SwapCoords();
    steps_done++;
+   if (fatigue_on_) AccumulateSlip();
 }
 
 int SystemDriver::RunAll() {
@@ -1540,6 +1552,7 @@ void SystemDriver::ComputeElementFields() {
    }
    op.EnsureSlipRates(op.matVars0);   // (the rows average slots 14..25)
    abi_check(ctx, exa_element_fields(ctx, jac.p, op.stress0.p, op.matVars0.p, xe.p, fields_dev_.p, s), "exa_element_fields");
+   fields_step_ = steps_done; fields_calls_ = op.model_calls;
    EXA_HC(hipStreamSynchronize(s));   // xe and jac leave scope
 }
 
@@ -1846,18 +1859,21 @@ void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const 
    if (!f) throw std::runtime_error("grain averages: writing " + path + " failed");
 }
 
-void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool fields_current, const std::vector<double>* curv) {
+void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool fields_current, const std::vector<double>* curv, const SlipActivityResult* fat) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
    if (!fields_current) ComputeElementFields();
    std::vector<double> curv_own;
    if (opt_.lattice_curvature && !curv) { double m[7]; LatticeCurvature(opt_.lattice_curvature_burgers, curv_own, m, true); curv = &curv_own; }
+   SlipActivityResult fat_own;
+   if (opt_.fatigue && !fat) { SlipActivity(opt_.fatigue_k, opt_.fatigue_sigma_y, fat_own, true); fat = &fat_own; }
    const std::vector<double> fields = fields_dev_.to_host(s);
    const std::vector<double> xc = op.x_cur.to_host(s), xr = op.x_ref.to_host(s), v = v_sol.to_host(s);
    vtu::Piece p;
    p.E = part.E; p.NN = part.NN; p.n = part.n; p.tet = part.geom == 1; p.conn = part.conn.data();
    p.x_cur = xc.data(); p.x_ref = xr.data(); p.vel = v.data(); p.fields = fields.data(); p.attr = elem_attr.data(); p.gid = part.elem_gid.data();
    if (opt_.lattice_curvature) { p.has_curv = true; p.curv = curv->data(); }
+   if (opt_.fatigue) { p.has_fatigue = true; p.fip = fat->fip.data(); p.slip_acc = fat->acc.data(); }
    vtu::save_cycle(dir, comm.rank, comm.nranks, cycle, t, opt_.light_up, p, pvd_cycles_[dir]);
 }
 

@@ -246,6 +246,10 @@ class NonlinearMechOperator {
    MixedTable mix_tab_; DevBuf<int32_t> mix_img_, mix_face_; DevBuf<uint8_t> mix_code_; DevBuf<double> mix_x_, mix_part_, mix_h_, mix_f_, mix_res_;
 };
 
+constexpr int FATIGUE_NSUMMARY = 8, FATIGUE_ROW = 9;   // SlipActivityResult::summary; row of the fatigue file: step, time, window start, mean FIP, max FIP, element, mean and max AccumulatedSlip, max ShearRange
+void write_fatigue_rows(const std::string& path, const std::vector<double>& rows, bool append);
+void write_fatigue_grains(const std::string& path, int n, const int32_t* ids, const double* vals3);
+
 class SystemDriver {
  public:
    SystemDriver(const ExaOptions& opt, int rank, int nranks, const void* nccl_uid);
@@ -321,7 +325,9 @@ class SystemDriver {
    // ParaView save of those fields as cycle `cycle` at time t under dir (host/vtu.hpp); every rank calls it.  fields_current: fields_dev_
    // already holds the rows of this state (computed once for both the save and the lattice strains of a step)
    // curv ([E][EXA_NCURV], Visualizations.lattice_curvature only): the rows of LatticeCurvature of this state; computed here when null
-   void SaveFields(const std::string& dir, int cycle, double t, bool fields_current = false, const std::vector<double>* curv = nullptr);
+   struct SlipActivityResult;
+   // fat (Visualizations.fatigue only): the evaluation of this state; computed here when null
+   void SaveFields(const std::string& dir, int cycle, double t, bool fields_current = false, const std::vector<double>* curv = nullptr, const SlipActivityResult* fat = nullptr);
    // lattice strains of the {hkl} families (3 integers each; options.hpp check_lightup) of the same state, summed over all ranks (every rank calls
    // it): strain[j] = volume-weighted mean of s^T eps s over the elements of fibre j (NaN when the fibre is empty), volfrac[j] = its volume fraction
    void LatticeStrains(const std::vector<int>& hkl, const double s_dir[3], double tol_deg, double* strain, double* volfrac, bool fields_current = false);
@@ -333,6 +339,23 @@ class SystemDriver {
    // means of GROD, KAM and the GND density, their maxima and the total volume: { mean GROD, max GROD, mean KAM, max KAM, mean GND, max GND, V }
    // want_rows = false: the summary alone (rows is left empty and the [E][EXA_NCURV] copy to the host is skipped)
    void LatticeCurvature(double burgers, std::vector<double>& rows, double* summary7, bool fields_current = false, bool want_rows = true);
+   // Slip-system activity and the Fatemi-Socie fatigue indicator parameter.  With the feature on (Visualizations.fatigue, or
+   // EnableSlipActivity before the first step) CommitStep adds the committed step to the 60 accumulators of every element, from the rows of one
+   // ComputeElementFields launch that the step's other analyses share.  A window reset is a request: it is carried out, fused into the accumulate
+   // launch, at the end of the next committed step, whose values start the new window (before step 1 the window is the initial state already).
+   struct SlipActivityResult {
+      std::vector<double> acc, fip;            // [E][EXA_NSLIPACC] (Gamma | A | Gamma_min | Gamma_max | N_max, 12 each) and [E][EXA_NFIP] of the local elements
+      double summary[FATIGUE_NSUMMARY];        // over all ranks: volume, mean FIP, max FIP, global element of the max, mean and max AccumulatedSlip, max ShearRange, window start step
+      std::vector<int32_t> grain_ids; std::vector<double> grain_vals;   // over all ranks, ascending ids of the grains with elements: volume, mean FIP, max FIP
+   };
+   void EnableSlipActivity();
+   bool slip_activity_on() const { return fatigue_on_; }
+   // evaluation of the committed state, read-only on the accumulators (every rank calls it); want_acc = false: res.acc is left empty
+   void SlipActivity(double k_fs, double sigma_y, SlipActivityResult& res, bool fields_current = false, bool want_acc = true);
+   void ResetFatigueWindow();
+   // one row of Visualizations.fatigue_fname and the per-grain file of this step, from an evaluation with the options' k and sigma_y
+   void WriteFatigue(int step, const SlipActivityResult& res);
+   std::vector<double> fatigue_rows;           // FATIGUE_ROW values per written evaluation (checkpoint host section)
    // grain map of a synthetic driver before its first step: grain (1..G) of every global element and the orientation of every grain (normalised
    // here); the elements' initial orientations and states become their grain's
    void SetGrains(const int32_t* grain_of_global_elem, int64_t n_global, const double* grain_quats, int G);
@@ -354,6 +377,10 @@ class SystemDriver {
    std::vector<uint8_t> ess_host_; std::vector<double> ess_val_host_;
    DevBuf<uint8_t> vel_mask_, vg_mask_; bool have_vel_ = false, have_vgrad_ = false; double vgrad_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
    double last_dt_ = 0.0;
+   double step_dt_ = 0.0;                       // size of the step last solved: Time.Auto after any cut-back, otherwise the dt Step took (AccumulateSlip)
+   // committed step and constitutive-launch count at which ComputeElementFields last filled fields_dev_: the rows are those of the state at hand iff both match
+   int fields_step_ = -1; long fields_calls_ = -1;
+   bool fields_are_current() const { return fields_step_ == steps_done && fields_calls_ == (long)oper_->model_calls && fields_dev_.n == (size_t)EXA_NFIELDS * part.E; }
    bool cycle0_saved_ = false;
    DevBuf<double> fields_dev_, lattice_sums_;   // [E][EXA_NFIELDS] element rows; 2 H + 1 lattice-strain sums
    bool synthetic_ = false;
@@ -368,6 +395,12 @@ class SystemDriver {
    DevBuf<double> curv_work_, curv_nodal_, curv_rows_, curv_sum_, curv_xe_;   // LatticeCurvature: records, nodal planes, rows, 7 sums, current coordinates as an E-vector
    void WriteLatticeCurvature(int step, const double* summary7);
    bool texture0_written_ = false;
+   // slip activity: on / accumulators initialised / reset requested; first step of the window; planar accumulators, FIP rows, 7 sums (+ per-grain sums),
+   // global element ids on the device; unit plane normals of the model
+   bool fatigue_on_ = false, fatigue_init_ = false, fatigue_pending_ = false; int64_t fatigue_window_start_ = 0;
+   DevBuf<double> fat_acc_, fat_rows_, fat_sum_, fat_grain_; DevBuf<int64_t> fat_gid_; double fat_normals_[36];
+   void EnsureFatigueInit();
+   void AccumulateSlip();
    // rows that exist only in append-mode files otherwise (checkpoint host sections): light-up strains / volume fractions, accepted dt of Time.Auto
    std::vector<double> lattice_rows_, volume_rows_, auto_dt_rows_;
    bool mixed_ = false, mac_have_ = false, mix_bc_changed_ = false; uint8_t free_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };

@@ -870,6 +870,63 @@ int exa_options_query_lattice_curvature(const char* toml_path, int* enabled, dou
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+int exa_driver_enable_slip_activity(exa_driver* d, char* err, int errlen) {
+   try { d->sd->EnableSlipActivity(); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+int exa_driver_reset_fatigue_window(exa_driver* d, char* err, int errlen) {
+   try { d->sd->ResetFatigueWindow(); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+int exa_driver_slip_activity(exa_driver* d, double k_fs, double sigma_y, double* acc_out, double* fip_out, int64_t* elem_gid, int32_t* attribute, double* summary8,
+                             int32_t* grain_ids, double* grain_vals3, int64_t grain_cap, int64_t* n_grains, char* err, int errlen) {
+   try {
+      SystemDriver& sd = *d->sd;
+      if (acc_out || fip_out || summary8 || n_grains) {
+         SystemDriver::SlipActivityResult r;
+         sd.SlipActivity(k_fs, sigma_y, r, false, acc_out != nullptr);
+         if (acc_out) std::memcpy(acc_out, r.acc.data(), sizeof(double) * r.acc.size());
+         if (fip_out) std::memcpy(fip_out, r.fip.data(), sizeof(double) * r.fip.size());
+         if (summary8) std::memcpy(summary8, r.summary, sizeof(r.summary));
+         const int64_t n = (int64_t)r.grain_ids.size();
+         if (n_grains) *n_grains = n;
+         if (n <= grain_cap) {
+            if (grain_ids) std::memcpy(grain_ids, r.grain_ids.data(), sizeof(int32_t) * n);
+            if (grain_vals3) std::memcpy(grain_vals3, r.grain_vals.data(), sizeof(double) * r.grain_vals.size());
+         }
+      }
+      if (elem_gid) std::memcpy(elem_gid, sd.part.elem_gid.data(), sizeof(int64_t) * sd.part.E);
+      if (attribute) std::memcpy(attribute, sd.elem_attr.data(), sizeof(int32_t) * sd.part.E);
+      return sd.part.E;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_options_query_fatigue(const char* toml_path, int* out2, double* out2d, char* fname, int fnamelen, char* err, int errlen) {
+   try {
+      ExaOptions o; o.parse_options(toml_path);
+      if (out2) { out2[0] = o.fatigue ? 1 : 0; out2[1] = o.fatigue_cycle_steps; }
+      if (out2d) { out2d[0] = o.fatigue_k; out2d[1] = o.fatigue_sigma_y; }
+      if (fname && fnamelen > 0) {
+         if ((int)o.fatigue_fname.size() >= fnamelen) throw std::runtime_error("Visualizations.fatigue_fname longer than the buffer");
+         std::strcpy(fname, o.fatigue_fname.c_str());
+      }
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
+int exa_fatigue_write(const char* path, int nrows, const double* rows9, int append, char* err, int errlen) {
+   try {
+      if (!path || nrows < 0 || (nrows > 0 && !rows9)) throw std::runtime_error("exa_fatigue_write: a path and nrows rows are required");
+      write_fatigue_rows(path, std::vector<double>(rows9, rows9 + (size_t)FATIGUE_ROW * nrows), append != 0);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+int exa_fatigue_grains_write(const char* path, int n, const int32_t* grain_ids, const double* vals3, char* err, int errlen) {
+   try {
+      if (!path || n < 0 || (n > 0 && (!grain_ids || !vals3))) throw std::runtime_error("exa_fatigue_grains_write: a path, ids and values are required");
+      write_fatigue_grains(path, n, grain_ids, vals3);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
 int exa_driver_set_grains(exa_driver* d, const int32_t* grain_of_global_element, const double* grain_quats, int G, int64_t n_global, char* err, int errlen) {
    try {
       d->sd->SetGrains(grain_of_global_element, n_global, grain_quats, G);

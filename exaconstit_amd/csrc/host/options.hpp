@@ -153,6 +153,11 @@ struct ExaOptions {
    // max of GROD, KAM and the GND density, 17 significant digits) appended to <out_dir>/<lattice_curvature_fname> every Visualizations.steps steps and
    // at the last step, and four more cell arrays in the ParaView pieces; lattice_curvature_burgers: Burgers vector length in the mesh's length unit
    bool lattice_curvature = false; double lattice_curvature_burgers = 1.0; std::string lattice_curvature_fname = "lattice_curvature.txt";
+   // slip-system activity and the Fatemi-Socie fatigue indicator parameter (driver.hip, SystemDriver::SlipActivity): accumulated in every
+   // committed step; evaluated every fatigue_cycle_steps steps (0: every Visualizations.steps steps) and at the last step - one row appended to
+   // <out_dir>/<fatigue_fname>, the per-grain file fatigue_grains_<step %06d>.txt - and, with fatigue_cycle_steps > 0, the window reset after it; four
+   // more cell arrays in the ParaView pieces.  fatigue_sigma_y (the yield stress that scales the normal stress) has no default
+   bool fatigue = false; double fatigue_k = 0.5, fatigue_sigma_y = 0.0; int fatigue_cycle_steps = 0; std::string fatigue_fname = "fatigue.txt";
    static const char* macro_tangent_needs_periodic() { return "Visualizations.macro_tangent = true needs BCs.periodic = true: the homogenised tangent is that of a periodic cell"; }
    // the checks of the texture keys, shared with exa_driver_pole_figures (hkl: 3 integers per family, dirs: 3 components per direction,
    // normalised in place; the driver takes 0 families as long as there is a direction)
@@ -385,6 +390,27 @@ struct ExaOptions {
          if (f->kind != TomlValue::STR || f->str.empty() || f->str.find('/') != std::string::npos)
             throw std::runtime_error("Visualizations.lattice_curvature_fname must be a non-empty file name without '/'");
          lattice_curvature_fname = f->str;
+      }
+      if (const TomlValue* t = d.get("Visualizations.fatigue")) {
+         if (t->kind != TomlValue::BOOL) throw std::runtime_error("Visualizations.fatigue must be true or false");
+         fatigue = t->b;
+      }
+      if (const TomlValue* k = d.get("Visualizations.fatigue_k")) {
+         if (k->kind != TomlValue::NUM || !(k->num >= 0.0) || !std::isfinite(k->num)) throw std::runtime_error("Visualizations.fatigue_k must be a number >= 0");
+         fatigue_k = k->num;
+      }
+      if (const TomlValue* y = d.get("Visualizations.fatigue_sigma_y")) {
+         if (y->kind != TomlValue::NUM || !(y->num > 0.0) || !std::isfinite(y->num)) throw std::runtime_error("Visualizations.fatigue_sigma_y must be a number > 0");
+         fatigue_sigma_y = y->num;
+      } else if (fatigue) throw std::runtime_error("Visualizations.fatigue = true needs Visualizations.fatigue_sigma_y (the yield stress in the stress unit of the run; no default is offered)");
+      if (const TomlValue* v = d.get("Visualizations.fatigue_cycle_steps")) {
+         if (v->kind != TomlValue::NUM || v->num != std::floor(v->num) || v->num < 0 || v->num > 1e9) throw std::runtime_error("Visualizations.fatigue_cycle_steps must be a whole number >= 0");
+         fatigue_cycle_steps = (int)v->num;
+      }
+      if (const TomlValue* f = d.get("Visualizations.fatigue_fname")) {
+         if (f->kind != TomlValue::STR || f->str.empty() || f->str.find('/') != std::string::npos)
+            throw std::runtime_error("Visualizations.fatigue_fname must be a non-empty file name without '/'");
+         fatigue_fname = f->str;
       }
       if (const TomlValue* r = d.get("Visualizations.macro_tangent_rel_tol")) {
          if (r->kind != TomlValue::NUM || !(r->num > 0.0) || !(r->num < 1.0)) throw std::runtime_error("Visualizations.macro_tangent_rel_tol must be a number in (0, 1)");

@@ -79,6 +79,7 @@ struct Piece {
    const double* fields = nullptr;                                // [E][EXA_NFIELDS] (exa_element_fields)
    const int32_t* attr = nullptr; const int64_t* gid = nullptr;   // grain id (element attribute), global element index
    bool has_curv = false; const double* curv = nullptr;           // Visualizations.lattice_curvature: [E][EXA_NCURV] (exa_curvature_elements)
+   bool has_fatigue = false; const double* fip = nullptr; const double* slip_acc = nullptr;   // Visualizations.fatigue: [E][EXA_NFIP] (exa_fip_rows), [E][EXA_NSLIPACC]
 };
 
 // the cell arrays of a save, in the order of the reference's RegisterField calls (ElemCentroid and XtalElasticStrain only with light_up)
@@ -101,6 +102,11 @@ inline std::vector<Array> cell_arrays(const Piece& p, bool light_up) {
       auto ccol = [&](const char* nm, int c0, int nc) { return Array{ nm, T::F64, nc, p.curv + c0, 8 * EXA_NCURV, 8 }; };
       a.push_back(ccol("GROD", EXA_C_GROD, 1)); a.push_back(ccol("KAM", EXA_C_KAM, 1)); a.push_back(ccol("GNDDensity", EXA_C_GND, 1));
       a.push_back(ccol("LatticeCurvature", EXA_C_CURVATURE, 9));
+   }
+   if (p.has_fatigue) {
+      auto fcol = [&](const char* nm, int c0) { return Array{ nm, T::F64, 1, p.fip + c0, 8 * EXA_NFIP, 8 }; };
+      a.push_back(fcol("FIP", EXA_FIP_FIP)); a.push_back(fcol("ShearRange", EXA_FIP_SHEARRANGE)); a.push_back(fcol("AccumulatedSlip", EXA_FIP_ACCUMULATEDSLIP));
+      a.push_back(Array{ "SlipAccumulated", T::F64, 12, p.slip_acc + EXA_ACC_SLIP, 8 * EXA_NSLIPACC, 8 });
    }
    return a;
 }
@@ -144,14 +150,14 @@ inline void write_piece(const std::string& path, const Piece& p, bool light_up) 
    if (!o) throw std::runtime_error("write failed: " + path);
 }
 
-inline void write_pvtu(const std::string& path, int nranks, bool light_up, bool has_curv = false) {
+inline void write_pvtu(const std::string& path, int nranks, bool light_up, bool has_curv = false, bool has_fatigue = false) {
    std::ofstream o(path);
    if (!o) throw std::runtime_error("cannot write " + path);
    o << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"" << (is_little() ? "LittleEndian" : "BigEndian") << "\" header_type=\"UInt32\">\n"
      << "  <PUnstructuredGrid GhostLevel=\"0\">\n    <PPoints>\n      <PDataArray type=\"Float64\" Name=\"Points\" NumberOfComponents=\"3\"/>\n    </PPoints>\n"
      << "    <PPointData>\n      <PDataArray type=\"Float64\" Name=\"Displacement\" NumberOfComponents=\"3\"/>\n"
      << "      <PDataArray type=\"Float64\" Name=\"Velocity\" NumberOfComponents=\"3\"/>\n    </PPointData>\n    <PCellData>\n";
-   Piece none; none.has_curv = has_curv;
+   Piece none; none.has_curv = has_curv; none.has_fatigue = has_fatigue;
    for (const Array& a : cell_arrays(none, light_up)) {
       o << "      <PDataArray type=\"" << type_name(a.type) << "\" Name=\"" << a.name << "\"";
       if (a.ncomp > 1) o << " NumberOfComponents=\"" << a.ncomp << "\"";
@@ -186,7 +192,7 @@ inline void save_cycle(const std::string& floc, int rank, int nranks, int cycle,
    mkdir_p(dir);
    write_piece(dir + "/" + piece_name(rank), p, light_up);
    if (rank != 0) return;
-   write_pvtu(dir + "/data.pvtu", nranks, light_up, p.has_curv);
+   write_pvtu(dir + "/data.pvtu", nranks, light_up, p.has_curv, p.has_fatigue);
    bool found = false;
    for (auto& c : cycles) if (c.first == cycle) { c.second = t; found = true; }
    if (!found) cycles.emplace_back(cycle, t);

@@ -344,6 +344,93 @@ def read_lattice_curvature(path):
     return out
 
 
+# slip-system activity and the Fatemi-Socie fatigue indicator parameter (include/exaconstit_hip.h)
+exa_slip_activity_sizes = _sig("exa_slip_activity_sizes", C.c_int, C.c_int64, C.POINTER(C.c_int64))
+exa_slip_accumulate = _sig("exa_slip_accumulate", C.c_int, C.c_void_p, dptr, C.POINTER(C.c_double), C.c_double, C.c_int, dptr, C.c_void_p)
+exa_fip_rows = _sig("exa_fip_rows", C.c_int, C.c_void_p, dptr, C.c_double, C.c_double, dptr, C.c_void_p)
+exa_fip_summary = _sig("exa_fip_summary", C.c_int, C.c_void_p, dptr, dptr, dptr, dptr, C.c_void_p)
+exa_slip_plane_normals = _sig("exa_slip_plane_normals", C.c_int, C.c_int, C.POINTER(C.c_double))
+exa_fatigue_scratch_bytes = _sig("exa_fatigue_scratch_bytes", C.c_int, C.POINTER(C.c_int))
+exa_driver_enable_slip_activity = _sig("exa_driver_enable_slip_activity", C.c_int, C.c_void_p, C.c_char_p, C.c_int)
+exa_driver_reset_fatigue_window = _sig("exa_driver_reset_fatigue_window", C.c_int, C.c_void_p, C.c_char_p, C.c_int)
+exa_driver_slip_activity = _sig("exa_driver_slip_activity", C.c_int, C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64,
+                                C.POINTER(C.c_int64), C.c_char_p, C.c_int)
+exa_options_query_fatigue = _sig("exa_options_query_fatigue", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_char_p, C.c_int, C.c_char_p, C.c_int)
+exa_fatigue_write = _sig("exa_fatigue_write", C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_char_p, C.c_int)
+exa_fatigue_grains_write = _sig("exa_fatigue_grains_write", C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_char_p, C.c_int)
+EXA_NSLIPACC, EXA_NFIP = 60, 6
+# planes of the accumulators (12 slip systems each) and columns of the rows of exa_fip_rows, in their stored order
+SLIP_ACC_PLANES = ("SlipAccumulated", "SlipAbsolute", "SlipMin", "SlipMax", "NormalStressMax")
+FIP_COLUMNS = ("FIP", "FIPSystem", "ShearRange", "NormalStressMax", "AccumulatedSlip", "NetSlipMax")
+# the values of "summary" (Driver.slip_activity); the fatigue file holds step, time, window_start_step and then the six after "volume"
+FATIGUE_SUMMARY = ("volume", "FIP_mean", "FIP_max", "FIP_max_element", "AccumulatedSlip_mean", "AccumulatedSlip_max", "ShearRange_max", "window_start_step")
+_FATIGUE_HEAD = ["step", "time", "window_start_step", "fip_mean", "fip_max", "fip_max_element", "accumulated_slip_mean", "accumulated_slip_max", "shear_range_max"]
+
+
+def slip_activity_sizes(E):
+    """doubles of the accumulators of E elements: 60 planes of E rounded up to 64 (host only)"""
+    n = C.c_int64()
+    if exa_slip_activity_sizes(int(E), C.byref(n)) != 0:
+        raise ValueError(f"E = {E} must not be negative")
+    return n.value
+
+
+def slip_plane_normals(model):
+    """(12, 3) unit slip-plane normals in the crystal frame of the model's systems, in the order of the slip rates (host only)"""
+    import numpy as np
+    out = np.zeros((12, 3))
+    if exa_slip_plane_normals(int(model), out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+        raise ValueError(f"model {model} has no slip-plane table")
+    return out
+
+
+def fatigue_scratch_bytes():
+    """private bytes per lane of k_slip_accumulate (plain, fused reset), k_fip_rows, k_fip_partial, k_fip_reduce in the loaded code object"""
+    o = (C.c_int * 8)()
+    if exa_fatigue_scratch_bytes(o) != 0:
+        raise RuntimeError("exa_fatigue_scratch_bytes: no device")
+    return list(o)[:5]
+
+
+def options_fatigue(path):
+    """fatigue keys of the Visualizations table: dict(enabled, k, sigma_y (0.0 when absent), cycle_steps, fname)"""
+    i2, d2 = (C.c_int * 2)(), (C.c_double * 2)()
+    f = C.create_string_buffer(4096)
+    err = C.create_string_buffer(512)
+    if exa_options_query_fatigue(path.encode(), i2, d2, f, 4096, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(enabled=bool(i2[0]), cycle_steps=int(i2[1]), k=d2[0], sigma_y=d2[1], fname=f.value.decode())
+
+
+def read_fatigue(path):
+    """a fatigue file of the driver: dict(step, window_start_step, FIP_max_element (n,) int64; time and the other FATIGUE_SUMMARY names (n,)), one entry per evaluation"""
+    import numpy as np
+    with open(path) as f:
+        head = f.readline().split()
+    if head != ["#"] + _FATIGUE_HEAD:
+        raise ValueError(f"{path}: not a fatigue file (header {head})")
+    with open(path) as f:
+        rows = [ln.split() for ln in f if ln.strip() and not ln.startswith("#")]
+    if any(len(r) != len(_FATIGUE_HEAD) for r in rows):
+        raise ValueError(f"{path}: a row does not hold {len(_FATIGUE_HEAD)} values")
+    col = lambda k, t: np.array([t(r[k]) for r in rows], dtype=np.int64 if t is int else np.float64)
+    out = {"step": col(0, int), "time": col(1, float), "window_start_step": col(2, int), "FIP_mean": col(3, float), "FIP_max": col(4, float),
+           "FIP_max_element": col(5, int), "AccumulatedSlip_mean": col(6, float), "AccumulatedSlip_max": col(7, float), "ShearRange_max": col(8, float)}
+    return out
+
+
+def read_fatigue_grains(path):
+    """a fatigue_grains file of the driver as the "grains" dict of Driver.slip_activity(): grain_id (n,) int64, volume, FIP_mean, FIP_max (n,)"""
+    import numpy as np
+    with open(path) as f:
+        head = f.readline().split()
+    if head != ["#", "grain_id", "volume", "fip_mean", "fip_max"]:
+        raise ValueError(f"{path}: not a fatigue_grains file (header {head})")
+    a = np.loadtxt(path, ndmin=2).reshape(-1, 4)
+    return {"grain_id": np.rint(a[:, 0]).astype(np.int64), "volume": a[:, 1].copy(), "FIP_mean": a[:, 2].copy(), "FIP_max": a[:, 3].copy()}
+
+
 exa_driver_pole_figures = _sig("exa_driver_pole_figures", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double), C.c_double,
                                C.POINTER(C.c_double), C.c_char_p, C.c_int)
 exa_options_query_texture = _sig("exa_options_query_texture", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
@@ -985,6 +1072,49 @@ class Driver:
         out["GlobalElementId"] = gid
         out["attribute"] = attr
         out["summary"] = dict(zip(CURVATURE_SUMMARY, m[:6].tolist()), volume=float(m[6]))
+        return out
+
+    def enable_slip_activity(self):
+        """Switches the slip-activity accumulators on, before the first step; an options-file driver does with Visualizations.fatigue."""
+        self._chk(exa_driver_enable_slip_activity(self.h, self._err, 512))
+
+    def reset_fatigue_window(self):
+        """Asks for a new window of SlipMin / SlipMax / NormalStressMax: it starts with the next committed step (before step 1: at once)."""
+        self._chk(exa_driver_reset_fatigue_window(self.h, self._err, 512))
+
+    def slip_activity(self, k=0.5, sigma_y=None):
+        """Slip-system activity and the Fatemi-Socie parameter FIP = ShearRange (1 + k NormalStressMax / sigma_y) (DESIGN 4.15) of the committed state;
+        every rank of the group calls it.  Rows of this rank in local element order: {"SlipAccumulated", "SlipAbsolute", "SlipMin", "SlipMax",
+        "NormalStressMax": (E, 12) per slip system (the last three over the window), "FIP", "FIPSystem", "ShearRange", "NormalStressMaxFIP" (of the
+        FIP system), "AccumulatedSlip", "NetSlipMax": (E,), "GlobalElementId", "attribute"}, "summary": over all ranks the values named by
+        FATIGUE_SUMMARY, and "grains": over all ranks {"grain_id", "volume", "FIP_mean", "FIP_max"} per grain with elements."""
+        import numpy as np
+        if sigma_y is None:
+            raise ValueError("slip_activity: sigma_y (the yield stress in the stress unit of the run) is required")
+        dp = C.POINTER(C.c_double)
+        E = self._chk(exa_driver_slip_activity(self.h, float(k), float(sigma_y), None, None, None, None, None, None, None, 0, None, self._err, 512))
+        acc, fip = np.zeros((E, EXA_NSLIPACC)), np.zeros((E, EXA_NFIP))
+        gid, attr, m = np.zeros(E, np.int64), np.zeros(E, np.int32), np.zeros(8)
+        cap = getattr(self, "_fat_grain_cap", 4096)
+        while True:
+            ids, vals, n = np.zeros(cap, np.int32), np.zeros((cap, 3)), C.c_int64()
+            self._chk(exa_driver_slip_activity(self.h, float(k), float(sigma_y), acc.ctypes.data_as(dp), fip.ctypes.data_as(dp), gid.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               attr.ctypes.data_as(C.POINTER(C.c_int32)), m.ctypes.data_as(dp), ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                               vals.ctypes.data_as(dp), cap, C.byref(n), self._err, 512))
+            if n.value <= cap:
+                break
+            cap = self._fat_grain_cap = n.value
+        out = {nm: acc[:, 12 * j:12 * j + 12].copy() for j, nm in enumerate(SLIP_ACC_PLANES)}
+        for j, nm in enumerate(FIP_COLUMNS):
+            out["NormalStressMaxFIP" if nm == "NormalStressMax" else nm] = fip[:, j].copy()
+        out["GlobalElementId"] = gid
+        out["attribute"] = attr
+        out["summary"] = dict(zip(FATIGUE_SUMMARY, m.tolist()))
+        for nm in ("FIP_max_element", "window_start_step"):
+            out["summary"][nm] = int(out["summary"][nm])
+        if n.value > 0:
+            out["grains"] = {"grain_id": ids[:n.value].astype(np.int64), "volume": vals[:n.value, 0].copy(), "FIP_mean": vals[:n.value, 1].copy(),
+                             "FIP_max": vals[:n.value, 2].copy()}
         return out
 
     def set_grains(self, grain_ids, quats):

@@ -280,6 +280,29 @@ int exa_options_query_grains(const char* toml_path, int* enabled, char* fname, i
  * unless > 0), lattice_curvature_fname ("lattice_curvature.txt"; refused if empty or with a '/') into a buffer of fnamelen bytes.  Every pointer
  * may be NULL.  Returns 0 or -1 (err). */
 int exa_options_query_lattice_curvature(const char* toml_path, int* enabled, double* burgers, char* fname, int fnamelen, char* err, int errlen);
+/* fatigue keys of the Visualizations table: out2 = { fatigue (default 0), fatigue_cycle_steps (0; refused if < 0) }, out2d = { fatigue_k (0.5;
+ * refused if < 0), fatigue_sigma_y (0 when absent; refused unless > 0, and required with fatigue = true) }, fatigue_fname ("fatigue.txt"; refused if empty or
+ * with a '/') into a buffer of fnamelen bytes.  Every pointer may be NULL.  Returns 0 or -1 (err). */
+int exa_options_query_fatigue(const char* toml_path, int* out2, double* out2d, char* fname, int fnamelen, char* err, int errlen);
+/* Slip-system activity and the Fatemi-Socie fatigue indicator parameter of a run (kernels: exa_slip_accumulate, exa_fip_rows, exa_fip_summary of
+ * exaconstit_hip.h).  exa_driver_enable_slip_activity switches the accumulators on before the first step (an options file does with Visualizations.fatigue):
+ * every committed step then adds itself, whether committed by exa_driver_step or by exa_driver_commit_step.  exa_driver_reset_fatigue_window asks for a new
+ * window: it starts with the next committed step (before step 1 the window is the initial state already).  exa_driver_slip_activity evaluates the committed
+ * state with k_fs >= 0 and sigma_y > 0, read-only on the accumulators; every rank of a group calls it with the same pointers NULL.  acc_out [E][60] (Gamma,
+ * A, Gamma_min, Gamma_max, N_max, 12 systems each) and fip_out [E][EXA_NFIP] of the local elements in local order, elem_gid / attribute as
+ * exa_driver_element_fields; summary8 = over all ranks { volume, mean FIP, max FIP, global element of the max (ties: the smallest), mean AccumulatedSlip, max
+ * AccumulatedSlip, max ShearRange, first step of the window }; per grain with elements over all ranks, ascending id: grain_ids and grain_vals3 [.][3] =
+ * volume, volume-weighted mean FIP, max FIP, copied when their count *n_grains <= grain_cap.  All outputs NULL: no evaluation.  Returns E or -1 (err). */
+int exa_driver_enable_slip_activity(exa_driver* d, char* err, int errlen);
+int exa_driver_reset_fatigue_window(exa_driver* d, char* err, int errlen);
+int exa_driver_slip_activity(exa_driver* d, double k_fs, double sigma_y, double* acc_out, double* fip_out, int64_t* elem_gid, int32_t* attribute, double* summary8,
+                             int32_t* grain_ids, double* grain_vals3, int64_t grain_cap, int64_t* n_grains, char* err, int errlen);
+/* the writers of the fatigue files (host only).  exa_fatigue_write: nrows rows of 9 doubles { step, time, first step of the window, mean FIP, max FIP, global
+ * element of the max, mean AccumulatedSlip, max AccumulatedSlip, max ShearRange } (the three counts as integers, the rest with 17 significant digits); append = 0
+ * starts the file anew with its '#' header, otherwise the rows are appended.  exa_fatigue_grains_write: a '#' header and n rows grain id, volume, mean FIP, max FIP.
+ * Return 0 or -1 (err). */
+int exa_fatigue_write(const char* path, int nrows, const double* rows9, int append, char* err, int errlen);
+int exa_fatigue_grains_write(const char* path, int n, const int32_t* grain_ids, const double* vals3, char* err, int errlen);
 /* [Checkpoint] table (all keys optional): out3 = { write (default 0), steps (1), keep (2) }, floc (default "checkpoint"), restart_from (default "") */
 int exa_options_query_checkpoint(const char* toml_path, int* out3, char* floc, int floclen, char* restart_from, int restartlen, char* err, int errlen);
 /* the grain_avgs file writer (host only): a '#' header naming the 46 columns, then n rows of grain_ids[i] and vals[i][EXA_GRAIN_NVALS] (the

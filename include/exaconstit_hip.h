@@ -440,6 +440,38 @@ int exa_curvature_summary(exa_ctx* ctx, const double* fields_dev, const double* 
 /* host only: doubles of work_dev for E elements and the plane count of nodal_dev (a multiple of 3; nodal_dev holds planes x nnodes doubles);
  * either output may be NULL.  Returns 0, or EXA_ERR_ARG for E < 0. */
 int exa_curvature_sizes(int64_t E, int64_t* work_doubles, int* nodal_planes);
+/* Slip-system activity and the Fatemi-Socie fatigue indicator parameter on the rows of exa_element_fields (fields_dev
+ * [E][EXA_NFIELDS], device), for any context: they read rows only.  Slip system a = 0 .. 11 in the order of the slip rates (state slots 14 .. 25).
+ * acc_dev (device) holds the accumulators that persist across the steps of a run, planar [EXA_NSLIPACC][E_pad] with E_pad = E rounded up to 64
+ * (exa_slip_activity_sizes), 12 planes each of: Gamma (EXA_ACC_SLIP), A (EXA_ACC_ABS), Gamma_min (EXA_ACC_MIN), Gamma_max (EXA_ACC_MAX), N_max
+ * (EXA_ACC_NMAX); the caller zero-fills it at the start of a run.  Entries [.][E .. E_pad) are never read or written.
+ *   exa_slip_accumulate  one committed step of size dt >= 0: with g_a = EXA_F_SHEARRATE + a, n_a = R(q) m_a (R = quat_to_mat of EXA_F_ORIENTATION, crystal ->
+ *                        sample; m_a = normals12x3 [12][3], host, normalised here: exa_slip_plane_normals) and sigma_n,a = n_a^T sigma n_a (sigma =
+ *                        EXA_F_STRESS): Gamma_a += dt g_a, A_a += dt |g_a|, then Gamma_min_a = min(Gamma_min_a, Gamma_a), Gamma_max_a = max(Gamma_max_a,
+ *                        Gamma_a), N_max_a = max(N_max_a, sigma_n,a).  reset != 0 restarts the window in the same pass: Gamma_min_a = Gamma_max_a =
+ *                        Gamma_a and N_max_a = sigma_n,a after the update (dt = 0 with reset: the reset alone, Gamma and A keep their bits).
+ *   exa_fip_rows         out_dev [E][EXA_NFIP] from the accumulators, read-only on them: FIP_a = (Gamma_max_a - Gamma_min_a) / 2 (1 + k_fs N_max_a /
+ *                        sigma_y) without a clamp (k_fs >= 0, sigma_y > 0 in the stress unit of the rows); EXA_FIP_FIP max_a FIP_a, EXA_FIP_SYSTEM the
+ *                        smallest a that attains it (as a double), EXA_FIP_SHEARRANGE and EXA_FIP_NORMALSTRESSMAX the half range and N_max of that
+ *                        system, EXA_FIP_ACCUMULATEDSLIP sum_a A_a, EXA_FIP_NETSLIPMAX max_a |Gamma_a|.
+ *   exa_fip_summary      out7_dev [7] (device) = local sum V, sum V FIP, sum V AccumulatedSlip, max FIP, max ShearRange, max AccumulatedSlip and the
+ *                        global id of the element of max FIP as a double (V = EXA_F_VOLUME of fields_dev, fip_dev the rows of exa_fip_rows,
+ *                        elem_gid_dev [E] int64 on the device; ties go to the smallest id).  Without rows: zeros, -inf for the maxima, 2^53 for the id.
+ *                        Partials per block in the context's scratch, then one block.
+ * No atomics, fixed summation orders: every call on the same data gives the same bits.  None of them synchronises. */
+enum { EXA_NSLIPACC = 60, EXA_ACC_SLIP = 0, EXA_ACC_ABS = 12, EXA_ACC_MIN = 24, EXA_ACC_MAX = 36, EXA_ACC_NMAX = 48 };
+enum { EXA_NFIP = 6, EXA_FIP_FIP = 0, EXA_FIP_SYSTEM = 1, EXA_FIP_SHEARRANGE = 2, EXA_FIP_NORMALSTRESSMAX = 3, EXA_FIP_ACCUMULATEDSLIP = 4, EXA_FIP_NETSLIPMAX = 5 };
+int exa_slip_accumulate(exa_ctx* ctx, const double* fields_dev, const double* normals12x3, double dt, int reset, double* acc_dev, exa_stream s);
+int exa_fip_rows(exa_ctx* ctx, const double* acc_dev, double k_fs, double sigma_y, double* out_dev, exa_stream s);
+int exa_fip_summary(exa_ctx* ctx, const double* fields_dev, const double* fip_dev, const int64_t* elem_gid_dev, double* out7_dev, exa_stream s);
+/* host only: doubles of acc_dev for E elements (may be NULL).  Returns 0, or EXA_ERR_ARG for E < 0. */
+int exa_slip_activity_sizes(int64_t E, int64_t* acc_doubles);
+/* host only: the unit slip-plane normals [12][3] in the crystal frame of the model's 12 systems, in the order of the slip rates: {111} for the FCC
+ * models, {110} for the BCC models.  Returns 0, or EXA_ERR_ARG for an unknown model. */
+int exa_slip_plane_normals(int model, double* out12x3);
+/* private (scratch) bytes per lane of the kernels behind the three calls above in the loaded code object: out8 = { k_slip_accumulate, k_slip_accumulate
+ * with the fused reset, k_fip_rows, k_fip_partial, k_fip_reduce, 0, 0, 0 }; returns 0, or -1 without a device */
+int exa_fatigue_scratch_bytes(int* out8);
 /* volume average  sum_q W detJ val / sum_q W detJ  (src/mechanics_kernels.hpp:19-134); out_host[vdim] (+ volume in out_host[vdim]).
  * Synchronises the stream. */
 int exa_vol_avg(exa_ctx* ctx, const double* jacobian_dev, const double* qf_dev, int vdim, int normalise, double* out_host, exa_stream s);
