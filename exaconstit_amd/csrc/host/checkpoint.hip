@@ -16,8 +16,6 @@
 
 namespace exa_host {
 
-void append_row(const std::string& path, const double* v, int n);   // driver.hip: one row of an avg_* / light-up file
-
 namespace {
 
 using namespace exa_ckpt;
@@ -128,6 +126,7 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
    exa_ctx* ctx = op.GetModel()->ctx();
+   StepAnalyses& an = *analyses_; const StepAnalyses::Checkpointed& ac = an.ckpt;
    EXA_HC(hipStreamSynchronize(s));
    const int Q = exa_qpts_per_elem(ctx), nsv = exa_num_state_vars(ctx);
    Header h;
@@ -135,7 +134,7 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
    h.nprops = (int)op.props.size(); h.nstatev = nsv; h.props_hash = fnv1a(op.props.data(), sizeof(double) * op.props.size());
    mesh_hashes(part, elem_attr, comm, s, h.grain_hash, h.conn_hash);
    h.steps_done = steps_done; h.time = time; h.dt_class = dt_class; h.last_dt = last_dt_; h.bc_index = bc_index_; h.nranks = comm.nranks;
-   h.flags = (cycle0_saved_ ? 1u : 0u) | (texture0_written_ ? 2u : 0u);
+   h.flags = (ac.cycle0_saved ? 1u : 0u) | (ac.texture0_written ? 2u : 0u);
    h.model_calls = op.model_calls; op.GetCapState(h.newton_cap, h.newton_cap2);
    // ---- host sections (the same on every rank; rank 0 writes them)
    std::vector<HostSec> hs;
@@ -143,22 +142,23 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
    if (opt_.additional_avgs) { hs.push_back(host_sec("avg_def_grad", avg_def_grad)); hs.push_back(host_sec("avg_pl_work", avg_pl_work)); hs.push_back(host_sec("avg_dp_tensor", avg_dp_tensor)); }
    { std::vector<int32_t> st; for (const SolverStats& x : stats) { st.push_back(x.newton_iters); st.push_back(x.krylov_iters); st.push_back(x.model_calls); st.push_back(x.converged ? 1 : 0); }
      hs.push_back(host_sec("solver_stats", st.data(), sizeof(int32_t) * st.size())); }
-   { std::vector<double> cyc; auto it = pvd_cycles_.find(vis_dir()); if (it != pvd_cycles_.end()) for (auto& c : it->second) { cyc.push_back((double)c.first); cyc.push_back(c.second); }
+   { std::vector<double> cyc; auto it = ac.pvd_cycles.find(an.vis_dir(state())); if (it != ac.pvd_cycles.end()) for (auto& c : it->second) { cyc.push_back((double)c.first); cyc.push_back(c.second); }
      hs.push_back(host_sec("pvd_cycles", cyc)); }
-   hs.push_back(host_sec("lattice_strains", lattice_rows_)); hs.push_back(host_sec("lattice_volumes", volume_rows_)); hs.push_back(host_sec("auto_dt", auto_dt_rows_));
+   hs.push_back(host_sec("lattice_strains", ac.lattice_rows)); hs.push_back(host_sec("lattice_volumes", ac.volume_rows)); hs.push_back(host_sec("auto_dt", auto_dt_rows_));
    if (opt_.macro_tangent) hs.push_back(host_sec("macro_tangent", macro_tangent_rows));   // (only with the option on: every other checkpoint stays byte for byte what it was)
    // slip activity (only with the feature on, like the tangent's rows): window start step and pending reset, the rows of the fatigue file
-   if (fatigue_on_) {
-      if (!fatigue_init_) EnsureFatigueInit();
-      const int64_t w[2] = { fatigue_window_start_, fatigue_pending_ ? 1 : 0 };
-      hs.push_back(host_sec("fatigue_window", w, sizeof(w))); hs.push_back(host_sec("fatigue_rows", fatigue_rows));
+   const bool slip = an.slip_activity_on();
+   const DevBuf<double>* slip_acc = slip ? &an.SlipAccumulators(state()) : nullptr;   // (started here if the run has not begun)
+   if (slip) {
+      const int64_t w[2] = { ac.fatigue_window_start, ac.fatigue_pending ? 1 : 0 };
+      hs.push_back(host_sec("fatigue_window", w, sizeof(w))); hs.push_back(host_sec("fatigue_rows", ac.fatigue_rows));
    }
    // ---- layout
    std::vector<Section> sec;
    for (const HostSec& x : hs) { Section t; t.name = x.name; t.nbytes = x.bytes.size(); t.checksum = sum64(x.bytes.data(), x.bytes.size()); sec.push_back(t); }
    // ... and its accumulators (60, global element), ahead of the field sections every file has
    const size_t slip_sec = sec.size();
-   if (fatigue_on_) { Section t; t.name = "slip_activity"; t.nbytes = 8ull * EXA_NSLIPACC * (uint64_t)part.E_glob; sec.push_back(t); }
+   if (slip) { Section t; t.name = "slip_activity"; t.nbytes = 8ull * EXA_NSLIPACC * (uint64_t)part.E_glob; sec.push_back(t); }
    const size_t first_field = sec.size();
    { Section t; t.name = "x_beg"; t.nbytes = 24 * (uint64_t)part.NN_glob; sec.push_back(t); t.name = "v_sol"; sec.push_back(t);
      t.name = "stress0"; t.nbytes = 8ull * 6 * Q * (uint64_t)part.E_glob; sec.push_back(t); t.name = "matVars0"; t.nbytes = 8ull * nsv * Q * (uint64_t)part.E_glob; sec.push_back(t);
@@ -242,8 +242,8 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
          std::vector<double> hv(n); can.download(hv.data(), n, s); cks.download(&sums[2 + f], 1, s);
          move_rows<true>(fd, sec[first_field + 2 + f].offset, sizeof(double) * W[f] * Q, part.elem_gid, nullptr, (char*)hv.data());
       }
-      if (fatigue_on_ && part.E > 0) {   // planar [60][E_pad] on the device -> rows of 60 by global element (480 B per element: transposed on the host)
-         const std::vector<double> pl = fat_acc_.to_host(s);
+      if (slip && part.E > 0) {   // planar [60][E_pad] on the device -> rows of 60 by global element (480 B per element: transposed on the host)
+         const std::vector<double> pl = slip_acc->to_host(s);
          const size_t Ep = pl.size() / EXA_NSLIPACC, El = (size_t)part.E;
          std::vector<double> hv(EXA_NSLIPACC * El);
          for (int k = 0; k < EXA_NSLIPACC; k++) for (size_t e = 0; e < El; e++) hv[EXA_NSLIPACC * e + k] = pl[k * Ep + e];
@@ -255,7 +255,7 @@ void SystemDriver::SaveCheckpoint(const std::string& path) {
    all_ok(comm, ok, why.empty() ? "checkpoint: write failed" : why);
    allreduce_u64(comm, sums, s);   // (also the barrier after which every rank's rows are in the file)
    for (int f = 0; f < 6; f++) sec[first_field + f].checksum = sums[f];
-   if (fatigue_on_) sec[slip_sec].checksum = sums[6];
+   if (slip) sec[slip_sec].checksum = sums[6];
    ok = true; why.clear();
    if (comm.rank == 0) {
       try {
@@ -339,7 +339,7 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    if (opt_.macro_tangent && find(sec, "macro_tangent")) host_doubles("macro_tangent", MACRO_TANGENT_ROW, r_mt);
    // slip activity: a run with the feature on continues the accumulators of the file; with it off the sections are ignored
    std::vector<double> r_fat; int64_t fat_window[2] = { 0, 0 }; const Section* fat_sec = nullptr;
-   if (fatigue_on_) {
+   if (analyses_->slip_activity_on()) {
       if (!find(sec, "slip_activity")) throw std::runtime_error("checkpoint: section 'slip_activity' is missing: the file was written without Visualizations.fatigue / enable_slip_activity and cannot continue the accumulators of this run (" + path + ")");
       fat_sec = &need("slip_activity", 8ull * EXA_NSLIPACC * (uint64_t)part.E_glob, true);
       const Section& w = need("fatigue_window", 16, true);
@@ -431,17 +431,17 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
    EXA_HC(hipStreamSynchronize(s));
    // ---- host state
    time = h.time; dt_class = h.dt_class; last_dt_ = h.last_dt; steps_done = (int)h.steps_done;
-   cycle0_saved_ = (h.flags & 1u) != 0; texture0_written_ = (h.flags & 2u) != 0;
+   StepAnalyses::Checkpointed& ac = analyses_->ckpt;
+   ac.cycle0_saved = (h.flags & 1u) != 0; ac.texture0_written = (h.flags & 2u) != 0;
    stats.resize((size_t)h.steps_done);
    for (size_t i = 0; i < stats.size(); i++) { stats[i].newton_iters = r_stats[4 * i]; stats[i].krylov_iters = r_stats[4 * i + 1]; stats[i].model_calls = r_stats[4 * i + 2]; stats[i].converged = r_stats[4 * i + 3] != 0; }
    avg_stress.swap(r_stress); avg_def_grad.swap(r_F); avg_pl_work.swap(r_pw); avg_dp_tensor.swap(r_dp);
-   lattice_rows_.swap(r_ls); volume_rows_.swap(r_lv); auto_dt_rows_.swap(r_dt);
+   ac.lattice_rows.swap(r_ls); ac.volume_rows.swap(r_lv); auto_dt_rows_.swap(r_dt);
    macro_tangent_rows.swap(r_mt);
-   if (fat_sec) {
-      fat_acc_.upload(fat_planar, s); fat_gid_.upload(part.elem_gid, s);
-      fatigue_window_start_ = fat_window[0]; fatigue_pending_ = fat_window[1] != 0; fatigue_init_ = true; fatigue_rows.swap(r_fat);
-   }
-   { auto& cyc = pvd_cycles_[vis_dir()]; cyc.clear(); for (size_t i = 0; i + 1 < r_cyc.size(); i += 2) cyc.emplace_back((int)r_cyc[i], r_cyc[i + 1]); if (cyc.empty()) pvd_cycles_.erase(vis_dir()); }
+   if (fat_sec) { ac.fatigue_window_start = fat_window[0]; ac.fatigue_pending = fat_window[1] != 0; ac.fatigue_rows.swap(r_fat); }
+   { const std::string vd = analyses_->vis_dir(state());
+     auto& cyc = ac.pvd_cycles[vd]; cyc.clear(); for (size_t i = 0; i + 1 < r_cyc.size(); i += 2) cyc.emplace_back((int)r_cyc[i], r_cyc[i + 1]); if (cyc.empty()) ac.pvd_cycles.erase(vd); }
+   analyses_->Restored(fat_sec ? &fat_planar : nullptr);   // (the element rows it holds are those of the state this one replaced)
    op.model_calls = (int)h.model_calls; op.SetCapState(h.newton_cap, h.newton_cap2);
    // the essential-boundary set in force, without the SolveInit that belongs to the step where it changed
    bc_index_ = h.bc_index;
@@ -454,9 +454,9 @@ void SystemDriver::LoadCheckpoint(const std::string& path) {
          rewrite_rows(out_dir + "/" + opt_.avg_pl_work_fname, avg_pl_work, 1); rewrite_rows(out_dir + "/" + opt_.avg_def_grad_fname, avg_def_grad, 9);
          rewrite_rows(out_dir + "/" + opt_.avg_dp_tensor_fname, avg_dp_tensor, 6);
       }
-      if (opt_.lightup()) { rewrite_rows(out_dir + "/" + opt_.lightup_strain_fname, lattice_rows_, H); rewrite_rows(out_dir + "/" + opt_.lightup_volume_fname, volume_rows_, H); }
+      if (opt_.lightup()) { rewrite_rows(out_dir + "/" + opt_.lightup_strain_fname, ac.lattice_rows, H); rewrite_rows(out_dir + "/" + opt_.lightup_volume_fname, ac.volume_rows, H); }
       if (opt_.macro_tangent) write_macro_tangent_rows(out_dir + "/" + opt_.macro_tangent_fname, macro_tangent_rows, false);
-      if (opt_.fatigue) write_fatigue_rows(out_dir + "/" + opt_.fatigue_fname, fatigue_rows, false);
+      if (opt_.fatigue) write_fatigue_rows(out_dir + "/" + opt_.fatigue_fname, ac.fatigue_rows, false);
       if (opt_.dt_auto) { std::ofstream f(out_dir + "/" + opt_.auto_dt_fname, std::ios_base::trunc); for (double v : auto_dt_rows_) f << std::setprecision(12) << v << std::endl; }
    }
    restarted_ = true; ckpt_foreign_calls_ = (long)op.model_calls;

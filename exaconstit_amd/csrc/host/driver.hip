@@ -2,7 +2,6 @@
 #include "driver.hpp"
 #include "multigrid.hpp"
 #include "roctx.hpp"
-#include "vtu.hpp"
 #include <rccl/rccl.h>
 #include <atomic>
 #include <chrono>
@@ -1081,10 +1080,10 @@ SystemDriver::SystemDriver(const ExaOptions& opt, int rank, int nranks, const vo
    add_selftest_neighbour(part, comm);
    if (opt.order == 1) part.order_boundary_first();   // several ranks: elements at shared nodes first (exchange overlapped with the interior, GradMult)
    if (opt.periodic) part.make_periodic(opt.periodic_mixed);            // (after the element order: it rewrites weights, neighbour lists and the group table only)
-   std::vector<double> props, quats; load_case_data(opt, part, props, quats, elem_attr, grain_qref_);
-   grain_qref_.resize(grain_qref_.size() / 4 * 4);
-   normalise_quats(grain_qref_);   // grain g: row g - 1 of the orientation file
-   init(props, quats);
+   std::vector<double> props, quats, qref; load_case_data(opt, part, props, quats, elem_attr, qref);
+   qref.resize(qref.size() / 4 * 4);
+   normalise_quats(qref);   // grain g: row g - 1 of the orientation file
+   init(props, quats, std::move(qref));
 }
 
 SystemDriver::SystemDriver(const ExaOptions& opt, const std::vector<double>& props, const std::vector<double>& quats_global, int rank, int nranks, const void* uid) : opt_(opt) {
@@ -1098,12 +1097,12 @@ SystemDriver::SystemDriver(const ExaOptions& opt, const std::vector<double>& pro
    elem_attr.resize((size_t)part.E);   // one grain per element (SetGrains: a grain map)
    for (int e = 0; e < part.E; e++) elem_attr[e] = (int32_t)(part.elem_gid[e] + 1);
    synthetic_ = true;
-   grain_qref_.assign(quats_global.begin(), quats_global.begin() + 4 * part.E_global());
-   normalise_quats(grain_qref_);
-   init(props, quats);
+   std::vector<double> qref(quats_global.begin(), quats_global.begin() + 4 * part.E_global());
+   normalise_quats(qref);
+   init(props, quats, std::move(qref));
 }
 
-void SystemDriver::init(const std::vector<double>& props, const std::vector<double>& quats_local) {
+void SystemDriver::init(const std::vector<double>& props, const std::vector<double>& quats_local, std::vector<double> grain_qref) {
    oper_.reset(new NonlinearMechOperator(opt_, part, comm, props, quats_local));
    if (opt_.periodic && opt_.periodic_mixed) set_free(opt_.periodic_free);
    oper_->precond = precond;
@@ -1115,7 +1114,7 @@ void SystemDriver::init(const std::vector<double>& props, const std::vector<doub
    ks.rel_tol = opt_.krylov_rel; ks.abs_tol = opt_.krylov_abs; ks.max_iter = opt_.krylov_iter;
    if (const char* g = std::getenv("EXA_PCG_GRAPH")) { if (std::string(g) == "0") ks.graph_max_dofs = 0; else if (std::string(g) == "all") ks.graph_max_dofs = INT64_MAX; }
    krylov_.reset(new PCGSolver(*oper_, ks));
-   if (opt_.fatigue) EnableSlipActivity();
+   analyses_.reset(new StepAnalyses(*oper_, comm, part, opt_, elem_attr, std::move(grain_qref)));
 }
 
 // BCManager::updateBCData + UpdateEssTDofs; component codes reference src/BCData.cpp:25-116
@@ -1380,11 +1379,6 @@ bool SystemDriver::Solve(double* x) {
    return ok;
 }
 
-void append_row(const std::string& path, const double* v, int n) {   // (also rewrites the files of a restarted run: host/checkpoint.hip)
-   std::ofstream f(path, std::ios_base::app);
-   for (int i = 0; i < n; i++) { f << v[i]; f << (i + 1 == n ? '\n' : ' '); }   // mfem::Vector::Print(out, width = n)
-}
-
 // reference src/system_driver.cpp:429-558
 void SystemDriver::UpdateModel() {
    NonlinearMechOperator& op = *oper_;
@@ -1431,14 +1425,7 @@ void SystemDriver::UpdateModel() {
 bool SystemDriver::Step(int ti, bool commit) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream(); const int64_t nd = op.Height();
-   // ParaView cycle 0: the initial state at t = 0, saved before the first step (reference src/mechanics_driver.cpp:640-700), outside the timed region
-   // texture file of step 0 (the initial texture) at the same point; the two share the element rows
-   const bool cycle0 = opt_.paraview && write_files && commit && steps_done == 0 && !cycle0_saved_;
-   const bool texture0 = opt_.texture && write_files && commit && steps_done == 0 && !texture0_written_;
-   if (fatigue_on_ && !fatigue_init_) EnsureFatigueInit();   // (leaves the rows of the initial state in fields_dev_)
-   else if (cycle0 || texture0) ComputeElementFields();
-   if (cycle0) { SaveFields(vis_dir(), 0, 0.0, true); cycle0_saved_ = true; }
-   if (texture0) { WriteTexture(0, time); texture0_written_ = true; }
+   analyses_->BeforeFirstStep(state(), commit);   // accumulators, ParaView cycle 0 and texture 0 of the initial state, outside the timed region
    double dt_real;
    if (opt_.dt_cust) dt_real = opt_.cust_dt[ti - 1];
    else if (opt_.dt_auto) dt_real = std::min(dt_class, opt_.t_final - time);
@@ -1469,48 +1456,8 @@ bool SystemDriver::Step(int ti, bool commit) {
    step_solved_ = true;
    if (!commit) return true;   // the converged state stays the END-of-step state: the next constitutive pass repeats this step's last residual evaluation
    CommitStep();
-   // ParaView cycle ti of the converged, swapped state every Visualizations.steps steps and at the last step (reference src/mechanics_driver.cpp:911-955)
-   // per-grain averages and texture on the same cadence, whether or not ParaView output is on
-   bool due = false;
-   bool last_step = false;
-   if ((opt_.paraview || opt_.grain_avgs || opt_.texture || opt_.macro_tangent || opt_.lattice_curvature || opt_.fatigue) && write_files) {
-      bool last = ti >= opt_.nsteps;
-      if (!opt_.dt_cust) { const double dtl = opt_.dt_auto ? last_dt_ : opt_.dt; last = last || std::fabs(time - opt_.t_final) <= std::fabs(1e-3 * dtl); }
-      due = last || ti % opt_.vis_steps == 0; last_step = last;
-   }
-   const bool save = opt_.paraview && due, grains = opt_.grain_avgs && due, texture = opt_.texture && due;
-   // light-up analysis: one row of lattice strains and one of fibre volume fractions per converged step, from the same element rows
-   const bool lattice = opt_.lightup() && write_files;
-   const bool curvature = opt_.lattice_curvature && due;
-   // slip activity: a file row every fatigue_cycle_steps steps, followed by the request to restart the window, and at the last step (0: on the cadence above)
-   const bool cycle_end = opt_.fatigue && write_files && opt_.fatigue_cycle_steps > 0 && ti % opt_.fatigue_cycle_steps == 0;
-   const bool fatigue = opt_.fatigue && write_files && (opt_.fatigue_cycle_steps > 0 ? (cycle_end || last_step) : due);
-   // (slip activity on: CommitStep left the rows of this state there - checked, not assumed: the stamp of the last element-field launch)
-   if ((save || lattice || grains || texture || curvature || fatigue) && !(fatigue_on_ && fields_are_current())) ComputeElementFields();
-   SlipActivityResult fat;
-   if (fatigue || (save && opt_.fatigue)) SlipActivity(opt_.fatigue_k, opt_.fatigue_sigma_y, fat, true, save);
-   if (fatigue) WriteFatigue(ti, fat);
-   if (cycle_end && !last_step) ResetFatigueWindow();
-   std::vector<double> curv_rows;
-   if (curvature) { double m[7]; LatticeCurvature(opt_.lattice_curvature_burgers, curv_rows, m, true, save); WriteLatticeCurvature(ti, m); }
-   if (save) SaveFields(vis_dir(), ti, time, true, curvature ? &curv_rows : nullptr, opt_.fatigue ? &fat : nullptr);
-   if (texture) WriteTexture(ti, time);
-   if (opt_.macro_tangent && due) WriteMacroTangent(ti);
-   if (grains) {
-      std::vector<int32_t> ids; std::vector<double> vals;
-      GrainAverages(ids, vals, true);
-      if (comm.rank == 0) {
-         char tag[16]; std::snprintf(tag, sizeof(tag), "_%06d.txt", ti);
-         write_grain_avgs(out_dir + "/" + opt_.grain_avgs_fname + tag, (int)ids.size(), ids.data(), vals.data());
-      }
-   }
-   if (lattice) {
-      const int H = (int)opt_.lightup_hkl.size() / 3;
-      std::vector<double> strain(H), vf(H);
-      LatticeStrains(opt_.lightup_hkl, opt_.lightup_s_dir, opt_.lightup_tol_deg, strain.data(), vf.data(), true);
-      lattice_rows_.insert(lattice_rows_.end(), strain.begin(), strain.end()); volume_rows_.insert(volume_rows_.end(), vf.begin(), vf.end());
-      if (comm.rank == 0) { append_row(out_dir + "/" + opt_.lightup_strain_fname, strain.data(), H); append_row(out_dir + "/" + opt_.lightup_volume_fname, vf.data(), H); }
-   }
+   // the output schedule of the analyses; the macroscopic tangent, which reads the state and leaves it alone, follows on the same cadence
+   if (analyses_->AfterCommit(state(), ti) && opt_.macro_tangent) WriteMacroTangent(ti);
    return true;
 }
 // end-of-step update of a solved step (also called later for a step solved with commit = false, as long as only residual evaluations at the
@@ -1519,7 +1466,7 @@ void SystemDriver::CommitStep() {
    UpdateModel();
    oper_->SwapCoords();
    steps_done++;
-   if (fatigue_on_) AccumulateSlip();
+   analyses_->Committed(state());
 }
 
 int SystemDriver::RunAll() {
@@ -1537,200 +1484,6 @@ int SystemDriver::RunAll() {
    }
    WriteStepTimes();
    return steps_done;
-}
-
-void SystemDriver::ComputeElementFields() {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   exa_ctx* ctx = op.GetModel()->ctx();
-   DevBuf<double> xe((size_t)3 * part.n * part.E), jac;
-   if (fields_dev_.n != (size_t)EXA_NFIELDS * part.E) fields_dev_.alloc((size_t)EXA_NFIELDS * part.E);
-   abi_check(ctx, exa_restrict(ctx, op.x_cur.p, xe.p, s), "exa_restrict");
-   if (part.p != 1 || part.geom == 1) {   // p = 1 hexahedra: det J comes from the node coordinates inside the launch
-      jac.alloc((size_t)exa_qf_size(ctx, 9));
-      abi_check(ctx, exa_jacobians(ctx, xe.p, jac.p, s), "exa_jacobians");
-   }
-   op.EnsureSlipRates(op.matVars0);   // (the rows average slots 14..25)
-   abi_check(ctx, exa_element_fields(ctx, jac.p, op.stress0.p, op.matVars0.p, xe.p, fields_dev_.p, s), "exa_element_fields");
-   fields_step_ = steps_done; fields_calls_ = op.model_calls;
-   EXA_HC(hipStreamSynchronize(s));   // xe and jac leave scope
-}
-
-void SystemDriver::ElementFields(std::vector<double>& out) {
-   ComputeElementFields();
-   out = fields_dev_.to_host(oper_->stream());
-}
-
-void SystemDriver::LatticeStrains(const std::vector<int>& hkl, const double s_dir[3], double tol_deg, double* strain, double* volfrac, bool fields_current) {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   exa_ctx* ctx = op.GetModel()->ctx();
-   double sd[3] = { s_dir[0], s_dir[1], s_dir[2] };
-   ExaOptions::check_lightup(hkl, sd, tol_deg);
-   const int H = (int)hkl.size() / 3;
-   if (H < 1) throw std::runtime_error("lattice strains: no {hkl} family given");
-   std::vector<double> axes; std::vector<int> off(1, 0);
-   for (int j = 0; j < H; j++) {
-      double a[3 * 24];
-      const int na = exa_cubic_fiber_axes(hkl[3 * j], hkl[3 * j + 1], hkl[3 * j + 2], a, 24);
-      if (na < 1 || na > 24) throw std::runtime_error("lattice strains: no fibre axes for a family");
-      axes.insert(axes.end(), a, a + 3 * na); off.push_back(off.back() + na);
-   }
-   if (!fields_current) ComputeElementFields();
-   if (lattice_sums_.n < (size_t)(2 * H + 1)) lattice_sums_.alloc(2 * EXA_LATTICE_MAX_HKL + 1);
-   const double cos_tol = std::cos(tol_deg * (M_PI / 180.0));
-   abi_check(ctx, exa_lattice_strains(ctx, fields_dev_.p, H, axes.data(), off.data(), sd, cos_tol, lattice_sums_.p, s), "exa_lattice_strains");
-   comm.allreduce_sum(lattice_sums_.p, 2 * H + 1, s);   // elements are not shared across ranks
-   std::vector<double> h(2 * H + 1); lattice_sums_.download(h.data(), 2 * H + 1, s);
-   for (int j = 0; j < H; j++) {
-      const double v = h[2 * j + 1];
-      strain[j] = v > 0.0 ? h[2 * j] / v : std::numeric_limits<double>::quiet_NaN();   // empty fibre: no lattice strain (written as nan)
-      volfrac[j] = v / h[2 * H];
-   }
-}
-
-// angle (degrees) of the rotation between unit quaternions a and b: d = conj(a) (x) b, 2 atan2(|d_vec|, |d_0|) (accurate near 0, unlike 2 acos |a . b|)
-static double misorientation_deg(const double* a, const double* b) {
-   const double d0 = a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3];
-   const double d1 = a[0] * b[1] - b[0] * a[1] - (a[2] * b[3] - a[3] * b[2]);
-   const double d2 = a[0] * b[2] - b[0] * a[2] - (a[3] * b[1] - a[1] * b[3]);
-   const double d3 = a[0] * b[3] - b[0] * a[3] - (a[1] * b[2] - a[2] * b[1]);
-   return 2.0 * std::atan2(std::sqrt(d1 * d1 + d2 * d2 + d3 * d3), std::fabs(d0)) * (180.0 / M_PI);
-}
-
-void SystemDriver::EnsureGrainPlan() {
-   if (!grain_plan_.empty()) return;
-   int gmax = 0;
-   for (int32_t a : elem_attr) gmax = std::max(gmax, (int)a);
-   const int G = (int)comm.max_over_ranks((double)gmax);
-   if (G < 1) throw std::runtime_error("grain averages: the mesh has no elements");
-   if ((int64_t)4 * G > (int64_t)grain_qref_.size()) throw std::runtime_error("grain averages: grain " + std::to_string(G) + " has no reference orientation");
-   if ((int64_t)G * EXA_GRAIN_NSUMS > (int64_t)INT32_MAX) throw std::runtime_error("grain averages: too many grains");
-   int64_t len = 0, work = 0;
-   if (exa_grain_plan(part.E, elem_attr.data(), nullptr, 0, &len, &work) != 0) throw std::runtime_error("grain averages: grain ids must be at least 1");
-   std::vector<int32_t> plan((size_t)len);
-   if (exa_grain_plan(part.E, elem_attr.data(), plan.data(), len, &len, &work) != 0) throw std::runtime_error("exa_grain_plan failed");
-   hipStream_t s = oper_->stream();
-   grain_plan_dev_.alloc((size_t)len); grain_plan_dev_.upload(plan.data(), (size_t)len, s);
-   grain_work_.alloc((size_t)std::max<int64_t>(work, 1));
-   grain_sums_.alloc((size_t)G * EXA_GRAIN_NSUMS);
-   grain_quat_dev_.alloc((size_t)4 * G);
-   grain_attr_dev_.upload(elem_attr, s);   // the map itself, for the analyses that take it element by element (LatticeCurvature)
-   grain_G_ = G;
-   grain_plan_ = std::move(plan);
-}
-
-void SystemDriver::GrainMeans(std::vector<double>& h, std::vector<double>& qbar, double& vtot) {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   exa_ctx* ctx = op.GetModel()->ctx();
-   const int G = grain_G_; constexpr int K = EXA_GRAIN_NSUMS;
-   // pass 1: the 39 sums of every grain; elements are not shared across ranks, grains are
-   grain_quat_dev_.upload(grain_qref_.data(), (size_t)4 * G, s);
-   grain_sums_.zero(s);
-   abi_check(ctx, exa_grain_sums(ctx, 1, fields_dev_.p, grain_plan_.data(), grain_plan_dev_.p, G, grain_quat_dev_.p, grain_work_.p, grain_sums_.p, s), "exa_grain_sums");
-   comm.allreduce_sum(grain_sums_.p, G * K, s);
-   h.resize((size_t)G * K); grain_sums_.download(h.data(), h.size(), s);
-   // the grain means, identical on every rank
-   qbar.assign(grain_qref_.begin(), grain_qref_.begin() + 4 * (size_t)G);
-   vtot = 0.0;
-   for (int g = 0; g < G; g++) {
-      const double* r = &h[(size_t)g * K];
-      if (!(r[1] > 0.0)) continue;
-      vtot += r[0];
-      const double n = std::sqrt(r[35] * r[35] + r[36] * r[36] + r[37] * r[37] + r[38] * r[38]);
-      if (n > 0.0) for (int k = 0; k < 4; k++) qbar[4 * (size_t)g + k] = r[35 + k] / n;
-   }
-}
-
-void SystemDriver::GrainAverages(std::vector<int32_t>& ids, std::vector<double>& vals, bool fields_current) {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   exa_ctx* ctx = op.GetModel()->ctx();
-   EnsureGrainPlan();
-   const int G = grain_G_; constexpr int K = EXA_GRAIN_NSUMS;
-   if (!fields_current) ComputeElementFields();
-   std::vector<double> h, qbar; double vtot = 0.0;
-   GrainMeans(h, qbar, vtot);
-   // pass 2: sum V theta and max theta about the means
-   grain_quat_dev_.upload(qbar.data(), (size_t)4 * G, s);
-   EXA_HC(hipMemsetAsync(grain_sums_.p, 0, sizeof(double) * 2 * G, s));
-   abi_check(ctx, exa_grain_sums(ctx, 2, fields_dev_.p, grain_plan_.data(), grain_plan_dev_.p, G, grain_quat_dev_.p, grain_work_.p, grain_sums_.p, s), "exa_grain_sums");
-   comm.allreduce_sum(grain_sums_.p, G, s);
-   comm.allreduce_max(grain_sums_.p + G, G, s);
-   std::vector<double> h2((size_t)2 * G); grain_sums_.download(h2.data(), h2.size(), s);
-   ids.clear(); vals.clear();
-   for (int g = 0; g < G; g++) {
-      const double* r = &h[(size_t)g * K];
-      if (!(r[1] > 0.0)) continue;
-      const double V = r[0], iv = 1.0 / V;
-      double o[GRAIN_NVALS];
-      o[0] = r[1]; o[1] = V; o[2] = V / vtot;
-      for (int k = 0; k < 6; k++) o[3 + k] = r[2 + k] * iv;
-      const double* t = o + 3;
-      const double d01 = t[0] - t[1], d12 = t[1] - t[2], d20 = t[2] - t[0];   // EXA_F_VONMISES, EXA_F_HYDROSTATIC of the mean stress
-      o[9] = std::sqrt(0.5 * (d01 * d01 + d12 * d12 + d20 * d20 + 6.0 * (t[3] * t[3] + t[4] * t[4] + t[5] * t[5])));
-      o[10] = (t[0] + t[1] + t[2]) * (1.0 / 3.0);
-      for (int k = 0; k < 12; k++) o[11 + k] = r[8 + k] * iv;    // elastic strain in the sample and the crystal frame
-      for (int k = 0; k < 15; k++) o[23 + k] = r[20 + k] * iv;   // EffPlasticStrain, DpEff, Hardness, ShearRate (12)
-      for (int k = 0; k < 4; k++) o[38 + k] = qbar[4 * (size_t)g + k];
-      o[42] = h2[g] * iv; o[43] = h2[(size_t)G + g];
-      o[44] = misorientation_deg(&qbar[4 * (size_t)g], &grain_qref_[4 * (size_t)g]);
-      ids.push_back(g + 1);
-      vals.insert(vals.end(), o, o + GRAIN_NVALS);
-   }
-}
-
-// element rows -> grain means (pass 1 of the grain sums) -> per-element rotation vectors and their nodal sums -> the sum over the
-// copies of a node, on the path every assembled L-vector takes (periodic images, then ranks; segment by segment in deterministic mode) ->
-// curvature rows -> summary
-void SystemDriver::LatticeCurvature(double burgers, std::vector<double>& rows, double* summary7, bool fields_current, bool want_rows) {
-   if (!(burgers > 0.0) || !std::isfinite(burgers)) throw std::runtime_error("lattice curvature: the Burgers vector length must be a finite number > 0");
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   exa_ctx* ctx = op.GetModel()->ctx();
-   EnsureGrainPlan();
-   const int G = grain_G_;
-   if (!fields_current) ComputeElementFields();
-   std::vector<double> h, qbar; double vtot = 0.0;
-   GrainMeans(h, qbar, vtot);
-   grain_quat_dev_.upload(qbar.data(), (size_t)4 * G, s);
-   int64_t work = 0; int planes = 0;
-   exa_curvature_sizes(part.E, &work, &planes);
-   const size_t nn = (size_t)part.NN;
-   if (curv_work_.n != (size_t)std::max<int64_t>(work, 1)) curv_work_.alloc((size_t)std::max<int64_t>(work, 1));
-   if (curv_nodal_.n != (size_t)planes * nn) curv_nodal_.alloc((size_t)planes * nn);
-   if (curv_rows_.n != (size_t)EXA_NCURV * part.E) curv_rows_.alloc((size_t)EXA_NCURV * part.E);
-   if (curv_sum_.n < 7) curv_sum_.alloc(7);
-   if (curv_xe_.n != (size_t)3 * part.n * part.E) curv_xe_.alloc((size_t)3 * part.n * part.E);
-   DevBuf<double>& xe = curv_xe_;
-   abi_check(ctx, exa_restrict(ctx, op.x_cur.p, xe.p, s), "exa_restrict");
-   abi_check(ctx, exa_curvature_nodal(ctx, fields_dev_.p, grain_attr_dev_.p, G, grain_quat_dev_.p, curv_work_.p, curv_nodal_.p, s), "exa_curvature_nodal");
-   for (int t = 0; t < planes / 3; t++) op.SumLVector(curv_nodal_.p + (size_t)3 * nn * t, nullptr, false);
-   abi_check(ctx, exa_curvature_elements(ctx, fields_dev_.p, grain_attr_dev_.p, G, grain_quat_dev_.p, curv_work_.p, curv_nodal_.p, xe.p, burgers, curv_rows_.p, s),
-             "exa_curvature_elements");
-   abi_check(ctx, exa_curvature_summary(ctx, fields_dev_.p, curv_rows_.p, curv_sum_.p, s), "exa_curvature_summary");
-   comm.allreduce_sum(curv_sum_.p, 4, s);   // elements are not shared across ranks
-   comm.allreduce_max(curv_sum_.p + 4, 3, s);
-   double t7[7]; curv_sum_.download(t7, 7, s);
-   rows.resize(want_rows ? (size_t)EXA_NCURV * part.E : 0);
-   if (!rows.empty()) curv_rows_.download(rows.data(), rows.size(), s);
-   const double iv = 1.0 / t7[0];
-   for (int k = 0; k < 3; k++) { summary7[2 * k] = t7[1 + k] * iv; summary7[2 * k + 1] = t7[4 + k]; }
-   summary7[6] = t7[0];
-}
-
-void SystemDriver::WriteLatticeCurvature(int step, const double* m) {
-   if (comm.rank != 0) return;
-   const std::string path = out_dir + "/" + opt_.lattice_curvature_fname;
-   bool fresh = true;
-   { std::ifstream g(path); fresh = !g || g.peek() == std::ifstream::traits_type::eof(); }
-   std::ofstream f(path, std::ios_base::app);   // a restarted run goes on in the file it finds
-   if (!f) throw std::runtime_error("lattice curvature: cannot write " + path);
-   if (fresh) f << "# step time grod_mean_deg grod_max_deg kam_mean_deg kam_max_deg gnd_density_mean gnd_density_max\n";
-   f << std::setprecision(17) << step << ' ' << time;
-   for (int k = 0; k < 6; k++) f << ' ' << m[k];
-   f << '\n';
 }
 
 void SystemDriver::SetGrains(const int32_t* grain, int64_t n_global, const double* grain_quats, int G) {
@@ -1753,128 +1506,7 @@ void SystemDriver::SetGrains(const int32_t* grain, int64_t n_global, const doubl
    hipStream_t s = op.stream();
    exa_ctx* ctx = op.GetModel()->ctx();
    { DevBuf<double> d; d.upload(ql, s); abi_check(ctx, exa_init_state(ctx, op.matVars0.p, d.p, s), "exa_init_state"); EXA_HC(hipStreamSynchronize(s)); }
-   grain_qref_ = std::move(q);
-   grain_plan_.clear(); grain_G_ = 0;
-}
-
-void SystemDriver::PoleFigures(const std::vector<int>& hkl, std::vector<double> dirs, double res_deg, std::vector<double>& mrd, bool fields_current) {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   exa_ctx* ctx = op.GetModel()->ctx();
-   ExaOptions::check_texture(hkl, dirs, res_deg, false);
-   const int H = (int)hkl.size() / 3, D = (int)dirs.size() / 3, nset = H + D;
-   int na = 0, nb = 0;
-   exa_texture_grid(res_deg, &na, &nb);
-   std::vector<double> axes; std::vector<int> off(1, 0);
-   for (int j = 0; j < H; j++) {
-      double a[3 * 24];
-      const int n = exa_cubic_fiber_axes(hkl[3 * j], hkl[3 * j + 1], hkl[3 * j + 2], a, 24);
-      if (n < 1 || n > 24) throw std::runtime_error("texture: no pole axes for a family");
-      axes.insert(axes.end(), a, a + 3 * n); off.push_back(off.back() + n);
-   }
-   if (!fields_current) ComputeElementFields();
-   // the quantum 2^q of the integer weights, the same on every rank and for any rank count: from the largest element volume and the element
-   // count over all ranks (a max and a sum of integers are exact)
-   if (texture_vmax_.n < 2) texture_vmax_.alloc(2);
-   abi_check(ctx, exa_texture_volume_max(ctx, fields_dev_.p, texture_vmax_.p, s), "exa_texture_volume_max");
-   const double ne = (double)part.E;
-   EXA_HC(hipMemcpyAsync(texture_vmax_.p + 1, &ne, sizeof(double), hipMemcpyHostToDevice, s));
-   comm.allreduce_max(texture_vmax_.p, 1, s);
-   comm.allreduce_sum(texture_vmax_.p + 1, 1, s);
-   double vn[2] = { 0.0, 0.0 }; texture_vmax_.download(vn, 2, s);
-   const int qlog2 = exa_texture_quantum_log2(vn[0], (int64_t)vn[1]);
-   const size_t nbins = (size_t)nset * na * nb;
-   if (texture_counts_.n < nbins) texture_counts_.alloc(nbins);
-   abi_check(ctx, exa_texture_weights(ctx, fields_dev_.p, H, axes.data(), off.data(), D, dirs.data(), res_deg, qlog2, texture_counts_.p, s), "exa_texture_weights");
-   std::vector<int64_t> c(nbins); texture_counts_.download(c.data(), nbins, s);
-   if (comm.nranks > 1) {   // exact sums over the ranks: the counts (< 2^62) travel as two 32-bit halves in doubles, whose sums stay below 2^53
-      std::vector<double> h2(2 * nbins);
-      for (size_t b = 0; b < nbins; b++) { h2[b] = (double)(uint64_t)(c[b] >> 32); h2[nbins + b] = (double)(uint64_t)(c[b] & 0xffffffffll); }
-      DevBuf<double> d; d.upload(h2, s);
-      comm.allreduce_sum(d.p, (int)(2 * nbins), s);
-      d.download(h2.data(), 2 * nbins, s);
-      for (size_t b = 0; b < nbins; b++) c[b] = (int64_t)(((uint64_t)h2[b] << 32) + (uint64_t)h2[nbins + b]);
-   }
-   // MRD_ik = (W_ik / W_tot) 2 pi / dOmega_i with dOmega_i = res (cos i res - cos (i + 1) res)
-   const double r = res_deg * (M_PI / 180.0);
-   std::vector<double> f(na);
-   for (int i = 0; i < na; i++) f[i] = 2.0 * M_PI / (r * (std::cos(i * r) - std::cos((i + 1) * r)));
-   mrd.assign(nbins, 0.0);
-   for (int j = 0; j < nset; j++) {
-      const int64_t* w = c.data() + (size_t)j * na * nb;
-      int64_t tot = 0;
-      for (int b = 0; b < na * nb; b++) tot += w[b];
-      const double inv = 1.0 / (double)tot;   // an empty set (no volume): NaN
-      for (int i = 0; i < na; i++)
-         for (int k = 0; k < nb; k++) mrd[(size_t)j * na * nb + (size_t)i * nb + k] = (double)w[i * nb + k] * inv * f[i];
-   }
-}
-
-void SystemDriver::WriteTexture(int step, double t) {
-   std::vector<double> dirs = opt_.texture_dirs, mrd;
-   PoleFigures(opt_.texture_hkl, dirs, opt_.texture_res_deg, mrd, true);
-   if (comm.rank != 0) return;
-   char tag[16]; std::snprintf(tag, sizeof(tag), "_%06d.txt", step);
-   write_texture(out_dir + "/" + opt_.texture_fname + tag, step, t, opt_.texture_res_deg, opt_.texture_hkl, dirs, mrd);
-}
-
-void write_texture(const std::string& path, int step, double t, double res_deg, const std::vector<int>& hkl, const std::vector<double>& dirs,
-                   const std::vector<double>& mrd) {
-   int na = 0, nb = 0;
-   if (exa_texture_grid(res_deg, &na, &nb) != 0) throw std::runtime_error("texture: bad res_deg");
-   const int H = (int)hkl.size() / 3, D = (int)dirs.size() / 3;
-   if (mrd.size() != (size_t)(H + D) * na * nb) throw std::runtime_error("texture: " + path + ": MRD of the wrong size");
-   std::ofstream f(path);
-   if (!f) throw std::runtime_error("texture: cannot write " + path);
-   f << std::setprecision(17);
-   f << "# texture step " << step << " time " << t << " res_deg " << res_deg << " n_alpha " << na << " n_beta " << nb << "\n";
-   for (int j = 0; j < H + D; j++) {
-      if (j < H) f << "# pole figure {" << hkl[3 * j] << ' ' << hkl[3 * j + 1] << ' ' << hkl[3 * j + 2] << "}\n";
-      else f << "# inverse pole figure [" << dirs[3 * (j - H)] << ' ' << dirs[3 * (j - H) + 1] << ' ' << dirs[3 * (j - H) + 2] << "]\n";
-      const double* m = mrd.data() + (size_t)j * na * nb;
-      for (int i = 0; i < na; i++) {
-         for (int k = 0; k < nb; k++) f << (k ? " " : "") << m[i * nb + k];
-         f << '\n';
-      }
-   }
-   if (!f) throw std::runtime_error("texture: writing " + path + " failed");
-}
-
-void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const double* vals) {
-   std::ofstream f(path);
-   if (!f) throw std::runtime_error("grain averages: cannot write " + path);
-   f << "# grain_id n_elements volume volume_fraction stress_11 stress_22 stress_33 stress_23 stress_13 stress_12 von_mises hydrostatic"
-        " elastic_strain_sample_11 elastic_strain_sample_22 elastic_strain_sample_33 elastic_strain_sample_23 elastic_strain_sample_13 elastic_strain_sample_12"
-        " elastic_strain_xtal_11 elastic_strain_xtal_22 elastic_strain_xtal_33 elastic_strain_xtal_23 elastic_strain_xtal_13 elastic_strain_xtal_12"
-        " eff_plastic_strain dp_eff hardness";
-   for (int k = 1; k <= 12; k++) f << " shear_rate_" << k;
-   f << " quat_0 quat_1 quat_2 quat_3 misori_mean_deg misori_max_deg rotation_deg\n";
-   f << std::setprecision(17);
-   for (int i = 0; i < n; i++) {
-      const double* v = vals + (size_t)i * GRAIN_NVALS;
-      f << ids[i] << ' ' << (int64_t)v[0];
-      for (int k = 1; k < GRAIN_NVALS; k++) f << ' ' << v[k];
-      f << '\n';
-   }
-   if (!f) throw std::runtime_error("grain averages: writing " + path + " failed");
-}
-
-void SystemDriver::SaveFields(const std::string& dir, int cycle, double t, bool fields_current, const std::vector<double>* curv, const SlipActivityResult* fat) {
-   NonlinearMechOperator& op = *oper_;
-   hipStream_t s = op.stream();
-   if (!fields_current) ComputeElementFields();
-   std::vector<double> curv_own;
-   if (opt_.lattice_curvature && !curv) { double m[7]; LatticeCurvature(opt_.lattice_curvature_burgers, curv_own, m, true); curv = &curv_own; }
-   SlipActivityResult fat_own;
-   if (opt_.fatigue && !fat) { SlipActivity(opt_.fatigue_k, opt_.fatigue_sigma_y, fat_own, true); fat = &fat_own; }
-   const std::vector<double> fields = fields_dev_.to_host(s);
-   const std::vector<double> xc = op.x_cur.to_host(s), xr = op.x_ref.to_host(s), v = v_sol.to_host(s);
-   vtu::Piece p;
-   p.E = part.E; p.NN = part.NN; p.n = part.n; p.tet = part.geom == 1; p.conn = part.conn.data();
-   p.x_cur = xc.data(); p.x_ref = xr.data(); p.vel = v.data(); p.fields = fields.data(); p.attr = elem_attr.data(); p.gid = part.elem_gid.data();
-   if (opt_.lattice_curvature) { p.has_curv = true; p.curv = curv->data(); }
-   if (opt_.fatigue) { p.has_fatigue = true; p.fip = fat->fip.data(); p.slip_acc = fat->acc.data(); }
-   vtu::save_cycle(dir, comm.rank, comm.nranks, cycle, t, opt_.light_up, p, pvd_cycles_[dir]);
+   analyses_->GrainsChanged(std::move(q));   // (exa_init_state is no constitutive launch: the stamp of the element rows would still match)
 }
 
 // per-rank wall time of every step's solve, one value per line with 8 digits: ./time/time_solve.<rank>.txt of the reference

@@ -8,6 +8,7 @@
 //   ExaNewtonSolver / ExaNewtonLSSolver  reference src/mechanics_solver.cpp:39-281
 //   PCGSolver (host/krylov.hpp)          MFEM CGSolver, set up at reference src/system_driver.cpp:166-177
 //   SystemDriver                         reference src/system_driver.cpp:221-558
+//   StepAnalyses (host/analyses.hpp)     reference src/system_driver.cpp:560-870 (the Project* outputs) and what this project adds to them
 //   time-step loop                       reference src/mechanics_driver.cpp:837-907
 #pragma once
 #include <map>
@@ -15,6 +16,7 @@
 #include <string>
 #include <vector>
 #include "../../../include/exaconstit_hip.h"
+#include "analyses.hpp"
 #include "device_utils.hpp"
 #include "krylov.hpp"
 #include "mesh.hpp"
@@ -66,15 +68,6 @@ class Comm {
    hipStream_t cs_ = nullptr; hipEvent_t ev_ready_ = nullptr, ev_done_ = nullptr;   // communication stream of halo_begin / halo_end
    void exchange(const Partition& part, hipStream_t s);   // send buffers -> neighbours' receive buffers (RCCL grouped send/recv or loopback copies) on stream s
 };
-
-// per-grain averages: value columns per grain (after the grain id) of SystemDriver::GrainAverages and the grain_avgs files
-constexpr int GRAIN_NVALS = 45;
-// one grain_avgs file: a '#' header naming the 46 columns, then one row per grain (id, element count, 43 values with 17 significant digits)
-void write_grain_avgs(const std::string& path, int n, const int32_t* ids, const double* vals);
-// one texture file: a '# texture step .. time .. res_deg .. n_alpha .. n_beta ..' header, then per set a '# pole figure {h k l}' or
-// '# inverse pole figure [d0 d1 d2]' line and n_alpha rows of n_beta MRD values (17 significant digits); mrd [nhkl + ndir][n_alpha][n_beta]
-void write_texture(const std::string& path, int step, double t, double res_deg, const std::vector<int>& hkl, const std::vector<double>& dirs,
-                   const std::vector<double>& mrd);
 
 class Multigrid;
 
@@ -246,10 +239,6 @@ class NonlinearMechOperator {
    MixedTable mix_tab_; DevBuf<int32_t> mix_img_, mix_face_; DevBuf<uint8_t> mix_code_; DevBuf<double> mix_x_, mix_part_, mix_h_, mix_f_, mix_res_;
 };
 
-constexpr int FATIGUE_NSUMMARY = 8, FATIGUE_ROW = 9;   // SlipActivityResult::summary; row of the fatigue file: step, time, window start, mean FIP, max FIP, element, mean and max AccumulatedSlip, max ShearRange
-void write_fatigue_rows(const std::string& path, const std::vector<double>& rows, bool append);
-void write_fatigue_grains(const std::string& path, int n, const int32_t* ids, const double* vals3);
-
 class SystemDriver {
  public:
    SystemDriver(const ExaOptions& opt, int rank, int nranks, const void* nccl_uid);
@@ -290,6 +279,8 @@ class SystemDriver {
    const double* mac_resultants() const { return mac_F_; }   // F_id, row by row
    double last_newton_norm = 0.0, last_newton_bound = 0.0;   // final residual norm and max(rel |r0|, abs) of the last Newton solve
    PCGSolver& krylov() { return *krylov_; }   // the run's linear solver
+   StepAnalyses& analyses() { return *analyses_; }   // the run's in-situ analyses (host/analyses.hpp) ...
+   StepState state() const { return { steps_done, time, step_dt_, out_dir, write_files, v_sol }; }   // ... and where the run stands, for their calls
    // Homogenised tangent d sigma_bar / d L_bar of the last solved step of a periodic cell (host/tangent.hip), every rank calls it.
    // rel_tol / max_iter <= 0: the Krylov options.  batched: -1 the automatic route, 0 column by column through PCGSolver::Solve, 1 the nine columns in
    // lockstep through the multi-column action (one rank, non-deterministic mode, a context exa_grad_apply_lvec_cols serves; refused elsewhere).
@@ -317,97 +308,30 @@ class SystemDriver {
    void SaveCheckpoint(const std::string& path);
    void LoadCheckpoint(const std::string& path);
    std::string checkpoint_path(int step) const;   // <out_dir>/<Checkpoint.floc>_<step %06d>.ckpt
-   // per-element output fields (reference SystemDriver::Project*, src/system_driver.cpp:560-870) of the begin-of-step state - after a completed
-   // step the converged one - and the current coordinates: host [E][EXA_NFIELDS] in local element order
-   void ElementFields(std::vector<double>& out);
-   // the same rows into the device buffer fields_dev_, kept across steps (allocated on first use)
-   void ComputeElementFields();
-   // ParaView save of those fields as cycle `cycle` at time t under dir (host/vtu.hpp); every rank calls it.  fields_current: fields_dev_
-   // already holds the rows of this state (computed once for both the save and the lattice strains of a step)
-   // curv ([E][EXA_NCURV], Visualizations.lattice_curvature only): the rows of LatticeCurvature of this state; computed here when null
-   struct SlipActivityResult;
-   // fat (Visualizations.fatigue only): the evaluation of this state; computed here when null
-   void SaveFields(const std::string& dir, int cycle, double t, bool fields_current = false, const std::vector<double>* curv = nullptr, const SlipActivityResult* fat = nullptr);
-   // lattice strains of the {hkl} families (3 integers each; options.hpp check_lightup) of the same state, summed over all ranks (every rank calls
-   // it): strain[j] = volume-weighted mean of s^T eps s over the elements of fibre j (NaN when the fibre is empty), volfrac[j] = its volume fraction
-   void LatticeStrains(const std::vector<int>& hkl, const double s_dir[3], double tol_deg, double* strain, double* volfrac, bool fields_current = false);
-   // per-grain averages of the same state over all ranks (every rank calls it): ids = the ascending 1-based ids of the grains with
-   // elements, vals = GRAIN_NVALS values per grain (the value columns of the grain_avgs files, write_grain_avgs)
-   void GrainAverages(std::vector<int32_t>& ids, std::vector<double>& vals, bool fields_current = false);
-   // intragranular misorientation and lattice curvature of the same state (every rank calls it): rows = [E][EXA_NCURV] of the local
-   // elements (exa_curvature_elements; burgers: Burgers vector length in the mesh's length unit), summary7 = over all ranks the volume-weighted
-   // means of GROD, KAM and the GND density, their maxima and the total volume: { mean GROD, max GROD, mean KAM, max KAM, mean GND, max GND, V }
-   // want_rows = false: the summary alone (rows is left empty and the [E][EXA_NCURV] copy to the host is skipped)
-   void LatticeCurvature(double burgers, std::vector<double>& rows, double* summary7, bool fields_current = false, bool want_rows = true);
-   // Slip-system activity and the Fatemi-Socie fatigue indicator parameter.  With the feature on (Visualizations.fatigue, or
-   // EnableSlipActivity before the first step) CommitStep adds the committed step to the 60 accumulators of every element, from the rows of one
-   // ComputeElementFields launch that the step's other analyses share.  A window reset is a request: it is carried out, fused into the accumulate
-   // launch, at the end of the next committed step, whose values start the new window (before step 1 the window is the initial state already).
-   struct SlipActivityResult {
-      std::vector<double> acc, fip;            // [E][EXA_NSLIPACC] (Gamma | A | Gamma_min | Gamma_max | N_max, 12 each) and [E][EXA_NFIP] of the local elements
-      double summary[FATIGUE_NSUMMARY];        // over all ranks: volume, mean FIP, max FIP, global element of the max, mean and max AccumulatedSlip, max ShearRange, window start step
-      std::vector<int32_t> grain_ids; std::vector<double> grain_vals;   // over all ranks, ascending ids of the grains with elements: volume, mean FIP, max FIP
-   };
-   void EnableSlipActivity();
-   bool slip_activity_on() const { return fatigue_on_; }
-   // evaluation of the committed state, read-only on the accumulators (every rank calls it); want_acc = false: res.acc is left empty
-   void SlipActivity(double k_fs, double sigma_y, SlipActivityResult& res, bool fields_current = false, bool want_acc = true);
-   void ResetFatigueWindow();
-   // one row of Visualizations.fatigue_fname and the per-grain file of this step, from an evaluation with the options' k and sigma_y
-   void WriteFatigue(int step, const SlipActivityResult& res);
-   std::vector<double> fatigue_rows;           // FATIGUE_ROW values per written evaluation (checkpoint host section)
    // grain map of a synthetic driver before its first step: grain (1..G) of every global element and the orientation of every grain (normalised
-   // here); the elements' initial orientations and states become their grain's
+   // here); the elements' initial orientations and states become their grain's; the analyses are told (GrainsChanged)
    void SetGrains(const int32_t* grain_of_global_elem, int64_t n_global, const double* grain_quats, int G);
-   // texture of the same state over all ranks (every rank calls it): pole figures of the {hkl} families (3 integers each) and
-   // inverse pole figures of the sample directions dirs (3 components each, normalised here; options.hpp check_texture) on the grid of
-   // res_deg; mrd = [nhkl + ndir][n_alpha][n_beta] multiples of random distribution, the same bits on every rank and for any rank count
-   void PoleFigures(const std::vector<int>& hkl, std::vector<double> dirs, double res_deg, std::vector<double>& mrd, bool fields_current = false);
-   std::string vis_dir() const { return (opt_.vis_floc.empty() || opt_.vis_floc[0] == '/') ? opt_.vis_floc : out_dir + "/" + opt_.vis_floc; }
    std::vector<int32_t> elem_attr;             // grain id (element attribute) of every local element
    Precond precond = Precond::IDENTITY;
    Partition part;
    Comm comm;
  private:
-   void init(const std::vector<double>& props, const std::vector<double>& quats_local);
+   void init(const std::vector<double>& props, const std::vector<double>& quats_local, std::vector<double> grain_qref);
    ExaOptions opt_;
    std::unique_ptr<NonlinearMechOperator> oper_;
    std::unique_ptr<PCGSolver> krylov_;
+   std::unique_ptr<StepAnalyses> analyses_;
    DevBuf<double> r_, c_, xt_, ess_val_;
    std::vector<uint8_t> ess_host_; std::vector<double> ess_val_host_;
    DevBuf<uint8_t> vel_mask_, vg_mask_; bool have_vel_ = false, have_vgrad_ = false; double vgrad_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-   double last_dt_ = 0.0;
-   double step_dt_ = 0.0;                       // size of the step last solved: Time.Auto after any cut-back, otherwise the dt Step took (AccumulateSlip)
-   // committed step and constitutive-launch count at which ComputeElementFields last filled fields_dev_: the rows are those of the state at hand iff both match
-   int fields_step_ = -1; long fields_calls_ = -1;
-   bool fields_are_current() const { return fields_step_ == steps_done && fields_calls_ == (long)oper_->model_calls && fields_dev_.n == (size_t)EXA_NFIELDS * part.E; }
-   bool cycle0_saved_ = false;
-   DevBuf<double> fields_dev_, lattice_sums_;   // [E][EXA_NFIELDS] element rows; 2 H + 1 lattice-strain sums
-   bool synthetic_ = false;
-   std::vector<double> grain_qref_;             // unit reference orientation of every grain: [grain id - 1][4]
-   // plan of exa_grain_sums for elem_attr (built on first use, dropped by SetGrains), its device copy and workspace; G = largest grain id over all ranks
-   std::vector<int32_t> grain_plan_; DevBuf<int32_t> grain_plan_dev_; DevBuf<double> grain_work_, grain_sums_, grain_quat_dev_; int grain_G_ = 0;
-   void EnsureGrainPlan();
-   // pass 1 of exa_grain_sums on fields_dev_, all-reduced: h = [G][EXA_GRAIN_NSUMS], qbar = the unit grain means (the reference orientation of a grain
-   // without elements), vtot = the volume of all grains
-   void GrainMeans(std::vector<double>& h, std::vector<double>& qbar, double& vtot);
-   DevBuf<int32_t> grain_attr_dev_;   // elem_attr on the device, uploaded with the grain plan
-   DevBuf<double> curv_work_, curv_nodal_, curv_rows_, curv_sum_, curv_xe_;   // LatticeCurvature: records, nodal planes, rows, 7 sums, current coordinates as an E-vector
-   void WriteLatticeCurvature(int step, const double* summary7);
-   bool texture0_written_ = false;
-   // slip activity: on / accumulators initialised / reset requested; first step of the window; planar accumulators, FIP rows, 7 sums (+ per-grain sums),
-   // global element ids on the device; unit plane normals of the model
-   bool fatigue_on_ = false, fatigue_init_ = false, fatigue_pending_ = false; int64_t fatigue_window_start_ = 0;
-   DevBuf<double> fat_acc_, fat_rows_, fat_sum_, fat_grain_; DevBuf<int64_t> fat_gid_; double fat_normals_[36];
-   void EnsureFatigueInit();
-   void AccumulateSlip();
-   // rows that exist only in append-mode files otherwise (checkpoint host sections): light-up strains / volume fractions, accepted dt of Time.Auto
-   std::vector<double> lattice_rows_, volume_rows_, auto_dt_rows_;
+   double last_dt_ = 0.0, step_dt_ = 0.0;      // step_dt_: size of the step last solved: Time.Auto after any cut-back, otherwise the dt Step took (StepState::dt)
+   // accepted dt of Time.Auto: rows that exist only in an append-mode file otherwise (checkpoint host section)
+   std::vector<double> auto_dt_rows_;
    bool mixed_ = false, mac_have_ = false, mix_bc_changed_ = false; uint8_t free_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
    double vgrad_eff_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_A_[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, mac_L_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_F_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_w0_[3] = { 0, 0, 0 };
    void set_free(const uint8_t* f);
    int bc_index_ = -1;                          // index in opt_.bcs of the essential-boundary entry in force
-   bool restarted_ = false;
+   bool synthetic_ = false, restarted_ = false;
    bool step_solved_ = false;                   // the last Step of this process converged and no constitutive launch has run since (MacroTangent)
    struct TangentScope;                         // host/tangent.hip: the essential set of the tangent's solves and what an evaluation puts back
    void WriteMacroTangent(int step);
@@ -415,9 +339,6 @@ class SystemDriver {
    // no constitutive launch has run since the load, so that load + save reproduces the file on any rank count
    std::vector<unsigned char> ckpt_foreign_copies_[2]; long ckpt_foreign_calls_ = -1;
    void PruneCheckpoints(int step);
-   DevBuf<double> texture_vmax_; DevBuf<int64_t> texture_counts_;   // largest element volume; [set][n_alpha][n_beta] counts of exa_texture_weights
-   void WriteTexture(int step, double t);
-   std::map<std::string, std::vector<std::pair<int, double>>> pvd_cycles_;   // saved cycles of each output directory (rank 0 writes the .pvd)
 };
 
 }  // namespace exa_host

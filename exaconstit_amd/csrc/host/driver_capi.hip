@@ -522,6 +522,8 @@ void exa_driver_get_diagnostics(exa_driver* d, int64_t* out) {
 }
 // launches of exa_slip_rates_from_state so far (lean end-of-step state: NonlinearMechOperator::EnsureSlipRates)
 int64_t exa_driver_get_rate_launches(exa_driver* d) { return d->sd->oper().rate_launches; }
+// launches of exa_element_fields so far (StepAnalyses::rows launches only when the rows it holds are not those of the state at hand)
+int64_t exa_driver_get_field_launches(exa_driver* d) { return d->sd->analyses().field_launches; }
 
 // out[0] = sqrt((r, M^-1 r) / (r0, M^-1 r0)) reached by the last PCG solve, out[1] = the worst value among the solves that stopped at max_iter
 void exa_driver_get_pcg_reduction(exa_driver* d, double* out2) { out2[0] = d->sd->krylov().diag.last_reduction; out2[1] = d->sd->krylov().diag.worst_capped_reduction; }
@@ -580,6 +582,7 @@ int exa_driver_bench_prepare(exa_driver* d, int nsteps, const double* dts, doubl
          op.Setup<true>(sd.v_sol.p);
          op.UpdateModel(); op.SwapCoords();
       }
+      sd.analyses().Invalidate();   // (the state was swapped without a commit)
       op.SetDt(dts[nsteps > 0 ? nsteps - 1 : 0]);   // nsteps == 0: keep the virgin state, passes are then the elastic first step with dt = dts[0]
       EXA_HC(hipStreamSynchronize(op.stream()));
       return 0;
@@ -782,7 +785,7 @@ int exa_choose_newton_caps(const int* hist64, double tail_cost, int* k1, int* k2
 int exa_driver_element_fields(exa_driver* d, double* out, int64_t* elem_gid, int32_t* attribute, char* err, int errlen) {
    try {
       SystemDriver& sd = *d->sd;
-      if (out) { std::vector<double> f; sd.ElementFields(f); std::memcpy(out, f.data(), sizeof(double) * f.size()); }
+      if (out) { std::vector<double> f; sd.analyses().ElementFields(sd.state(), f); std::memcpy(out, f.data(), sizeof(double) * f.size()); }
       if (elem_gid) std::memcpy(elem_gid, sd.part.elem_gid.data(), sizeof(int64_t) * sd.part.E);
       if (attribute) std::memcpy(attribute, sd.elem_attr.data(), sizeof(int32_t) * sd.part.E);
       return sd.part.E;
@@ -792,7 +795,7 @@ int exa_driver_element_fields(exa_driver* d, double* out, int64_t* elem_gid, int
 int exa_driver_write_fields(exa_driver* d, const char* dir, int cycle, double t, char* err, int errlen) {
    try {
       if (!dir || !*dir) throw std::runtime_error("exa_driver_write_fields: no directory");
-      d->sd->SaveFields(dir, cycle, t);
+      d->sd->analyses().SaveFields(d->sd->state(), dir, cycle, t);
       return 0;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
@@ -824,7 +827,7 @@ int exa_driver_lattice_strains(exa_driver* d, int nhkl, const int* hkl3, const d
    try {
       if (nhkl < 1 || nhkl > EXA_LATTICE_MAX_HKL || !hkl3 || !s_dir3 || !strain_out || !volfrac_out) throw std::runtime_error("exa_driver_lattice_strains: 1 to 16 families, a direction and two outputs are required");
       const std::vector<int> hkl(hkl3, hkl3 + 3 * nhkl);
-      d->sd->LatticeStrains(hkl, s_dir3, tol_deg, strain_out, volfrac_out);
+      d->sd->analyses().LatticeStrains(d->sd->state(), hkl, s_dir3, tol_deg, strain_out, volfrac_out);
       return 0;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
@@ -832,7 +835,7 @@ int exa_driver_lattice_strains(exa_driver* d, int nhkl, const int* hkl3, const d
 int exa_driver_grain_averages(exa_driver* d, int32_t* grain_ids, double* vals, int64_t cap, char* err, int errlen) {
    try {
       std::vector<int32_t> ids; std::vector<double> v;
-      d->sd->GrainAverages(ids, v);
+      d->sd->analyses().GrainAverages(d->sd->state(), ids, v);
       const int64_t n = (int64_t)ids.size();
       if (n <= cap) {
          if (grain_ids) std::memcpy(grain_ids, ids.data(), sizeof(int32_t) * n);
@@ -847,7 +850,7 @@ int exa_driver_lattice_curvature(exa_driver* d, double burgers, double* out, int
       SystemDriver& sd = *d->sd;
       if (out || summary7) {
          std::vector<double> rows; double m[7];
-         sd.LatticeCurvature(burgers, rows, m);
+         sd.analyses().LatticeCurvature(sd.state(), burgers, rows, m);
          if (out) std::memcpy(out, rows.data(), sizeof(double) * rows.size());
          if (summary7) std::memcpy(summary7, m, sizeof(m));
       }
@@ -871,18 +874,18 @@ int exa_options_query_lattice_curvature(const char* toml_path, int* enabled, dou
 }
 
 int exa_driver_enable_slip_activity(exa_driver* d, char* err, int errlen) {
-   try { d->sd->EnableSlipActivity(); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+   try { d->sd->analyses().EnableSlipActivity(); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 int exa_driver_reset_fatigue_window(exa_driver* d, char* err, int errlen) {
-   try { d->sd->ResetFatigueWindow(); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+   try { d->sd->analyses().ResetFatigueWindow(d->sd->state()); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 int exa_driver_slip_activity(exa_driver* d, double k_fs, double sigma_y, double* acc_out, double* fip_out, int64_t* elem_gid, int32_t* attribute, double* summary8,
                              int32_t* grain_ids, double* grain_vals3, int64_t grain_cap, int64_t* n_grains, char* err, int errlen) {
    try {
       SystemDriver& sd = *d->sd;
       if (acc_out || fip_out || summary8 || n_grains) {
-         SystemDriver::SlipActivityResult r;
-         sd.SlipActivity(k_fs, sigma_y, r, false, acc_out != nullptr);
+         StepAnalyses::SlipActivityResult r;
+         sd.analyses().SlipActivity(sd.state(), k_fs, sigma_y, r, acc_out != nullptr);
          if (acc_out) std::memcpy(acc_out, r.acc.data(), sizeof(double) * r.acc.size());
          if (fip_out) std::memcpy(fip_out, r.fip.data(), sizeof(double) * r.fip.size());
          if (summary8) std::memcpy(summary8, r.summary, sizeof(r.summary));
@@ -940,7 +943,7 @@ int exa_driver_pole_figures(exa_driver* d, int nhkl, const int* hkl3, int ndir, 
          throw std::runtime_error("exa_driver_pole_figures: 0 to 16 families, 0 to 3 directions (at least one set) and an output are required");
       const std::vector<int> hkl(hkl3, hkl3 + 3 * nhkl);
       std::vector<double> mrd;
-      d->sd->PoleFigures(hkl, std::vector<double>(dirs3, dirs3 + 3 * ndir), res_deg, mrd);
+      d->sd->analyses().PoleFigures(d->sd->state(), hkl, std::vector<double>(dirs3, dirs3 + 3 * ndir), res_deg, mrd);
       std::memcpy(mrd_out, mrd.data(), sizeof(double) * mrd.size());
       return 0;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }

@@ -138,9 +138,9 @@ struct ExaOptions {
       for (int i = 0; i < 3; i++) s[i] /= n;
       if (!(tol_deg > 0.0 && tol_deg <= 90.0)) throw std::runtime_error("Visualizations.light_up_dist_tol_deg must lie in (0, 90]");
    }
-   // per-grain averages written every Visualizations.steps steps (driver.hip, SystemDriver::GrainAverages): <out_dir>/<grain_avgs_fname>_<step %06d>.txt
+   // per-grain averages written every Visualizations.steps steps (host/analyses.hip, StepAnalyses::GrainAverages): <out_dir>/<grain_avgs_fname>_<step %06d>.txt
    bool grain_avgs = false; std::string grain_avgs_fname = "grain_avgs";
-   // texture (driver.hip, SystemDriver::PoleFigures): pole figures of the texture_hkl families and inverse pole figures of the
+   // texture (host/analyses.hip, StepAnalyses::PoleFigures): pole figures of the texture_hkl families and inverse pole figures of the
    // texture_ipf_dirs (unit) in multiples of random distribution, written at step 0, every Visualizations.steps steps and at the last step
    // to <out_dir>/<texture_fname>_<step %06d>.txt
    bool texture = false; std::vector<int> texture_hkl = { 1, 1, 1, 2, 0, 0, 2, 2, 0 }; std::vector<double> texture_dirs = { 0, 0, 1 };
@@ -149,11 +149,11 @@ struct ExaOptions {
    // one row (step, time, dt, V, 81 values with 17 significant digits) appended to <out_dir>/<macro_tangent_fname> every Visualizations.steps steps
    // and at the last step.  rel_tol / max_iter of its nine solves: 0 = the Solvers.Krylov values
    bool macro_tangent = false; std::string macro_tangent_fname = "macro_tangent.txt"; double macro_tangent_rel_tol = 0.0; int macro_tangent_max_iter = 0;
-   // intragranular misorientation and lattice curvature (driver.hip, SystemDriver::LatticeCurvature): one row (step, time, mean and
+   // intragranular misorientation and lattice curvature (host/analyses.hip, StepAnalyses::LatticeCurvature): one row (step, time, mean and
    // max of GROD, KAM and the GND density, 17 significant digits) appended to <out_dir>/<lattice_curvature_fname> every Visualizations.steps steps and
    // at the last step, and four more cell arrays in the ParaView pieces; lattice_curvature_burgers: Burgers vector length in the mesh's length unit
    bool lattice_curvature = false; double lattice_curvature_burgers = 1.0; std::string lattice_curvature_fname = "lattice_curvature.txt";
-   // slip-system activity and the Fatemi-Socie fatigue indicator parameter (driver.hip, SystemDriver::SlipActivity): accumulated in every
+   // slip-system activity and the Fatemi-Socie fatigue indicator parameter (host/analyses.hip, StepAnalyses::SlipActivity): accumulated in every
    // committed step; evaluated every fatigue_cycle_steps steps (0: every Visualizations.steps steps) and at the last step - one row appended to
    // <out_dir>/<fatigue_fname>, the per-grain file fatigue_grains_<step %06d>.txt - and, with fatigue_cycle_steps > 0, the window reset after it; four
    // more cell arrays in the ParaView pieces.  fatigue_sigma_y (the yield stress that scales the normal stress) has no default

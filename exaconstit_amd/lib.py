@@ -224,6 +224,7 @@ exa_driver_get_qf_component = _sig("exa_driver_get_qf_component", C.c_int, C.c_v
 exa_driver_nfev_hist_of = _sig("exa_driver_nfev_hist_of", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int)
 exa_driver_get_diagnostics = _sig("exa_driver_get_diagnostics", None, C.c_void_p, C.POINTER(C.c_int64))
 exa_driver_get_rate_launches = _sig("exa_driver_get_rate_launches", C.c_int64, C.c_void_p)
+exa_driver_get_field_launches = _sig("exa_driver_get_field_launches", C.c_int64, C.c_void_p)
 exa_rccl_microbench = _sig("exa_rccl_microbench", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_char_p, C.c_int)
 exa_bootstrap_env = _sig("exa_bootstrap_env", C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
 exa_bootstrap_reply_fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p)
@@ -964,7 +965,7 @@ class Driver:
         exa_driver_get_pcg_reduction(self.h, r.ctypes.data_as(C.POINTER(C.c_double)))
         return dict(model_failed_points=int(o[0]), pcg_not_converged=int(o[1]), pcg_indefinite_iters=int(o[2]), pcg_last_flag=int(o[3]),
                     pcg_last_reduction=float(r[0]), pcg_worst_capped_reduction=float(r[1]),
-                    slip_rate_launches=int(exa_driver_get_rate_launches(self.h)))
+                    slip_rate_launches=int(exa_driver_get_rate_launches(self.h)), element_field_launches=int(exa_driver_get_field_launches(self.h)))
 
     def bench_prepare(self, dts, perturb=1.0, advance=True):
         """Kinematic drive to the state the timed passes start from; advance=False keeps the virgin state (elastic first step, dt = dts[0])."""

@@ -141,6 +141,10 @@ void exa_driver_get_diagnostics(exa_driver* d, int64_t* out4);
  * exa_set_lean_state; EXA_LEAN_STATE=off at creation: the full state) and the 12 slip rates are written when a reader of state slots 14..25 asks:
  * the additional averages, the element fields, a checkpoint, exa_driver_get_qf_component of those slots.  A run that asks for none of them stays at 0. */
 int64_t exa_driver_get_rate_launches(exa_driver* d);
+/* Launches of exa_element_fields so far.  Every analysis of the element rows (fields, lattice strains, grain averages, texture, curvature, slip
+ * activity, the ParaView save) takes them from one accessor, which launches only when the rows it holds are not those of the state at hand:
+ * analyses asked for in a row on one state share one launch (exa_driver_element_fields itself always launches). */
+int64_t exa_driver_get_field_launches(exa_driver* d);
 /* Residual reduction |r|_M / |r0|_M the PCG reached: out2[0] last solve, out2[1] the worst among the solves that stopped at max_iter
  * (MFEM's CGSolver prints "No convergence!" with the final norms, linalg/solvers.cpp; the reference's Newton loop goes on regardless). */
 void exa_driver_get_pcg_reduction(exa_driver* d, double* out2);
