@@ -284,6 +284,11 @@ int exa_model_tail_count(exa_ctx* ctx, exa_stream s) {
    EXA_HIP_CHECK(ctx, hipStreamSynchronize(S(s)));
    return h;
 }
+int exa_model_record_launches(exa_ctx* ctx, long long* out2) {
+   if (!ctx || !out2) return fail(ctx, EXA_ERR_ARG, "exa_model_record_launches: null pointer");
+   out2[0] = ctx->rec_policy_launches; out2[1] = ctx->rec_generic_launches;
+   return EXA_OK;
+}
 
 int exa_calc_dp(exa_ctx* ctx, const double* state, double* dp, exa_stream s) {
    if (!ctx || !state || !dp) return fail(ctx, EXA_ERR_ARG, "exa_calc_dp: null pointer");

@@ -1257,14 +1257,15 @@ ECM_DI void staged_tangent(const IO& io, double* cmat, Emit&& emit) {
 // LEAN (record launches of the stand-alone driver, element-blocked): the end-of-step state carries, instead of the 12 slip rates (slots 14..25), what
 // they are a function of besides the hardness in slot 13 - the lattice strain e_f in slots 14..18 and, for the Kocks-Mecking kinds, the thermal
 // factor c_e in slot 19 - and k_slip_rates_from_state (model_kernels.hip) writes the rates when somebody reads them; slots 20..25 are not written
-template <int KIN, int QS, bool REC = false, bool STG = false, bool LEAN = false, class IO>
+// TAIL = false (launches that are never split, model_kernel.hpp): kcap and tio are not looked at - no cap test, no hand-over, never a resumed solve
+template <int KIN, int QS, bool REC = false, bool STG = false, bool LEAN = false, bool TAIL = true, class IO>
 ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io, const int kcap, const PointIn& pin,
                         const double* pq_lds = nullptr, const double tsc = 0.0, const bool trd = false, const TailIO tio = TailIO()) {
    // (STG with REC: state and stress rows staged, the compact record written by each lane straight to its slot of the element-blocked record array)
    static_assert(!STG || QS == 1, "staged outputs: AOS rows");
    static_assert(!LEAN || (!STG && REC), "lean end-of-step state: the per-lane record launches");
    bool cut = false;   // STG: handed over to the dense launch (the lane stays for the wave's stores; what it writes the dense launch overwrites)
-   const bool resume = tio.rs_in != nullptr;
+   const bool resume = TAIL && tio.rs_in != nullptr;
    double* st = io.stash();
    Prob pb; pb.st = st; pb.gs = QS; pb.pqt = pq_lds;
    pb.dt_ri = 1.0 / dt;
@@ -1340,6 +1341,10 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
    // it repeats one the cut-off launch has made, bit for bit), then the iteration goes on as if it had never stopped.
    double x[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
    if (resume) { for (int i = 0; i < 8; i++) x[i] = ldg(&tio.rs_in[i * tio.stride]); }
+   // TAIL = false: never resumed, so the first evaluation is known to run at x = 0 and the compiler folds what is exact there (the exponential map of a zero
+   // rotation, products with 1) - and then contracts other multiply-add pairs than the generic kernel does: the elastic first step differed in the last bit of
+   // the lattice strain (tests/test_gpu_record_launch_policy.py).  The iterate is pinned opaque, which gives that specialisation up and keeps the generic bits.
+   if constexpr (!TAIL) { for (int i = 0; i < 8; i++) asm volatile("" : "+v"(x[i])); }
    double r[8], dis_rate, shrate;
    Jac J; Fact F;
    int nfev = 1; bool conv = false;
@@ -1385,7 +1390,7 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
       for (int it = 0; it < 200; it++) {
          // tail split: a point that needs more than kcap evaluations is handed to the dense tail launch (which starts over, so the
          // result is the one of an uncapped solve); the wave stops waiting for its slowest lanes
-         if (nfev >= kcap || (DEFER && hand_over)) {
+         if (TAIL && (nfev >= kcap || (DEFER && hand_over))) {
             const int slot = atomicAdd(&tio.list_out[0], 1); tio.list_out[1 + slot] = io.ipt();
             if (tio.rs_out) {
                double* o = tio.rs_out + slot;
@@ -1471,7 +1476,9 @@ ECM_DI int point_update(const MatParams& mp, double dt, const double L[9], IO io
    double* __restrict__ sv1 = io.sv1(); double* __restrict__ s1 = io.s1();
    [[maybe_unused]] double* __restrict__ cmat = io.cm();   // (unused in a -DECM_NO_TANGENT timing build, like bulkNew below)
    double e_f[5], xi[3];
-   for (int i = 0; i < 5; i++) e_f[i] = ECM_ST(st, ST_EN + i) + x[i] * pb.esc;
+   // (TAIL = false: the generic kernel contracts this product into its sum; without the cap exit the loop leaves x[i] * esc in another block than the
+   //  sum, where the backend does not contract them - the lattice strain differed in its last bit.  Written as the fused operation, it is the same bits.)
+   for (int i = 0; i < 5; i++) { if constexpr (TAIL) e_f[i] = ECM_ST(st, ST_EN + i) + x[i] * pb.esc; else e_f[i] = fma(x[i], pb.esc, ECM_ST(st, ST_EN + i)); }
    for (int i = 0; i < 3; i++) xi[i] = x[5 + i] * R_SCALE;
    double Cf[9], qout[4];
    {

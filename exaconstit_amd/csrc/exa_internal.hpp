@@ -71,6 +71,8 @@ struct exa_ctx {
    // exa_set_lean_state: the element-blocked record launches leave the inputs of the slip rates in state slots 14..19 instead of the 12 rates;
    // lean_kin: kernel kind (ecmdev::KIN_* with its flags) of the last such launch, which exa_slip_rates_from_state instantiates the kinetics with
    bool lean_state = false; int lean_kin = -1;
+   // element-blocked p = 1 record launches so far: through the entry without tail-split arguments (k_model_setup_rec_nt) / through the generic kernel (exa_model_record_launches)
+   int64_t rec_policy_launches = 0, rec_generic_launches = 0;
    double* scratch_dev = nullptr; size_t scratch_bytes = 0;   // reductions
    double hist_init[ecmdev::NUM_HIST];
 };

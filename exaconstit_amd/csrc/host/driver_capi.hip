@@ -522,6 +522,11 @@ void exa_driver_get_diagnostics(exa_driver* d, int64_t* out) {
 }
 // launches of exa_slip_rates_from_state so far (lean end-of-step state: NonlinearMechOperator::EnsureSlipRates)
 int64_t exa_driver_get_rate_launches(exa_driver* d) { return d->sd->oper().rate_launches; }
+void exa_driver_get_record_launches(exa_driver* d, int64_t* out2) {
+   long long n[2] = { 0, 0 };
+   (void)exa_model_record_launches(d->sd->oper().GetModel()->ctx(), n);
+   out2[0] = n[0]; out2[1] = n[1];
+}
 // launches of exa_element_fields so far (StepAnalyses::rows launches only when the rows it holds are not those of the state at hand)
 int64_t exa_driver_get_field_launches(exa_driver* d) { return d->sd->analyses().field_launches; }
 

@@ -124,6 +124,18 @@ static void launch_model_rec_l(exa_ctx* ctx, double dt, double* J, const double*
    const int bs = EXA_MODEL_BS;
    const int64_t nb = (((int64_t)((ctx->E + 63) / 64) * ctx->Q) + (bs / 64) - 1) / (bs / 64);
    const int trd = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
+   // A Voce launch that is not split and writes no Jacobian field (the driver's production route: Voce stays uncapped) runs the entry that has the tail-split
+   // plumbing compiled out (model_kernel.hpp, k_model_setup_rec_nt).  A launch with a cap keeps the generic kernel for its main AND its dense launches: a
+   // listed point is finished by the instantiation that began it.
+   if constexpr (!ecmdev::kin_is_km(KIN)) {
+      if (J == nullptr && !model_split(ctx) && model_policy()) {
+         ctx->rec_policy_launches++;
+         hipLaunchKernelGGL((k_model_setup_rec_nt<KIN, LEAN>), dim3((unsigned)nb), dim3(bs), model_lds_bytes(ctx, false, false, true, 0, true), s, ctx->mp, ctx->Q, ctx->P, dt, ctx->G_dev, vel, xl, ctx->conn,
+                            ctx->nnodes, stress0, state0, stress1, state1, ctx->pa_c, ctx->fail_count_dev, ctx->W_dev, trd);
+         return;
+      }
+   }
+   ctx->rec_generic_launches++;
    launch_levels(ctx, nb, [&](int64_t blocks, int kcap, int* list, int mode, int* list_out, const double* rs_in, double* rs_out) {
       hipLaunchKernelGGL((k_model_setup<KIN, true, 8, true, true, false, LEAN>), dim3((unsigned)blocks), dim3(bs), model_lds_bytes(ctx, ecmdev::kin_is_km(KIN), false, true, mode, true), s, ctx->mp, ctx->Q, ctx->n, ctx->P, dt, J, ctx->G_dev, vel, xl, ctx->conn,
                          ctx->nnodes, stress0, state0, stress1, state1, ctx->pa_c, ctx->fail_count_dev, kcap, list, mode, ctx->W_dev, trd, list_out, rs_in, rs_out);

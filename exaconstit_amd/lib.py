@@ -76,6 +76,7 @@ exa_set_newton_cap = _sig("exa_set_newton_cap", C.c_int, C.c_void_p, C.c_int)
 exa_selftest_km_math = _sig("exa_selftest_km_math", C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 exa_set_newton_caps = _sig("exa_set_newton_caps", C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int)
 exa_model_tail_count = _sig("exa_model_tail_count", C.c_int, C.c_void_p, C.c_void_p)
+exa_model_record_launches = _sig("exa_model_record_launches", C.c_int, C.c_void_p, C.POINTER(C.c_longlong))
 exa_set_newton_cap_auto = _sig("exa_set_newton_cap_auto", C.c_int, C.c_void_p, C.c_int, C.c_double)
 exa_get_newton_cap = _sig("exa_get_newton_cap", C.c_int, C.c_void_p)
 exa_set_lean_state = _sig("exa_set_lean_state", C.c_int, C.c_void_p, C.c_int)
@@ -224,6 +225,7 @@ exa_driver_get_qf_component = _sig("exa_driver_get_qf_component", C.c_int, C.c_v
 exa_driver_nfev_hist_of = _sig("exa_driver_nfev_hist_of", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_char_p, C.c_int)
 exa_driver_get_diagnostics = _sig("exa_driver_get_diagnostics", None, C.c_void_p, C.POINTER(C.c_int64))
 exa_driver_get_rate_launches = _sig("exa_driver_get_rate_launches", C.c_int64, C.c_void_p)
+exa_driver_get_record_launches = _sig("exa_driver_get_record_launches", None, C.c_void_p, C.POINTER(C.c_int64))
 exa_driver_get_field_launches = _sig("exa_driver_get_field_launches", C.c_int64, C.c_void_p)
 exa_rccl_microbench = _sig("exa_rccl_microbench", C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_char_p, C.c_int)
 exa_bootstrap_env = _sig("exa_bootstrap_env", C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int))
@@ -963,7 +965,9 @@ class Driver:
         exa_driver_get_diagnostics(self.h, o.ctypes.data_as(C.POINTER(C.c_int64)))
         r = np.zeros(2)
         exa_driver_get_pcg_reduction(self.h, r.ctypes.data_as(C.POINTER(C.c_double)))
-        return dict(model_failed_points=int(o[0]), pcg_not_converged=int(o[1]), pcg_indefinite_iters=int(o[2]), pcg_last_flag=int(o[3]),
+        n = np.zeros(2, np.int64)
+        exa_driver_get_record_launches(self.h, n.ctypes.data_as(C.POINTER(C.c_int64)))
+        return dict(record_policy_launches=int(n[0]), record_generic_launches=int(n[1]), model_failed_points=int(o[0]), pcg_not_converged=int(o[1]), pcg_indefinite_iters=int(o[2]), pcg_last_flag=int(o[3]),
                     pcg_last_reduction=float(r[0]), pcg_worst_capped_reduction=float(r[1]),
                     slip_rate_launches=int(exa_driver_get_rate_launches(self.h)), element_field_launches=int(exa_driver_get_field_launches(self.h)))
 

@@ -141,6 +141,9 @@ void exa_driver_get_diagnostics(exa_driver* d, int64_t* out4);
  * exa_set_lean_state; EXA_LEAN_STATE=off at creation: the full state) and the 12 slip rates are written when a reader of state slots 14..25 asks:
  * the additional averages, the element fields, a checkpoint, exa_driver_get_qf_component of those slots.  A run that asks for none of them stays at 0. */
 int64_t exa_driver_get_rate_launches(exa_driver* d);
+/* p = 1 record launches of the driver's context so far (include/exaconstit_hip.h, exa_model_record_launches): out2[0] through the entry without tail-split
+ * arguments, out2[1] through the generic kernel; both 0 on the other routes. */
+void exa_driver_get_record_launches(exa_driver* d, int64_t* out2);
 /* Launches of exa_element_fields so far.  Every analysis of the element rows (fields, lattice strains, grain averages, texture, curvature, slip
  * activity, the ParaView save) takes them from one accessor, which launches only when the rows it holds are not those of the state at hand:
  * analyses asked for in a row on one state share one launch (exa_driver_element_fields itself always launches). */

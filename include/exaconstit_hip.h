@@ -213,6 +213,10 @@ int exa_set_newton_cap(exa_ctx* ctx, int max_evals);
  * exa_set_newton_cap(ctx, K) is exa_set_newton_caps(ctx, K, 0, <current resume setting>). */
 int exa_set_newton_caps(exa_ctx* ctx, int max_evals, int max_evals_2, int resume);
 int exa_model_tail_count(exa_ctx* ctx, exa_stream s);
+/* Element-blocked p = 1 record launches (exa_model_setup_lvec_records) of this context so far: out2[0] through the kernel entry that has the tail-split
+ * arguments compiled out - Voce kinds, no cap in force, no Jacobian field asked for -, out2[1] through the generic kernel (a sequence of capped and dense
+ * launches counts once).  EXA_MODEL_POLICY=off in the environment (read per launch) keeps every launch generic: an A/B switch, the bits are the same. */
+int exa_model_record_launches(exa_ctx* ctx, long long* out2);
 /* Let the library choose max_evals itself (what the stand-alone driver does for its own launches, host/driver.hip): after the first four launches
  * of exa_model_setup / _lvec / _lvec_records and after every fourth one from then on, the evaluation counts the launch left in state1 are binned
  * (exa_model_nfev_hist: one small launch and a 256-byte read-back that waits for the stream) and the cap of the next launches is the K that

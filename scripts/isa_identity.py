@@ -15,7 +15,8 @@ Exit status 0 only if every symbol present on both sides is identical.
 Compare listings, not objects: the bundled object files differ in their wrapper even where the code is the same.  Masked, because they are no code:
 __hip_cuid_<hash>, a one-byte marker named after a hash of the source file's PATH, which differs between the two directories by construction, and the
 running number of the function in its local labels and loop comments (.LBB<n>_<m>, .Lfunc_end<n>, Header=BB<n>_<m>), which shifts behind a
-removed function.
+removed function - and with it the padding in front of a block label's loop comment, which the assembly printer aligns to a column: a label whose
+function number gains a digit (functions ADDED in front of it) gets one space less.
 """
 import os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -26,6 +27,7 @@ MODEL_UNITS = set(UNITS)
 CUID = re.compile(r"__hip_cuid_[0-9a-f]+")
 FN_LABEL = re.compile(r"\.L(func_begin|func_end|[A-Za-z]+)\d+(_\d+)?\b")
 LOOP_NOTE = re.compile(r"\bBB\d+(_\d+)\b")      # the block names in the loop comments ("in Loop: Header=BB<n>_<m>")
+LABEL_PAD = re.compile(r"^(\.L\w+:)\s+;")      # block label, padding, loop comment
 BEGIN = re.compile(r"-- Begin function (\S+)")
 
 
@@ -46,7 +48,7 @@ def listing(job):
 
 
 def mask(line):
-    return LOOP_NOTE.sub(r"BB\1", FN_LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) or ""), CUID.sub("__hip_cuid", line)))
+    return LABEL_PAD.sub(r"\1 ;", LOOP_NOTE.sub(r"BB\1", FN_LABEL.sub(lambda m: ".L" + m.group(1) + (m.group(2) or ""), CUID.sub("__hip_cuid", line))))
 
 
 def symbols(path):

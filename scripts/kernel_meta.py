@@ -17,3 +17,9 @@ for m in re.finditer(r'\.name:\s+(_Z13k_model_setupILi(\d+)ELb(\d)ELi(\d+)ELb(\d
     g = lambda k: int(re.search(k + r':\s+(\d+)', body).group(1))
     ag = re.search(r'\.agpr_count:\s+(\d+)', body)
     print("%-13s lvec=%s n=%s qb=%s stg=%s rec=%s lean=%s  vgpr %d  agpr %s  sgpr-spills %d  vgpr-spills %d  scratch %d B" % (names.get(kin, kin), lvec, nfix, qb, stg, rec, lean, g(r'\.vgpr_count'), ag.group(1) if ag else "?", g(r'\.sgpr_spill_count'), g(r'\.vgpr_spill_count'), g(r'\.private_segment_fixed_size')))
+# the entry without tail-split arguments (model_kernel.hpp, k_model_setup_rec_nt<KIN, LEAN, ...>): what an unsplit Voce record launch runs - the headline launch of bench.py
+for m in re.finditer(r'\.name:\s+(_Z20k_model_setup_rec_ntILi(\d+)ELb(\d)E\S*)\n((?:.*\n){1,14})', t):
+    kin, lean, body = m.group(2), m.group(3), m.group(4)
+    g = lambda k: int(re.search(k + r':\s+(\d+)', body).group(1))
+    ag = re.search(r'\.agpr_count:\s+(\d+)', body)
+    print("%-13s record launch, no tail split   lean=%s  vgpr %d  agpr %s  sgpr-spills %d  vgpr-spills %d  scratch %d B" % (names.get(kin, kin), lean, g(r'\.vgpr_count'), ag.group(1) if ag else "?", g(r'\.sgpr_spill_count'), g(r'\.vgpr_spill_count'), g(r'\.private_segment_fixed_size')))

@@ -80,7 +80,7 @@ def dynamic_lds(kernel, row):
     per-lane stash of ST_SLOTS = 38 doubles x block size (+ 8 x 12 doubles of slip table for the Kocks-Mecking kinds 2, 3, 6, 7; + the shape table in the
     dense tail launch / reference layout, not counted here).  Other kernels: unknown to this script (empty)."""
     import re
-    m = re.match(r"k_model_setup<(\d+),", kernel)
+    m = re.match(r"k_model_setup(?:_rec_nt)?<(\d+),", kernel)
     if not m:
         return ""
     try:
