@@ -1,7 +1,7 @@
 // Process-group bootstrap of the `mechanics` executable: who am I, how many are we, and the 128 bytes of the RCCL unique id on every rank.
 //
 // The reference is `mpirun -np N mechanics -opt options.toml` (src/mechanics_driver.cpp:119-150: MPI_Init, MPI_Comm_rank/size) and uses
-// MPI for every collective.  Here the collectives are RCCL over xGMI (host/driver.hip, class Comm); the only thing a launcher has to
+// MPI for every collective.  Here the collectives are RCCL over xGMI (host/comm.hip, class Comm); the only thing a launcher has to
 // provide is a rank number, so the executable runs unchanged under
 //    mpirun / mpiexec.hydra (MPICH: PMI_RANK, PMI_SIZE; Open MPI: OMPI_COMM_WORLD_RANK/SIZE/LOCAL_RANK), srun (SLURM_PROCID, SLURM_NTASKS,
 //    SLURM_LOCALID), torchrun-style environments (RANK, WORLD_SIZE, LOCAL_RANK) or a shell loop (EXA_RANK, EXA_NRANKS)

@@ -2,20 +2,10 @@
 #include "driver.hpp"
 #include "multigrid.hpp"
 #include "roctx.hpp"
-#include <rccl/rccl.h>
-#include <atomic>
 #include <chrono>
 #include <memory>
-#include <thread>
-#include <fcntl.h>
-#include <sys/mman.h>
 #include <sys/stat.h>
-#include <unistd.h>
-#include <dlfcn.h>
-#include <link.h>
 #include <algorithm>
-#include <condition_variable>
-#include <mutex>
 #include <cmath>
 #include <limits>
 #include <cstring>
@@ -32,402 +22,6 @@ extern "C" int exa_grad_apply_lvec_cols_w(exa_ctx* ctx, int nch, int ncols, cons
 
 
 namespace exa_host {
-
-// =====================================================================================================================
-// Comm: RCCL loaded at run time so that single-GPU use has no collective-library dependency
-// =====================================================================================================================
-namespace {
-struct RcclApi {
-   void* h = nullptr;
-   ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-   ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-   ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-   ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;
-   ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-   ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-   ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-   ncclResult_t (*GroupStart)() = nullptr;
-   ncclResult_t (*GroupEnd)() = nullptr;
-   const char* (*GetErrorString)(ncclResult_t) = nullptr;
-};
-RcclApi& rccl() {
-   static RcclApi api;
-   if (!api.h) {
-      // prefer the RCCL already mapped into the process (PyTorch bundles its own copy next to its HIP runtime): two RCCL builds in
-      // one process would each bring their own device state
-      std::string loaded;
-      dl_iterate_phdr([](struct dl_phdr_info* info, size_t, void* out) -> int {
-         if (info->dlpi_name && std::strstr(info->dlpi_name, "librccl")) { *static_cast<std::string*>(out) = info->dlpi_name; return 1; }
-         return 0; }, &loaded);
-      if (!loaded.empty()) api.h = dlopen(loaded.c_str(), RTLD_NOW | RTLD_GLOBAL);
-      if (!api.h) for (const char* name : { "librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so.1" }) { api.h = dlopen(name, RTLD_NOW | RTLD_GLOBAL); if (api.h) break; }
-      if (!api.h) throw std::runtime_error(std::string("cannot load RCCL: ") + dlerror());
-      auto sym = [&](const char* n) { void* p = dlsym(api.h, n); if (!p) throw std::runtime_error(std::string("RCCL symbol missing: ") + n); return p; };
-      api.GetUniqueId = (decltype(api.GetUniqueId))sym("ncclGetUniqueId");
-      api.CommInitRank = (decltype(api.CommInitRank))sym("ncclCommInitRank");
-      api.CommDestroy = (decltype(api.CommDestroy))sym("ncclCommDestroy");
-      api.CommCount = (decltype(api.CommCount))sym("ncclCommCount");
-      api.AllReduce = (decltype(api.AllReduce))sym("ncclAllReduce");
-      api.Send = (decltype(api.Send))sym("ncclSend");
-      api.Recv = (decltype(api.Recv))sym("ncclRecv");
-      api.GroupStart = (decltype(api.GroupStart))sym("ncclGroupStart");
-      api.GroupEnd = (decltype(api.GroupEnd))sym("ncclGroupEnd");
-      api.GetErrorString = (decltype(api.GetErrorString))sym("ncclGetErrorString");
-   }
-   return api;
-}
-void nccl_check(ncclResult_t r, const char* what) { if (r != ncclSuccess) throw std::runtime_error(std::string(what) + ": " + rccl().GetErrorString(r)); }
-}  // namespace
-
-// ---- in-process loopback transport (test infrastructure for the multi-rank logic on a one-GPU box) -----------------------------
-// Several SystemDrivers, one host thread each, share one device; collectives are host-synchronous exchanges through this group.
-// It exercises exactly the code RCCL is used from (partition, pack / unpack-add, weighted dots, reductions); only the RCCL calls
-// themselves are replaced.  RCCL cannot be used for this: it refuses two ranks on one device ("Duplicate GPU detected").
-struct LoopbackGroup {
-   int n; std::mutex m; std::condition_variable cv; int waiting = 0; uint64_t gen = 0;
-   std::vector<std::vector<double>> red;                 // per-rank contribution of the current reduction
-   std::vector<std::vector<const double*>> sendbuf;      // [rank][neighbour slot] device send buffers of the current halo exchange
-   std::vector<std::vector<int>> nbr_rank;               // [rank][slot] neighbour rank
-   // stream-asynchronous exchange (Comm::exchange): "my send buffer is packed" / "I have read my neighbours' send buffers", recorded by every rank
-   // on its own stream and waited for by its peers' streams - the host threads only meet to know that the events have been recorded
-   std::vector<hipEvent_t> ev_packed, ev_read;
-   explicit LoopbackGroup(int n_) : n(n_), red(n_), sendbuf(n_), nbr_rank(n_), ev_packed(n_, nullptr), ev_read(n_, nullptr) {}
-   ~LoopbackGroup() { for (hipEvent_t e : ev_packed) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : ev_read) if (e) (void)hipEventDestroy(e); }
-   void barrier() {
-      std::unique_lock<std::mutex> lk(m);
-      const uint64_t g = gen;
-      if (++waiting == n) { waiting = 0; gen++; cv.notify_all(); }
-      else cv.wait(lk, [&] { return gen != g; });
-   }
-};
-static const char kLoopMagic[8] = { 'E', 'X', 'A', 'L', 'O', 'O', 'P', '1' };
-
-void Comm::loopback_create(int nranks, void* out128) {
-   std::memset(out128, 0, 128);
-   std::memcpy(out128, kLoopMagic, 8);
-   LoopbackGroup* g = new LoopbackGroup(nranks);
-   std::memcpy((char*)out128 + 8, &g, sizeof(g));
-}
-void Comm::loopback_destroy(const void* id128) {
-   if (std::memcmp(id128, kLoopMagic, 8) != 0) return;
-   LoopbackGroup* g; std::memcpy(&g, (const char*)id128 + 8, sizeof(g)); delete g;
-}
-
-// ---- inter-process transport for ranks that share ONE device (test / plumbing transport, like the loopback group but across processes) -----
-// RCCL refuses two ranks on one device, so `mpirun -np 2 mechanics ...` or `torchrun --nproc-per-node 2 bench.py --gpus 2` could never run
-// end to end on a one-GPU box: launcher environment, TCP rendez-vous, local-rank -> device mapping, per-rank files, torch's communicator
-// beside this library's.  With EXA_TRANSPORT=ipc (or automatically when there are more ranks than visible devices) rank 0 hands out an id
-// of this kind instead of a RCCL id.  Control data lives in a POSIX shared-memory segment named after the id; the halo segments travel
-// device-to-device through hipIpcMemHandle mappings of the neighbours' send buffers; reductions go through the segment in rank order.
-// Exchanges are host-synchronous (stream sync + barrier), so this is NOT a performance path.
-constexpr int IPC_MAX_RANKS = 64, IPC_MAX_NBR = 32, IPC_MAX_RED = 32;   // reductions longer than IPC_MAX_RED doubles pass through the slots in pieces
-struct IpcShared {
-   std::atomic<uint32_t> ready; uint32_t n;
-   std::atomic<uint64_t> arrived, generation;
-   double red[IPC_MAX_RANKS][IPC_MAX_RED];
-   hipIpcMemHandle_t sbuf[IPC_MAX_RANKS]; uint64_t sbuf_len[IPC_MAX_RANKS];
-   int32_t nnbr[IPC_MAX_RANKS]; int32_t nbr_rank[IPC_MAX_RANKS][IPC_MAX_NBR]; uint64_t seg_off[IPC_MAX_RANKS][IPC_MAX_NBR + 1];
-};
-struct IpcGroup {
-   IpcShared* sh = nullptr; int n = 0, rank = 0; std::string name;
-   std::vector<double*> peer_sbuf;      // neighbours' send buffers mapped into this process (by rank; nullptr: not a neighbour)
-   void barrier() {
-      const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(120);
-      const uint64_t g = sh->generation.load(std::memory_order_acquire);
-      if (sh->arrived.fetch_add(1, std::memory_order_acq_rel) + 1 == (uint64_t)n) { sh->arrived.store(0, std::memory_order_release); sh->generation.fetch_add(1, std::memory_order_acq_rel); }
-      else while (sh->generation.load(std::memory_order_acquire) == g) {
-         std::this_thread::yield();
-         if (std::chrono::steady_clock::now() > t_end) throw std::runtime_error("ipc transport: a rank did not reach the barrier within 120 s (did a peer fail?)");
-      }
-   }
-   ~IpcGroup() {
-      for (double* p : peer_sbuf) if (p) (void)hipIpcCloseMemHandle(p);
-      if (sh) ::munmap(sh, sizeof(IpcShared));
-   }
-};
-static const char kIpcMagic[8] = { 'E', 'X', 'A', 'I', 'P', 'C', '0', '1' };
-static std::string ipc_name(const void* uid) {
-   static const char* hex = "0123456789abcdef"; std::string s = "/exaipc_";
-   for (int i = 8; i < 24; i++) { const unsigned char c = ((const unsigned char*)uid)[i]; s += hex[c >> 4]; s += hex[c & 15]; }
-   return s;
-}
-static IpcGroup* ipc_attach(const void* uid, int rank, int nranks) {
-   if (nranks > IPC_MAX_RANKS) throw std::runtime_error("ipc transport: too many ranks");
-   auto g = std::make_unique<IpcGroup>(); g->n = nranks; g->rank = rank; g->name = ipc_name(uid); g->peer_sbuf.assign((size_t)nranks, nullptr);
-   const auto t_end = std::chrono::steady_clock::now() + std::chrono::seconds(60);
-   int fd = -1;
-   if (rank == 0) {
-      ::shm_unlink(g->name.c_str());
-      fd = ::shm_open(g->name.c_str(), O_CREAT | O_EXCL | O_RDWR, 0600);
-      if (fd < 0 || ::ftruncate(fd, (off_t)sizeof(IpcShared)) != 0) throw std::runtime_error(std::string("ipc transport: shm_open ") + g->name + ": " + std::strerror(errno));
-   } else {
-      while ((fd = ::shm_open(g->name.c_str(), O_RDWR, 0600)) < 0) {
-         if (std::chrono::steady_clock::now() > t_end) throw std::runtime_error("ipc transport: rank 0's segment " + g->name + " did not appear");
-         std::this_thread::sleep_for(std::chrono::milliseconds(20));
-      }
-      struct stat st; while (::fstat(fd, &st) == 0 && (size_t)st.st_size < sizeof(IpcShared)) { if (std::chrono::steady_clock::now() > t_end) throw std::runtime_error("ipc transport: segment not sized"); std::this_thread::sleep_for(std::chrono::milliseconds(5)); }
-   }
-   void* m = ::mmap(nullptr, sizeof(IpcShared), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
-   ::close(fd);
-   if (m == MAP_FAILED) throw std::runtime_error("ipc transport: mmap failed");
-   g->sh = (IpcShared*)m;
-   if (rank == 0) { g->sh->n = (uint32_t)nranks; g->sh->arrived.store(0); g->sh->generation.store(0); g->sh->ready.store(1, std::memory_order_release); }   // (a fresh segment is zero-filled)
-   else while (g->sh->ready.load(std::memory_order_acquire) != 1) { if (std::chrono::steady_clock::now() > t_end) throw std::runtime_error("ipc transport: rank 0 never became ready"); std::this_thread::yield(); }
-   if ((int)g->sh->n != nranks) throw std::runtime_error("ipc transport: group size mismatch");
-   g->barrier();                                   // everybody is attached: the name can go
-   if (rank == 0) ::shm_unlink(g->name.c_str());
-   return g.release();
-}
-void Comm::ipc_unique_id(void* out128) {
-   std::memset(out128, 0, 128); std::memcpy(out128, kIpcMagic, 8);
-   FILE* f = std::fopen("/dev/urandom", "rb");
-   if (!f || std::fread((char*)out128 + 8, 1, 16, f) != 16) { const uint64_t t = (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() ^ ((uint64_t)::getpid() << 32); std::memcpy((char*)out128 + 8, &t, 8); }
-   if (f) std::fclose(f);
-}
-bool Comm::want_ipc_transport(int nranks) {
-   if (const char* e = std::getenv("EXA_TRANSPORT")) { if (std::string(e) == "ipc") return true; if (std::string(e) == "rccl") return false; }
-   // Without identities (exa_comm_unique_id called by a launcher that did not compare them): ranks of THIS NODE against its visible devices.
-   // The node-local count comes from the launcher when it says so; the global count only stands in for it on a one-node launch.
-   int local = nranks;
-   for (const char* k : { "EXA_LOCAL_NRANKS", "LOCAL_WORLD_SIZE", "OMPI_COMM_WORLD_LOCAL_SIZE", "MPI_LOCALNRANKS", "SLURM_NTASKS_PER_NODE" })
-      if (const char* v = std::getenv(k)) { const int n = std::atoi(v); if (n > 0) { local = n; break; } }
-   int nd = 0; return nranks > 1 && hipGetDeviceCount(&nd) == hipSuccess && nd > 0 && local > nd;      // more ranks than devices on the node: RCCL cannot serve them
-}
-
-int Comm::reported_ranks() const {
-   if (comm_) { int n = 0; nccl_check(rccl().CommCount((ncclComm_t)comm_, &n), "ncclCommCount"); return n; }
-   if (ipc_) return (int)((IpcGroup*)ipc_)->sh->n;
-   if (loop_) return ((LoopbackGroup*)loop_)->n;
-   return 1;
-}
-
-void Comm::get_unique_id(void* out128) { ncclUniqueId id; nccl_check(rccl().GetUniqueId(&id), "ncclGetUniqueId"); std::memcpy(out128, &id, sizeof(id)); }
-
-void Comm::init(int rank_, int nranks_, const void* uid, bool force_rccl) {
-   rank = rank_; nranks = nranks_;
-   // EXA_FORCE_RCCL=1 routes the one-rank case through RCCL too (plumbing check on a single-GPU box)
-   force_ = (nranks == 1 && (force_rccl || std::getenv("EXA_FORCE_RCCL") != nullptr));
-   // EXA_HALO_SELFTEST=1 (with the forced one-rank communicator): the rank is its own neighbour across its x-max face (SystemDriver adds the entry) and sends
-   // ZEROS of the real halo size to itself - the grouped ncclSend / ncclRecv of an exchange, on the communication stream beside the interior blocks when the
-   // overlapped form is on, between the all-reduces of the PCG on the main stream: the two-stream use of one communicator on the hardware there is
-   selftest_zero_ = force_ && std::getenv("EXA_HALO_SELFTEST") != nullptr;
-   if (uid && std::memcmp(uid, kLoopMagic, 8) == 0) {
-      LoopbackGroup* g; std::memcpy(&g, (const char*)uid + 8, sizeof(g));
-      if (g->n != nranks) throw std::runtime_error("Comm::init: loopback group size mismatch");
-      loop_ = g; loop_async_ = std::getenv("EXA_LOOPBACK_SYNC") == nullptr;
-   } else if (uid && std::memcmp(uid, kIpcMagic, 8) == 0 && nranks > 1) {
-      ipc_ = ipc_attach(uid, rank, nranks);
-   } else if (nranks > 1 || force_) {
-      ncclUniqueId id;
-      if (uid) std::memcpy(&id, uid, sizeof(id));
-      else if (force_) nccl_check(rccl().GetUniqueId(&id), "ncclGetUniqueId");
-      else throw std::runtime_error("Comm::init: a RCCL unique id is required for nranks > 1");
-      ncclComm_t c; nccl_check(rccl().CommInitRank(&c, nranks, id, rank), "ncclCommInitRank");
-      comm_ = c;
-   }
-   tmp_.alloc(64);
-}
-Comm::~Comm() {
-   delete (IpcGroup*)ipc_;
-   if (comm_) rccl().CommDestroy((ncclComm_t)comm_);
-   if (cs_) { (void)hipStreamDestroy(cs_); (void)hipEventDestroy(ev_ready_); (void)hipEventDestroy(ev_done_); }
-}
-
-// op: 0 sum, 1 min, 2 max; host-synchronous, rank-ordered (deterministic)
-void Comm::loopback_reduce(double* dev, int n, int op, hipStream_t s) {
-   if (ipc_) {
-      IpcGroup* g = (IpcGroup*)ipc_;
-      std::vector<double> v((size_t)n);
-      EXA_HC(hipMemcpyAsync(v.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
-      for (int i0 = 0; i0 < n; i0 += IPC_MAX_RED) {   // piece by piece through the rank slots, every rank in the same order
-         const int m = std::min(IPC_MAX_RED, n - i0);
-         for (int i = 0; i < m; i++) g->sh->red[rank][i] = v[i0 + i];
-         g->barrier();
-         double r[IPC_MAX_RED];
-         for (int i = 0; i < m; i++) r[i] = g->sh->red[0][i];
-         for (int k = 1; k < g->n; k++) for (int i = 0; i < m; i++) { const double x = g->sh->red[k][i]; r[i] = op == 0 ? r[i] + x : (op == 1 ? std::min(r[i], x) : std::max(r[i], x)); }
-         g->barrier();   // everybody has read before the next piece overwrites
-         for (int i = 0; i < m; i++) v[i0 + i] = r[i];
-      }
-      EXA_HC(hipMemcpyAsync(dev, v.data(), sizeof(double) * n, hipMemcpyHostToDevice, s)); EXA_HC(hipStreamSynchronize(s));
-      return;
-   }
-   LoopbackGroup* g = (LoopbackGroup*)loop_;
-   std::vector<double>& mine = g->red[rank]; mine.resize(n);
-   EXA_HC(hipMemcpyAsync(mine.data(), dev, sizeof(double) * n, hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
-   g->barrier();
-   std::vector<double> r(g->red[0].begin(), g->red[0].begin() + n);
-   for (int k = 1; k < g->n; k++) for (int i = 0; i < n; i++) { const double v = g->red[k][i]; r[i] = op == 0 ? r[i] + v : (op == 1 ? std::min(r[i], v) : std::max(r[i], v)); }
-   g->barrier();   // everybody has read before the next reduction overwrites
-   EXA_HC(hipMemcpyAsync(dev, r.data(), sizeof(double) * n, hipMemcpyHostToDevice, s)); EXA_HC(hipStreamSynchronize(s));
-}
-void Comm::allreduce_sum(double* dev, int n, hipStream_t s) {
-   if (loop_ || ipc_) { if (nranks > 1) loopback_reduce(dev, n, 0, s); return; }
-   if (nranks > 1 || force_) nccl_check(rccl().AllReduce(dev, dev, n, ncclDouble, ncclSum, (ncclComm_t)comm_, s), "ncclAllReduce");
-}
-void Comm::allreduce_min(double* dev, int n, hipStream_t s) {
-   if (loop_ || ipc_) { if (nranks > 1) loopback_reduce(dev, n, 1, s); return; }
-   if (nranks > 1 || force_) nccl_check(rccl().AllReduce(dev, dev, n, ncclDouble, ncclMin, (ncclComm_t)comm_, s), "ncclAllReduce");
-}
-
-void Comm::allreduce_max(double* dev, int n, hipStream_t s) {
-   if (loop_ || ipc_) { if (nranks > 1) loopback_reduce(dev, n, 2, s); return; }
-   if (nranks > 1 || force_) nccl_check(rccl().AllReduce(dev, dev, n, ncclDouble, ncclMax, (ncclComm_t)comm_, s), "ncclAllReduce");
-}
-
-double Comm::max_over_ranks(double v) {
-   if (nranks == 1) return v;
-   if (loop_ || ipc_) { EXA_HC(hipMemcpy(tmp_.p, &v, sizeof(double), hipMemcpyHostToDevice)); loopback_reduce(tmp_.p, 1, 2, nullptr); EXA_HC(hipMemcpy(&v, tmp_.p, sizeof(double), hipMemcpyDeviceToHost)); return v; }
-   EXA_HC(hipMemcpy(tmp_.p, &v, sizeof(double), hipMemcpyHostToDevice));
-   nccl_check(rccl().AllReduce(tmp_.p, tmp_.p, 1, ncclDouble, ncclMax, (ncclComm_t)comm_, nullptr), "ncclAllReduce");
-   EXA_HC(hipMemcpy(&v, tmp_.p, sizeof(double), hipMemcpyDeviceToHost));
-   return v;
-}
-
-void Comm::microbench(int iters, int n, double* us_allreduce, double* us_sendrecv) {
-   if (!comm_) throw std::runtime_error("Comm::microbench needs a RCCL communicator (EXA_FORCE_RCCL=1 on one rank)");
-   DevBuf<double> a(2), sb((size_t)n), rb((size_t)n); a.zero(); sb.zero(); rb.zero();
-   hipStream_t s; EXA_HC(hipStreamCreate(&s));
-   hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1));
-   auto timed = [&](auto&& body) {
-      for (int i = 0; i < 10; i++) body();
-      EXA_HC(hipEventRecord(e0, s));
-      for (int i = 0; i < iters; i++) body();
-      EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1));
-      float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e0, e1)); return 1e3 * ms / iters;
-   };
-   *us_allreduce = timed([&] { nccl_check(rccl().AllReduce(a.p, a.p, 2, ncclDouble, ncclSum, (ncclComm_t)comm_, s), "ncclAllReduce"); });
-   *us_sendrecv = timed([&] {
-      nccl_check(rccl().GroupStart(), "ncclGroupStart");
-      nccl_check(rccl().Send(sb.p, (size_t)n, ncclDouble, rank, (ncclComm_t)comm_, s), "ncclSend");
-      nccl_check(rccl().Recv(rb.p, (size_t)n, ncclDouble, rank, (ncclComm_t)comm_, s), "ncclRecv");
-      nccl_check(rccl().GroupEnd(), "ncclGroupEnd"); });
-   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipStreamDestroy(s);
-}
-
-// One pack and one unpack launch per exchange: the neighbours' dof lists are concatenated (segment i = neighbour i), the send /
-// receive buffers are one allocation each.  (A launch per neighbour is 14 tiny kernels per operator action on a 2 x 2 x 2 grid -
-// more than the exchange itself.)  A dof shared with several neighbours appears in several segments: the unpack adds atomically.
-void Comm::setup_halo(const Partition& part) {
-   seg_off_.assign(1, 0);
-   std::vector<int32_t> all;
-   for (const Neighbor& nb : part.nbrs) { all.insert(all.end(), nb.dofs.begin(), nb.dofs.end()); seg_off_.push_back(all.size()); }
-   idx_all_.release(); sbuf_all_.release(); rbuf_all_.release();
-   if (!all.empty()) { idx_all_.alloc(all.size()); idx_all_.upload(all); sbuf_all_.alloc(all.size()); rbuf_all_.alloc(all.size()); }
-   if (ipc_) {   // publish this rank's send buffer and segment table, then map the neighbours' send buffers
-      IpcGroup* g = (IpcGroup*)ipc_; IpcShared* sh = g->sh;
-      if (part.nbrs.size() > (size_t)IPC_MAX_NBR) throw std::runtime_error("ipc transport: too many neighbours");
-      for (double*& p : g->peer_sbuf) if (p) { (void)hipIpcCloseMemHandle(p); p = nullptr; }
-      sh->nnbr[rank] = (int32_t)part.nbrs.size(); sh->sbuf_len[rank] = all.size();
-      for (size_t i = 0; i < part.nbrs.size(); i++) { sh->nbr_rank[rank][i] = part.nbrs[i].rank; sh->seg_off[rank][i] = seg_off_[i]; }
-      sh->seg_off[rank][part.nbrs.size()] = seg_off_.back();
-      if (!all.empty()) EXA_HC(hipIpcGetMemHandle(&sh->sbuf[rank], sbuf_all_.p));
-      g->barrier();
-      for (const Neighbor& nb : part.nbrs) if (!g->peer_sbuf[nb.rank]) {
-         void* p = nullptr; EXA_HC(hipIpcOpenMemHandle(&p, sh->sbuf[nb.rank], hipIpcMemLazyEnablePeerAccess));
-         g->peer_sbuf[nb.rank] = (double*)p;
-      }
-      g->barrier();
-   }
-}
-
-void Comm::halo_sum(const Partition& part, double* y, hipStream_t s) {
-   if (nranks == 1 && !force_) return;
-   vk_pack((int64_t)seg_off_.back(), idx_all_.p, y, sbuf_all_.p, s);
-   if (selftest_zero_) EXA_HC(hipMemsetAsync(sbuf_all_.p, 0, sizeof(double) * seg_off_.back(), s));
-   exchange(part, s);
-   unpack(y, s);
-}
-
-// Overlapped form: everything enqueued on s before halo_begin (the element blocks that touch shared dofs) is waited for by the
-// communication stream, which packs and exchanges while s goes on with the interior blocks; halo_end makes s wait for the exchange and
-// adds the received segments.  Same arithmetic as halo_sum: only the stream the pack / exchange run on differs.
-void Comm::halo_begin(const Partition& part, double* y, hipStream_t s) {
-   if (nranks == 1 && !force_) return;
-   if (!cs_) { EXA_HC(hipStreamCreateWithFlags(&cs_, hipStreamNonBlocking)); EXA_HC(hipEventCreateWithFlags(&ev_ready_, hipEventDisableTiming)); EXA_HC(hipEventCreateWithFlags(&ev_done_, hipEventDisableTiming)); }
-   EXA_HC(hipEventRecord(ev_ready_, s));
-   EXA_HC(hipStreamWaitEvent(cs_, ev_ready_, 0));
-   vk_pack((int64_t)seg_off_.back(), idx_all_.p, y, sbuf_all_.p, cs_);
-   if (selftest_zero_) EXA_HC(hipMemsetAsync(sbuf_all_.p, 0, sizeof(double) * seg_off_.back(), cs_));
-   exchange(part, cs_);
-   EXA_HC(hipEventRecord(ev_done_, cs_));
-}
-void Comm::halo_end(const Partition&, double* y, hipStream_t s) {
-   if (nranks == 1 && !force_) return;
-   EXA_HC(hipStreamWaitEvent(s, ev_done_, 0));
-   unpack(y, s);
-}
-
-void Comm::exchange(const Partition& part, hipStream_t s) {
-   const size_t nb = part.nbrs.size();
-   auto sb = [&](size_t i) { return sbuf_all_.p + seg_off_[i]; };
-   auto rb = [&](size_t i) { return rbuf_all_.p + seg_off_[i]; };
-   auto cnt = [&](size_t i) { return seg_off_[i + 1] - seg_off_[i]; };
-   if (ipc_) {
-      IpcGroup* g = (IpcGroup*)ipc_; const IpcShared* sh = g->sh;
-      EXA_HC(hipStreamSynchronize(s));      // my send buffer is packed
-      g->barrier();                         // ... and so is everybody else's
-      for (size_t i = 0; i < nb; i++) {     // my slot i talks to rank r; r's slot that talks to me holds what I receive (same dof order on both sides)
-         const int r = part.nbrs[i].rank; int k = -1;
-         for (int j = 0; j < sh->nnbr[r]; j++) if (sh->nbr_rank[r][j] == rank) { k = j; break; }
-         if (k < 0 || sh->seg_off[r][k + 1] - sh->seg_off[r][k] != cnt(i)) throw std::runtime_error("ipc halo: asymmetric neighbour lists");
-         EXA_HC(hipMemcpyAsync(rb(i), g->peer_sbuf[r] + sh->seg_off[r][k], sizeof(double) * cnt(i), hipMemcpyDeviceToDevice, s));
-      }
-      EXA_HC(hipStreamSynchronize(s));
-      g->barrier();                         // nobody repacks its send buffer before everybody has read it
-      return;
-   }
-   if (loop_) {
-      LoopbackGroup* g = (LoopbackGroup*)loop_;
-      g->sendbuf[rank].resize(nb); g->nbr_rank[rank].resize(nb);
-      for (size_t i = 0; i < nb; i++) { g->sendbuf[rank][i] = sb(i); g->nbr_rank[rank][i] = part.nbrs[i].rank; }
-      auto peer_src = [&](size_t i) {   // my slot i talks to rank r; r's slot that talks to me holds what I receive (same dof order on both sides)
-         const int r = part.nbrs[i].rank;
-         for (size_t k = 0; k < g->nbr_rank[r].size(); k++) if (g->nbr_rank[r][k] == rank) return g->sendbuf[r][k];   // one neighbour entry per pair of ranks
-         throw std::runtime_error("loopback halo: asymmetric neighbour lists");
-      };
-      if (loop_async_) {
-         // Stream-asynchronous form (default; EXA_LOOPBACK_SYNC=1 keeps the host-synchronous one): NO stream is drained.  Every rank records
-         // "packed" on its stream, its peers' streams wait for that event before they copy, every rank records "read" behind its copies and a
-         // rank's NEXT pack waits for its neighbours' "read" (the waits at the end of this function, on the stream of this exchange).  The host threads meet twice
-         // per exchange only so that an event is recorded before somebody waits for it - the device work of all ranks stays in flight, which is
-         // how the overlapped halo (halo_begin / halo_end: cs_, ev_ready_, ev_done_) runs over RCCL.
-         if (!g->ev_packed[rank]) { EXA_HC(hipEventCreateWithFlags(&g->ev_packed[rank], hipEventDisableTiming)); EXA_HC(hipEventCreateWithFlags(&g->ev_read[rank], hipEventDisableTiming)); }
-         EXA_HC(hipEventRecord(g->ev_packed[rank], s));
-         g->barrier();                                            // every rank's "packed" is recorded (host side only)
-         for (size_t i = 0; i < nb; i++) {
-            EXA_HC(hipStreamWaitEvent(s, g->ev_packed[part.nbrs[i].rank], 0));
-            EXA_HC(hipMemcpyAsync(rb(i), peer_src(i), sizeof(double) * cnt(i), hipMemcpyDeviceToDevice, s));
-         }
-         EXA_HC(hipEventRecord(g->ev_read[rank], s));
-         g->barrier();                                            // every rank's "read" is recorded
-         // nobody repacks its send buffer before its readers are done: the stream that packs next is the stream of this exchange or a later one of
-         // this rank - ordered behind these waits either way (halo_sum packs on s, halo_begin on cs_, and cs_ waits for ev_ready_ recorded on s)
-         for (size_t i = 0; i < nb; i++) EXA_HC(hipStreamWaitEvent(s, g->ev_read[part.nbrs[i].rank], 0));
-         return;
-      }
-      EXA_HC(hipStreamSynchronize(s));
-      g->barrier();
-      for (size_t i = 0; i < nb; i++) EXA_HC(hipMemcpyAsync(rb(i), peer_src(i), sizeof(double) * cnt(i), hipMemcpyDeviceToDevice, s));
-      EXA_HC(hipStreamSynchronize(s));
-      g->barrier();
-      return;
-   }
-   nccl_check(rccl().GroupStart(), "ncclGroupStart");
-   for (size_t i = 0; i < nb; i++) {
-      nccl_check(rccl().Send(sb(i), cnt(i), ncclDouble, part.nbrs[i].rank, (ncclComm_t)comm_, s), "ncclSend");
-      nccl_check(rccl().Recv(rb(i), cnt(i), ncclDouble, part.nbrs[i].rank, (ncclComm_t)comm_, s), "ncclRecv");
-   }
-   nccl_check(rccl().GroupEnd(), "ncclGroupEnd");
-}
-
-// adds the received segments to y.  A dof on an edge or corner of the block occurs in several segments: one launch over all of them adds
-// with atomics in arbitrary order; in deterministic mode the segments are added one after the other (no dof twice within a segment)
-void Comm::unpack(double* y, hipStream_t s) {
-   if (!deterministic) { vk_unpack_add((int64_t)seg_off_.back(), idx_all_.p, rbuf_all_.p, y, s); return; }
-   for (size_t i = 0; i + 1 < seg_off_.size(); i++)
-      vk_unpack_add((int64_t)(seg_off_[i + 1] - seg_off_[i]), idx_all_.p + seg_off_[i], rbuf_all_.p + seg_off_[i], y, s);
-}
 
 // =====================================================================================================================
 // model seam
@@ -555,7 +149,7 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
       // all-reduces of the main stream works, but at 64^3 per rank it costs 162 us per PCG iteration against 141 us in line (profiles/r06_rccl_self_exchange.txt):
       // two launches of the action and two cross-stream waits to hide a 24 us exchange.  A box with real xGMI neighbours has to show where the balance tips.
       const char* ho = std::getenv("EXA_HALO_OVERLAP");
-      const bool want = ho ? std::string(ho) != "off" && std::string(ho) != "0" : std::string(comm.transport()) != "rccl";
+      const bool want = ho ? std::string(ho) != "off" && std::string(ho) != "0" : comm.kind() != Comm::RCCL;
       // (periodic partitions keep the plain sequence: the elements at the box surface touch shared dofs too, and the boundary-first order does not know them)
       overlap_ = fast_p1_ && lvec_grad_ && !det && part.E_bdr > 0 && !part.nbrs.empty() && (opt.assembly == Assembly::PA || ea_rec) && want && !part.periodic;
       // decided collectively: every rank runs the same form (a partition in which one rank has no boundary block would otherwise put its
@@ -616,8 +210,8 @@ void NonlinearMechOperator::SetupPeriodic() {
 }
 
 void NonlinearMechOperator::SumLVector(double* y, const double* flag, bool raw) {
-   if (!part_.periodic) { comm_.halo_sum(part_, y, stream_); return; }
-   const bool one = comm_.nranks == 1 && !comm_.forced();
+   if (!part_.periodic) { comm_.halo_sum(y, stream_); return; }
+   const bool one = !comm_.active();
    const bool mix = part_.mixed && raw;
    if (mix) vk_face_resultants(mix_tab_, nn_, y, flag, mix_part_.p, stream_);
    if (mix && one) { vk_periodic_sum_controls(per_tab_, mix_tab_, nn_, y, flag, mix_part_.p, mix_f_.p, stream_); return; }
@@ -625,7 +219,7 @@ void NonlinearMechOperator::SumLVector(double* y, const double* flag, bool raw) 
    vk_periodic_sum(per_tab_, nn_, y, flag, false, stream_);
    if (!one) {
       // the exchange carries the representative of a group: its local sum out, the other ranks' sums added to it, then back to its local images
-      comm_.halo_sum(part_, y, stream_);
+      comm_.halo_sum(y, stream_);
       vk_periodic_sum(per_tab_, nn_, y, flag, true, stream_);
    }
    if (mix) vk_face_combine(mix_tab_, nn_, nullptr, mix_f_.p, y, flag, stream_);
@@ -960,9 +554,9 @@ void NonlinearMechOperator::GradMult(const double* x, double* y, bool constraine
       if (rc0 == EXA_ERR_UNSUPPORTED) overlap_ = false;
       else {
          abi_check(ctx_, rc0, "exa_grad_apply_lvec_blocks");
-         comm_.halo_begin(part_, y, stream_);
+         comm_.halo_begin(y, stream_);
          abi_check(ctx_, exa_grad_apply_lvec_blocks(ctx_, x, y, m, done_flag, nblk_bdr_, nball - nblk_bdr_, stream_), "exa_grad_apply_lvec_blocks");
-         comm_.halo_end(part_, y, stream_);
+         comm_.halo_end(y, stream_);
          if (constrained && !skip_out_mask) vk_mask_zero(nd_, ess_mask.p, y, stream_);
          return;
       }

@@ -8,6 +8,7 @@
 //   ExaNewtonSolver / ExaNewtonLSSolver  reference src/mechanics_solver.cpp:39-281
 //   PCGSolver (host/krylov.hpp)          MFEM CGSolver, set up at reference src/system_driver.cpp:166-177
 //   SystemDriver                         reference src/system_driver.cpp:221-558
+//   Comm (host/comm.hpp)               MPI in the reference (src/mechanics_driver.cpp:312, src/system_driver.cpp:167, src/mechanics_kernels.hpp:119,124)
 //   StepAnalyses (host/analyses.hpp)     reference src/system_driver.cpp:560-870 (the Project* outputs) and what this project adds to them
 //   time-step loop                       reference src/mechanics_driver.cpp:837-907
 #pragma once
@@ -17,57 +18,13 @@
 #include <vector>
 #include "../../../include/exaconstit_hip.h"
 #include "analyses.hpp"
+#include "comm.hpp"
 #include "device_utils.hpp"
 #include "krylov.hpp"
 #include "mesh.hpp"
 #include "options.hpp"
 
 namespace exa_host {
-
-// ---- communication: RCCL over xGMI when nranks > 1 (loaded at run time), no-ops on one rank -----------------------
-class Comm {
- public:
-   int rank = 0, nranks = 1;
-   ~Comm();
-   // force_rccl: run the RCCL calls on a one-rank communicator too (what EXA_FORCE_RCCL=1 selects from the environment)
-   void init(int rank_, int nranks_, const void* nccl_unique_id /*128 bytes, identical on all ranks*/, bool force_rccl = false);
-   static void get_unique_id(void* out128);
-   // inter-process transport for ranks that share a device (driver.hip): an id of that kind, and whether this launch needs it
-   static void ipc_unique_id(void* out128);
-   static bool want_ipc_transport(int nranks);
-   int reported_ranks() const;            // what the transport itself says (ncclCommCount for RCCL)
-   const char* transport() const { return ipc_ ? "ipc" : (loop_ ? "loopback" : (comm_ ? "rccl" : "none")); }
-   // in-process loopback transport for tests: several ranks (one host thread each) on ONE device, host-synchronous exchanges
-   static void loopback_create(int nranks, void* out128);
-   static void loopback_destroy(const void* id128);
-   void allreduce_sum(double* dev, int n, hipStream_t s);
-   void allreduce_min(double* dev, int n, hipStream_t s);
-   void allreduce_max(double* dev, int n, hipStream_t s);
-   // y(shared dofs) <- sum over all ranks holding them
-   void halo_sum(const Partition& part, double* y, hipStream_t s);
-   // the same in two halves for overlap with work on stream s: begin = pack + exchange on the communication stream once everything
-   // enqueued on s so far has finished; end = s waits for the exchange, then adds the received segments
-   void halo_begin(const Partition& part, double* y, hipStream_t s);
-   void halo_end(const Partition& part, double* y, hipStream_t s);
-   void setup_halo(const Partition& part);
-   double max_over_ranks(double v);
-   // us per call of the fused 16-byte all-reduce and of a grouped send/recv of `n` doubles to the own rank (one-rank communicator: latency floor of the RCCL calls)
-   void microbench(int iters, int n, double* us_allreduce, double* us_sendrecv);
-   bool deterministic = false;               // halo contributions added segment by segment (fixed order) instead of one atomic pass
-   size_t halo_dofs() const { return seg_off_.back(); }   // doubles this rank sends (= receives) per exchange, all neighbours
-   bool selftest() const { return selftest_zero_; }   // EXA_HALO_SELFTEST: the forced one-rank communicator exchanges zeros with itself (driver.hip, Comm::init)
-   bool forced() const { return force_; }   // EXA_FORCE_RCCL=1: the one-rank communicator runs the multi-rank code paths and every RCCL call
- private:
-   void unpack(double* y, hipStream_t s);
-   void loopback_reduce(double* dev, int n, int op, hipStream_t s);
-   void* comm_ = nullptr; void* loop_ = nullptr; void* ipc_ = nullptr; bool force_ = false;
-   bool selftest_zero_ = false;
-   bool loop_async_ = false;   // loopback: exchanges ordered by events only, no stream is drained (driver.hip, Comm::exchange)
-   DevBuf<int32_t> idx_all_; DevBuf<double> sbuf_all_, rbuf_all_; std::vector<size_t> seg_off_{ 0 };   // concatenated neighbour segments
-   DevBuf<double> tmp_;
-   hipStream_t cs_ = nullptr; hipEvent_t ev_ready_ = nullptr, ev_done_ = nullptr;   // communication stream of halo_begin / halo_end
-   void exchange(const Partition& part, hipStream_t s);   // send buffers -> neighbours' receive buffers (RCCL grouped send/recv or loopback copies) on stream s
-};
 
 class Multigrid;
 

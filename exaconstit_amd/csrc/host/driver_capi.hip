@@ -4,6 +4,7 @@
 // with Caliper (ecmech_kernel, krylov_solver: src/mechanics_ecmech.cpp:237-257, src/mechanics_solver.cpp:99-103).
 #include "driver.hpp"
 #include "multigrid.hpp"
+#include "rank_sync.hpp"
 #include "roctx.hpp"
 #include "vtu.hpp"
 #include "checkpoint.hpp"
@@ -27,7 +28,7 @@ void set_err(char* err, int n, const std::string& m) { if (err && n > 0) { std::
 extern "C" {
 
 // Transport from the identity of the ranks' devices (96-byte records: host name[64], PCI bus id[32]).  RCCL needs one device per rank; the
-// shared-device transport (POSIX shm + hipIpc, host/driver.hip) needs every rank on ONE host.  Counting ranks against visible devices cannot
+// shared-device transport (POSIX shm + hipIpc, host/comm.hip) needs every rank on ONE host.  Counting ranks against visible devices cannot
 // tell the two apart (16 ranks on 2 x 8 GPUs, or one visible device per rank under srun --gpus-per-task=1), identities can.
 int exa_transport_from_identities(const void* ids, int nranks, char* err, int errlen) {
    const char* t = (const char*)ids;
@@ -110,7 +111,7 @@ int exa_device_identity(char* out, int len) {
    return hipDeviceGetPCIBusId(out, len, dev) == hipSuccess ? 0 : -1;
 }
 // the id rank 0 hands out for a group of `nranks` when the caller has NOT compared device identities itself: a RCCL unique id, or - with
-// EXA_TRANSPORT=ipc, or when the ranks of this node outnumber its visible devices - the id of the inter-process transport of host/driver.hip
+// EXA_TRANSPORT=ipc, or when the ranks of this node outnumber its visible devices - the id of the inter-process transport of host/comm.hip
 // (class Comm).  bench.py compares identities and sets EXA_TRANSPORT; exa_bootstrap decides from identities (exa_transport_from_identities).
 int exa_comm_unique_id(void* out128, int nranks) {
    try { if (Comm::want_ipc_transport(nranks)) Comm::ipc_unique_id(out128); else Comm::get_unique_id(out128); return 0; }
@@ -119,8 +120,8 @@ int exa_comm_unique_id(void* out128, int nranks) {
 // out2 = { ranks the transport itself reports (ncclCommCount for RCCL), kind: 0 none (one rank), 1 rccl, 2 ipc (shared device), 3 in-process loopback }
 int exa_driver_comm_info(exa_driver* d, int* out2) {
    try {
-      const Comm& c = d->sd->comm; const std::string t = c.transport();
-      out2[0] = c.reported_ranks(); out2[1] = t == "rccl" ? 1 : (t == "ipc" ? 2 : (t == "loopback" ? 3 : 0));
+      const Comm& c = d->sd->comm;
+      out2[0] = c.reported_ranks(); out2[1] = (int)c.kind();
       return 0;
    } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_comm_info: %s\n", e.what()); return -1; }
 }
@@ -135,6 +136,29 @@ int exa_driver_comm_details(exa_driver* d, int64_t* out8) {
       out8[4] = d->sd->oper().halo_overlap() ? 1 : 0; out8[5] = info[1]; out8[6] = info[0]; out8[7] = 0;
       return 0;
    } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_comm_details: %s\n", e.what()); return -1; }
+}
+
+// The transport on its own (tests): what 0 / 1 / 2 = Comm::allreduce_sum / _min / _max of n host doubles on the operator's stream; 3 = Comm::halo_sum of a
+// host L-vector of the local dofs (n = exa_driver_local_dofs, dof = node + local nodes * component).  In place; every rank of the group calls it.
+int exa_driver_comm_probe(exa_driver* d, int what, double* host_vec, int n) {
+   try {
+      SystemDriver& sd = *d->sd; hipStream_t s = sd.oper().stream();
+      if (what < 0 || what > 3 || n < 1 || (what == 3 && n != 3 * sd.part.NN)) throw std::runtime_error("what must be 0 .. 3 and n >= 1 (halo sum: the local dofs)");
+      DevBuf<double> v((size_t)n); v.upload(host_vec, (size_t)n, s);
+      if (what == 0) sd.comm.allreduce_sum(v.p, n, s);
+      else if (what == 1) sd.comm.allreduce_min(v.p, n, s);
+      else if (what == 2) sd.comm.allreduce_max(v.p, n, s);
+      else sd.comm.halo_sum(v.p, s);
+      v.download(host_vec, (size_t)n, s);
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_comm_probe: %s\n", e.what()); return -1; }
+}
+
+// host only: the fold of the host-synchronous reductions (rank_sync.hpp) over contributions[nranks][n]; op 0 sum, 1 min, 2 max
+int exa_comm_rank_fold(int op, int nranks, int n, const double* contributions, double* out) {
+   if (op < 0 || op > 2 || nranks < 1) return -1;
+   rank_fold((RankOp)op, nranks, n, [&](int k) { return contributions + (size_t)k * n; }, out);
+   return 0;
 }
 
 int exa_loopback_group_create(int nranks, void* out128) { try { Comm::loopback_create(nranks, out128); return 0; } catch (...) { return -1; } }

@@ -61,7 +61,7 @@ void PCGSolver::Finish(Frame& f, const Outcome* o, int n) {
 
 int PCGSolver::Solve(const double* b, double* x) {
    if (op_.precond == Precond::MULTIGRID) return SolveMultigrid(b, x);
-   if ((comm_.nranks > 1 || comm_.forced()) && std::getenv("EXA_PCG_TWO_REDUCTIONS") == nullptr) return SolveSingleReduction(b, x);
+   if (comm_.active() && std::getenv("EXA_PCG_TWO_REDUCTIONS") == nullptr) return SolveSingleReduction(b, x);
    return SolveDeviceScalars(b, x);
 }
 
@@ -133,7 +133,7 @@ int PCGSolver::SolveDeviceScalars(const double* b, double* x) {
    // the blocks of the update and direction kernels sum the <= 1024 partial sums themselves.  Same bits as the one-block reduction launches (EXA_PCG_REDUCE_LAUNCH=1).
    const char* red_env = std::getenv("EXA_PCG_REDUCE_LAUNCH");      // (read per solve: the tests switch it between drivers of one process)
    const int64_t red_max_dofs = red_env ? (std::atoll(red_env) == 1 ? (int64_t)0 : (int64_t)std::atoll(red_env)) : (int64_t)EXA_PCG_CONSUMER_REDUCE_MAX_DOFS;
-   const bool red = one && !comm_.forced() && nd <= red_max_dofs;
+   const bool red = !comm_.active() && nd <= red_max_dofs;
    double* partD = op.partial.p + 2 * DOT_BLOCKS;      // partial sums of the denominator (the (r, z) ones use the front of the buffer)
    op.GradMult(d_.p, z_.p, true, S + pcg::FLAG);
    if (red) vk_dot_partial(nd, nn, op.weight.p, z_.p, d_.p, S + pcg::FLAG, partD, s);      // the first update kernel turns them into alpha
@@ -165,7 +165,7 @@ int PCGSolver::SolveDeviceScalars(const double* b, double* x) {
    // The capture bakes in every kernel argument: the solution pointer, the preconditioner variant, the iteration cap (an argument of
    // k_cg_step1 / the reductions) and the chunk length - all of them are part of the key.
    const GraphKey key{ x, op.precond, red, set.check_every, set.max_iter };
-   bool use_graph = one && !comm_.forced() && nd <= set.graph_max_dofs && set.check_every > 1;
+   bool use_graph = !comm_.active() && nd <= set.graph_max_dofs && set.check_every > 1;
    if (use_graph && !(graph_ && graph_key_ == key)) {
       DropGraph();
       // whatever happens between begin and end, the stream must leave capture mode and the graph must not leak
@@ -243,7 +243,7 @@ int PCGSolver::SolveMultigrid(const double* b, double* x) {
 
 void PCGSolver::SolveColumns(int nc, const double* B, double* X, int64_t ld, int nch, int* iters, double* reduction, int* flag) {
    if (nc < 1 || nc > EXA_GRAD_COLS_MAX) throw std::runtime_error("SolveColumns: between 1 and 16 columns");
-   if (comm_.nranks > 1 || comm_.forced() || op_.deterministic() || op_.precond == Precond::MULTIGRID)
+   if (comm_.active() || op_.deterministic() || op_.precond == Precond::MULTIGRID)
       throw std::runtime_error("the batched tangent solve is built for one rank in non-deterministic mode with the identity or Jacobi preconditioner");
    NonlinearMechOperator& op = op_;
    hipStream_t s = op.stream();

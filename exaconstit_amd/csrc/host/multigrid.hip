@@ -48,12 +48,12 @@ Multigrid::~Multigrid() {
 // coarse halo sum on the fine exchange plan: the level-l nodes are level-0 nodes, and the fine neighbour lists hold every shared one
 void Multigrid::halo(int l, double* y) {
    Comm& comm = op_.comm();
-   if (comm.nranks == 1 && !comm.forced()) return;
+   if (!comm.active()) return;
    hipStream_t s = op_.stream();
-   if (l == 0) { comm.halo_sum(op_.part(), y, s); return; }
+   if (l == 0) { comm.halo_sum(y, s); return; }
    fine_tmp_.zero(s);
    mg_to_fine(lv_[0].g, lv_[l].g, lv_[l].stride, y, fine_tmp_.p, s);
-   comm.halo_sum(op_.part(), fine_tmp_.p, s);
+   comm.halo_sum(fine_tmp_.p, s);
    mg_from_fine(lv_[0].g, lv_[l].g, lv_[l].stride, fine_tmp_.p, y, s);
 }
 
@@ -201,7 +201,7 @@ void Multigrid::Prolong(int l, const double* xc, double* xf) {
 void Multigrid::Restrict(int l, const double* rf, double* rc) {
    if (l < 0 || l >= levels()) throw std::runtime_error("multigrid: no transfer below level " + std::to_string(l));
    const Level& f = lv_[l];
-   mg_restrict(f.g, lv_[l + 1].g, (op_.comm().nranks == 1 && !op_.comm().forced()) ? nullptr : (l == 0 ? op_.weight.p : f.wp), rf, rc, op_.stream());
+   mg_restrict(f.g, lv_[l + 1].g, !op_.comm().active() ? nullptr : (l == 0 ? op_.weight.p : f.wp), rf, rc, op_.stream());
    halo(l + 1, rc);
 }
 

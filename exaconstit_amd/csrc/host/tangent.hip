@@ -74,7 +74,7 @@ void SystemDriver::MacroTangent(double rel_tol, int max_iter, int batched, Macro
    const int64_t nd = op.Height(); const int nn = part.NN;
    const double rel = rel_tol > 0.0 ? rel_tol : opt_.krylov_rel;
    const int mi = max_iter > 0 ? max_iter : opt_.krylov_iter;
-   const bool can_batch = comm.nranks == 1 && !comm.forced() && !op.deterministic() && op.precond != Precond::MULTIGRID;
+   const bool can_batch = !comm.active() && !op.deterministic() && op.precond != Precond::MULTIGRID;
    if (batched == 1 && !can_batch) throw std::runtime_error("macro_tangent: the batched route is built for one rank in non-deterministic mode; use batched = 0 or the automatic route");
    const int auto_env = env_int("EXA_TANGENT_BATCHED", tangent_auto_batched ? 1 : 0);
    bool want = batched < 0 ? (can_batch && auto_env != 0) : batched == 1;
@@ -151,7 +151,7 @@ void SystemDriver::GradApplyColumns(int nc, const double* x, double* y, bool ass
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
    const int64_t nd = op.Height();
-   if (batched && (comm.nranks > 1 || comm.forced())) throw std::runtime_error("grad_apply_columns: the batched route is built for one rank");
+   if (batched && comm.active()) throw std::runtime_error("grad_apply_columns: the batched route is built for one rank");
    const int nch = tangent_nch > 0 ? tangent_nch : env_int("EXA_TANGENT_NCH", 0);
    TangentScope scope(*this);
    op.GetGradient();

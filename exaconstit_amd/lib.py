@@ -204,6 +204,8 @@ exa_driver_comm_info = _sig("exa_driver_comm_info", C.c_int, C.c_void_p, C.POINT
 exa_loopback_group_create = _sig("exa_loopback_group_create", C.c_int, C.c_int, C.c_void_p)
 exa_loopback_group_destroy = _sig("exa_loopback_group_destroy", None, C.c_void_p)
 exa_driver_comm_details = _sig("exa_driver_comm_details", C.c_int, C.c_void_p, C.POINTER(C.c_int64))
+exa_driver_comm_probe = _sig("exa_driver_comm_probe", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int)
+exa_comm_rank_fold = _sig("exa_comm_rank_fold", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
 exa_driver_create = _sig("exa_driver_create", C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int)
 exa_driver_create_synthetic = _sig("exa_driver_create_synthetic", C.c_void_p, C.POINTER(ExaSynthConfig), C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_int)
 exa_driver_destroy = _sig("exa_driver_destroy", None, C.c_void_p)
@@ -990,6 +992,13 @@ class Driver:
         o = (C.c_int * 2)()
         assert exa_driver_comm_info(self.h, o) == 0
         return int(o[0]), ("none", "rccl", "ipc", "loopback")[o[1]]
+
+    def comm_probe(self, what, vec):
+        """The transport on its own: what 0 / 1 / 2 = all-reduce (sum / min / max) of vec, 3 = halo sum of an L-vector of the local dofs.  Every rank calls it."""
+        import numpy as np
+        v = np.array(vec, dtype=np.float64).ravel()
+        assert exa_driver_comm_probe(self.h, int(what), v.ctypes.data_as(C.POINTER(C.c_double)), v.size) == 0
+        return v
 
     def comm_details(self):
         out = (C.c_int64 * 8)()

@@ -43,6 +43,12 @@ int exa_driver_comm_info(exa_driver* d, int* out2);
  *          halo exchange overlapped with the interior blocks (0 / 1; over RCCL opt-in with EXA_HALO_OVERLAP=on), transport kind, ranks the
  *          transport reports, 0 } - what bench.py prints per rank of a multi-rank run */
 int exa_driver_comm_details(exa_driver* d, int64_t* out8);
+/* The transport on its own, for the tests; in place, every rank of the group calls it.  what 0 / 1 / 2: all-reduce (sum / min / max) of n host
+ * doubles on the driver's stream; what 3: halo sum of a host L-vector of the local dofs (n = exa_driver_local_dofs, dof = node + local nodes * component) */
+int exa_driver_comm_probe(exa_driver* d, int what, double* host_vec, int n);
+/* host only: the rank-ordered fold every host-synchronous reduction uses - out[i] = ((c[0][i] op c[1][i]) op c[2][i]) ..., a left fold from rank 0 over
+ * contributions[nranks][n]; op 0 sum, 1 min, 2 max.  Returns 0, or -1 for another op or nranks < 1 */
+int exa_comm_rank_fold(int op, int nranks, int n, const double* contributions, double* out);
 /* latency floor of the RCCL calls of one PCG iteration on this device (one-rank communicator): out2 = { us per 16-byte all-reduce,
  * us per grouped send/recv of n doubles to the own rank } */
 int exa_rccl_microbench(int iters, int n, double* out2, char* err, int errlen);

@@ -30,3 +30,29 @@ def global_node_ids(part, N):
     p = part.get("order", 1)
     i = np.rint(X[0] * N[0] * p).astype(np.int64); j = np.rint(X[1] * N[1] * p).astype(np.int64); k = np.rint(X[2] * N[2] * p).astype(np.int64)
     return i + (N[0] * p + 1) * (j + (N[1] * p + 1) * k)
+
+
+# ---- inputs and expected values of the transport probe (Driver.comm_probe; tests/test_gpu_comm.py and the probe mode of tests/rccl_worker.py) ----
+def probe_reduce_input(rank, n):
+    """integer-valued doubles that differ by rank and position: their sums, minima and maxima over the ranks are exact in any order"""
+    i = np.arange(n)
+    return ((7 * rank + 3 * i) % 11 - 5 + rank).astype(np.float64)
+
+
+def probe_node_ids(coords_ref, N):
+    """global lexicographic node id of a p = 1 driver's local nodes, from Driver.nodal_field("coords_ref") on the unit cube"""
+    return global_node_ids(dict(X=np.asarray(coords_ref).T), N)
+
+
+def probe_halo_input(rank, gid):
+    """L-vector (dof = node + local nodes * component) of small integers that depend on the rank, the global node id and the component"""
+    return np.concatenate([(rank + 1) * (gid + 1) + 100 * c for c in range(3)]).astype(np.float64)
+
+
+def probe_halo_expected(N, nranks, gid):
+    """the halo sum of probe_halo_input at the nodes `gid`: at every node the sum over the ranks that hold it (block decomposition of exa_partition_query)"""
+    tot = np.zeros((3, (N[0] + 1) * (N[1] + 1) * (N[2] + 1)))
+    for r in range(nranks):
+        g = global_node_ids(query(N, r, nranks), N)
+        tot[:, g] += probe_halo_input(r, g).reshape(3, -1)
+    return tot[:, gid].ravel()

@@ -67,7 +67,7 @@ def test_halo_overlap_switch(oracle, tmp_path, monkeypatch, case, nranks):
     on = _run_ranks(L, toml, nranks, 5, tmp_path / "on")
     monkeypatch.setenv("EXA_HALO_OVERLAP", "off")
     off = _run_ranks(L, toml, nranks, 5, tmp_path / "off")
-    # The loopback exchange is stream-asynchronous by default (host/driver.hip, Comm::exchange: peers' copies ordered by events, no stream is
+    # The loopback exchange is stream-asynchronous by default (host/comm.hip, LoopbackTransport::exchange: peers' copies ordered by events, no stream is
     # drained - how the choreography of halo_begin / halo_end runs over RCCL); EXA_LOOPBACK_SYNC=1 is the host-synchronous form of rounds 1-4
     monkeypatch.delenv("EXA_HALO_OVERLAP")
     monkeypatch.setenv("EXA_LOOPBACK_SYNC", "1")

@@ -66,7 +66,7 @@ def test_forced_rccl_self_exchange(oracle, tmp_path, overlap):
 def test_two_ranks_two_processes(oracle, tmp_path):
     """torchrun --nproc-per-node 2: two processes, TCP rendez-vous of torch beside this library's communicator, per-rank device mapping.  With
     two GPUs the ranks talk over RCCL; on a one-GPU box RCCL refuses the second rank on the device, and the same launch goes through the
-    shared-device inter-process transport (POSIX shared memory + hipIpcMemHandle, host/driver.hip) - every line but the RCCL calls, which
+    shared-device inter-process transport (POSIX shared memory + hipIpcMemHandle, host/comm.hip) - every line but the RCCL calls, which
     test_forced_rccl_on_one_rank covers."""
     import torch
     n = 5

@@ -457,3 +457,34 @@ def test_generated_mesh_nodes_sit_at_gauss_lobatto_points():
     assert np.allclose(xs, expect, atol=1e-12)
     g3 = _generated(1, 3)
     assert np.allclose(np.unique(np.round(g3["X"][0], 12)), [0.0, 0.5 - 0.5 / np.sqrt(5.0), 0.5 + 0.5 / np.sqrt(5.0), 1.0], atol=1e-12)
+
+
+def _rank_fold(op, rows):
+    import exaconstit_amd.lib as L
+    rows = np.ascontiguousarray(rows, dtype=np.float64); out = np.zeros(rows.shape[1])
+    dp = C.POINTER(C.c_double)
+    assert L.exa_comm_rank_fold(op, rows.shape[0], rows.shape[1], rows.ctypes.data_as(dp), out.ctypes.data_as(dp)) == 0
+    return out
+
+
+def test_rank_fold_is_a_left_fold_from_rank_zero():
+    """The fold of the host-synchronous reductions (loopback and shared-device transport, host/comm.hip): sum, min and max of three ranks' rows,
+    and the order of the additions - ((1e16 + 1) + -1e16) is 0 in doubles, every other order of the three gives 1."""
+    rows = np.array([[3.0, -2.0, 7.5, 0.0], [1.0, 4.0, -7.5, 0.0], [-5.0, 4.0, 0.25, -0.5]])
+    assert np.array_equal(_rank_fold(0, rows), [-1.0, 6.0, 0.25, -0.5])
+    assert np.array_equal(_rank_fold(1, rows), [-5.0, -2.0, -7.5, -0.5])
+    assert np.array_equal(_rank_fold(2, rows), [3.0, 4.0, 7.5, 0.0])
+    assert np.array_equal(_rank_fold(0, [[1e16, 5.0], [1.0, 6.0], [-1e16, 7.0]]), [0.0, 18.0])
+    assert np.array_equal(_rank_fold(0, [[2.5]]), [2.5])
+    import exaconstit_amd.lib as L
+    assert L.exa_comm_rank_fold(3, 1, 1, None, None) == -1 and L.exa_comm_rank_fold(0, 0, 1, None, None) == -1
+
+
+def test_rank_sync_check_program(tmp_path):
+    """tests/rank_sync_check.cpp - four threads, a few hundred rounds of meet / fold / meet on the barrier and the fold of host/rank_sync.hpp - builds
+    and passes as a plain program (scripts/rank_sync_sanitize.sh is the same program under the thread and address sanitizers)."""
+    import subprocess
+    exe = str(tmp_path / "rank_sync_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-pthread", "-o", exe, os.path.join(ROOT, "tests", "rank_sync_check.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "0 wrong values" in r.stdout, r.stdout + r.stderr
