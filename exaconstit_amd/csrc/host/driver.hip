@@ -28,9 +28,6 @@ namespace exa_host {
 // =====================================================================================================================
 static void abi_check(exa_ctx* ctx, int rc, const char* what) { if (rc < 0) throw std::runtime_error(std::string(what) + ": " + exa_last_error(ctx)); }
 
-void ExaCMechModel::ModelSetup(const double* jacobian, const double* vel_evec, hipStream_t s) {
-   abi_check(ctx_, exa_model_setup(ctx_, dt_, jacobian, vel_evec, stress0_->p, matVars0_->p, stress1_->p, matVars1_->p, matGrad_->p, s), "exa_model_setup");
-}
 void ExaCMechModel::ModelSetupLVec(const double* x_lvec, const double* v_lvec, double* jacobian_out, hipStream_t s) {
    abi_check(ctx_, exa_model_setup_lvec(ctx_, dt_, x_lvec, v_lvec, stress0_->p, matVars0_->p, stress1_->p, matVars1_->p, matGrad_->p, jacobian_out, s), "exa_model_setup_lvec");
 }
@@ -42,7 +39,16 @@ void ExaCMechModel::calcDpMat(double* dp, hipStream_t s) const { abi_check(ctx_,
 // =====================================================================================================================
 // NonlinearMechOperator
 // =====================================================================================================================
-static bool env_is_off(const char* k) { const char* e = std::getenv(k); return e && std::string(e) == "off"; }
+static bool is_bbar(const ExaOptions& o) { return ExaOptions::lower(o.integ_model) == "bbar"; }
+// what the route decision (host/routes.hpp) needs from options, partition and transport
+static RouteFacts route_facts(const ExaOptions& o, const Partition& part, const Comm& comm) {
+   RouteFacts f;
+   f.geom = part.geom; f.order = part.p; f.bbar = is_bbar(o); f.ea = o.assembly == Assembly::EA;
+   f.slip = o.slip == SlipType::POWERVOCE ? RouteFacts::VOCE : (o.slip == SlipType::POWERVOCENL ? RouteFacts::VOCE_NL : RouteFacts::KMDD);
+   f.several_ranks = comm.nranks > 1; f.rccl = comm.kind() == Comm::RCCL;
+   f.has_bdr_blocks = part.E_bdr > 0; f.has_nbrs = !part.nbrs.empty(); f.periodic = part.periodic;
+   return f;
+}
 static int model_id(const ExaOptions& o) {
    const bool bcc = o.xtal == XtalType::BCC;
    switch (o.slip) {
@@ -54,10 +60,10 @@ static int model_id(const ExaOptions& o) {
 
 NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partition& part, Comm& comm, const std::vector<double>& props,
                                              const std::vector<double>& quats_per_elem)
-   : opt_(opt), part_(part), comm_(comm) {
+   : opt_(opt), part_(part), comm_(comm), routes_(decide_routes(route_facts(opt, part, comm), RouteSwitches::from_env())) {
    EXA_HC(hipStreamCreate(&stream_)); EXA_HC(hipEventCreate(&ev0_)); EXA_HC(hipEventCreate(&ev1_));
-   const bool bbar = ExaOptions::lower(opt.integ_model) == "bbar";
-   const bool tet = part.geom == 1;   // tetrahedra: table-driven kernels + the fused action of tet_kernels.hip, never a hexahedron fast path
+   const bool bbar = is_bbar(opt);
+   const bool tet = part.geom == 1;
    if (tet && bbar) throw std::runtime_error("integ_model = \"BBAR\" is built for hexahedral meshes only (this mesh has tetrahedra)");
    exa_config cfg; cfg.model = model_id(opt); cfg.nprops = (int)props.size(); cfg.props = props.data(); cfg.temp_k = opt.temp_k; cfg.order = part.p;
    cfg.nelems = part.E; cfg.assembly = opt.assembly == Assembly::PA ? EXA_ASSEMBLY_PA : EXA_ASSEMBLY_EA; cfg.integ = bbar ? EXA_INTEG_BBAR : EXA_INTEG_FULL; cfg.device = -1;
@@ -65,98 +71,33 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
    if (!ctx_) throw std::runtime_error("exa_create failed (" + std::to_string(err) + ")");
    this->props = props; cfg_used = cfg; cfg_used.props = nullptr;
    nn_ = part.NN; nd_ = 3 * nn_; E_ = part.E; npe_ = part.n;
-   fast_p1_ = (part.p == 1 && !bbar && !tet);          // fused L-vector kernels exist for p = 1 full integration
-   const bool hex_p2 = part.p == 2 && !tet;
-   // EXA_TET_ACTION=generic: tetrahedra keep the table-driven PA (E-vector) / EA action (A/B switch)
-   tet_fused_ = tet && !(std::getenv("EXA_TET_ACTION") && std::string(std::getenv("EXA_TET_ACTION")) == "generic");
-   lvec_grad_ = fast_p1_ || opt.assembly == Assembly::EA || hex_p2 || tet_fused_;   // p = 2: matrix-free action from the point records (PA and EA)
-   // EXA_DETERMINISTIC=1: ordered E->L sums and halo additions instead of FP64 atomics: bit-reproducible residuals, CG iterates and results.
-   // The fused kernels are ordered for p = 1 full integration; the other contexts take the E-vector entries + the ordered E->L sum.
-   const bool det = std::getenv("EXA_DETERMINISTIC") && std::string(std::getenv("EXA_DETERMINISTIC")) == "1";
-   const bool det_unfused = det && !fast_p1_;
-   if (det_unfused) lvec_grad_ = false;
-   fused_setup_ = std::getenv("EXA_UNFUSED_SETUP") == nullptr;
-   // tail split of the constitutive launch (include/exaconstit_hip.h): EXA_NEWTON_CAP=off | <K> | unset (chosen from the evaluation-count histogram of the previous launch)
-   // The controller runs for the Kocks-Mecking family only: for the Voce kernels the model never finds a paying cap in steady state and
-   // a stale histogram costs 20 % in the elastic-plastic transition passes (measured).  EXA_NEWTON_CAP=auto forces it on.
-   cap_auto_ = (opt.slip == SlipType::MTSDD);
-   if (const char* nc = std::getenv("EXA_NEWTON_CAP")) {
-      if (std::string(nc) == "auto") cap_auto_ = true;
-      else {   // "off", "<K>" or "<K>,<K2>" (second level)
-         cap_auto_ = false; newton_cap_ = (std::string(nc) == "off") ? 0 : std::atoi(nc);
-         if (const char* c2 = std::strchr(nc, ',')) newton_cap2_ = std::atoi(c2 + 1);
-      }
-   }
-   tail_resume_ = !env_is_off("EXA_TAIL_RESUME");   // A/B switch: the dense launch starts its points over (round 2) instead of resuming them
-   if (!tail_resume_) newton_cap2_ = 0;
-   tail_cost_ = (opt.slip == SlipType::MTSDD) ? 1.5 : 4.0;   // (Kocks-Mecking: re-measured on the final round-3 kernels - resumed tail points, rejecting points handed over: w = 1.2 ... 2 picks cap 6 for FCC, 16.6 instead of 16.9 ms at cap 5 (w <= 1); BCC 4 either way)
-   if (const char* tc = std::getenv("EXA_TAIL_COST")) { const double v = std::atof(tc); if (v > 0.0) tail_cost_ = v; }   // A/B switch of the controller's cost model
-   // element assembly: the element matrices are 2x (p = 1) to 5x (p = 2) the bytes of the records they are built from, so the action is
-   // computed from the records and the matrices only exist if somebody asks for them (diagonal, export); EXA_EA_ASSEMBLED=1 streams them instead
-   const bool ea_matfree = !det_unfused && opt.assembly == Assembly::EA && (hex_p2 || fast_p1_ || tet_fused_) &&
-                           !(std::getenv("EXA_EA_ASSEMBLED") && std::string(std::getenv("EXA_EA_ASSEMBLED")) == "1");
-   if (ea_matfree) abi_check(ctx_, exa_set_ea_matrix_free(ctx_, 1), "exa_set_ea_matrix_free");
-   // tetrahedra: the fused kernel runs for PA and for matrix-free EA, in atomic mode; assembled EA matrices (EXA_EA_ASSEMBLED=1) take the
-   // table-driven L-vector kernel, and the records of the fused action are then not built per Newton iteration
-   if (tet_fused_ && (det_unfused || (opt.assembly == Assembly::EA && !ea_matfree))) tet_fused_ = false;
-   // p = 1 fused action: J^-1 recomputed from the current coordinates (EXA_TET_APPLY_GEO=off: read from the element record)
-   tet_geo_ = tet_fused_ && part.p == 1 && !env_is_off("EXA_TET_APPLY_GEO");
-   if (tet) abi_check(ctx_, exa_tet_set_fused_action(ctx_, tet_fused_ ? 1 : 0), "exa_tet_set_fused_action");
-   {  // compact tangent records wherever a record-based action runs: p = 1 PA / matrix-free EA with the geometry recomputed, p = 2 matrix-free
-      auto env_is = [](const char* k, const char* v) { const char* e = std::getenv(k); return e && std::string(e) == v; };
-      const bool ea_streamed = opt.assembly == Assembly::EA && env_is("EXA_EA_ASSEMBLED", "1");
-      compact_tangent_ = !det_unfused && !env_is("EXA_TANGENT_FORM", "full") && !ea_streamed && ((fast_p1_ && !env_is("EXA_APPLY_GEO", "off")) || hex_p2);
-   }
-   if (compact_tangent_) abi_check(ctx_, exa_set_tangent_form(ctx_, EXA_TANGENT_DEV5_BULK), "exa_set_tangent_form");
-   // Gradient records straight from the constitutive launch (p = 1, compact form, identity "Jacobi" of the reference): no tangent field, no
-   // defect check, no AssembleGradPA pass per Newton iteration.  EXA_TANGENT_RECORDS=off keeps the tangent field + exa_grad_setup (A/B switch);
-   // true Jacobi needs the 46-double records for the diagonal and takes that route as well (SetPrecond).
-   // p = 2 (round 6): the same behind the geometry pre-pass - the launch writes the 18-pair records of the matrix-free action (plain or B-bar, PA or EA)
-   const bool p2_records = hex_p2 && !det && (opt.assembly == Assembly::PA || !(std::getenv("EXA_EA_ASSEMBLED") && std::string(std::getenv("EXA_EA_ASSEMBLED")) == "1")) &&
-                           !env_is_off("EXA_P2_PREPASS");
-   // (p = 1: on either layout - the reference layout through the staged launch; p = 2: element-blocked only)
-   records_setup_ = (fast_p1_ || p2_records) && compact_tangent_ && fused_setup_ && !det && !env_is_off("EXA_TANGENT_RECORDS") &&
-                    (fast_p1_ || !(std::getenv("EXA_QLAYOUT") && std::string(std::getenv("EXA_QLAYOUT")) == "aos"));
-   geo_resid_ = !(std::getenv("EXA_JAC_FIELD") && std::string(std::getenv("EXA_JAC_FIELD")) == "on");   // A/B switch: the record route writes and reads the Jacobian field as before
-   if (det) { abi_check(ctx_, exa_set_deterministic(ctx_, 1), "exa_set_deterministic"); comm_.deterministic = true; }
-   abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, tail_resume_ ? 1 : 0), "exa_set_newton_caps");   // A/B switch for measurements; the fused launch is the product path
-   // slip rates on demand (EnsureSlipRates): the element-blocked record launches write 56 B per point less (Kocks-Mecking: 48); EXA_LEAN_STATE=off is the A/B switch
-   abi_check(ctx_, exa_set_lean_state(ctx_, env_is_off("EXA_LEAN_STATE") ? 0 : 1), "exa_set_lean_state");
-   // internal quadrature-function layout: element-blocked on the fused p = 1 and p = 2 paths (EXA_QLAYOUT=aos switches back for A/B runs)
-   const char* ql = std::getenv("EXA_QLAYOUT");
-   lvec_resid_ = fast_p1_ || (hex_p2 && !det);      // fused L-vector residual kernels (p = 1 full integration; p = 2 plain and B-bar)
-   if (lvec_resid_ && !(ql && std::string(ql) == "aos")) abi_check(ctx_, exa_set_quadrature_layout(ctx_, EXA_QLAYOUT_EB64), "exa_set_quadrature_layout");
+   const OperatorRoutes& r = routes_;
+   compact_tangent_ = r.compact_tangent; newton_cap_ = r.newton_cap; newton_cap2_ = r.newton_cap2;
+   if (r.ea_matrix_free) abi_check(ctx_, exa_set_ea_matrix_free(ctx_, 1), "exa_set_ea_matrix_free");
+   if (tet) abi_check(ctx_, exa_tet_set_fused_action(ctx_, r.tet_fused ? 1 : 0), "exa_tet_set_fused_action");
+   if (r.compact_tangent) abi_check(ctx_, exa_set_tangent_form(ctx_, EXA_TANGENT_DEV5_BULK), "exa_set_tangent_form");
+   if (r.det) { abi_check(ctx_, exa_set_deterministic(ctx_, 1), "exa_set_deterministic"); comm_.deterministic = true; }
+   abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, r.tail_resume ? 1 : 0), "exa_set_newton_caps");   // A/B switch for measurements; the fused launch is the product path
+   abi_check(ctx_, exa_set_lean_state(ctx_, r.lean_state ? 1 : 0), "exa_set_lean_state");
+   if (r.qlayout_eb64) abi_check(ctx_, exa_set_quadrature_layout(ctx_, EXA_QLAYOUT_EB64), "exa_set_quadrature_layout");
    auto qf = [&](int vdim) { return (size_t)exa_qf_size(ctx_, vdim); };
    conn.upload(part.conn); abi_check(ctx_, exa_set_connectivity(ctx_, conn.p, nn_), "exa_set_connectivity");
    x_ref.upload(part.X); x_beg.upload(part.X); x_cur.upload(part.X);
    weight.upload(part.weight);
-   el_x.alloc(3 * (size_t)npe_ * E_); el_v.alloc(3 * (size_t)npe_ * E_); el_y_.alloc(3 * (size_t)npe_ * E_); el_jac.alloc(qf(9));
+   el_x.alloc(3 * (size_t)npe_ * E_); el_y_.alloc(3 * (size_t)npe_ * E_); el_jac.alloc(qf(9));
    stress0.alloc(qf(6)); stress1.alloc(qf(6)); matVars0.alloc(qf(28)); matVars1.alloc(qf(28));
-   if (!records_setup_) { matGrad.alloc(qf(36)); matGrad.zero(); }   // (allocated on demand if the records route is left, see SetPrecond)
+   if (!r.records_setup) { matGrad.alloc(qf(36)); matGrad.zero(); }   // (allocated on demand if the records route is left, see SetPrecond)
    stress0.zero(); stress1.zero(); matVars1.zero();
    diag.alloc(nd_); dinv.alloc(nd_); tmp_l_.alloc(nd_); tmp_r_.alloc(nd_); el_x2_.alloc(3 * (size_t)npe_ * E_); ess_mask.alloc(nd_); ess_mask.zero();
    partial.alloc(DOT_BLOCKS * 4); scal.alloc(SCAL_LEN); scal.zero();
    { DevBuf<double> q; q.upload(quats_per_elem); abi_check(ctx_, exa_init_state(ctx_, matVars0.p, q.p, stream_), "exa_init_state"); EXA_HC(hipStreamSynchronize(stream_)); }
    model_.reset(new ExaCMechModel(ctx_, &stress0, &stress1, &matGrad, &matVars0, &matVars1));
    comm_.setup_halo(part);
-   // Halo exchange overlapped with the interior blocks: several ranks, the atomic p = 1 record-based action (PA, and EA computed from the
-   // records).  The deterministic mode keeps the plain sequence (its ordered E->L gather runs over all elements at once); EXA_HALO_OVERLAP=off
-   // is the A/B switch.  part.E_bdr > 0 only after Partition::order_boundary_first (SystemDriver).
-   {
-      const bool ea_rec = opt.assembly == Assembly::EA && !(std::getenv("EXA_EA_ASSEMBLED") && std::string(std::getenv("EXA_EA_ASSEMBLED")) == "1");
-      // Over RCCL the overlapped form is OPT-IN (EXA_HALO_OVERLAP=on).  Round 6 ran it on the hardware a one-GPU box has - the forced one-rank communicator
-      // exchanging a face of the real size with itself (EXA_HALO_SELFTEST, tests/test_gpu_rccl.py): the grouped send/recv on the second stream between the
-      // all-reduces of the main stream works, but at 64^3 per rank it costs 162 us per PCG iteration against 141 us in line (profiles/r06_rccl_self_exchange.txt):
-      // two launches of the action and two cross-stream waits to hide a 24 us exchange.  A box with real xGMI neighbours has to show where the balance tips.
-      const char* ho = std::getenv("EXA_HALO_OVERLAP");
-      const bool want = ho ? std::string(ho) != "off" && std::string(ho) != "0" : comm.kind() != Comm::RCCL;
-      // (periodic partitions keep the plain sequence: the elements at the box surface touch shared dofs too, and the boundary-first order does not know them)
-      overlap_ = fast_p1_ && lvec_grad_ && !det && part.E_bdr > 0 && !part.nbrs.empty() && (opt.assembly == Assembly::PA || ea_rec) && want && !part.periodic;
-      // decided collectively: every rank runs the same form (a partition in which one rank has no boundary block would otherwise put its
-      // exchange on another stream than its peers')
-      if (comm.nranks > 1) overlap_ = comm.max_over_ranks(overlap_ ? 0.0 : 1.0) == 0.0;
-      nblk_bdr_ = (part.E_bdr + 63) / 64;
-   }
+   // the overlapped halo exchange is decided collectively: every rank runs the same form (a partition in which one rank has no boundary block
+   // would otherwise put its exchange on another stream than its peers')
+   overlap_ = r.overlap_wish;
+   if (comm.nranks > 1) overlap_ = comm.max_over_ranks(overlap_ ? 0.0 : 1.0) == 0.0;
+   nblk_bdr_ = (part.E_bdr + 63) / 64;
    if (part.periodic) SetupPeriodic();
 }
 
@@ -282,82 +223,12 @@ NonlinearMechOperator::~NonlinearMechOperator() {
 }
 
 void NonlinearMechOperator::SetCapState(int cap, int cap2) {
-   if (!cap_auto_) return;   // a fixed cap (EXA_NEWTON_CAP) or none: nothing follows the run
+   if (!routes_.cap_auto) return;   // a fixed cap (EXA_NEWTON_CAP) or none: nothing follows the run
    newton_cap_ = cap; newton_cap2_ = cap2;
-   abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, tail_resume_ ? 1 : 0), "exa_set_newton_caps");
+   abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, routes_.tail_resume ? 1 : 0), "exa_set_newton_caps");
 }
 
 void NonlinearMechOperator::UpdateEssTDofs(const std::vector<uint8_t>& mask) { ess_mask.upload(mask); }
-
-// Cost model of the tail split in units of one residual evaluation per point.  A wave costs the largest evaluation count among its 64
-// lanes: E[max of 64 draws].  With cap K the first launch draws from min(n, K) and the dense second launch from {n > K} (plus ~2
-// evaluations' worth of set-up / tangent / I/O per redone point):  C(K) = Emax64(min(n,K)) + 0.2 + f_tail w (Emax64(n | n > K) + 2).
-// w = measured cost of a point in the second launch relative to the first (its lanes are scattered points: 8-byte accesses into the
-// blocked rows): 4 for the Voce kernels, whose first launch is close to the memory system's limits, 1.5 for the compute-heavy
-// Kocks-Mecking kernel; 0.2 = the second launch's fixed cost.  Measured at 128^3: BCC KM-DD 31.6 -> 16.0 ms, FCC KM-DD 70.9 -> 55.9 ms,
-// Voce stays uncapped (6.9 ms; K = 5 would cost 10.2 ms, which the model reproduces).  Round 3: w = 1.0 at mid-round, 1.5 again on the final kernels (EXA_TAIL_COST overrides).
-// Returns the K minimising C, or 0 (off) when it does not beat the uncapped launch by 3 %.
-// With resumed tail points (exa_set_newton_caps) a listed point does not repeat its K evaluations: the dense launch pays the point set-up again
-// (~0.7 evaluations), one evaluation that restores (r, J), and the evaluations beyond K.  A second cap K2 splits the dense launch once more:
-//   C(K, K2) = Emax64(min(n,K)) + 0.2 + f1 w (Emax64(min(n,K2) | n > K) - K + 1.7) + [0.2 + f2 w (Emax64(n | n > K2) - K2 + 1.7)]
-// The pair (K, K2) minimising C is returned (K2 = 0: one dense launch), or (0, 0) when it does not beat the uncapped launch by 3 %.
-void choose_newton_caps_resume(const int* hist, double w, int& k1, int& k2) {
-   k1 = k2 = 0;
-   double tot = 0; for (int i = 0; i < 64; i++) tot += hist[i];
-   if (tot <= 0) return;
-   // E[max of 64 draws] of min(n, hi) over the population n > lo
-   auto emax = [&](int lo, int hi) {
-      double n = 0; for (int m = lo + 1; m < 64; m++) n += hist[m];
-      if (n <= 0) return 0.0;
-      double F = 0, prev = 0, e = 0;
-      for (int m = lo + 1; m <= hi; m++) {
-         double pm = hist[m]; if (m == hi) for (int j = hi + 1; j < 64; j++) pm += hist[j];
-         F += pm / n; const double f64 = std::pow(std::min(F, 1.0), 64.0); e += m * (f64 - prev); prev = f64;
-      }
-      return e;
-   };
-   auto above = [&](int k) { double n = 0; for (int m = k + 1; m < 64; m++) n += hist[m]; return n / tot; };
-   const double c_inf = emax(-1, 63);
-   double best = c_inf;
-   for (int K = 3; K < 40; K++) {
-      const double f1 = above(K);
-      if (f1 == 0) break;
-      const double first = emax(-1, K) + 0.2;
-      {  const double c = first + f1 * w * (emax(K, 63) - K + 1.7);
-         if (c < best) { best = c; k1 = K; k2 = 0; } }
-      for (int K2 = K + 2; K2 < 48; K2++) {
-         const double f2 = above(K2);
-         if (f2 == 0) break;
-         const double c = first + f1 * w * (emax(K, K2) - K + 1.7) + 0.2 + f2 * w * (emax(K2, 63) - K2 + 1.7);
-         if (c < best) { best = c; k1 = K; k2 = K2; }
-      }
-   }
-   if (!(best < 0.97 * c_inf)) k1 = k2 = 0;
-}
-
-int choose_newton_cap(const int* hist, double tail_cost_) {
-   double tot = 0; for (int i = 0; i < 64; i++) tot += hist[i];
-   if (tot <= 0) return 0;
-   auto emax = [&](int lo, int hi, double n) {   // E[max of 64 draws] of the histogram restricted to bins lo..hi (n = its population)
-      if (n <= 0) return 0.0;
-      double F = 0, prev = 0, e = 0;
-      for (int m = lo; m <= hi; m++) { F += hist[m] / n; const double f64 = std::pow(std::min(F, 1.0), 64.0); e += m * (f64 - prev); prev = f64; }
-      return e;
-   };
-   const double c_inf = emax(0, 63, tot);
-   double best = c_inf; int bestk = 0;
-   for (int K = 3; K < 40; K++) {
-      double ntail = 0; for (int m = K + 1; m < 64; m++) ntail += hist[m];
-      if (ntail == 0) break;
-      // first launch: bins above K collapse onto K
-      double F = 0, prev = 0, e = 0;
-      for (int m = 0; m <= K; m++) { F += (m < K ? hist[m] : tot - [&] { double a = 0; for (int j = 0; j < K; j++) a += hist[j]; return a; }()) / tot;
-                                     const double f64 = std::pow(std::min(F, 1.0), 64.0); e += m * (f64 - prev); prev = f64; }
-      const double c = e + 0.2 + ntail / tot * tail_cost_ * (emax(K + 1, 63, ntail) + 2.0);
-      if (c < best) { best = c; bestk = K; }
-   }
-   return (best < 0.97 * c_inf) ? bestk : 0;
-}
 
 template <bool upd_crds>
 void NonlinearMechOperator::Setup(const double* k) {
@@ -370,32 +241,23 @@ void NonlinearMechOperator::Setup(const double* k) {
    EXA_HC(hipEventRecord(ev.a, stream_));
    // ... and AssembleGradPA: the launch writes the action's point records.  With the L-vector residual both integrator actions take the geometry
    // from x_cur, so no Jacobian field is written (72 of 848 B per point); UpdateModel refreshes it once per step for the volume averages
-   if (use_records()) { model_->ModelSetupLVecRecords(x_cur.p, k, geo_resid() ? nullptr : el_jac.p, stream_); jac_stale_ = geo_resid(); MarkRates(matVars1.p, exa_get_lean_state(ctx_) == 1); }
-   else if (fused_setup_) { ensure_mat_grad(); model_->ModelSetupLVec(x_cur.p, k, el_jac.p, stream_); jac_stale_ = false; MarkRates(matVars1.p, false); }   // L->E of x and v + SetupJacobianTerms inside the constitutive launch
-   else {
-      ensure_mat_grad();
-      abi_check(ctx_, exa_restrict(ctx_, x_cur.p, el_x.p, stream_), "exa_restrict");
-      abi_check(ctx_, exa_jacobians(ctx_, el_x.p, el_jac.p, stream_), "exa_jacobians");   // SetupJacobianTerms
-      abi_check(ctx_, exa_restrict(ctx_, k, el_v.p, stream_), "exa_restrict");
-      model_->ModelSetup(el_jac.p, el_v.p, stream_);
-      jac_stale_ = false; MarkRates(matVars1.p, false);
-   }
+   if (use_records()) { model_->ModelSetupLVecRecords(x_cur.p, k, routes_.geo_resid ? nullptr : el_jac.p, stream_); jac_stale_ = routes_.geo_resid; MarkRates(matVars1.p, exa_get_lean_state(ctx_) == 1); }
+   else { ensure_mat_grad(); model_->ModelSetupLVec(x_cur.p, k, el_jac.p, stream_); jac_stale_ = false; MarkRates(matVars1.p, false); }   // L->E of x and v + SetupJacobianTerms inside the constitutive launch
    EXA_HC(hipEventRecord(ev.b, stream_)); ev.pending = true;
    timers.qpt_updates += (int64_t)E_ * exa_qpts_per_elem(ctx_); model_calls++;
    model_status_pending_ = true;
-   static const bool log_hist = std::getenv("EXA_NFEV_LOG") != nullptr;      // measurement aid: evaluation-count histogram of every launch on stderr (synchronises)
-   if (log_hist) {
+   if (routes_.nfev_log) {
       int h[64]; abi_check(ctx_, exa_model_nfev_hist(ctx_, matVars1.p, h, stream_), "exa_model_nfev_hist");
       std::fprintf(stderr, "nfev_hist call %ld dt %.4g cap %d tail %d:", (long)model_calls, dt_, newton_cap_, newton_cap_ > 0 ? exa_model_tail_count(ctx_, stream_) : 0);
       for (int i = 0; i < 64; i++) if (h[i]) std::fprintf(stderr, " %d:%d", i, h[i]);
       std::fprintf(stderr, "\n");
    }
-   if (cap_auto_ && (model_calls <= 4 || model_calls % 4 == 0)) {   // tail split: next cap from the evaluation counts of this launch (the distribution drifts slowly)
+   if (routes_.cap_auto && (model_calls <= 4 || model_calls % 4 == 0)) {   // tail split: next cap from the evaluation counts of this launch (the distribution drifts slowly)
       int h[64]; abi_check(ctx_, exa_model_nfev_hist(ctx_, matVars1.p, h, stream_), "exa_model_nfev_hist");
       // (one dense launch: measured at 128^3, a second level loses - FCC 5: 18.0 ms, 5+11: 19.0, 4+6: 21.1; BCC 4: 9.7, 3+5: 13.1 - because
       //  the dense launches pay for scattered 8-byte accesses into the blocked rows, not for idle lanes; EXA_NEWTON_CAP=K,K2 runs two levels)
-      newton_cap_ = choose_newton_cap(h, tail_cost_); newton_cap2_ = 0;
-      abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, tail_resume_ ? 1 : 0), "exa_set_newton_caps");
+      newton_cap_ = choose_newton_cap(h, routes_.tail_cost); newton_cap2_ = 0;
+      abi_check(ctx_, exa_set_newton_caps(ctx_, newton_cap_, newton_cap2_, routes_.tail_resume ? 1 : 0), "exa_set_newton_caps");
    }
 }
 template void NonlinearMechOperator::Setup<true>(const double*);
@@ -422,8 +284,7 @@ NonlinearMechOperator::EvPair& NonlinearMechOperator::NextModelTimer() {
 }
 void NonlinearMechOperator::ReadTimer(EvPair& e) {
    EXA_HC(hipEventSynchronize(e.b)); float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e.a, e.b)); timers.t_model_ms += ms; e.pending = false;
-   static const bool print = std::getenv("EXA_MODEL_TIMES") != nullptr;      // per-launch durations on stderr (measurement aid)
-   if (print) std::fprintf(stderr, "model_launch call %ld: %.4f ms\n", e.call, ms);
+   if (routes_.model_times) std::fprintf(stderr, "model_launch call %ld: %.4f ms\n", e.call, ms);
 }
 // adds the launches timed since the last call to timers.t_model_ms (waits for the last of them)
 void NonlinearMechOperator::FlushModelTimers() {
@@ -439,10 +300,10 @@ void NonlinearMechOperator::ReadModelStatus() {
 
 void NonlinearMechOperator::ResidualAction(double* y) {
    EXA_HC(hipMemsetAsync(y, 0, sizeof(double) * nd_, stream_));
-   if (lvec_resid_ && jac_stale_) {   // geometry from the nodes of the configuration the stress belongs to
+   if (routes_.lvec_resid && jac_stale_) {   // geometry from the nodes of the configuration the stress belongs to
       abi_check(ctx_, exa_grad_set_coords(ctx_, x_cur.p), "exa_grad_set_coords");
       abi_check(ctx_, exa_residual_lvec(ctx_, nullptr, stress1.p, y, stream_), "exa_residual_lvec");
-   } else if (lvec_resid_) abi_check(ctx_, exa_residual_lvec(ctx_, el_jac.p, stress1.p, y, stream_), "exa_residual_lvec");
+   } else if (routes_.lvec_resid) abi_check(ctx_, exa_residual_lvec(ctx_, el_jac.p, stress1.p, y, stream_), "exa_residual_lvec");
    else {   // Hform->Setup() = AssemblePA, Hform->Mult = L->E, AddMultPA, E->L
       abi_check(ctx_, exa_residual_setup(ctx_, el_jac.p, stress1.p, stream_), "exa_residual_setup");
       el_y_.zero(stream_);
@@ -473,7 +334,7 @@ void NonlinearMechOperator::GetGradient() {
    if (use_records()) {   // the constitutive launch of the last residual evaluation wrote the records of this state; the action recomputes the geometry from x_cur
       abi_check(ctx_, exa_grad_set_coords(ctx_, x_cur.p), "exa_grad_set_coords");
       // (B-bar, p = 2: the element-average gradients the action reads; the residual refreshes them as well, but GetUpdateBCsAction applies the gradient first)
-      if (!fast_p1_) abi_check(ctx_, exa_grad_refresh_bbar(ctx_, el_jac.p, stream_), "exa_grad_refresh_bbar");
+      if (!routes_.fast_p1) abi_check(ctx_, exa_grad_refresh_bbar(ctx_, el_jac.p, stream_), "exa_grad_refresh_bbar");
       vk_jacobi_setup(nd_, ess_mask.p, diag.p, 1, dinv.p, stream_);
       if (precond == Precond::MULTIGRID) mg->Build();
       return;
@@ -491,8 +352,7 @@ void NonlinearMechOperator::GetGradient() {
    }
    abi_check(ctx_, exa_grad_setup(ctx_, dt_, el_jac.p, matGrad.p, stream_), "exa_grad_setup");
    // geometry of the action recomputed from x_cur (unchanged until the next residual evaluation); EXA_APPLY_GEO=off streams it instead
-   if ((fast_p1_ && !(std::getenv("EXA_APPLY_GEO") && std::string(std::getenv("EXA_APPLY_GEO")) == "off")) || tet_geo_)
-      abi_check(ctx_, exa_grad_set_coords(ctx_, x_cur.p), "exa_grad_set_coords");   // read by the record-based actions (PA, matrix-free EA) only
+   if (routes_.grad_set_coords) abi_check(ctx_, exa_grad_set_coords(ctx_, x_cur.p), "exa_grad_set_coords");   // read by the record-based actions (PA, matrix-free EA) only
    // The reference assembles the operator diagonal here on every call, but its Jacobi smoother never reads it (dinv is built once
    // from diag = 1).  With that default the assembly is skipped: no result depends on it, and for p = 2 element
    // assembly it would be the only consumer of the 81 x 81 matrices.
@@ -508,24 +368,8 @@ void NonlinearMechOperator::GetGradient() {
    if (precond == Precond::MULTIGRID) mg->Build();
 }
 
-void NonlinearMechOperator::GradMultLocal(const double* x, double* y) {
-   EXA_HC(hipMemsetAsync(y, 0, sizeof(double) * nd_, stream_));
-   if (lvec_grad_) abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, ess_mask.p, nullptr, stream_), "exa_grad_apply_lvec");
-   else {
-      EXA_HC(hipMemcpyAsync(tmp_l_.p, x, sizeof(double) * nd_, hipMemcpyDeviceToDevice, stream_));
-      vk_mask_zero(nd_, ess_mask.p, tmp_l_.p, stream_);
-      abi_check(ctx_, exa_restrict(ctx_, tmp_l_.p, el_x2_.p, stream_), "exa_restrict");
-      el_y_.zero(stream_);
-      abi_check(ctx_, exa_grad_apply(ctx_, el_x2_.p, el_y_.p, stream_), "exa_grad_apply");
-      abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
-   }
-   vk_mask_zero(nd_, ess_mask.p, y, stream_);
-}
-
-// y = this rank's element contributions of K x as they stand (DESIGN 4.13): no expansion, no sum over images or ranks, no output mask
-void NonlinearMechOperator::GradMultRaw(const double* x, double* y, const uint8_t* in_mask) {
-   EXA_HC(hipMemsetAsync(y, 0, sizeof(double) * nd_, stream_));
-   if (lvec_grad_) { abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, in_mask, nullptr, stream_), "exa_grad_apply_lvec"); return; }
+// generic-order partial assembly, added into y: mask, L->E, AddMultGradPA, E->L (spec reference src/mechanics_operator_ext.cpp:143-157)
+void NonlinearMechOperator::ElementAction(const double* x, const uint8_t* in_mask, double* y) {
    EXA_HC(hipMemcpyAsync(tmp_l_.p, x, sizeof(double) * nd_, hipMemcpyDeviceToDevice, stream_));
    if (in_mask) vk_mask_zero(nd_, in_mask, tmp_l_.p, stream_);
    abi_check(ctx_, exa_restrict(ctx_, tmp_l_.p, el_x2_.p, stream_), "exa_restrict");
@@ -534,9 +378,21 @@ void NonlinearMechOperator::GradMultRaw(const double* x, double* y, const uint8_
    abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
 }
 
+void NonlinearMechOperator::GradMultLocal(const double* x, double* y) {
+   GradMultRaw(x, y, ess_mask.p);
+   vk_mask_zero(nd_, ess_mask.p, y, stream_);
+}
+
+// y = this rank's element contributions of K x as they stand (DESIGN 4.13): no expansion, no sum over images or ranks, no output mask
+void NonlinearMechOperator::GradMultRaw(const double* x, double* y, const uint8_t* in_mask) {
+   EXA_HC(hipMemsetAsync(y, 0, sizeof(double) * nd_, stream_));
+   if (routes_.lvec_grad) abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, in_mask, nullptr, stream_), "exa_grad_apply_lvec");
+   else ElementAction(x, in_mask, y);
+}
+
 // the raw action on nc columns in one call (exa_grad_apply_lvec_cols): false when the context has no such kernel - y is then untouched
 bool NonlinearMechOperator::GradMultRawCols(int nch, int nc, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* in_mask, const double* const* gates) {
-   if (!lvec_grad_) return false;
+   if (!routes_.lvec_grad) return false;
    const int rc = exa_grad_apply_lvec_cols_w(ctx_, nch, nc, x, ldx, y, ldy, in_mask, gates, stream_);
    if (rc == EXA_ERR_UNSUPPORTED) return false;
    abi_check(ctx_, rc, "exa_grad_apply_lvec_cols");
@@ -545,7 +401,7 @@ bool NonlinearMechOperator::GradMultRawCols(int nch, int nc, const double* x, in
 
 void NonlinearMechOperator::GradMult(const double* x, double* y, bool constrained, const double* done_flag, bool y_prezeroed, bool skip_out_mask) {
    if (!y_prezeroed) vk_fill_if(nd_, done_flag, 0.0, y, stream_);
-   if (lvec_grad_ && overlap_) {
+   if (routes_.lvec_grad && overlap_) {
       // blocks that touch shared nodes, exchange of the shared dofs on the communication stream, interior blocks meanwhile, unpack last
       const uint8_t* m = constrained ? ess_mask.p : nullptr;
       const int nball = (E_ + 63) / 64;
@@ -565,15 +421,9 @@ void NonlinearMechOperator::GradMult(const double* x, double* y, bool constraine
    // every component that a free H_id reaches), so the action itself runs without an input mask.
    const bool mix = mixed();
    if (mix) x = MixedExpand(x, done_flag, constrained);
-   if (lvec_grad_) abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, constrained && !mix ? ess_mask.p : nullptr, done_flag, stream_), "exa_grad_apply_lvec");
-   else {   // generic-order partial assembly: mask, L->E, AddMultGradPA, E->L (spec reference src/mechanics_operator_ext.cpp:143-157)
-      EXA_HC(hipMemcpyAsync(tmp_l_.p, x, sizeof(double) * nd_, hipMemcpyDeviceToDevice, stream_));
-      if (constrained && !mix) vk_mask_zero(nd_, ess_mask.p, tmp_l_.p, stream_);
-      abi_check(ctx_, exa_restrict(ctx_, tmp_l_.p, el_x2_.p, stream_), "exa_restrict");
-      el_y_.zero(stream_);
-      abi_check(ctx_, exa_grad_apply(ctx_, el_x2_.p, el_y_.p, stream_), "exa_grad_apply");
-      abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
-   }
+   const uint8_t* in_mask = constrained && !mix ? ess_mask.p : nullptr;
+   if (routes_.lvec_grad) abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, in_mask, done_flag, stream_), "exa_grad_apply_lvec");
+   else ElementAction(x, in_mask, y);
    SumLVector(y, done_flag);
    if (constrained && !skip_out_mask) vk_mask_zero(nd_, ess_mask.p, y, stream_);
 }
@@ -699,7 +549,6 @@ SystemDriver::SystemDriver(const ExaOptions& opt, const std::vector<double>& pro
 void SystemDriver::init(const std::vector<double>& props, const std::vector<double>& quats_local, std::vector<double> grain_qref) {
    oper_.reset(new NonlinearMechOperator(opt_, part, comm, props, quats_local));
    if (opt_.periodic && opt_.periodic_mixed) set_free(opt_.periodic_free);
-   oper_->precond = precond;
    const int nd = oper_->Height();
    v_sol.alloc(nd); v_sol.zero(); r_.alloc(nd); c_.alloc(nd); xt_.alloc(nd); ess_val_.alloc(nd);
    ess_host_.assign(nd, 0); ess_val_host_.assign(nd, 0.0);
@@ -747,6 +596,17 @@ void SystemDriver::UpdateEssBdr(const BCEntry& bc) {
    ess_val_.upload(ess_val_host_); vel_mask_.upload(vel); vg_mask_.upload(vg);
 }
 
+// origin of the velocity-gradient conditions, left in the operator's scal[SCAL_ORIGIN]: Problem.vgrad_origin when it is given, otherwise the
+// componentwise minimum of the current coordinates over all ranks
+const double* SystemDriver::VgradOrigin() {
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   double* org = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
+   if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
+   else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
+   return org;
+}
+
 // SystemDriver::UpdateVelocity (reference src/system_driver.cpp:326-426): velocity conditions, then the velocity-gradient
 // conditions v = L (x - x_min) evaluated on the current mesh nodes (end of the previous step) for their own essential dofs.
 void SystemDriver::UpdateVelocity(double* v) {
@@ -754,9 +614,7 @@ void SystemDriver::UpdateVelocity(double* v) {
    hipStream_t s = op.stream();
    if (have_vel_) vk_mask_set(op.Height(), vel_mask_.p, ess_val_.p, v, s);
    if (have_vgrad_) {
-      double* org = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
-      if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
-      else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
+      const double* org = VgradOrigin();
       vk_vgrad_velocity(part.NN, vg_mask_.p, op.x_cur.p, org, mixed_ ? vgrad_eff_ : vgrad_, v, s);
    }
    if (part.periodic) op.PeriodicJump(mixed_ ? vgrad_eff_ : vgrad_, v);
@@ -808,9 +666,7 @@ void SystemDriver::MixedStepStart() {
       double Lold[9], dL[9];
       mul3(Hp, Ai, Lold);
       for (int k = 0; k < 9; k++) dL[k] = vgrad_eff_[k] - Lold[k];
-      double* org = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
-      if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
-      else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
+      const double* org = VgradOrigin();
       vk_periodic_affine_add(part.NN, op.x_cur.p, org, dL, v_sol.p, s);
       mix_bc_changed_ = false;
    }
@@ -819,8 +675,7 @@ void SystemDriver::MixedStepStart() {
    double org[3];
    if (opt_.vgrad_origin_flag) for (int k = 0; k < 3; k++) org[k] = opt_.vgrad_origin[k];
    else {
-      double* org_dev = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
-      vk_min3(part.NN, op.x_cur.p, op.partial.p, org_dev, s); comm.allreduce_min(org_dev, 3, s);
+      const double* org_dev = VgradOrigin();
       EXA_HC(hipMemcpyAsync(org, org_dev, 3 * sizeof(double), hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
    }
    for (int k = 0; k < 3; k++) mac_w0_[k] = cx[k] - org[k];
@@ -854,9 +709,7 @@ void SystemDriver::PeriodicBCChange(const BCEntry& bc) {
    bc_index_ = (int)(&bc - opt_.bcs.data());
    UpdateEssBdr(bc);
    if (mixed_) { mix_bc_changed_ = true; return; }   // (MixedStepStart swaps the affine part of the prescribed entries)
-   double* org = op.scal.p + NonlinearMechOperator::SCAL_ORIGIN;
-   if (opt_.vgrad_origin_flag) EXA_HC(hipMemcpyAsync(org, opt_.vgrad_origin, 3 * sizeof(double), hipMemcpyHostToDevice, s));
-   else { vk_min3(part.NN, op.x_cur.p, op.partial.p, org, s); comm.allreduce_min(org, 3, s); }
+   const double* org = VgradOrigin();
    vk_periodic_affine_add(part.NN, op.x_cur.p, org, dL, v_sol.p, s);
 }
 
@@ -869,8 +722,7 @@ void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
       op.mg.reset(new Multigrid(op, levels, degree));   // throws where no hierarchy can be built
    } else op.mg.reset();
    krylov_->DropGraph();
-   precond = kind == 0 ? Precond::IDENTITY : (kind == 1 ? Precond::JACOBI : Precond::MULTIGRID);
-   op.precond = precond;
+   op.precond = kind == 0 ? Precond::IDENTITY : (kind == 1 ? Precond::JACOBI : Precond::MULTIGRID);
 }
 
 void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
@@ -878,7 +730,7 @@ void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
    if (!L9) throw std::runtime_error("set_periodic: a 3 x 3 velocity gradient is required");
    for (int k = 0; k < 9; k++) if (!std::isfinite(L9[k])) throw std::runtime_error("set_periodic: the velocity gradient must be finite");
    if (part.from_file || part.geom != 0) throw std::runtime_error(ExaOptions::periodic_needs_generated_mesh());
-   if (precond == Precond::MULTIGRID) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
+   if (oper_->precond == Precond::MULTIGRID) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
    bool any = false;
    if (free9) {
       uint8_t f[9]; for (int k = 0; k < 9; k++) { f[k] = free9[k] ? 1 : 0; any = any || f[k]; }

@@ -9,6 +9,7 @@
 //   PCGSolver (host/krylov.hpp)          MFEM CGSolver, set up at reference src/system_driver.cpp:166-177
 //   SystemDriver                         reference src/system_driver.cpp:221-558
 //   Comm (host/comm.hpp)               MPI in the reference (src/mechanics_driver.cpp:312, src/system_driver.cpp:167, src/mechanics_kernels.hpp:119,124)
+//   OperatorRoutes (host/routes.hpp)     the operator's EXA_* switches and which kernels it runs for them (no counterpart in the reference)
 //   StepAnalyses (host/analyses.hpp)     reference src/system_driver.cpp:560-870 (the Project* outputs) and what this project adds to them
 //   time-step loop                       reference src/mechanics_driver.cpp:837-907
 #pragma once
@@ -23,6 +24,7 @@
 #include "krylov.hpp"
 #include "mesh.hpp"
 #include "options.hpp"
+#include "routes.hpp"
 
 namespace exa_host {
 
@@ -54,9 +56,7 @@ class ExaCMechModel {
       : ctx_(ctx), stress0_(stress0), stress1_(stress1), matGrad_(matGrad), matVars0_(matVars0), matVars1_(matVars1) {}
    void SetModelDt(double dt) { dt_ = dt; }
    double GetModelDt() const { return dt_; }
-   // ExaCMechModel::ModelSetup (reference src/mechanics_ecmech.cpp:192-258)
-   void ModelSetup(const double* jacobian, const double* vel_evec, hipStream_t s);
-   // the same with the operator's L->E restrictions and Jacobian refresh fused in (writes the Jacobians)
+   // ExaCMechModel::ModelSetup (reference src/mechanics_ecmech.cpp:192-258) with the operator's L->E restrictions and Jacobian refresh fused in (writes the Jacobians)
    void ModelSetupLVec(const double* x_lvec, const double* v_lvec, double* jacobian_out, hipStream_t s);
    // ... and with AssembleGradPA fused in too: writes the compact gradient records instead of the tangent field (p = 1 fast path)
    void ModelSetupLVecRecords(const double* x_lvec, const double* v_lvec, double* jacobian_out, hipStream_t s);
@@ -71,10 +71,6 @@ class ExaCMechModel {
    exa_ctx* ctx_; double dt_ = 1.0;
    DevBuf<double>*stress0_, *stress1_, *matGrad_, *matVars0_, *matVars1_;
 };
-
-// tail-split controller (see driver.hip): cap on local-solver evaluations from a 64-bin histogram of their counts; 0 = no cap
-int choose_newton_cap(const int* hist64, double tail_cost);
-void choose_newton_caps_resume(const int* hist64, double tail_cost, int& k1, int& k2);
 
 class NonlinearMechOperator {
  public:
@@ -131,7 +127,7 @@ class NonlinearMechOperator {
    const Partition& part() const { return part_; }
    Comm& comm() { return comm_; }
    // route of the Krylov action (Driver.mesh_info): 0 hexahedron kernels, 1 fused tetrahedron action, 2 table-driven E-vector PA, 3 table-driven EA on L-vectors
-   int action_route() const { return part_.geom != 1 ? 0 : (lvec_grad_ && tet_fused_ ? 1 : (lvec_grad_ ? 3 : 2)); }
+   int action_route() const { return routes_.action_route; }
    // state of the automatic Newton cap (checkpoint files carry it: the cap in force decides how the next constitutive launch is split)
    void GetCapState(int& cap, int& cap2) const { cap = newton_cap_; cap2 = newton_cap2_; }
    void SetCapState(int cap, int cap2);
@@ -145,11 +141,11 @@ class NonlinearMechOperator {
    void ForgetPendingRates() { rates_pending_[0] = rates_pending_[1] = nullptr; }   // the state arrays have been replaced (checkpoint load)
    int64_t rate_launches = 0;                          // materialisation launches so far (Driver.diagnostics)
    // data (device)
-   DevBuf<double> x_ref, x_beg, x_cur, el_x, el_v, el_jac, diag, dinv, weight;
+   DevBuf<double> x_ref, x_beg, x_cur, el_x, el_jac, diag, dinv, weight;
    DevBuf<double> stress0, stress1, matVars0, matVars1, matGrad;
    DevBuf<uint8_t> ess_mask;
    DevBuf<int32_t> conn;
-   Precond precond = Precond::IDENTITY;
+   Precond precond = Precond::IDENTITY;   // (SystemDriver::SetPreconditioner is its only writer)
    std::unique_ptr<Multigrid> mg;   // precond == MULTIGRID: rebuilt after every gradient set-up
    Timers timers;
    int model_calls = 0;
@@ -172,22 +168,23 @@ class NonlinearMechOperator {
    DevBuf<double> partial, scal;
  private:
    ExaOptions opt_; const Partition& part_; Comm& comm_;
+   // Which kernels run (host/routes.hpp), decided once at construction.  What changes afterwards is held by the members below: overlap_ (agreed over
+   // the ranks, demoted when the context cannot run block ranges, off on periodic partitions), compact_tangent_ (dropped when the defect check
+   // fails), jac_stale_, the caps of the tail-split controller (newton_cap_, newton_cap2_) and the pending-rates marks (rates_pending_).
+   const OperatorRoutes routes_;
    exa_ctx* ctx_ = nullptr; std::unique_ptr<ExaCMechModel> model_;
    hipStream_t stream_ = nullptr; hipEvent_t ev0_, ev1_;
    std::vector<EvPair> ev_ring_; int ev_head_ = 0;   // event pairs around the constitutive launches, read back lazily
    int nn_, nd_, E_, npe_ = 8; double dt_ = 1.0;
-   bool records_setup_ = false;   // gradient records written by the constitutive launch (p = 1 fast path, identity preconditioner)
-   bool use_records() const { return records_setup_ && precond != Precond::JACOBI; }
-   bool geo_resid_ = true, jac_stale_ = false;   // record route + L-vector residual: no Jacobian field is written, both actions recompute the geometry (EXA_JAC_FIELD=on keeps it)
-   bool geo_resid() const { return geo_resid_ && lvec_resid_ && fast_p1_; }      // (p = 2: the Jacobian field is written by the geometry pre-pass and read by the residual)
+   bool use_records() const { return routes_.records_setup && precond != Precond::JACOBI; }   // gradient records written by the constitutive launch
+   bool jac_stale_ = false;       // the record route left the Jacobian field unwritten (RefreshJacobians)
    void ensure_mat_grad();
    bool overlap_ = false; int nblk_bdr_ = 0;   // halo exchange overlapped with the interior element blocks (several ranks, atomic p = 1 record action)
-   bool fast_p1_ = true, lvec_grad_ = true, fused_setup_ = true; bool lvec_resid_ = false; bool compact_tangent_ = false;
-   bool tet_fused_ = false;       // tetrahedra: the Krylov action is the fused kernel of tet_kernels.hip (EXA_TET_ACTION=generic: the table-driven PA / EA action)
-   bool tet_geo_ = false;         // tetrahedra, p = 1 fused action: J^-1 from the nodal coordinates (exa_grad_set_coords) instead of the element record
+   bool compact_tangent_ = false;
    const double* rates_pending_[2] = { nullptr, nullptr };   // state arrays whose slots 14..25 wait for EnsureSlipRates
    void MarkRates(const double* p, bool pending);
-   bool cap_auto_ = true; int newton_cap_ = 0, newton_cap2_ = 0; bool tail_resume_ = true; double tail_cost_ = 4.0;
+   int newton_cap_ = 0, newton_cap2_ = 0;
+   void ElementAction(const double* x, const uint8_t* in_mask, double* y);   // the generic E-vector action, added into y (in_mask nullable)
    DevBuf<double> tmp_l_, tmp_r_, el_y_, el_x2_;
    // periodic partitions: the group table, and for several ranks 1 / holders on the node that carries the canonical id and the box-surface mask
    DevBuf<int32_t> per_idx_; PeriodicTable per_tab_; DevBuf<double> per_repw_; DevBuf<uint8_t> per_surf_, per_notown_;
@@ -269,7 +266,6 @@ class SystemDriver {
    // here); the elements' initial orientations and states become their grain's; the analyses are told (GrainsChanged)
    void SetGrains(const int32_t* grain_of_global_elem, int64_t n_global, const double* grain_quats, int G);
    std::vector<int32_t> elem_attr;             // grain id (element attribute) of every local element
-   Precond precond = Precond::IDENTITY;
    Partition part;
    Comm comm;
  private:
@@ -287,6 +283,7 @@ class SystemDriver {
    bool mixed_ = false, mac_have_ = false, mix_bc_changed_ = false; uint8_t free_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
    double vgrad_eff_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_A_[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, mac_L_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_F_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_w0_[3] = { 0, 0, 0 };
    void set_free(const uint8_t* f);
+   const double* VgradOrigin();                 // leaves the origin of the velocity-gradient conditions in the operator's scal[SCAL_ORIGIN]
    int bc_index_ = -1;                          // index in opt_.bcs of the essential-boundary entry in force
    bool synthetic_ = false, restarted_ = false;
    bool step_solved_ = false;                   // the last Step of this process converged and no constitutive launch has run since (MacroTangent)

@@ -161,6 +161,17 @@ int exa_comm_rank_fold(int op, int nranks, int n, const double* contributions, d
    return 0;
 }
 
+// host only: the operator's route decision for the facts under the switches of the environment as it is now (order of facts and out: exaconstit_driver.h)
+int exa_operator_routes_query(const int* facts, int nfacts, int* out, int nout) {
+   if (!facts || !out || nfacts != RouteFacts::COUNT || nout < OperatorRoutes::QUERY_FIELDS) return -1;
+   RouteFacts f;
+   f.geom = facts[0]; f.order = facts[1]; f.bbar = facts[2] != 0; f.ea = facts[3] != 0; f.slip = facts[4]; f.several_ranks = facts[5] != 0;
+   f.rccl = facts[6] != 0; f.has_bdr_blocks = facts[7] != 0; f.has_nbrs = facts[8] != 0; f.periodic = facts[9] != 0;
+   if (f.geom < 0 || f.geom > 1 || f.order < 1 || f.slip < 0 || f.slip > 2 || (f.geom == 1 && f.bbar)) return -1;
+   decide_routes(f, RouteSwitches::from_env()).to_ints(out);
+   return OperatorRoutes::QUERY_FIELDS;
+}
+
 int exa_loopback_group_create(int nranks, void* out128) { try { Comm::loopback_create(nranks, out128); return 0; } catch (...) { return -1; } }
 void exa_loopback_group_destroy(const void* id128) { Comm::loopback_destroy(id128); }
 
@@ -176,7 +187,7 @@ exa_driver* exa_driver_create_restart(const char* toml_path, const char* out_dir
       std::unique_ptr<exa_driver> d(new exa_driver());
       d->sd.reset(new SystemDriver(opt, rank, nranks, uid));
       d->sd->out_dir = out_dir ? out_dir : "."; d->sd->write_files = write_files != 0;
-      d->sd->precond = jacobi ? Precond::JACOBI : Precond::IDENTITY; d->sd->oper().precond = d->sd->precond;
+      d->sd->SetPreconditioner(jacobi ? 1 : 0, 0, 0);
       if (opt.precond != 0) d->sd->SetPreconditioner(opt.precond, opt.mg_levels, opt.mg_degree);   // Solvers.Krylov.preconditioner decides when it is present
       const std::string from = restart_path ? std::string(restart_path) : opt.resolve(opt.ckpt_restart_from);
       if (!from.empty()) d->sd->LoadCheckpoint(from);
@@ -267,7 +278,7 @@ exa_driver* exa_driver_create_synthetic(const exa_synth_config* c, int rank, int
       auto d = new exa_driver();
       d->sd.reset(new SystemDriver(opt, props, quats, rank, nranks, uid));
       d->sd->write_files = false;
-      d->sd->precond = c->jacobi ? Precond::JACOBI : Precond::IDENTITY; d->sd->oper().precond = d->sd->precond;
+      d->sd->SetPreconditioner(c->jacobi ? 1 : 0, 0, 0);
       return d;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return nullptr; }
 }

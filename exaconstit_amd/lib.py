@@ -206,6 +206,7 @@ exa_loopback_group_destroy = _sig("exa_loopback_group_destroy", None, C.c_void_p
 exa_driver_comm_details = _sig("exa_driver_comm_details", C.c_int, C.c_void_p, C.POINTER(C.c_int64))
 exa_driver_comm_probe = _sig("exa_driver_comm_probe", C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_int)
 exa_comm_rank_fold = _sig("exa_comm_rank_fold", C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
+exa_operator_routes_query = _sig("exa_operator_routes_query", C.c_int, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.c_int)
 exa_driver_create = _sig("exa_driver_create", C.c_void_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_int)
 exa_driver_create_synthetic = _sig("exa_driver_create_synthetic", C.c_void_p, C.POINTER(ExaSynthConfig), C.c_int, C.c_int, C.c_void_p, C.c_char_p, C.c_int)
 exa_driver_destroy = _sig("exa_driver_destroy", None, C.c_void_p)

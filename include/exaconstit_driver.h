@@ -49,6 +49,17 @@ int exa_driver_comm_probe(exa_driver* d, int what, double* host_vec, int n);
 /* host only: the rank-ordered fold every host-synchronous reduction uses - out[i] = ((c[0][i] op c[1][i]) op c[2][i]) ..., a left fold from rank 0 over
  * contributions[nranks][n]; op 0 sum, 1 min, 2 max.  Returns 0, or -1 for another op or nranks < 1 */
 int exa_comm_rank_fold(int op, int nranks, int n, const double* contributions, double* out);
+/* host only: which kernels an operator would run for these facts under the EXA_* switches of the environment as it is now (host/routes.hpp).
+ * facts[10] = { geometry (0 hexahedra, 1 tetrahedra), order, B-bar, element assembly, slip family (0 Voce, 1 Voce NL, 2 Kocks-Mecking), several ranks,
+ *               the transport is RCCL, the partition has boundary blocks (E_bdr > 0), it has neighbours, it is periodic }
+ * out[23]   = { fused p = 1 kernels, L-vector action, L-vector residual, compact tangent form, records from the constitutive launch, no Jacobian field,
+ *               fused tetrahedron action, its geometry from the coordinates, this rank's wish for the overlapped halo exchange, cap controller,
+ *               element-blocked layout, lean state, matrix-free EA, deterministic, deterministic on the E-vector route, GetGradient hands the coordinates
+ *               to the tangent-field action, first cap, second cap, resumed tail, tail cost weight in tenths, action route (exa_driver_mesh_info),
+ *               EXA_NFEV_LOG, EXA_MODEL_TIMES }
+ * ("several ranks" changes no field: with several ranks the live flag of the overlapped exchange is the agreement of all ranks' wishes.)
+ * Returns 23, or -1 for nfacts != 10, nout < 23 or facts an operator refuses (geometry, slip family, order < 1, B-bar on tetrahedra) */
+int exa_operator_routes_query(const int* facts, int nfacts, int* out, int nout);
 /* latency floor of the RCCL calls of one PCG iteration on this device (one-rank communicator): out2 = { us per 16-byte all-reduce,
  * us per grouped send/recv of n doubles to the own rank } */
 int exa_rccl_microbench(int iters, int n, double* out2, char* err, int errlen);

@@ -228,7 +228,7 @@ int exa_model_record_launches(exa_ctx* ctx, long long* out2);
 int exa_set_newton_cap_auto(exa_ctx* ctx, int mode, double tail_cost);
 int exa_get_newton_cap(exa_ctx* ctx);   /* the cap in force (0 = none) */
 /* histogram (64 bins, last bin = 63 and more) of the evaluation counts stored in slot 3 of a state array; synchronises.  The driver
- * picks max_evals from it (host/driver.hip, choose_newton_cap). */
+ * picks max_evals from it (host/routes.cpp, choose_newton_cap). */
 int exa_model_nfev_hist(exa_ctx* ctx, const double* state_dev, int* hist64_host, exa_stream s);
 /* synchronises the stream; returns the number of non-converged points of the last exa_model_setup (>= 0) */
 int exa_model_status(exa_ctx* ctx, exa_stream s);

@@ -488,3 +488,65 @@ def test_rank_sync_check_program(tmp_path):
     subprocess.run(["g++", "-std=c++17", "-O1", "-pthread", "-o", exe, os.path.join(ROOT, "tests", "rank_sync_check.cpp")], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "0 wrong values" in r.stdout, r.stdout + r.stderr
+
+
+def _route_table():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    import route_table
+    return route_table
+
+
+def test_operator_routes_equal_the_recorded_table():
+    """The operator's route decision (csrc/host/routes.hpp) through exa_operator_routes_query: every row of tests/operator_routes_table.txt - recorded
+    from the constructor's own expressions on the commit before routes.hpp existed (profiles/operator_routes.txt) - field by field."""
+    import exaconstit_amd.lib as L
+    RT = _route_table()
+    with open(os.path.join(ROOT, "tests", "operator_routes_table.txt")) as fh:
+        want = RT.parse(fh.readlines())
+    got = RT.parse(RT.table(L))
+    assert sorted(got) == sorted(want) and len(want) > 1700
+    for key in want:
+        for field, v in want[key].items():
+            assert got[key][field] == v, (key, field, got[key][field], v)
+
+
+def test_operator_routes_readable_rows():
+    import exaconstit_amd.lib as L
+    RT = _route_table()
+    # default p = 1 hex PA Voce on one rank: fused L-vector residual and action, compact form, records from the launch, no Jacobian field,
+    # element-blocked layout, lean state, no cap controller, no overlap
+    r = RT.query(L, RT.facts("hex", 1, 0, 0, 0, "one"))
+    assert r["fast_p1"] == r["lvec_resid"] == r["lvec_grad"] == r["compact_tangent"] == r["records_setup"] == r["geo_resid"] == r["qlayout_eb64"] == r["lean_state"] == 1
+    assert r["cap_auto"] == 0 and r["newton_cap"] == 0 and r["overlap_wish"] == 0 and r["action_route"] == 0 and r["det"] == 0 and r["tail_cost_tenths"] == 40
+    # EXA_DETERMINISTIC=1 at p = 2: E-vector action, no records
+    for ea in (0, 1):
+        r = RT.query(L, RT.facts("hex", 2, 0, ea, 0, "one"), {"EXA_DETERMINISTIC": "1"})
+        assert r["det"] == r["det_unfused"] == 1 and r["lvec_grad"] == 0 and r["records_setup"] == 0 and r["lvec_resid"] == 0
+    # tetrahedra with EXA_TET_ACTION=generic: route 2 for PA and route 3 for EA; fused otherwise
+    assert RT.query(L, RT.facts("tet", 1, 0, 0), {"EXA_TET_ACTION": "generic"})["action_route"] == 2
+    assert RT.query(L, RT.facts("tet", 1, 0, 1), {"EXA_TET_ACTION": "generic"})["action_route"] == 3
+    assert RT.query(L, RT.facts("tet", 1, 0, 0))["action_route"] == 1 and RT.query(L, RT.facts("tet", 2, 0, 1))["action_route"] == 1
+    # the Kocks-Mecking family runs the cap controller
+    r = RT.query(L, RT.facts(slip=2))
+    assert r["cap_auto"] == 1 and r["tail_cost_tenths"] == 15
+    # refused facts: a wrong count, tetrahedra with B-bar
+    f = (C.c_int * 10)(*RT.facts("tet", 1, 1, 0)); out = (C.c_int * 23)()
+    assert L.exa_operator_routes_query(f, 10, out, 23) == -1 and L.exa_operator_routes_query(f, 9, out, 23) == -1 and L.exa_operator_routes_query(f, 10, out, 22) == -1
+
+
+def test_retired_switches_change_no_route():
+    """EXA_UNFUSED_SETUP and EXA_TAIL_COST are no longer read: every row of the table stays what it is with both set"""
+    import exaconstit_amd.lib as L
+    RT = _route_table()
+    assert RT.table(L, extra={"EXA_UNFUSED_SETUP": "1", "EXA_TAIL_COST": "2.5"}) == RT.table(L)
+
+
+def test_routes_check_program(tmp_path):
+    """tests/routes_check.cpp - RouteSwitches::from_env over awkward values and the two cap choosers over empty, single-bin and saturated histograms -
+    builds and passes as a plain program (scripts/routes_sanitize.sh is the same program under the address and undefined-behaviour sanitizers)."""
+    import subprocess
+    exe = str(tmp_path / "routes_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "routes_check.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "0 wrong values" in r.stdout, r.stdout + r.stderr
