@@ -101,118 +101,21 @@ NonlinearMechOperator::NonlinearMechOperator(const ExaOptions& opt, const Partit
    if (part.periodic) SetupPeriodic();
 }
 
-// Periodic partition (Partition::make_periodic): the weights and the halo lists of the partition as it is now, the group table in the layout of
-// periodic_kernels.hip and, for several ranks, the two nodal arrays of the jump through the fluctuation (PeriodicJump)
+// Periodic partition (Partition::make_periodic): the weights and the halo lists of the partition as it is now, and the cell's tables
 void NonlinearMechOperator::SetupPeriodic() {
-   const Partition& part = part_;
-   weight.upload(part.weight);
-   comm_.setup_halo(part);
+   weight.upload(part_.weight);
+   comm_.setup_halo(part_);
    overlap_ = false;
-   const int n2 = part.grp_count[0], n4 = part.grp_count[1], n8 = part.grp_count[2];
-   std::vector<int32_t> idx(part.grp_nodes.size());
-   size_t base = 0; int g0 = 0;
-   for (int cls = 0; cls < 3; cls++) {   // CSR (group-major) -> member-major within each size class
-      const int m = 2 << cls, n = part.grp_count[cls];
-      for (int g = 0; g < n; g++) for (int j = 0; j < m; j++) idx[base + (size_t)j * n + g] = part.grp_nodes[(size_t)part.grp_off[g0 + g] + j];
-      base += (size_t)m * n; g0 += n;
-   }
-   per_idx_.release(); if (!idx.empty()) per_idx_.upload(idx);
-   per_tab_.idx = per_idx_.p; per_tab_.n2 = n2; per_tab_.n4 = n4; per_tab_.n8 = n8;
-   if (comm_.nranks > 1) {
-      std::vector<double> rw((size_t)nn_, 0.0); std::vector<uint8_t> surf((size_t)nn_, 0);
-      for (int g = 0; g < nn_; g++) { if (part.node_gid[g] == part.canon[g]) rw[g] = part.weight_node[g]; surf[g] = part.on_box_surface(g) ? 1 : 0; }
-      if (part.mixed) for (int g = 0; g < nn_; g++) if (part.is_corner(g)) { rw[g] = 0.0; surf[g] = 0; }   // (the corners take their velocity from the control values: UpdateVelocity)
-      per_repw_.upload(rw); per_surf_.upload(surf);
-      // the owner of a canonical id: its representative on the lowest rank that holds the id (ResidualAction)
-      std::vector<uint8_t> notown((size_t)nd_, 1), lower((size_t)nn_, 0);
-      for (const Neighbor& nb : part.nbrs) if (nb.rank < comm_.rank) for (int32_t d : nb.dofs) lower[(size_t)(d % nn_)] = 1;
-      std::vector<uint8_t> image((size_t)nn_, 0);      // local images other than the representative
-      for (size_t g = 0; g + 1 < part.grp_off.size(); g++) for (int32_t k = part.grp_off[g] + 1; k < part.grp_off[g + 1]; k++) image[(size_t)part.grp_nodes[k]] = 1;
-      for (int g = 0; g < nn_; g++) if (!lower[g] && !image[g]) for (int c = 0; c < 3; c++) notown[g + (size_t)nn_ * c] = 0;
-      per_notown_.upload(notown);
-   }
-   if (part.mixed) {
-      const uint32_t fb = mix_tab_.free_bits;
-      mix_tab_ = MixedTable(); mix_tab_.free_bits = fb;
-      mix_img_.release(); mix_code_.release(); mix_face_.release();
-      if (!part.img_nodes.empty()) { mix_img_.upload(part.img_nodes); mix_code_.upload(part.img_code); }
-      std::vector<int32_t> face;
-      for (int d = 0; d < 3; d++) {
-         face.insert(face.end(), part.face_nodes[d].begin(), part.face_nodes[d].end());
-         mix_tab_.foff[d + 1] = (int)face.size();
-         mix_tab_.fblk[d + 1] = mix_tab_.fblk[d] + (int)((part.face_nodes[d].size() + 255) / 256);
-      }
-      if (!face.empty()) mix_face_.upload(face);
-      mix_tab_.img = mix_img_.p; mix_tab_.code = mix_code_.p; mix_tab_.nimg = (int)part.img_nodes.size(); mix_tab_.face = mix_face_.p;
-      for (int k = 0; k < 4; k++) mix_tab_.ctrl[k] = part.ctrl_node[k];
-      if (mix_x_.n == 0) { mix_x_.alloc(nd_); mix_h_.alloc(12); mix_f_.alloc(9); mix_res_.alloc(9); mix_f_.zero(stream_); mix_res_.zero(stream_); }
-      mix_part_.release(); mix_part_.alloc((size_t)std::max(1, 3 * mix_tab_.fblk[3]));
-   }
+   if (!cell_) cell_.reset(new PeriodicCell(part_, comm_, stream_));
+   cell_->Build();
 }
 
 void NonlinearMechOperator::SumLVector(double* y, const double* flag, bool raw) {
    if (!part_.periodic) { comm_.halo_sum(y, stream_); return; }
-   const bool one = !comm_.active();
-   const bool mix = part_.mixed && raw;
-   if (mix) vk_face_resultants(mix_tab_, nn_, y, flag, mix_part_.p, stream_);
-   if (mix && one) { vk_periodic_sum_controls(per_tab_, mix_tab_, nn_, y, flag, mix_part_.p, mix_f_.p, stream_); return; }
-   if (mix) { vk_face_combine(mix_tab_, nn_, mix_part_.p, mix_f_.p, nullptr, flag, stream_); comm_.allreduce_sum(mix_f_.p, 9, stream_); }
-   vk_periodic_sum(per_tab_, nn_, y, flag, false, stream_);
-   if (!one) {
-      // the exchange carries the representative of a group: its local sum out, the other ranks' sums added to it, then back to its local images
-      comm_.halo_sum(y, stream_);
-      vk_periodic_sum(per_tab_, nn_, y, flag, true, stream_);
-   }
-   if (mix) vk_face_combine(mix_tab_, nn_, nullptr, mix_f_.p, y, flag, stream_);
-}
-
-// x -> P x.  One rank reads the control values from x itself; several ranks gather { x(c_0), H } where they hold them and add them up
-// (the first of the two small all-reduces of an action).
-const double* NonlinearMechOperator::MixedExpand(const double* x, const double* flag, bool constrained) {
-   // (the copy is not gated by the flag: a finished PCG never reads it)
-   EXA_HC(hipMemcpyAsync(mix_x_.p, x, sizeof(double) * nd_, hipMemcpyDeviceToDevice, stream_));
-   if (constrained) vk_mask_zero(nd_, ess_mask.p, mix_x_.p, stream_);
-   const double* h12 = nullptr;
-   if (comm_.nranks > 1) {
-      int32_t idx[12];
-      for (int c = 0; c < 3; c++) {
-         idx[c] = mix_tab_.ctrl[0] >= 0 ? mix_tab_.ctrl[0] + nn_ * c : -1;
-         for (int d = 0; d < 3; d++) idx[3 + 3 * c + d] = mix_tab_.ctrl[1 + d] >= 0 ? mix_tab_.ctrl[1 + d] + nn_ * c : -1;
-      }
-      vk_gather_slots(idx, 12, x, mix_h_.p, stream_);
-      comm_.allreduce_sum(mix_h_.p, 12, stream_);
-      h12 = mix_h_.p;
-   }
-   vk_periodic_expand(mix_tab_, nn_, x, h12, mix_x_.p, flag, constrained, stream_);
-   return mix_x_.p;
-}
-
-void NonlinearMechOperator::ExpandCorrection(double* c) {
-   const double* f = MixedExpand(c, nullptr, true);
-   EXA_HC(hipMemcpyAsync(c, f, sizeof(double) * nd_, hipMemcpyDeviceToDevice, stream_));
+   cell_->Sum(y, flag, raw);
 }
 
 void NonlinearMechOperator::UpdateEndCoords(const double* k) { vk_update_coords(nd_, x_beg.p, k, dt_, x_cur.p, stream_); }
-
-void NonlinearMechOperator::ReadResultants(double* f9_host) {
-   EXA_HC(hipMemcpyAsync(f9_host, mix_res_.p, 9 * sizeof(double), hipMemcpyDeviceToHost, stream_)); EXA_HC(hipStreamSynchronize(stream_));
-}
-
-void NonlinearMechOperator::CornerValues(const double* v, double* out12_host) {
-   int32_t idx[12];
-   for (int k = 0; k < 4; k++) for (int c = 0; c < 3; c++) idx[3 * k + c] = mix_tab_.ctrl[k] >= 0 ? mix_tab_.ctrl[k] + nn_ * c : -1;
-   vk_gather_slots(idx, 12, v, mix_h_.p, stream_);
-   comm_.allreduce_sum(mix_h_.p, 12, stream_);
-   EXA_HC(hipMemcpyAsync(out12_host, mix_h_.p, 12 * sizeof(double), hipMemcpyDeviceToHost, stream_)); EXA_HC(hipStreamSynchronize(stream_));
-}
-
-void NonlinearMechOperator::PeriodicJump(const double* L9, double* v) {
-   if (comm_.nranks == 1) { vk_periodic_jump(per_tab_, nn_, x_cur.p, L9, v, stream_); return; }
-   // several ranks: the images of a node sit on different ranks - the node that carries the canonical id hands its fluctuation v - L x to all of them
-   vk_periodic_fluct(nn_, per_repw_.p, x_cur.p, L9, v, tmp_l_.p, stream_);
-   SumLVector(tmp_l_.p, nullptr, false);
-   vk_periodic_unfluct(nn_, per_surf_.p, x_cur.p, L9, tmp_l_.p, v, stream_);
-}
 
 void NonlinearMechOperator::ensure_mat_grad() { if (matGrad.n == 0) { matGrad.alloc((size_t)exa_qf_size(ctx_, 36)); matGrad.zero(stream_); } }
 
@@ -311,12 +214,7 @@ void NonlinearMechOperator::ResidualAction(double* y) {
       abi_check(ctx_, exa_restrict_transpose_add(ctx_, el_y_.p, y, stream_), "exa_restrict_transpose_add");
    }
    SumLVector(y);
-   // Several ranks, periodic: three or more holders add their contributions in different orders, so their copies of a residual entry differ in
-   // the last bits of the element forces - which is far above the last bits of a residual near equilibrium, and a part of the right-hand side
-   // that differs between the copies of a dof is out of the PCG's reach (tight Krylov tolerances then stop at the cap).  Every holder takes the
-   // owner's bits: all other copies are zeroed and summed again - one non-zero term per dof, an exact sum.
-   if (part_.periodic && comm_.nranks > 1) { vk_mask_zero(nd_, per_notown_.p, y, stream_); SumLVector(y, nullptr, false); }
-   if (mixed()) EXA_HC(hipMemcpyAsync(mix_res_.p, mix_f_.p, 9 * sizeof(double), hipMemcpyDeviceToDevice, stream_));
+   if (cell_) { cell_->OwnerBits(y); cell_->KeepResultants(); }   // several ranks: one copy of every entry; mixed loading: the resultants of this residual
    vk_mask_zero(nd_, ess_mask.p, y, stream_);
 }
 
@@ -420,7 +318,7 @@ void NonlinearMechOperator::GradMult(const double* x, double* y, bool constraine
    // Mixed loading: the action sees P x.  The essential entries of the reduced vector are masked before the expansion (a corner image stays free in
    // every component that a free H_id reaches), so the action itself runs without an input mask.
    const bool mix = mixed();
-   if (mix) x = MixedExpand(x, done_flag, constrained);
+   if (mix) x = cell_->Expand(x, done_flag, constrained ? ess_mask.p : nullptr);
    const uint8_t* in_mask = constrained && !mix ? ess_mask.p : nullptr;
    if (routes_.lvec_grad) abi_check(ctx_, exa_grad_apply_lvec_gated(ctx_, x, y, in_mask, done_flag, stream_), "exa_grad_apply_lvec");
    else ElementAction(x, in_mask, y);
@@ -569,12 +467,10 @@ void SystemDriver::UpdateEssBdr(const BCEntry& bc) {
    for (int k = 0; k < 9; k++) vgrad_[k] = bc.vgrad[k];
    if (part.periodic) {   // the eight corners, all components, as velocity-gradient dofs: v = L (x - origin) pins the rigid translation
       for (int g = 0; g < nn; g++) {
-         const int l[3] = { g % part.nn[0], (g / part.nn[0]) % part.nn[1], g / (part.nn[0] * part.nn[1]) };
-         bool corner = true;
-         for (int d = 0; d < 3; d++) { const int gi = part.e0[d] * part.p + l[d]; corner = corner && (gi == 0 || gi == part.N[d] * part.p); }
+         const bool corner = part.is_corner(g);
          if (corner) for (int k = 0; k < 3; k++) { ess_host_[g + nn * k] = 1; vg[g + nn * k] = 1; }
          // mixed loading: the slot (c_d, i) holds the unknown H_id where it is free
-         if (corner && mixed_) for (int d = 0; d < 3; d++) if (g == part.ctrl_node[1 + d]) for (int k = 0; k < 3; k++) if (free_[3 * k + d]) ess_host_[g + nn * k] = 0;
+         if (corner && mix_.on) for (int d = 0; d < 3; d++) if (g == part.ctrl_node[1 + d]) for (int k = 0; k < 3; k++) if (mix_.free[3 * k + d]) ess_host_[g + nn * k] = 0;
       }
       have_vgrad_ = true;
    }
@@ -612,65 +508,38 @@ const double* SystemDriver::VgradOrigin() {
 void SystemDriver::UpdateVelocity(double* v) {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
+   const double* L = mix_.on ? mix_.L_eff : vgrad_;
    if (have_vel_) vk_mask_set(op.Height(), vel_mask_.p, ess_val_.p, v, s);
    if (have_vgrad_) {
       const double* org = VgradOrigin();
-      vk_vgrad_velocity(part.NN, vg_mask_.p, op.x_cur.p, org, mixed_ ? vgrad_eff_ : vgrad_, v, s);
+      vk_vgrad_velocity(part.NN, vg_mask_.p, op.x_cur.p, org, L, v, s);
    }
-   if (part.periodic) op.PeriodicJump(mixed_ ? vgrad_eff_ : vgrad_, v);
+   if (part.periodic) op.cell()->Jump(L, op.x_cur.p, v, xt_.p);
 }
-
-namespace {
-void inv3(const double* A, double* B) {
-   const double c0 = A[4] * A[8] - A[5] * A[7], c1 = A[5] * A[6] - A[3] * A[8], c2 = A[3] * A[7] - A[4] * A[6];
-   const double det = A[0] * c0 + A[1] * c1 + A[2] * c2;
-   B[0] = c0 / det; B[1] = (A[2] * A[7] - A[1] * A[8]) / det; B[2] = (A[1] * A[5] - A[2] * A[4]) / det;
-   B[3] = c1 / det; B[4] = (A[0] * A[8] - A[2] * A[6]) / det; B[5] = (A[2] * A[3] - A[0] * A[5]) / det;
-   B[6] = c2 / det; B[7] = (A[1] * A[6] - A[0] * A[7]) / det; B[8] = (A[0] * A[4] - A[1] * A[3]) / det;
-}
-void mul3(const double* A, const double* B, double* C) {
-   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-// A (column d = a_d) and H (column d = h_d) from the values of a field at c_0 .. c_3
-void corner_differences(const double* c12, double* M) { for (int d = 0; d < 3; d++) for (int i = 0; i < 3; i++) M[3 * i + d] = c12[3 * (d + 1) + i] - c12[i]; }
-}  // namespace
 
 void SystemDriver::set_free(const uint8_t* f) {
-   uint32_t bits = 0; mixed_ = false;
-   for (int k = 0; k < 9; k++) { free_[k] = f[k] ? 1 : 0; if (free_[k]) { bits |= 1u << k; mixed_ = true; } }
-   oper_->SetMixedFree(bits);
-   for (int k = 0; k < 9; k++) vgrad_eff_[k] = opt_.bcs.empty() ? 0.0 : opt_.bcs.front().vgrad[k];
+   oper_->cell()->set_free_bits(mix_.set_free(f, opt_.bcs.empty() ? nullptr : opt_.bcs.front().vgrad));
 }
 
+// Three stages: the corner values from the cell, the step algebra of host/mixed_loading.hpp, the launches that follow from it.
 void SystemDriver::MixedStepStart() {
    NonlinearMechOperator& op = *oper_;
    hipStream_t s = op.stream();
-   double cx[12], cv[12], A[9], Hp[9], H[9], Ai[9], LA[9];
-   op.CornerValues(op.x_cur.p, cx); op.CornerValues(v_sol.p, cv);
+   double cx[12], cv[12], A[9], Hp[9], H[9];
+   op.cell()->CornerValues(op.x_cur.p, cx); op.cell()->CornerValues(v_sol.p, cv);
    corner_differences(cx, A); corner_differences(cv, Hp);
-   for (int d = 0; d < 3; d++) {
-      const double len = std::sqrt(A[d] * A[d] + A[3 + d] * A[3 + d] + A[6 + d] * A[6 + d]);
-      for (int i = 0; i < 3; i++) if (!free_[3 * i + d]) for (int j = 0; j < 3; j++) if (free_[3 * i + j] && std::fabs(A[3 * j + d]) > 1e-12 * len) {
-         char m[320];
-         std::snprintf(m, sizeof(m), "periodic_free: entry (%d,%d) of the velocity gradient is free and entry (%d,%d) is prescribed, but period vector %d has the component %.3e "
-                       "along direction %d - the prescribed entry is no condition on one corner difference alone (DESIGN 4.12)", i + 1, j + 1, i + 1, d + 1, d + 1, A[3 * j + d], j + 1);
-         throw std::runtime_error(m);
-      }
-   }
-   mul3(vgrad_, A, LA);
-   const bool first = steps_done == 0 && !restarted_;
-   for (int k = 0; k < 9; k++) H[k] = (!free_[k] || first) ? LA[k] : Hp[k];
-   inv3(A, Ai);
-   mul3(H, Ai, vgrad_eff_);
-   if (mix_bc_changed_) {   // the affine part of the prescribed entries: v += (H - H_prev) A^-1 (x - origin)
-      double Lold[9], dL[9];
-      mul3(Hp, Ai, Lold);
-      for (int k = 0; k < 9; k++) dL[k] = vgrad_eff_[k] - Lold[k];
+   const std::string refusal = mixed_free_refusal(mix_.free, A);
+   if (!refusal.empty()) throw std::runtime_error(refusal);
+   mixed_choose_H(mix_.free, steps_done == 0 && !restarted_, vgrad_, A, Hp, H);
+   mixed_gradient(H, A, mix_.L_eff);
+   if (mix_.bc_changed) {   // the affine part of the prescribed entries: v += (H - H_prev) A^-1 (x - origin)
+      double dL[9];
+      mixed_bc_dL(mix_.L_eff, Hp, A, dL);
       const double* org = VgradOrigin();
       vk_periodic_affine_add(part.NN, op.x_cur.p, org, dL, v_sol.p, s);
-      mix_bc_changed_ = false;
+      mix_.bc_changed = false;
    }
-   for (int k = 0; k < 9; k++) mac_A_[k] = A[k];
+   for (int k = 0; k < 9; k++) mix_.A[k] = A[k];
    // c_0 relative to the origin of the velocity-gradient conditions (UpdateVelocity pins v(c_0) = L (x(c_0) - origin)): MixedStepEnd
    double org[3];
    if (opt_.vgrad_origin_flag) for (int k = 0; k < 3; k++) org[k] = opt_.vgrad_origin[k];
@@ -678,21 +547,19 @@ void SystemDriver::MixedStepStart() {
       const double* org_dev = VgradOrigin();
       EXA_HC(hipMemcpyAsync(org, org_dev, 3 * sizeof(double), hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
    }
-   for (int k = 0; k < 3; k++) mac_w0_[k] = cx[k] - org[k];
+   for (int k = 0; k < 3; k++) mix_.w0[k] = cx[k] - org[k];
 }
 
 void SystemDriver::MixedStepEnd() {
-   double cv[12], H[9], Ai[9];
-   oper_->CornerValues(v_sol.p, cv);
+   double cv[12], H[9], t[3];
+   oper_->cell()->CornerValues(v_sol.p, cv);
+   oper_->cell()->ReadResultants(mix_.F);
    corner_differences(cv, H);
-   inv3(mac_A_, Ai);
-   mul3(H, Ai, mac_L_);
-   oper_->ReadResultants(mac_F_);
-   mac_have_ = true;
+   mixed_gradient(H, mix_.A, mix_.L);
+   mix_.solved = true;
    // The step pinned c_0 at L (x(c_0) - origin) with the gradient it started from.  A rigid translation of the converged field (the residual does
    // not see it) moves the pin to the realised gradient: the run is then the one the fully prescribed route makes of that gradient, node by node.
-   double t[3];
-   for (int i = 0; i < 3; i++) { t[i] = 0.0; for (int j = 0; j < 3; j++) t[i] += (mac_L_[3 * i + j] - vgrad_eff_[3 * i + j]) * mac_w0_[j]; }
+   mixed_pin_translation(mix_.L, mix_.L_eff, mix_.w0, t);
    if (t[0] != 0.0 || t[1] != 0.0 || t[2] != 0.0) { vk_translate(part.NN, t, v_sol.p, oper_->stream()); oper_->UpdateEndCoords(v_sol.p); }
 }
 
@@ -708,7 +575,7 @@ void SystemDriver::PeriodicBCChange(const BCEntry& bc) {
    for (int k = 0; k < 9; k++) dL[k] = bc.vgrad[k] - (bc_index_ >= 0 ? vgrad_[k] : 0.0);
    bc_index_ = (int)(&bc - opt_.bcs.data());
    UpdateEssBdr(bc);
-   if (mixed_) { mix_bc_changed_ = true; return; }   // (MixedStepStart swaps the affine part of the prescribed entries)
+   if (mix_.on) { mix_.bc_changed = true; return; }   // (MixedStepStart swaps the affine part of the prescribed entries)
    const double* org = VgradOrigin();
    vk_periodic_affine_add(part.NN, op.x_cur.p, org, dL, v_sol.p, s);
 }
@@ -731,17 +598,15 @@ void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
    for (int k = 0; k < 9; k++) if (!std::isfinite(L9[k])) throw std::runtime_error("set_periodic: the velocity gradient must be finite");
    if (part.from_file || part.geom != 0) throw std::runtime_error(ExaOptions::periodic_needs_generated_mesh());
    if (oper_->precond == Precond::MULTIGRID) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
-   bool any = false;
-   if (free9) {
-      uint8_t f[9]; for (int k = 0; k < 9; k++) { f[k] = free9[k] ? 1 : 0; any = any || f[k]; }
-      if (const char* why = ExaOptions::periodic_free_refusal(f)) throw std::runtime_error(why);
-   }
+   uint8_t f[9];
+   const bool any = free_mask_bits(free9, f) != 0;
+   if (free9) if (const char* why = ExaOptions::periodic_free_refusal(f)) throw std::runtime_error(why);
    part.make_periodic(any);
    BCEntry e; e.step = 1; for (int k = 0; k < 9; k++) e.vgrad[k] = L9[k];
    opt_.bcs.assign(1, e); opt_.periodic = true; opt_.periodic_mixed = any;
-   for (int k = 0; k < 9; k++) opt_.periodic_free[k] = any && free9[k] ? 1 : 0;
-   set_free(opt_.periodic_free);
+   for (int k = 0; k < 9; k++) opt_.periodic_free[k] = f[k];
    oper_->SetupPeriodic();
+   set_free(opt_.periodic_free);   // (after the set-up: the bits live in the cell)
    krylov_->DropGraph();
 }
 
@@ -762,7 +627,7 @@ bool SystemDriver::NewtonSolve(double* x, SolverStats& st) {
       if (it >= opt_.newton_iter) { converged = false; break; }
       op.GetGradient();
       st.krylov_iters += krylov_->Solve(r_.p, c_.p);
-      if (mixed_) op.ExpandCorrection(c_.p);   // the correction of the reduced unknowns -> of the nodal velocities
+      if (mix_.on) op.cell()->ExpandCorrection(c_.p, op.ess_mask.p);   // the correction of the reduced unknowns -> of the nodal velocities
       if (opt_.nl_solver == NLSolver::NRLS) {
          const double q1 = norm;
          EXA_HC(hipMemcpyAsync(xt_.p, x, sizeof(double) * nd, hipMemcpyDeviceToDevice, s)); vk_axpby(nd, -1.0, c_.p, 1.0, xt_.p, s);
@@ -890,7 +755,7 @@ bool SystemDriver::Step(int ti, bool commit) {
       UpdateVelocity(v_sol.p);
       SolveInit(v_prev.p, v_sol.p);
    }
-   if (mixed_) MixedStepStart();
+   if (mix_.on) MixedStepStart();
    UpdateVelocity(v_sol.p);
    const bool ok = Solve(v_sol.p);
    EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1));
@@ -898,7 +763,7 @@ bool SystemDriver::Step(int ti, bool commit) {
    op.timers.t_solve_ms += ms;
    step_wall_s.push_back(std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count());
    if (!ok) return false;
-   if (mixed_) MixedStepEnd();
+   if (mix_.on) MixedStepEnd();
    step_solved_ = true;
    if (!commit) return true;   // the converged state stays the END-of-step state: the next constitutive pass repeats this step's last residual evaluation
    CommitStep();

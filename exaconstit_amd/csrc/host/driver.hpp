@@ -10,6 +10,7 @@
 //   SystemDriver                         reference src/system_driver.cpp:221-558
 //   Comm (host/comm.hpp)               MPI in the reference (src/mechanics_driver.cpp:312, src/system_driver.cpp:167, src/mechanics_kernels.hpp:119,124)
 //   OperatorRoutes (host/routes.hpp)     the operator's EXA_* switches and which kernels it runs for them (no counterpart in the reference)
+//   PeriodicCell (host/periodic.hpp)     periodic images, their sums and mixed loading on the device; MixedLoading (host/mixed_loading.hpp): its step algebra (no counterpart)
 //   StepAnalyses (host/analyses.hpp)     reference src/system_driver.cpp:560-870 (the Project* outputs) and what this project adds to them
 //   time-step loop                       reference src/mechanics_driver.cpp:837-907
 #pragma once
@@ -23,7 +24,9 @@
 #include "device_utils.hpp"
 #include "krylov.hpp"
 #include "mesh.hpp"
+#include "mixed_loading.hpp"
 #include "options.hpp"
+#include "periodic.hpp"
 #include "routes.hpp"
 
 namespace exa_host {
@@ -95,30 +98,18 @@ class NonlinearMechOperator {
    // ... of nc columns at once, ADDED into y, nch columns per pass over the records (0: the library's default); gates: one device flag per column
    // (nullable).  false: the context has no multi-column kernel (y untouched) and the caller goes column by column
    bool GradMultRawCols(int nch, int nc, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* in_mask, const double* const* gates);
-   uint32_t MixedFree() const { return mix_tab_.free_bits; }
    bool deterministic() const { return comm_.deterministic; }
    // reference src/mechanics_operator.cpp:446-483
    void GetUpdateBCsAction(const double* k, const double* x, double* y);
    void ResidualAction(double* y);
-   // The one place where an L-vector of element contributions becomes the assembled vector: the sum over the local periodic images (periodic
-   // partitions, DESIGN 4.11: one launch), then the sum over the ranks.  flag: the PCG's done flag (the periodic launch is a no-op once it is set).
-   // Mixed loading, raw = true (y holds raw element contributions): the nine face resultants are taken first and the free ones are
-   // written to their control slots after the sums; raw = false: the sums alone.
+   // The one place where an L-vector of element contributions becomes the assembled vector: the sum over the ranks, on a periodic partition the
+   // cell's sum over images and ranks (PeriodicCell::Sum, DESIGN 4.11 / 4.12, which explains flag and raw).
    void SumLVector(double* y, const double* flag = nullptr, bool raw = true);
    bool mixed() const { return part_.periodic && part_.mixed; }
-   void SetMixedFree(uint32_t free_bits) { mix_tab_.free_bits = free_bits; }
-   // full nodal field of the stored vector x in the scratch L-vector (mixed loading): masked first when constrained
-   const double* MixedExpand(const double* x, const double* flag, bool constrained);
-   void ExpandCorrection(double* c);         // the same in place: the PCG solution before Newton adds it to the velocity
    void UpdateEndCoords(const double* k);    // x_cur = x_beg + dt k, as the residual evaluation at k computes it
-   void ReadResultants(double* f9_host);     // face resultants of the last residual evaluation (all ranks' sum); waits for the stream
-   // values of an L-vector at the nodes c_0 .. c_3 (12 numbers, node by node), summed over the ranks; waits for the stream
-   void CornerValues(const double* v, double* out12_host);
-   // device tables, weights and halo lists of a partition that has (just) become periodic
+   // weights, halo lists and the cell of a partition that has (just) become periodic
    void SetupPeriodic();
-   // v(image) - v(representative) = L (x_cur(image) - x_cur(representative)) on every periodic group (UpdateVelocity)
-   void PeriodicJump(const double* L9, double* v);
-   const PeriodicTable& periodic_table() const { return per_tab_; }
+   PeriodicCell* cell() { return cell_.get(); }   // null on a partition that is not periodic
    void RefreshJacobians();                // el_jac of x_cur when the record route left it unwritten (volume averages)
    void UpdateModel();                     // swap begin/end state, x_beg <- x_cur
    void SwapCoords();
@@ -186,11 +177,7 @@ class NonlinearMechOperator {
    int newton_cap_ = 0, newton_cap2_ = 0;
    void ElementAction(const double* x, const uint8_t* in_mask, double* y);   // the generic E-vector action, added into y (in_mask nullable)
    DevBuf<double> tmp_l_, tmp_r_, el_y_, el_x2_;
-   // periodic partitions: the group table, and for several ranks 1 / holders on the node that carries the canonical id and the box-surface mask
-   DevBuf<int32_t> per_idx_; PeriodicTable per_tab_; DevBuf<double> per_repw_; DevBuf<uint8_t> per_surf_, per_notown_;
-   // mixed loading: tables, the scratch L-vector of the expanded input, block partials of the resultants, { v(c_0), H } of the input (several ranks),
-   // resultants of the last action / of the last residual
-   MixedTable mix_tab_; DevBuf<int32_t> mix_img_, mix_face_; DevBuf<uint8_t> mix_code_; DevBuf<double> mix_x_, mix_part_, mix_h_, mix_f_, mix_res_;
+   std::unique_ptr<PeriodicCell> cell_;
 };
 
 class SystemDriver {
@@ -220,17 +207,13 @@ class SystemDriver {
    // free9 (row by row, may be null: all prescribed): the entries of L that are unknowns, their mean tractions zero (mixed loading)
    void SetPeriodic(const double* L9, const uint8_t* free9 = nullptr);
    // (mixed loading: the realised gradient H A^-1 of the last solved step, once there is one)
-   const double* vgrad_in_force() const { return mixed_ && mac_have_ ? mac_L_ : (bc_index_ >= 0 ? vgrad_ : opt_.bcs.front().vgrad); }
+   const double* vgrad_in_force() const { return mix_.on && mix_.solved ? mix_.L : (bc_index_ >= 0 ? vgrad_ : opt_.bcs.front().vgrad); }
    // Mixed loading, start of a step: period vectors A and corner differences H from the fields, the run-time check that "prescribed L_id" is a
    // condition on H_id alone, the prescribed H_id = (L a_d)_i (step 1: all of them), the gradient L = H A^-1 that UpdateVelocity imposes; when the
    // options' L has just changed, the affine part of the velocity is swapped for the prescribed entries
    void MixedStepStart();
    void MixedStepEnd();   // realised gradient and face resultants of the converged step
-   bool mixed() const { return mixed_; }
-   bool mac_solved() const { return mac_have_; }
-   const uint8_t* mac_free() const { return free_; }
-   const double* mac_period() const { return mac_A_; }       // A, column d = a_d (row by row), of the start of the last step
-   const double* mac_resultants() const { return mac_F_; }   // F_id, row by row
+   const MixedLoading& mixed_loading() const { return mix_; }
    double last_newton_norm = 0.0, last_newton_bound = 0.0;   // final residual norm and max(rel |r0|, abs) of the last Newton solve
    PCGSolver& krylov() { return *krylov_; }   // the run's linear solver
    StepAnalyses& analyses() { return *analyses_; }   // the run's in-situ analyses (host/analyses.hpp) ...
@@ -280,9 +263,8 @@ class SystemDriver {
    double last_dt_ = 0.0, step_dt_ = 0.0;      // step_dt_: size of the step last solved: Time.Auto after any cut-back, otherwise the dt Step took (StepState::dt)
    // accepted dt of Time.Auto: rows that exist only in an append-mode file otherwise (checkpoint host section)
    std::vector<double> auto_dt_rows_;
-   bool mixed_ = false, mac_have_ = false, mix_bc_changed_ = false; uint8_t free_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-   double vgrad_eff_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_A_[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 }, mac_L_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_F_[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, mac_w0_[3] = { 0, 0, 0 };
-   void set_free(const uint8_t* f);
+   MixedLoading mix_;
+   void set_free(const uint8_t* f);             // the free mask into mix_ and the cell's free bits
    const double* VgradOrigin();                 // leaves the origin of the velocity-gradient conditions in the operator's scal[SCAL_ORIGIN]
    int bc_index_ = -1;                          // index in opt_.bcs of the essential-boundary entry in force
    bool synthetic_ = false, restarted_ = false;

@@ -292,8 +292,7 @@ int exa_driver_set_periodic(exa_driver* d, const double* vel_grad9, char* err, i
 // mixed loading: free9[3 i + d] != 0 makes entry (i, d) of the velocity gradient an unknown with zero mean traction; NULL or all zero = exa_driver_set_periodic
 int exa_driver_set_periodic_mixed(exa_driver* d, const double* vel_grad9, const int* free9, char* err, int errlen) {
    try {
-      uint8_t f[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-      if (free9) for (int k = 0; k < 9; k++) f[k] = free9[k] ? 1 : 0;
+      uint8_t f[9]; free_mask_bits(free9, f);
       d->sd->SetPeriodic(vel_grad9, f); return 0;
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
@@ -301,11 +300,11 @@ int exa_driver_set_periodic_mixed(exa_driver* d, const double* vel_grad9, const 
 // row; resultants9: F_id of the last converged residual, row by row.  Returns 1 when mixed loading is on (0: all outputs zero), -1 on error.
 int exa_driver_macro_info(exa_driver* d, int* free9, double* vel_grad9, double* period9, double* resultants9) {
    try {
-      const SystemDriver& sd = *d->sd;
+      const SystemDriver& sd = *d->sd; const MixedLoading& m = sd.mixed_loading();
       for (int k = 0; k < 9; k++) { free9[k] = 0; vel_grad9[k] = period9[k] = resultants9[k] = 0.0; }
-      if (!sd.mixed()) return 0;
-      for (int k = 0; k < 9; k++) { free9[k] = sd.mac_free()[k]; period9[k] = sd.mac_period()[k]; resultants9[k] = sd.mac_resultants()[k]; }
-      if (sd.mac_solved()) for (int k = 0; k < 9; k++) vel_grad9[k] = sd.vgrad_in_force()[k];
+      if (!m.on) return 0;
+      for (int k = 0; k < 9; k++) { free9[k] = m.free[k]; period9[k] = m.A[k]; resultants9[k] = m.F[k]; }
+      if (m.solved) for (int k = 0; k < 9; k++) vel_grad9[k] = sd.vgrad_in_force()[k];
       return 1;
    } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_macro_info: %s\n", e.what()); return -1; }
 }
@@ -351,7 +350,7 @@ int exa_driver_set_tangent_route(exa_driver* d, int nch, int auto_batched) {
 // host only: C_pp - C_pf C_ff^-1 C_fp of c81[9 (kl) + (mn)] for the free mask free9 (row by row); out81: the condensed tangent in the prescribed rows /
 // columns, zeros in the free ones.  Returns 0, or -1 when C_ff is singular.
 int exa_macro_tangent_condense(const double* c81, const int* free9, double* out81) {
-   uint8_t f[9]; for (int k = 0; k < 9; k++) f[k] = free9 && free9[k] ? 1 : 0;
+   uint8_t f[9]; free_mask_bits(free9, f);
    return macro_tangent_condense(c81, f, out81) ? 0 : -1;
 }
 

@@ -265,7 +265,7 @@ void PCGSolver::SolveColumns(int nc, const double* B, double* X, int64_t ld, int
       vk_cg_init(S, set.rel_tol, set.abs_tol, s);
    }
    // Z += K_uu D on the columns still running: one pass over the records per nch columns, then the periodic sum of every column (the control
-   // slots are essential in every solve of the tangent, so the masked direction is its own expansion: no MixedExpand); the output mask rides
+   // slots are essential in every solve of the tangent, so the masked direction is its own expansion: no PeriodicCell::Expand); the output mask rides
    // in the dot product that follows
    auto action = [&]() {
       if (!op.GradMultRawCols(nch, nc, D.p, nd, Z.p, nd, op.ess_mask.p, gates.data()))

@@ -37,15 +37,15 @@ int env_int(const char* k, int dflt) { const char* e = std::getenv(k); return e 
 // and captured chunk are never touched; the records, the Newton cap state, stats and the model timers are never written: no constitutive launch runs.
 struct SystemDriver::TangentScope {
    SystemDriver& sd; NonlinearMechOperator& op;
-   double scal[NonlinearMechOperator::SCAL_LEN]; uint32_t free_bits; bool mask_changed = false; bool closed = false;
+   double scal[NonlinearMechOperator::SCAL_LEN]; uint32_t free_bits = 0; bool mask_changed = false; bool closed = false;
    TangentScope(SystemDriver& d) : sd(d), op(*d.oper_) {
       op.scal.download(scal, NonlinearMechOperator::SCAL_LEN, op.stream());
-      free_bits = op.MixedFree();
-      if (sd.mixed_) {
+      if (sd.mix_.on) {
+         free_bits = op.cell()->free_bits();
          std::vector<uint8_t> m = sd.ess_host_;
          const int nn = sd.part.NN;
          for (int d3 = 0; d3 < 3; d3++) if (sd.part.ctrl_node[1 + d3] >= 0) for (int k = 0; k < 3; k++) m[(size_t)sd.part.ctrl_node[1 + d3] + (size_t)nn * k] = 1;
-         op.UpdateEssTDofs(m); op.SetMixedFree(0);
+         op.UpdateEssTDofs(m); op.cell()->set_free_bits(0);
          mask_changed = true;
       }
    }
@@ -55,7 +55,7 @@ struct SystemDriver::TangentScope {
       hipStream_t s = op.stream();
       (void)hipStreamSynchronize(s);
       if (mask_changed) {
-         op.UpdateEssTDofs(sd.ess_host_); op.SetMixedFree(free_bits);
+         op.UpdateEssTDofs(sd.ess_host_); op.cell()->set_free_bits(free_bits);
          op.GetGradient();   // (the inverse diagonal follows the mask: back to the run's)
       }
       op.scal.upload(scal, NonlinearMechOperator::SCAL_LEN, s);

@@ -550,3 +550,14 @@ def test_routes_check_program(tmp_path):
     subprocess.run(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "routes_check.cpp")], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "0 wrong values" in r.stdout, r.stdout + r.stderr
+
+
+def test_mixed_loading_check_program(tmp_path):
+    """tests/mixed_loading_check.cpp - the 3 x 3 helpers, the run-time check of the free mask with its threshold and text, the choice of H, H A^-1, the dL
+    of a changed boundary condition and the pin translation of host/mixed_loading.hpp - builds and passes as a plain program
+    (scripts/mixed_loading_sanitize.sh is the same program under the address and undefined-behaviour sanitizers)."""
+    import subprocess
+    exe = str(tmp_path / "mixed_loading_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-o", exe, os.path.join(ROOT, "tests", "mixed_loading_check.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "0 wrong values" in r.stdout, r.stdout + r.stderr
