@@ -227,6 +227,14 @@ class SystemDriver {
    // tangent's solves (periodic and rank sums, the run's essential set plus the control slots, input and output); otherwise the raw element action.
    // gated (nullable): columns with a non-zero entry are left out - their y stays as passed in.
    void GradApplyColumns(int nc, const double* x, double* y, bool assembled, bool batched, const int* gated);
+   // probe of the linear solver (exa_driver_pcg_solve): K_uu x_m = b_m for nc host columns of local dofs (byNODES), the operator and the scope of
+   // GradApplyColumns(assembled), in a PCGSolver of the probe's own built from the run's settings with rel_tol, abs_tol, max_iter, check_every
+   // (0: the run's) and graph (-1 the run's limit, 0 no replay, 1 replay at any size).  mode 0: Solve for each column in turn into one fixed device
+   // buffer (a later column replays the chunk the first one captured and starts from the record it left); mode 1: SolveColumns on all of them
+   // (tangent_nch columns per pass).  Per column: x, iterations, flag, the solver's reduction, indefinite iterations, sc[2 m] = (r0, z0) and
+   // sc[2 m + 1] = the last (r, z).  Every rank calls it.  Leaves the run as it found it.
+   void PcgSolveProbe(int nc, const double* b, double rel_tol, double abs_tol, int max_iter, int check_every, int graph, int mode, double* x, int* iters, int* flag,
+                      double* reduction, int* indefinite, double* sc);
    int tangent_nch = 0;                 // columns per pass of the multi-column action (0: the library's default; EXA_TANGENT_NCH)
    bool tangent_auto_batched = true;    // what batched = -1 picks where the batched route is available (EXA_TANGENT_BATCHED=0 | 1)
    std::vector<double> macro_tangent_rows;   // Visualizations.macro_tangent: MACRO_TANGENT_ROW values per written evaluation

@@ -340,6 +340,21 @@ int exa_driver_grad_apply_columns(exa_driver* d, int ncols, const double* x, dou
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+// Probe of the linear solver, next to the one of its operator: K_uu x_m = b_m from x = 0 for nrhs <= 16 host columns of local dofs (byNODES, column m at
+// m * local dofs), K_uu the assembled and masked operator of exa_driver_grad_apply_columns (flags bit 0), in a PCG solver of the probe's own: the run's
+// settings with rel_tol, abs_tol, max_iter, check_every (0: the run's) and graph (-1: replay as the run decides, 0: never, 1: at any size).  mode 0:
+// the single-system solve for each column in turn, into one fixed device buffer by one solver object; mode 1: all columns in lockstep (the columns per
+// pass of exa_driver_set_tangent_route).  Per column: x, iterations, flag (1 converged, 2 max_iter, -1 breakdown), the solver's own reduction
+// sqrt((r, z) / (r0, z0)), iterations that saw (Ad, d) < 0, scalars2[2 m] = (r0, z0) and scalars2[2 m + 1] = the last (r, z).  Needs a solved step;
+// every rank calls it.  The run's solver, captured chunk, diagnostics and totals are not touched.  Returns 0 or -1 (err).
+int exa_driver_pcg_solve(exa_driver* d, int nrhs, const double* b, double rel_tol, double abs_tol, int max_iter, int check_every, int graph, int mode, double* x, int* iters,
+                         int* flags, double* reduction, int* indefinite, double* scalars2, char* err, int errlen) {
+   try {
+      d->sd->PcgSolveProbe(nrhs, b, rel_tol, abs_tol, max_iter, check_every, graph, mode, x, iters, flags, reduction, indefinite, scalars2);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+
 // columns per pass of the batched route (1 .. 3; 0: the library's default) and what the automatic route picks where both exist (batched != 0)
 int exa_driver_set_tangent_route(exa_driver* d, int nch, int auto_batched) {
    if (nch < 0 || nch > 3) return -1;

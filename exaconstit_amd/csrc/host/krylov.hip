@@ -9,6 +9,8 @@
 
 namespace exa_host {
 
+static_assert(sizeof(PCGSolver::last) / sizeof(PCGSolver::Last) == EXA_GRAD_COLS_MAX, "one entry per column of the lockstep solve");
+
 PCGSolver::PCGSolver(NonlinearMechOperator& op, const Settings& set_) : set(set_), op_(op), comm_(op.comm()) {
    const size_t nd = (size_t)op.Height();
    r_.alloc(nd); z_.alloc(nd); d_.alloc(nd);
@@ -46,6 +48,7 @@ void PCGSolver::Finish(Frame& f, const Outcome* o, int n) {
    for (int m = 0; m < n; m++) {
       const bool converged = o[m].flag == (int)pcg::CONVERGED;
       krylov_iters += o[m].iters;
+      last[m] = Last{ o[m].iters, o[m].flag, o[m].indefinite, o[m].r0z0, o[m].betanom };
       diag.last_flag = o[m].flag; diag.indefinite_iters += o[m].indefinite;
       if (!converged) diag.not_converged++;
       diag.last_reduction = o[m].reduction();

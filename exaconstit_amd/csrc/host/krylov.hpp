@@ -43,6 +43,10 @@ class PCGSolver {
 
    Settings set;
    Diagnostics diag;
+   // what the last solve left per column (a single solve: column 0): iterations, flag, iterations that saw (Ad, d) < 0, (r0, z0) and the last (r, z)
+   // as the read-back of the device record gave them (multigrid: as the host loop had them)
+   struct Last { int iters = 0, flag = 0, indefinite = 0; double r0z0 = 0.0, rz = 0.0; };
+   Last last[16];   // EXA_GRAD_COLS_MAX columns
    double krylov_ms = 0.0; int64_t krylov_iters = 0;   // totals over all solves since ResetTotals
    void ResetTotals() { krylov_ms = 0.0; krylov_iters = 0; }
 

@@ -176,6 +176,46 @@ void SystemDriver::GradApplyColumns(int nc, const double* x, double* y, bool ass
    scope.close();
 }
 
+void SystemDriver::PcgSolveProbe(int nc, const double* b, double rel_tol, double abs_tol, int max_iter, int check_every, int graph, int mode, double* x, int* iters, int* flag,
+                                 double* reduction, int* indefinite, double* sc) {
+   if (nc < 1 || nc > EXA_GRAD_COLS_MAX) throw std::runtime_error("pcg_solve: between 1 and 16 columns");
+   if (!step_solved_) throw std::runtime_error("pcg_solve: no solved step - the operator is that of the converged iterate of the last step");
+   if (mode != 0 && mode != 1) throw std::runtime_error("pcg_solve: mode 0 (Solve, column by column) or 1 (SolveColumns)");
+   if (graph < -1 || graph > 1) throw std::runtime_error("pcg_solve: graph -1 (as the run), 0 (off) or 1 (on)");
+   if (max_iter < 0 || check_every < 0 || !(rel_tol >= 0.0) || !(abs_tol >= 0.0)) throw std::runtime_error("pcg_solve: tolerances, max_iter and check_every must not be negative");
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   const int64_t nd = op.Height();
+   const int nch = tangent_nch > 0 ? tangent_nch : env_int("EXA_TANGENT_NCH", 0);
+   TangentScope scope(*this);
+   op.GetGradient();
+   PCGSolver::Settings ks = krylov_->set;
+   ks.rel_tol = rel_tol; ks.abs_tol = abs_tol; ks.max_iter = max_iter;
+   if (check_every > 0) ks.check_every = check_every;
+   if (graph == 0) ks.graph_max_dofs = 0; else if (graph == 1) ks.graph_max_dofs = INT64_MAX;
+   PCGSolver pcg(op, ks);
+   DevBuf<double> B((size_t)nc * nd), X((size_t)nc * nd);
+   B.upload(b, (size_t)nc * nd, s);
+   DevBuf<double> tmp((size_t)nd);   // mode 0: one fixed solution buffer, as the tangent's column-by-column route has it
+   if (mode == 1) {
+      std::vector<int> it(nc), fl(nc); std::vector<double> red(nc);
+      pcg.SolveColumns(nc, B.p, X.p, nd, nch, it.data(), red.data(), fl.data());
+      for (int m = 0; m < nc; m++) {
+         const PCGSolver::Last& l = pcg.last[m];
+         iters[m] = it[m]; flag[m] = fl[m]; reduction[m] = red[m]; indefinite[m] = l.indefinite; sc[2 * m] = l.r0z0; sc[2 * m + 1] = l.rz;
+      }
+   } else {
+      for (int m = 0; m < nc; m++) {
+         iters[m] = pcg.Solve(B.p + (size_t)m * nd, tmp.p);
+         const PCGSolver::Last& l = pcg.last[0];
+         flag[m] = pcg.diag.last_flag; reduction[m] = pcg.diag.last_reduction; indefinite[m] = l.indefinite; sc[2 * m] = l.r0z0; sc[2 * m + 1] = l.rz;
+         EXA_HC(hipMemcpyAsync(X.p + (size_t)m * nd, tmp.p, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
+      }
+   }
+   X.download(x, (size_t)nc * nd, s);
+   scope.close();
+}
+
 void SystemDriver::WriteMacroTangent(int step) {
    MacroTangentResult r;
    MacroTangent(opt_.macro_tangent_rel_tol, opt_.macro_tangent_max_iter, -1, r);

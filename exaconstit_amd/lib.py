@@ -556,6 +556,8 @@ exa_partition_query_periodic_mixed = _sig("exa_partition_query_periodic_mixed", 
 
 exa_driver_macro_tangent = _sig("exa_driver_macro_tangent", C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int), C.c_char_p, C.c_int)
 exa_driver_grad_apply_columns = _sig("exa_driver_grad_apply_columns", C.c_int, C.c_void_p, C.c_int, _dp, _dp, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_char_p, C.c_int)
+exa_driver_pcg_solve = _sig("exa_driver_pcg_solve", C.c_int, C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int),
+                            C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp, C.c_char_p, C.c_int)
 exa_driver_set_tangent_route = _sig("exa_driver_set_tangent_route", C.c_int, C.c_void_p, C.c_int, C.c_int)
 exa_macro_tangent_condense = _sig("exa_macro_tangent_condense", C.c_int, _dp, C.POINTER(C.c_int), _dp)
 exa_options_macro_tangent = _sig("exa_options_macro_tangent", C.c_int, C.c_char_p, C.POINTER(C.c_int), _dp, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
@@ -1253,6 +1255,25 @@ class Driver:
         self._chk(exa_driver_grad_apply_columns(self.h, x.shape[0], x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), (1 if assembled else 0) | (2 if batched else 0), g, int(nch),
                                                 self._err, 512))
         return y
+
+    def pcg_solve(self, b, rel_tol, abs_tol, max_iter, check_every=0, graph=None, columns=False):
+        """Probe of the linear solver: K_uu x_m = b_m from x = 0 for b (nrhs, local dofs), K_uu the operator of grad_apply_columns(assembled=True), in a
+        PCG solver of the probe's own (the run's settings with these tolerances and this cap); every rank calls it.  check_every 0: the run's chunk
+        length; graph None: replay as the run decides, False / True: never / at any size.  columns False: the single-system solve for each column in
+        turn, by one solver object into one device buffer; True: all columns in lockstep (columns per pass: set_tangent_route).
+        dict(x (nrhs, local dofs), iters, flags (1 converged, 2 max_iter, -1 breakdown), reduction the solver's own, indefinite, r0z0, rz the last (r, z))"""
+        import numpy as np
+        b = np.ascontiguousarray(np.atleast_2d(b), dtype=np.float64)
+        if b.shape[1] != exa_driver_local_dofs(self.h) or not 1 <= b.shape[0] <= 16:
+            raise RuntimeError("pcg_solve: b holds 1 to 16 columns of %d local dofs" % exa_driver_local_dofs(self.h))
+        n = b.shape[0]
+        x, red, sc = np.zeros_like(b), np.zeros(n), np.zeros((n, 2))
+        it, fl, ind = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        ip = C.POINTER(C.c_int)
+        self._chk(exa_driver_pcg_solve(self.h, n, b.ctypes.data_as(_dp), float(rel_tol), float(abs_tol), int(max_iter), int(check_every), -1 if graph is None else int(bool(graph)),
+                                       int(bool(columns)), x.ctypes.data_as(_dp), it.ctypes.data_as(ip), fl.ctypes.data_as(ip), red.ctypes.data_as(_dp), ind.ctypes.data_as(ip),
+                                       sc.ctypes.data_as(_dp), self._err, 512))
+        return dict(x=x, iters=it.astype(int), flags=fl.astype(int), reduction=red, indefinite=ind.astype(int), r0z0=sc[:, 0].copy(), rz=sc[:, 1].copy())
 
     def set_tangent_route(self, nch=0, auto_batched=True):
         assert exa_driver_set_tangent_route(self.h, int(nch), int(bool(auto_batched))) == 0

@@ -244,6 +244,15 @@ int exa_driver_macro_tangent(exa_driver* d, double rel_tol, int max_iter, int ba
  * be NULL): columns with a non-zero entry are left out and keep the y passed in.  nch: 1 .. 3 columns per pass of the batched route from now on
  * (0: unchanged).  Needs a solved step. */
 int exa_driver_grad_apply_columns(exa_driver* d, int ncols, const double* x, double* y, int flags, const int* gated, int nch, char* err, int errlen);
+/* Probe of the linear solver next to the one of its operator: K_uu x_m = b_m from x = 0 for nrhs <= 16 host columns of local dofs (byNODES, column m at
+ * m * local dofs), K_uu the assembled, masked operator of exa_driver_grad_apply_columns (flags bit 0), in a PCG solver of the probe's own: the run's
+ * settings with rel_tol, abs_tol, max_iter, check_every (0: the run's) and graph (-1: replay of captured chunks as the run decides, 0: never, 1: at any
+ * size).  mode 0: the single-system solve for each column in turn, into one fixed device buffer by one solver object; mode 1: all columns in lockstep
+ * (columns per pass: exa_driver_set_tangent_route).  Per column: x, iterations, flag (1 converged, 2 max_iter, -1 breakdown), the solver's own
+ * reduction sqrt((r, z) / (r0, z0)), iterations that saw (Ad, d) < 0, scalars2[2 m] = (r0, z0), scalars2[2 m + 1] = the last (r, z).  Needs a solved
+ * step; every rank calls it.  The run's solver, captured chunk, diagnostics and totals are not touched. */
+int exa_driver_pcg_solve(exa_driver* d, int nrhs, const double* b, double rel_tol, double abs_tol, int max_iter, int check_every, int graph, int mode, double* x, int* iters,
+                         int* flags, double* reduction, int* indefinite, double* scalars2, char* err, int errlen);
 /* columns per pass of the batched route (1 .. 3, 0: the default) and whether the automatic route takes it where it exists */
 int exa_driver_set_tangent_route(exa_driver* d, int nch, int auto_batched);
 /* host only: the condensed tangent of the prescribed entries, C_pp - C_pf C_ff^-1 C_fp, of the 9 x 9 c81[9 (kl) + (mn)] for the free mask of a mixed
