@@ -584,7 +584,7 @@ void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
    if (kind < 0 || kind > 2) throw std::runtime_error("preconditioner kind must be 0 (identity), 1 (jacobi) or 2 (multigrid)");
    NonlinearMechOperator& op = *oper_;
    if (kind == 2) {
-      if (part.periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
+      if (part.periodic && !opt_.mg_periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
       if (ExaOptions::lower(opt_.integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
       op.mg.reset(new Multigrid(op, levels, degree));   // throws where no hierarchy can be built
    } else op.mg.reset();
@@ -597,7 +597,7 @@ void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
    if (!L9) throw std::runtime_error("set_periodic: a 3 x 3 velocity gradient is required");
    for (int k = 0; k < 9; k++) if (!std::isfinite(L9[k])) throw std::runtime_error("set_periodic: the velocity gradient must be finite");
    if (part.from_file || part.geom != 0) throw std::runtime_error(ExaOptions::periodic_needs_generated_mesh());
-   if (oper_->precond == Precond::MULTIGRID) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
+   if (oper_->precond == Precond::MULTIGRID && !opt_.mg_periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
    uint8_t f[9];
    const bool any = free_mask_bits(free9, f) != 0;
    if (free9) if (const char* why = ExaOptions::periodic_free_refusal(f)) throw std::runtime_error(why);
@@ -607,6 +607,8 @@ void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
    for (int k = 0; k < 9; k++) opt_.periodic_free[k] = f[k];
    oper_->SetupPeriodic();
    set_free(opt_.periodic_free);   // (after the set-up: the bits live in the cell)
+   // a hierarchy made for the prescribed-face cell took its weights and its sums from the partition as it was: make it again
+   if (oper_->mg) oper_->mg.reset(new Multigrid(*oper_, oper_->mg->levels_cap(), oper_->mg->degree()));
    krylov_->DropGraph();
 }
 

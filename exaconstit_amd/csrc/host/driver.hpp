@@ -201,9 +201,12 @@ class SystemDriver {
    // preconditioner of the PCG (set before the first step; takes effect at the next gradient set-up): kind 0 identity, 1 Jacobi, 2 multigrid with at most `levels` coarse levels (0: as
    // many as the mesh allows) and a Chebyshev smoother of `degree`; refuses multigrid where no hierarchy can be built
    void SetPreconditioner(int kind, int levels, int degree);
+   // multigrid on a periodic cell is opt-in (Solvers.Krylov.mg_periodic; DESIGN 4.6, "periodic cells"): without it SetPreconditioner and SetPeriodic
+   // refuse the combination with the options reader's message, as they always did
+   void AllowPeriodicMultigrid(bool on) { opt_.mg_periodic = on; }
    // periodic boundary conditions under the macroscopic velocity gradient L9 (row by row) on a freshly created driver before its first step,
    // like SetPreconditioner: rebuilds the partition tables, weights, essential set and halo lists (every rank calls it).  Refuses file meshes
-   // and the multigrid preconditioner with the messages of the options reader.  The boundary-condition schedule becomes one entry: L from step 1.
+   // and, without AllowPeriodicMultigrid, the multigrid preconditioner with the messages of the options reader; a hierarchy that exists is made again.  The boundary-condition schedule becomes one entry: L from step 1.
    // free9 (row by row, may be null: all prescribed): the entries of L that are unknowns, their mean tractions zero (mixed loading)
    void SetPeriodic(const double* L9, const uint8_t* free9 = nullptr);
    // (mixed loading: the realised gradient H A^-1 of the last solved step, once there is one)

@@ -413,6 +413,9 @@ int exa_driver_get_nodal(exa_driver* d, int which, double* out, char* err, int e
 // out2 = { residual norm the last Newton solve ended with, its bound max(rel |r0|, abs) }
 int exa_driver_newton_info(exa_driver* d, double* out2) { out2[0] = d->sd->last_newton_norm; out2[1] = d->sd->last_newton_bound; return 0; }
 
+// multigrid on a periodic cell is opt-in (Solvers.Krylov.mg_periodic): on != 0 lets exa_driver_set_preconditioner(2) and exa_driver_set_periodic meet
+int exa_driver_set_mg_periodic(exa_driver* d, int on) { d->sd->AllowPeriodicMultigrid(on != 0); return 0; }
+
 int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen) {
    try { d->sd->SetPreconditioner(kind, levels, degree); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
@@ -430,8 +433,9 @@ void check_level(Multigrid& mg, int l, bool transfer) {
 }
 extern "C" {
 
-// out (>= 4 + 4 (levels + 1) doubles): { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree,
-// then per level l = 0 ... L: local elements per direction (3), lmax estimate of D^-1 A_l (0 before the first set-up) }
+// out (>= 6 + 4 (levels + 1) doubles): { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree,
+// then per level l = 0 ... L: local elements per direction (3), lmax estimate of D^-1 A_l (0 before the first set-up),
+// then: 1 on a periodic cell, free control entries in the control block of mixed loading (0 before the first set-up) }
 int exa_driver_mg_info(exa_driver* d, double* out) {
    try {
       Multigrid& mg = mg_of(d);
@@ -440,6 +444,7 @@ int exa_driver_mg_info(exa_driver* d, double* out) {
          for (int k = 0; k < 3; k++) out[4 + 4 * l + k] = mg.grid(l).n[k] - 1;
          out[4 + 4 * l + 3] = mg.lmax(l);
       }
+      out[4 + 4 * (mg.levels() + 1)] = mg.periodic() ? 1.0 : 0.0; out[5 + 4 * (mg.levels() + 1)] = mg.control_dofs();
       return 0;
    } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_info: %s\n", e.what()); return -1; }
 }

@@ -7,8 +7,9 @@
 
 namespace exa_host {
 
-Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op_(op), degree_(degree) {
+Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op_(op), degree_(degree), levels_cap_(levels_cap) {
    const Partition& part = op.part();
+   periodic_ = part.periodic; mixed_ = part.periodic && part.mixed; fused_ = part.periodic && !op.comm().active();
    if (part.from_file || part.p != 1) throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\") at p_refinement = 1");
    if (degree < 1 || degree > 8) throw std::runtime_error("Solvers.Krylov.mg_smoother_degree must lie in 1 ... 8");
    if (levels_cap < 0) throw std::runtime_error("Solvers.Krylov.mg_levels must be >= 0 (0: as many as the mesh allows)");
@@ -37,6 +38,7 @@ Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op
    }
    if ((int64_t)lv_[0].nn != part.NN) throw std::runtime_error("multigrid: the partition is not a structured p = 1 box");
    fine_tmp_.alloc(lv_[0].nd); partial_.alloc(DOT_BLOCKS * 4); scal_.alloc(4);
+   if (mixed_) { mask0_.alloc(lv_[0].nd); ctrl_slot_.alloc(8); ctrl_dinv_.alloc(8); }
    EXA_HC(hipEventCreate(&ev0_)); EXA_HC(hipEventCreate(&ev1_));
 }
 
@@ -48,8 +50,19 @@ Multigrid::~Multigrid() {
 // coarse halo sum on the fine exchange plan: the level-l nodes are level-0 nodes, and the fine neighbour lists hold every shared one
 void Multigrid::halo(int l, double* y) {
    Comm& comm = op_.comm();
-   if (!comm.active()) return;
    hipStream_t s = op_.stream();
+   if (periodic_) {
+      // Periodic partition: the sum over the local images, the ranks and back to the images is the cell's (PeriodicCell::Sum through SumLVector,
+      // raw = false: no resultants).  On one rank this detour through a zeroed fine vector serves the build only (the diagonals): the V-cycle
+      // runs the fused kernels and never comes here, so it is not hot.  On several ranks it is today's cost model of every coarse sum.
+      if (l == 0) { op_.SumLVector(y, nullptr, false); return; }
+      fine_tmp_.zero(s);
+      mg_to_fine(lv_[0].g, lv_[l].g, lv_[l].stride, y, fine_tmp_.p, s);
+      op_.SumLVector(fine_tmp_.p, nullptr, false);
+      mg_from_fine(lv_[0].g, lv_[l].g, lv_[l].stride, fine_tmp_.p, y, s);
+      return;
+   }
+   if (!comm.active()) return;
    if (l == 0) { comm.halo_sum(y, s); return; }
    fine_tmp_.zero(s);
    mg_to_fine(lv_[0].g, lv_[l].g, lv_[l].stride, y, fine_tmp_.p, s);
@@ -58,14 +71,47 @@ void Multigrid::halo(int l, double* y) {
 }
 
 void Multigrid::ALocal(int l, const double* x, double* y) {
-   if (l == 0) op_.GradMultLocal(x, y);
-   else mg_stencil_apply(lv_[l].g, lv_[l].S.p, x, y, op_.stream());
+   if (l == 0 && mixed_) { op_.GradMultRaw(x, y, mask0_.p); vk_mask_zero(lv_[0].nd, mask0_.p, y, op_.stream()); }
+   else if (l == 0) op_.GradMultLocal(x, y);
+   else mg_stencil_apply(lv_[l].g, lv_[l].S.p, x, y, op_.stream());   // (periodic cells too: the probes act on the operator of distinct nodes)
 }
 
 void Multigrid::A(int l, const double* x, double* y) {
+   if (l == 0 && mixed_) {
+      // Fluctuation block M0 K M0 of a mixed partition: with every control slot masked the masked vector is its own expansion, so
+      // the raw action on M0 x followed by the plain sums is NonlinearMechOperator::GradMult(M0 x) without its expansion and resultant launches
+      op_.GradMultRaw(x, y, mask0_.p); op_.SumLVector(y, nullptr, false); vk_mask_zero(lv_[0].nd, mask0_.p, y, op_.stream());
+      return;
+   }
    if (l == 0) { op_.GradMult(x, y, true); return; }
+   if (fused_) { mg_stencil_apply_periodic(lv_[l].g, lv_[l].S.p, x, y, op_.stream()); return; }
    mg_stencil_apply(lv_[l].g, lv_[l].S.p, x, y, op_.stream());
    halo(l, y);
+}
+
+// Mixed loading: the level-0 mask of the fluctuation block, and d = the diagonal entry of the reduced operator on every free
+// control slot, read off one constrained action on its unit vector (at most 8 actions per build; the rank that holds the slot keeps 1 / d).
+void Multigrid::BuildControlBlock() {
+   hipStream_t s = op_.stream();
+   const Partition& part = op_.part();
+   Level& f = lv_[0];
+   const uint32_t bits = op_.cell()->free_bits();
+   EXA_HC(hipMemcpyAsync(mask0_.p, op_.ess_mask.p, f.nd, hipMemcpyDeviceToDevice, s));
+   int32_t slot[8]; double dinv[8]; ctrl_local_ = 0; control_dofs_ = 0;
+   for (int i = 0; i < 3; i++) for (int d = 0; d < 3; d++) {
+      if (!(bits >> (3 * i + d) & 1u) || control_dofs_ == 8) continue;
+      control_dofs_++;
+      const int64_t at = part.ctrl_node[1 + d] >= 0 ? part.ctrl_node[1 + d] + f.nn * i : -1;   // (-1: another rank's)
+      f.t.zero(s);
+      const double one = 1.0; double dd = 0.0;
+      if (at >= 0) EXA_HC(hipMemcpyAsync(f.t.p + at, &one, sizeof(double), hipMemcpyHostToDevice, s));
+      op_.GradMult(f.t.p, f.u.p, true);
+      if (at < 0) continue;
+      EXA_HC(hipMemcpyAsync(&dd, f.u.p + at, sizeof(double), hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
+      slot[ctrl_local_] = (int32_t)at; dinv[ctrl_local_] = dd > 0.0 ? 1.0 / dd : 0.0; ctrl_at_[ctrl_local_] = at; ctrl_d_[ctrl_local_] = dd; ctrl_local_++;
+      EXA_HC(hipMemsetAsync(mask0_.p + at, 1, 1, s));
+   }
+   if (ctrl_local_ > 0) { ctrl_slot_.upload(slot, ctrl_local_, s); ctrl_dinv_.upload(dinv, ctrl_local_, s); EXA_HC(hipStreamSynchronize(s)); }
 }
 
 double Multigrid::dot(int l, const double* a, const double* b) {
@@ -82,6 +128,7 @@ void Multigrid::Build() {
    hipStream_t s = op_.stream();
    const int L = levels();
    lv_[0].mask = op_.ess_mask.p; lv_[0].wp = op_.weight.p;
+   if (mixed_) { BuildControlBlock(); lv_[0].mask = mask0_.p; }
    for (int l = 1; l <= L; l++) mg_mask_coarsen(lv_[l - 1].g, lv_[l].g, lv_[l - 1].mask, lv_[l].mask_own.p, s);
    // fine diagonal: the fine operator couples nodes at most one apart, so probes of the 8 colours mod 2 (per component) read it off
    {
@@ -90,7 +137,7 @@ void Multigrid::Build() {
       for (int colour = 0; colour < 8; colour++)
          for (int c = 0; c < 3; c++) {
             mg_probe(f.g, 2, colour, c, f.mask, f.t.p, s);
-            op_.GradMult(f.t.p, f.u.p, true);
+            A(0, f.t.p, f.u.p);
             mg_diag_probe(f.g, 2, colour, c, f.u.p, f.diag.p, s);
          }
    }
@@ -114,7 +161,7 @@ void Multigrid::Build() {
       Level& v = lv_[l];
       mg_dinv(v.nd, v.mask, v.diag.p, v.dinv.p, s);
       int ng[3]; for (int d = 0; d < 3; d++) ng[d] = (ng_[d] >> l) + 1;
-      mg_seed(v.g, ng, v.mask, v.v.p, s);
+      mg_seed(v.g, ng, periodic_, v.mask, v.v.p, s);
       double lam = 0.0;
       for (int it = 0; it < MG_POWER_ITERS; it++) {
          const double nrm = std::sqrt(dot(l, v.v.p, v.v.p));
@@ -172,6 +219,7 @@ void Multigrid::Apply(const double* b, double* x) {
    hipStream_t s = op_.stream();
    EXA_HC(hipEventRecord(ev0_, s));
    vcycle(0, b, x);
+   if (mixed_) mg_control_block(ctrl_local_, ctrl_slot_.p, ctrl_dinv_.p, b, x, s);   // block-diagonal: z = r / d on the free control slots
    EXA_HC(hipEventRecord(ev1_, s));
    ev_pending_ = true;
 }
@@ -193,6 +241,11 @@ void Multigrid::LevelDiag(int l, double* out) {
    if (l < 0 || l > levels()) throw std::runtime_error("multigrid: no level " + std::to_string(l));
    if (!built_) throw std::runtime_error("multigrid: the hierarchy has not been built (no gradient set-up yet)");
    EXA_HC(hipMemcpyAsync(out, lv_[l].diag.p, sizeof(double) * lv_[l].nd, hipMemcpyDeviceToDevice, op_.stream()));
+   // mixed loading: the diagonal of the control block on this rank's free control slots (the fluctuation block has zeros there)
+   if (l == 0 && mixed_) {
+      for (int k = 0; k < ctrl_local_; k++) EXA_HC(hipMemcpyAsync(out + ctrl_at_[k], &ctrl_d_[k], sizeof(double), hipMemcpyHostToDevice, op_.stream()));
+      EXA_HC(hipStreamSynchronize(op_.stream()));
+   }
 }
 void Multigrid::Prolong(int l, const double* xc, double* xf) {
    if (l < 0 || l >= levels()) throw std::runtime_error("multigrid: no transfer below level " + std::to_string(l));
@@ -201,7 +254,8 @@ void Multigrid::Prolong(int l, const double* xc, double* xf) {
 void Multigrid::Restrict(int l, const double* rf, double* rc) {
    if (l < 0 || l >= levels()) throw std::runtime_error("multigrid: no transfer below level " + std::to_string(l));
    const Level& f = lv_[l];
-   mg_restrict(f.g, lv_[l + 1].g, !op_.comm().active() ? nullptr : (l == 0 ? op_.weight.p : f.wp), rf, rc, op_.stream());
+   if (fused_) { mg_restrict_periodic(f.g, lv_[l + 1].g, rf, rc, op_.stream()); return; }
+   mg_restrict(f.g, lv_[l + 1].g, !(periodic_ || op_.comm().active()) ? nullptr : (l == 0 ? op_.weight.p : f.wp), rf, rc, op_.stream());
    halo(l + 1, rc);
 }
 

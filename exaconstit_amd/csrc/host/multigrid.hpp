@@ -15,6 +15,12 @@
 // Smoother: Chebyshev on D^-1 A (the same polynomial before and after the coarse correction, so the V-cycle is symmetric), interval
 // [0.3 * 1.2 lmax, 1.2 lmax], lmax from 10 power iterations started from a hash of the global dof index (the same vector on every
 // decomposition), D^-1 = 0 on essential dofs.  The coarsest level runs the same smoother at degree 16 instead of a direct solve.
+//
+// Periodic cells ("periodic cells"): an image pair is a rank interface with oneself, so the stencils, probes and transfers of the
+// build stay what they are (nodes taken as distinct, rows summed afterwards) and only the sums change.  One rank: the V-cycle runs the fused
+// kernels mg_stencil_apply_periodic / mg_restrict_periodic (the sum over the images inside the launch).  Several ranks: the unfused kernels and
+// NonlinearMechOperator::SumLVector at the fine positions (PeriodicCell::Sum), never both.  Mixed loading: the hierarchy is that of the fluctuation
+// block (level-0 mask = essential set + every control slot), and Apply adds the control block z = r / d on the free control slots.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -39,7 +45,11 @@ void mg_dinv(int64_t n, const uint8_t* mask, const double* diag, double* dinv, h
 void mg_mask_coarsen(const MgGrid& F, const MgGrid& C, const uint8_t* mf, uint8_t* mc, hipStream_t s);
 void mg_cheb(int64_t n, double* x, double* r, double* d, const double* Ad, const double* dinv, double c1, double c2, bool first, hipStream_t s);
 void mg_resid(int64_t n, const uint8_t* mask, const double* b, const double* y, double* r, hipStream_t s);
-void mg_seed(const MgGrid& C, const int ng[3], const uint8_t* mask, double* v, hipStream_t s);
+void mg_seed(const MgGrid& C, const int ng[3], bool periodic, const uint8_t* mask, double* v, hipStream_t s);   // periodic: hash of the canonical coordinate
+// periodic cell on one rank: y = (sum over the images)(S x) written to every image, and the reduced restriction with wrap-around, one launch each
+void mg_stencil_apply_periodic(const MgGrid& C, const double* S, const double* x, double* y, hipStream_t s);
+void mg_restrict_periodic(const MgGrid& F, const MgGrid& C, const double* rf, double* rc, hipStream_t s);
+void mg_control_block(int n, const int32_t* slot, const double* dinv, const double* r, double* z, hipStream_t s);                // z[slot] = dinv r[slot]
 void mg_to_fine(const MgGrid& F0, const MgGrid& C, int stride, const double* xc, double* x0, hipStream_t s);
 void mg_from_fine(const MgGrid& F0, const MgGrid& C, int stride, const double* x0, double* xc, hipStream_t s);
 
@@ -73,10 +83,13 @@ class Multigrid {
    void Apply(const double* b, double* x);                 // x = B b, one V-cycle
    int levels() const { return (int)lv_.size() - 1; }       // coarse levels
    int degree() const { return degree_; }
+   int levels_cap() const { return levels_cap_; }           // as asked for at construction (0: as many as the mesh allows)
+   bool periodic() const { return periodic_; }
+   int control_dofs() const { return control_dofs_; }      // free control entries of the control block (all ranks' count; 0 before the first Build)
    bool built() const { return built_; }
    // test hooks (level l of the hierarchy of the last Build): y = A_l x (level 0: the constrained fine operator), the diagonal, transfers
    void LevelApply(int l, const double* x, double* y);
-   void LevelDiag(int l, double* out);
+   void LevelDiag(int l, double* out);                     // (mixed loading, level 0: d on the free control slots this rank holds)
    void Prolong(int l, const double* xc, double* xf);      // level l + 1 -> l
    void Restrict(int l, const double* rf, double* rc);     // level l -> l + 1: halo_sum(sum_local w_j P_jI r(j))
    int64_t level_dofs(int l) const { return lv_[l].nd; }
@@ -95,12 +108,17 @@ class Multigrid {
    void A(int l, const double* x, double* y);              // A_l x, halo-summed
    void ALocal(int l, const double* x, double* y);         // this rank's part
    void halo(int l, double* y);
+   void BuildControlBlock();                               // mixed loading: the level-0 mask and the diagonal of the free control slots
    double dot(int l, const double* a, const double* b);
    void smooth(int l, const double* b, double* x);
    void vcycle(int l, const double* b, double* x);
    NonlinearMechOperator& op_;
    std::vector<Level> lv_;
-   int degree_ = 2; bool built_ = false;
+   int degree_ = 2, levels_cap_ = 0; bool built_ = false;
+   bool periodic_ = false, fused_ = false, mixed_ = false;  // fused_: periodic on one rank (the image sums run inside the coarse kernels)
+   DevBuf<uint8_t> mask0_;                                  // mixed loading: essential set + the free control slots
+   DevBuf<int32_t> ctrl_slot_; DevBuf<double> ctrl_dinv_; int ctrl_local_ = 0, control_dofs_ = 0;   // this rank's free control slots and 1 / d
+   int64_t ctrl_at_[8] = {}; double ctrl_d_[8] = {};
    int ng_[3] = { 0, 0, 0 };                                // global elements per direction at level 0
    DevBuf<double> fine_tmp_, partial_, scal_;
    hipEvent_t ev0_ = nullptr, ev1_ = nullptr; bool ev_pending_ = false; double vcycle_ms_ = 0.0;

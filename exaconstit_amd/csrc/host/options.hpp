@@ -109,8 +109,8 @@ struct ExaOptions {
          return "BCs.periodic_free: both entries of an off-diagonal pair (i, j), (j, i) are free - the rigid rotation would be free";
       return nullptr;
    }
+   static const char* periodic_no_multigrid() { return "BCs.periodic = true runs under Solvers.Krylov.preconditioner = \"multigrid\" only where it is asked for: Solvers.Krylov.mg_periodic = true (Driver.set_preconditioner(\"multigrid\", periodic=True)); without it the combination is refused as before"; }
    static const char* periodic_needs_generated_mesh() { return "BCs.periodic = true needs a generated hexahedral mesh (Mesh.type = \"auto\"): file and tetrahedral meshes need node matching"; }
-   static const char* periodic_no_multigrid() { return "BCs.periodic = true is not built for Solvers.Krylov.preconditioner = \"multigrid\" (the coarse levels have no periodic transfer)"; }
    XtalType xtal = XtalType::FCC; SlipType slip = SlipType::POWERVOCE;
    bool dt_cust = false, dt_auto = false; std::vector<double> cust_dt; double dt = 1.0, t_final = 1.0;
    double dt_min = 1.0, dt_scale = 0.25; int nsteps = 1; std::string auto_dt_fname = "auto_dt_out.txt";
@@ -183,6 +183,7 @@ struct ExaOptions {
    // decides), 1 "jacobi", 2 "multigrid" (host/multigrid.hpp) with mg_levels coarse levels at most (0: as many as the mesh allows) and a
    // Chebyshev smoother of degree mg_smoother_degree (1 ... 8)
    int precond = 0, mg_levels = 0, mg_degree = 2;
+   bool mg_periodic = false;   // Solvers.Krylov.mg_periodic: multigrid on a periodic cell ("periodic cells"); refused without it, as before the hierarchy served periodic cells
    int ref_ser = 0, order = 1; int ncuts[3] = { 1, 1, 1 }; double length[3] = { 1, 1, 1 }; std::string mesh_type = "auto", mesh_file;
 
    static std::vector<double> load_numbers(const std::string& path) {
@@ -487,7 +488,11 @@ struct ExaOptions {
             if (order != 1) throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is built for p_refinement = 1 only");
             if (lower(integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
             if (mesh_type != "auto") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\"): file meshes need algebraic coarsening");
-            if (periodic) throw std::runtime_error(periodic_no_multigrid());
+            if (const TomlValue* mp = d.get("Solvers.Krylov.mg_periodic")) {
+               if (mp->kind != TomlValue::BOOL) throw std::runtime_error("Solvers.Krylov.mg_periodic must be true or false");
+               mg_periodic = mp->b;
+            }
+            if (periodic && !mg_periodic) throw std::runtime_error(periodic_no_multigrid());
          } else throw std::runtime_error("Solvers.Krylov.preconditioner must be \"jacobi\" or \"multigrid\"");
       }
    }

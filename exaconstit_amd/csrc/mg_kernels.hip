@@ -94,6 +94,86 @@ __global__ __launch_bounds__(MG_BS) void k_mg_stencil_apply(const MgGrid C, cons
    for (int r = 0; r < 3; r++) y[t + nn * r] = s[r];
 }
 
+// Periodic cell on one rank ("periodic cells"): in every direction index 0 and index n - 1 are images of each other, at every level.
+// y = G (S x), G the sum over the images of a node written to every image, in ONE launch: the thread of a surface node evaluates the stored rows
+// of all local images of its node (2 on a face, 4 on an edge, 8 at a corner), each exactly as k_mg_stencil_apply evaluates it (no wrap inside a
+// row: S holds the operator of nodes taken as distinct), and adds the row sums in ascending local index of the image.  Every image of a node runs
+// the same instructions on the same data, so all of them carry the same bits: no atomics, no second launch, no group table.  Interior threads do
+// what k_mg_stencil_apply does.  The loops run over image counts (1 or 2 per direction), never over an array: nothing is spilled.
+__global__ __launch_bounds__(MG_BS) void k_mg_stencil_apply_periodic(const MgGrid C, const double* __restrict__ S, const double* __restrict__ x, double* __restrict__ y) {
+   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   const int64_t nn = grid_nn(C);
+   if (t >= nn) return;
+   const int i = (int)(t % C.n[0]), j = (int)((t / C.n[0]) % C.n[1]), k = (int)(t / ((int64_t)C.n[0] * C.n[1]));
+   const int ci = (i == 0 || i == C.n[0] - 1) ? 2 : 1, cj = (j == 0 || j == C.n[1] - 1) ? 2 : 1, ck = (k == 0 || k == C.n[2] - 1) ? 2 : 1;
+   double acc[3] = { 0.0, 0.0, 0.0 };
+   for (int mk = 0; mk < ck; mk++) {
+      const int kk = ck == 2 ? mk * (C.n[2] - 1) : k;
+      for (int mj = 0; mj < cj; mj++) {
+         const int jj = cj == 2 ? mj * (C.n[1] - 1) : j;
+         for (int mi = 0; mi < ci; mi++) {
+            const int ii = ci == 2 ? mi * (C.n[0] - 1) : i;
+            const int64_t u = ii + (int64_t)C.n[0] * (jj + (int64_t)C.n[1] * kk);   // the image whose row this is
+            // One row: the neighbours free of branches - one outside the box reads the image itself and counts as 0 - and unrolled by the nine of a
+            // plane, so that the loads of a plane are in flight together (all 27 at once would spill).  A corner thread walks 8 rows one after the other: with k_mg_stencil_apply's loop (a
+            // round trip to memory per neighbour) it would hold every launch of every level for 8 x 27 round trips instead of 8 x 3, and the coarse levels are
+            // nothing but latency.  The order of the sum is k_mg_stencil_apply's.
+            double s[3] = { 0.0, 0.0, 0.0 };
+#pragma unroll 1
+            for (int dz = -1; dz <= 1; dz++)
+#pragma unroll
+            for (int q = 0; q < 9; q++) {
+               const int dx = q % 3 - 1, dy = q / 3 - 1, o = q + 9 * (dz + 1);
+               const bool in = (unsigned)(ii + dx) < (unsigned)C.n[0] && (unsigned)(jj + dy) < (unsigned)C.n[1] && (unsigned)(kk + dz) < (unsigned)C.n[2];
+               const int64_t v = in ? u + dx + (int64_t)C.n[0] * (dy + (int64_t)C.n[1] * dz) : u;
+               const double x0 = x[v], x1 = x[v + nn], x2 = x[v + 2 * nn];
+               const double xv[3] = { in ? x0 : 0.0, in ? x1 : 0.0, in ? x2 : 0.0 };
+#pragma unroll
+               for (int r = 0; r < 3; r++)
+#pragma unroll
+                  for (int c = 0; c < 3; c++) s[r] += S[(o * 9 + 3 * r + c) * nn + u] * xv[c];
+            }
+#pragma unroll
+            for (int r = 0; r < 3; r++) acc[r] += s[r];
+         }
+      }
+   }
+#pragma unroll
+   for (int r = 0; r < 3; r++) y[t + nn * r] = acc[r];
+}
+
+// Reduced restriction of the periodic cell on one rank: r_c(I) = sum_j P_jI r_f(j) over the fine nodes within one step of I WITH wrap-around
+// (fine index -1 is index n - 2, index n is index 1), from an assembled r_f (equal on the images of a node).  The wrapped neighbourhood holds
+// every canonical fine node once, so no weights are needed; every image of I gathers the same values in the same order and so writes the same bits.
+__global__ __launch_bounds__(MG_BS) void k_mg_restrict_periodic(const MgGrid F, const MgGrid C, const double* __restrict__ rf, double* __restrict__ rc) {
+   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   const int64_t nnf = grid_nn(F), nnc = grid_nn(C);
+   if (t >= nnc) return;
+   const int I = (int)(t % C.n[0]), J = (int)((t / C.n[0]) % C.n[1]), K = (int)(t / ((int64_t)C.n[0] * C.n[1]));
+   double s[3] = { 0.0, 0.0, 0.0 };
+   for (int dz = -1; dz <= 1; dz++) {
+      int fk = 2 * K + dz; if (fk < 0) fk += F.n[2] - 1; else if (fk >= F.n[2]) fk -= F.n[2] - 1;
+      for (int dy = -1; dy <= 1; dy++) {
+         int fj = 2 * J + dy; if (fj < 0) fj += F.n[1] - 1; else if (fj >= F.n[1]) fj -= F.n[1] - 1;
+         for (int dx = -1; dx <= 1; dx++) {
+            int fi = 2 * I + dx; if (fi < 0) fi += F.n[0] - 1; else if (fi >= F.n[0]) fi -= F.n[0] - 1;
+            const int64_t v = fi + (int64_t)F.n[0] * (fj + (int64_t)F.n[1] * fk);
+            const double wt = (dx ? 0.5 : 1.0) * (dy ? 0.5 : 1.0) * (dz ? 0.5 : 1.0);
+#pragma unroll
+            for (int c = 0; c < 3; c++) s[c] += wt * rf[v + nnf * c];
+         }
+      }
+   }
+#pragma unroll
+   for (int c = 0; c < 3; c++) rc[t + nnc * c] = s[c];
+}
+
+// control block of the preconditioner under mixed loading: z = r / d on this rank's free control slots (at most 8; not hot)
+__global__ void k_mg_control_block(const int n, const int32_t* __restrict__ slot, const double* __restrict__ dinv, const double* __restrict__ r, double* __restrict__ z) {
+   const int t = threadIdx.x;
+   if (t < n) z[slot[t]] = dinv[t] * r[slot[t]];
+}
+
 // probe vector: 1 on component comp of the free nodes of colour `colour` (colour = global coordinates mod m), 0 elsewhere
 __global__ __launch_bounds__(MG_BS) void k_mg_probe(const MgGrid C, const int m, const int colour, const int comp, const uint8_t* __restrict__ mask, double* __restrict__ x) {
    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -172,14 +252,16 @@ __global__ __launch_bounds__(MG_BS) void k_mg_resid(const int64_t n, const uint8
    if (t < n) r[t] = mask[t] ? 0.0 : b[t] - y[t];
 }
 
-// start vector of the power iteration: a hash of the GLOBAL dof index in (0, 1], zero on essential dofs (the same vector on every decomposition)
-__global__ __launch_bounds__(MG_BS) void k_mg_seed(const MgGrid C, const int ng0, const int ng1, const int ng2, const uint8_t* __restrict__ mask, double* __restrict__ v) {
+// start vector of the power iteration: a hash of the GLOBAL dof index in (0, 1], zero on essential dofs (the same vector on every decomposition).
+// periodic: of the canonical coordinate (the last index of a direction is index 0), so that the images of a node start equal
+__global__ __launch_bounds__(MG_BS) void k_mg_seed(const MgGrid C, const int ng0, const int ng1, const int ng2, const int periodic, const uint8_t* __restrict__ mask, double* __restrict__ v) {
    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
    const int64_t nn = grid_nn(C);
    if (t >= nn) return;
    const int i = (int)(t % C.n[0]), j = (int)((t / C.n[0]) % C.n[1]), k = (int)(t / ((int64_t)C.n[0] * C.n[1]));
-   const uint64_t g = (uint64_t)(C.g0[0] + i) + (uint64_t)ng0 * ((uint64_t)(C.g0[1] + j) + (uint64_t)ng1 * (uint64_t)(C.g0[2] + k));
-   (void)ng2;
+   int gi = C.g0[0] + i, gj = C.g0[1] + j, gk = C.g0[2] + k;
+   if (periodic) { gi %= ng0 - 1; gj %= ng1 - 1; gk %= ng2 - 1; }
+   const uint64_t g = (uint64_t)gi + (uint64_t)ng0 * ((uint64_t)gj + (uint64_t)ng1 * (uint64_t)gk);
 #pragma unroll
    for (int c = 0; c < 3; c++) {
       uint64_t z = (3 * g + c) + 0x9E3779B97F4A7C15ull;   // splitmix64
@@ -222,6 +304,16 @@ void mg_restrict(const MgGrid& F, const MgGrid& C, const double* w, const double
 void mg_stencil_apply(const MgGrid& C, const double* S, const double* x, double* y, hipStream_t s) {
    hipLaunchKernelGGL(k_mg_stencil_apply, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, C, S, x, y); launched("k_mg_stencil_apply");
 }
+void mg_stencil_apply_periodic(const MgGrid& C, const double* S, const double* x, double* y, hipStream_t s) {
+   hipLaunchKernelGGL(k_mg_stencil_apply_periodic, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, C, S, x, y); launched("k_mg_stencil_apply_periodic");
+}
+void mg_restrict_periodic(const MgGrid& F, const MgGrid& C, const double* rf, double* rc, hipStream_t s) {
+   hipLaunchKernelGGL(k_mg_restrict_periodic, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, F, C, rf, rc); launched("k_mg_restrict_periodic");
+}
+void mg_control_block(int n, const int32_t* slot, const double* dinv, const double* r, double* z, hipStream_t s) {
+   if (n < 1) return;
+   hipLaunchKernelGGL(k_mg_control_block, dim3(1), dim3(64), 0, s, n, slot, dinv, r, z); launched("k_mg_control_block");
+}
 void mg_probe(const MgGrid& C, int m, int colour, int comp, const uint8_t* mask, double* x, hipStream_t s) {
    hipLaunchKernelGGL(k_mg_probe, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, C, m, colour, comp, mask, x); launched("k_mg_probe");
 }
@@ -246,8 +338,8 @@ void mg_cheb(int64_t n, double* x, double* r, double* d, const double* Ad, const
 void mg_resid(int64_t n, const uint8_t* mask, const double* b, const double* y, double* r, hipStream_t s) {
    hipLaunchKernelGGL(k_mg_resid, dim3(blocks(n)), dim3(MG_BS), 0, s, n, mask, b, y, r); launched("k_mg_resid");
 }
-void mg_seed(const MgGrid& C, const int ng[3], const uint8_t* mask, double* v, hipStream_t s) {
-   hipLaunchKernelGGL(k_mg_seed, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, C, ng[0], ng[1], ng[2], mask, v); launched("k_mg_seed");
+void mg_seed(const MgGrid& C, const int ng[3], bool periodic, const uint8_t* mask, double* v, hipStream_t s) {
+   hipLaunchKernelGGL(k_mg_seed, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, C, ng[0], ng[1], ng[2], periodic ? 1 : 0, mask, v); launched("k_mg_seed");
 }
 void mg_to_fine(const MgGrid& F0, const MgGrid& C, int stride, const double* xc, double* x0, hipStream_t s) {
    hipLaunchKernelGGL(k_mg_to_fine, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, F0, C, stride, xc, x0); launched("k_mg_to_fine");
@@ -257,3 +349,14 @@ void mg_from_fine(const MgGrid& F0, const MgGrid& C, int stride, const double* x
 }
 
 }  // namespace exa_host
+
+// private-memory bytes per lane of the two periodic kernels as the loaded code object reports them (both must be 0: nothing is spilled)
+extern "C" int exa_mg_periodic_scratch_bytes(int* out2) {
+   const void* f[2] = { reinterpret_cast<const void*>(exa_host::k_mg_stencil_apply_periodic), reinterpret_cast<const void*>(exa_host::k_mg_restrict_periodic) };
+   for (int k = 0; k < 2; k++) {
+      hipFuncAttributes a;
+      if (hipFuncGetAttributes(&a, f[k]) != hipSuccess) { (void)hipGetLastError(); return -1; }
+      out2[k] = (int)a.localSizeBytes;
+   }
+   return 0;
+}

@@ -543,6 +543,8 @@ exa_driver_set_periodic = _sig("exa_driver_set_periodic", C.c_int, C.c_void_p, _
 exa_driver_periodic_info = _sig("exa_driver_periodic_info", C.c_int, C.c_void_p, C.POINTER(C.c_int64), _dp)
 exa_driver_get_nodal = _sig("exa_driver_get_nodal", C.c_int, C.c_void_p, C.c_int, _dp, C.c_char_p, C.c_int)
 exa_periodic_sum_scratch_bytes = _sig("exa_periodic_sum_scratch_bytes", C.c_int)
+exa_driver_set_mg_periodic = _sig("exa_driver_set_mg_periodic", C.c_int, C.c_void_p, C.c_int)
+exa_mg_periodic_scratch_bytes = _sig("exa_mg_periodic_scratch_bytes", C.c_int, C.POINTER(C.c_int))
 exa_driver_newton_info = _sig("exa_driver_newton_info", C.c_int, C.c_void_p, _dp)
 exa_options_query_bcs = _sig("exa_options_query_bcs", C.c_int, C.c_char_p, C.POINTER(C.c_int), _dp, C.c_int, C.c_char_p, C.c_int)
 exa_partition_query_periodic = _sig("exa_partition_query_periodic", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
@@ -1186,9 +1188,12 @@ class Driver:
         return dict(pcg_ms=o[0], iters=int(o[1]), apply_ms=o[2])
 
     # ---- preconditioner (exa_driver_set_preconditioner) and the multigrid test hooks ---------------------------------------
-    def set_preconditioner(self, kind, levels=0, degree=2):
-        """kind: "identity", "jacobi" or "multigrid" (or 0 / 1 / 2); levels: max coarse levels (0 = as many as the mesh allows); degree: Chebyshev degree"""
+    def set_preconditioner(self, kind, levels=0, degree=2, periodic=False):
+        """kind: "identity", "jacobi" or "multigrid" (or 0 / 1 / 2); levels: max coarse levels (0 = as many as the mesh allows); degree: Chebyshev degree;
+        periodic=True: multigrid may meet set_periodic, before or after this call (opt-in, like Solvers.Krylov.mg_periodic; refused without it)"""
         k = PRECOND_KINDS[kind] if isinstance(kind, str) else int(kind)
+        if periodic:
+            exa_driver_set_mg_periodic(self.h, 1)
         self._chk(exa_driver_set_preconditioner(self.h, k, int(levels), int(degree), self._err, 512))
 
     def set_periodic(self, vel_grad, free=None):
@@ -1304,14 +1309,16 @@ class Driver:
         return dict(norm=float(o[0]), bound=float(o[1]))
 
     def mg_info(self):
-        """dict(levels, setup_ms, vcycle_ms, degree, boxes (L+1, 3) local elements per direction, lmax (L+1,))"""
+        """dict(levels, setup_ms, vcycle_ms, degree, boxes (L+1, 3) local elements per direction, lmax (L+1,), periodic, control_dofs: free
+        control entries of mixed loading the preconditioner scales by their diagonal)"""
         import numpy as np
-        out = np.zeros(4 + 4 * 32)
+        out = np.zeros(6 + 4 * 32)
         if exa_driver_mg_info(self.h, out.ctypes.data_as(_dp)) != 0:
             raise RuntimeError("exa_driver_mg_info failed (no multigrid preconditioner)")
         L = int(out[0])
         per = out[4:4 + 4 * (L + 1)].reshape(L + 1, 4)
-        return dict(levels=L, setup_ms=float(out[1]), vcycle_ms=float(out[2]), degree=int(out[3]), boxes=per[:, :3].astype(int), lmax=per[:, 3].copy())
+        return dict(levels=L, setup_ms=float(out[1]), vcycle_ms=float(out[2]), degree=int(out[3]), boxes=per[:, :3].astype(int), lmax=per[:, 3].copy(),
+                    periodic=bool(out[4 + 4 * (L + 1)]), control_dofs=int(out[5 + 4 * (L + 1)]))
 
     def mg_setup(self):
         """gradient set-up of the current state + hierarchy build (the hooks then act on the operator the driver holds now)"""

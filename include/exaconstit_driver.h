@@ -115,9 +115,13 @@ void exa_driver_destroy(exa_driver* d);
  * meshes, not B-bar) with at most `levels` coarse levels (0: as many as the mesh allows) and a Chebyshev smoother of `degree` (1 ... 8).
  * Refused (-1, err) where no coarse level can be built for the decomposition. */
 int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen);
-/* out (>= 4 + 4 (L + 1) doubles) = { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree, then per level
- * l = 0 ... L: local elements per direction (3), lmax estimate of D^-1 A_l }.  Returns 0 or -1 (no multigrid preconditioner). */
+/* out (>= 6 + 4 (L + 1) doubles) = { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree, then per level
+ * l = 0 ... L: local elements per direction (3), lmax estimate of D^-1 A_l; then 1 on a periodic cell, the free control entries of mixed loading
+ * in the preconditioner's control block }.  Returns 0 or -1 (no multigrid preconditioner). */
 int exa_driver_mg_info(exa_driver* d, double* out);
+/* Multigrid on a periodic cell is opt-in ([Solvers.Krylov] mg_periodic = true in an options file): on != 0 before exa_driver_set_preconditioner(2) /
+ * exa_driver_set_periodic lets the two meet, in either order; without it either call refuses the other, as before.  Returns 0. */
+int exa_driver_set_mg_periodic(exa_driver* d, int on);
 /* Test hooks on the hierarchy of the last gradient set-up; host arrays of exa_driver_mg_level_dofs(level) doubles (node-major per component,
  * node = i + n0 (j + n1 k) of the rank's local box at that level).  Level 0 is the constrained operator the PCG applies. */
 int64_t exa_driver_mg_level_dofs(exa_driver* d, int level);
@@ -217,8 +221,9 @@ int exa_driver_pole_figures(exa_driver* d, int nhkl, const int* hkl3, int ndir, 
 /* Periodic boundary conditions in all three directions under the macroscopic velocity gradient vel_grad9 (row by row), on a freshly
  * created driver before its first step - also one made by exa_driver_create_synthetic, whose prescribed faces it replaces: the velocity satisfies
  * v(image) - v(node) = L (x(image) - x(node)) between the images of a surface node, the eight corners carry v = L (x - origin).  Rebuilds the
- * partition tables, weights, essential set and halo lists; every rank of the group calls it.  Refuses meshes read from a file and the multigrid
- * preconditioner, like the options reader ([BCs] periodic = true).  Returns 0 or -1 (err). */
+ * partition tables, weights, essential set and halo lists; every rank of the group calls it.  Refuses meshes read from a file and, unless
+ * exa_driver_set_mg_periodic allowed it, the multigrid preconditioner, like the options reader ([BCs] periodic = true); a multigrid hierarchy
+ * that exists already is made again for the periodic partition.  Returns 0 or -1 (err). */
 int exa_driver_set_periodic(exa_driver* d, const double* vel_grad9, char* err, int errlen);
 /* Mixed stress / velocity-gradient loading of a periodic cell: like exa_driver_set_periodic, with free9[3 i + d] != 0 making entry
  * (i, d) of the velocity gradient an unknown whose conjugate mean traction (component i on face pair d) is zero; the other entries stay
@@ -262,6 +267,8 @@ int exa_macro_tangent_condense(const double* c81, const int* free9, double* out8
 int exa_options_macro_tangent(const char* toml_path, int* out2, double* rel_tol, char* fname, int fnamelen, char* err, int errlen);
 /* private (scratch) bytes per lane of k_periodic_expand and k_face_resultants in the loaded code object: out2; returns 0, or -1 without a device */
 int exa_periodic_mixed_scratch_bytes(int* out2);
+/* the same of the multigrid kernels of a periodic cell on one rank: out2 = { k_mg_stencil_apply_periodic, k_mg_restrict_periodic } */
+int exa_mg_periodic_scratch_bytes(int* out2);
 /* out8 = { periodic (0 / 1), local periodic groups of 2, of 4, of 8 images, canonical ids exchanged with other ranks, neighbours, 0, 0 };
  * vel_grad9 = the macroscopic velocity gradient in force (zeros when the driver is not periodic).  Returns 0 or -1. */
 int exa_driver_periodic_info(exa_driver* d, int64_t* out8, double* vel_grad9);

@@ -3,7 +3,11 @@ synthetic FCC Voce RVE, both in one invocation, at each --n: three steps through
 tolerances of BASELINE config 1 (Newton 5e-5, PCG rel 1e-7, 1000-iteration cap).  Prints one JSON document:
   per case and preconditioner: per step wall ms, Newton and Krylov iterations; the worst residual reduction reached; PCG ms per iteration;
   multigrid only: hierarchy set-up ms (last Newton iteration), V-cycle ms, levels and the lmax estimates.
-    python scripts/mg_compare.py --n 64 128 > profiles/mg_compare.json"""
+--periodic: the same three-step run on a periodic cell under L = diag(0, 0, 1e-3) ("periodic cells"); --free with it: uniaxial
+stress, xx and yy free - the control block of the preconditioner is then reported as control_dofs; --kinds picks the
+preconditioners (identity, jacobi, multigrid).
+    python scripts/mg_compare.py --n 64 128 > profiles/mg_compare.json
+    python scripts/mg_compare.py --periodic --free --n 64 128"""
 import argparse
 import json
 import os
@@ -17,10 +21,12 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def run(L, N, kind, dts, props, quats):
+def run(L, N, kind, dts, props, quats, periodic=False, free=False):
     d = L.Driver.synthetic(N, props, quats, dts, assembly=0)
+    if periodic:
+        d.set_periodic(np.diag([0.0, 0.0, 1.0e-3]), np.diag([1, 1, 0]) if free else None)
     if kind != "identity":
-        d.set_preconditioner(kind)
+        d.set_preconditioner(kind, periodic=periodic) if kind == "multigrid" else d.set_preconditioner(kind)
     steps = []
     worst = 0.0
     setups = []
@@ -41,7 +47,7 @@ def run(L, N, kind, dts, props, quats):
     if kind == "multigrid":
         info = d.mg_info()
         out.update(levels=info["levels"], setup_ms_per_newton_iter=float(np.mean(setups)), vcycle_ms=info["vcycle_ms"],
-                   lmax=[float(v) for v in info["lmax"]])
+                   lmax=[float(v) for v in info["lmax"]], periodic=info["periodic"], control_dofs=info["control_dofs"])
     d.close()
     return out
 
@@ -49,15 +55,20 @@ def run(L, N, kind, dts, props, quats):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[64, 128])
+    ap.add_argument("--periodic", action="store_true", help="a periodic cell under L = diag(0, 0, 1e-3) instead of the prescribed faces")
+    ap.add_argument("--free", action="store_true", help="with --periodic: xx and yy free (uniaxial stress)")
+    ap.add_argument("--kinds", nargs="+", default=["identity", "multigrid"], choices=["identity", "jacobi", "multigrid"])
     a = ap.parse_args()
+    if a.free and not a.periodic:
+        ap.error("--free needs --periodic")
     import exaconstit_amd.lib as L
     import hipref
     props = np.loadtxt(os.path.join(ROOT, "tests", "golden", "refdata", "props_cp_voce.txt")).ravel()
     dts = np.array([0.1, 0.2, 0.3])
-    res = dict(schedule=dict(dts=dts.tolist(), vz=1e-3, newton_rel=5e-5, krylov_rel=1e-7, krylov_iter=1000), cases={})
+    res = dict(schedule=dict(dts=dts.tolist(), vz=1e-3, newton_rel=5e-5, krylov_rel=1e-7, krylov_iter=1000, periodic=a.periodic, free_xx_yy=a.free), cases={})
     for N in a.n:
         quats = hipref.random_quats(N ** 3, seed=16)
-        res["cases"][str(N)] = {k: run(L, N, k, dts, props, quats) for k in ("identity", "multigrid")}
+        res["cases"][str(N)] = {k: run(L, N, k, dts, props, quats, a.periodic, a.free) for k in a.kinds}
     print(json.dumps(res, indent=1))
 
 
