@@ -51,6 +51,21 @@ namespace {
 constexpr int VOL_AVG_BLOCKS = 512;
 inline hipStream_t S(exa_stream s) { return reinterpret_cast<hipStream_t>(s); }
 int fail(exa_ctx* ctx, int code, const char* msg) { if (ctx) ctx->err = msg; return code; }
+// What every entry point of the gradient action checks before it looks at the form of the context.  `needs`: the connectivity; the 46-double records or
+// element matrices (refused on the records of the constitutive launch); the geometry (refused on those records unless the nodal coordinates are named)
+enum { NEEDS_CONN = 1, NEEDS_FULL_RECORDS = 2, NEEDS_GEOMETRY = 4 };
+int grad_ready(exa_ctx* ctx, const char* entry, bool pointers, int needs) {
+   const bool model_records = ctx && ctx->grad_src == EXA_GRAD_FROM_MODEL_RECORDS;
+   const char* why = nullptr;
+   if (!ctx || !pointers) why = "null pointer";
+   else if ((needs & NEEDS_CONN) && !ctx->conn) why = "connectivity not set";
+   else if (ctx->grad_src == EXA_GRAD_NONE) why = "called before exa_grad_setup";
+   else if (model_records && (needs & NEEDS_FULL_RECORDS)) why = "the gradient data are the compact records of exa_model_setup_lvec_records; call exa_grad_setup for the full records";
+   else if (model_records && (needs & NEEDS_GEOMETRY) && !ctx->coords_lvec) why = "name the nodal coordinates with exa_grad_set_coords (the compact records hold no geometry)";
+   if (!why) return EXA_OK;
+   if (ctx) ctx->err = std::string(entry) + ": " + why;
+   return !ctx || !pointers ? EXA_ERR_ARG : EXA_ERR_STATE;
+}
 }
 
 extern "C" {
@@ -127,9 +142,9 @@ int exa_shape_table(const exa_ctx* ctx, double* G_host, double* W_host) {
 
 int exa_set_quadrature_layout(exa_ctx* ctx, int layout) {
    if (!ctx || (layout != EXA_QLAYOUT_AOS && layout != EXA_QLAYOUT_EB64)) return fail(ctx, EXA_ERR_ARG, "exa_set_quadrature_layout: bad argument");
-   if (layout == EXA_QLAYOUT_EB64 && !(exa_is_hex(ctx) && ((ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL) || ctx->p == 2)))
+   if (layout == EXA_QLAYOUT_EB64 && !(exa_is_hex(ctx) && (exa_p1_full(ctx) || ctx->p == 2)))
       return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_set_quadrature_layout: the element-blocked layout is built for hexahedra at p = 1 full integration and at p = 2");
-   ctx->qblk = (layout == EXA_QLAYOUT_EB64); ctx->have_resid = false; ctx->have_grad = false;
+   ctx->qblk = (layout == EXA_QLAYOUT_EB64); ctx->have_resid = false; exa_forget_grad(ctx);
    return EXA_OK;
 }
 int exa_set_aos_staging(exa_ctx* ctx, int on) { if (!ctx) return EXA_ERR_ARG; ctx->aos_stage = on != 0; return EXA_OK; }
@@ -205,21 +220,21 @@ int exa_model_setup_lvec_records(exa_ctx* ctx, double dt, const double* x_lvec, 
    if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_model_setup_lvec_records: call exa_set_connectivity first");
    if (!(dt > 0.0)) return fail(ctx, EXA_ERR_ARG, "exa_model_setup_lvec_records: dt must be positive");
    if (!exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_model_setup_lvec_records: the record-writing constitutive launches are built for hexahedra (tetrahedra: exa_model_setup_lvec + exa_grad_setup)");
-   const bool p1 = ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL, p2 = ctx->p == 2;      // p = 2: plain or B-bar, behind the geometry pre-pass (a Jacobian field is part of it)
-   if (!(p1 || p2) || (!ctx->qblk && !p1) || ctx->tangent_form != EXA_TANGENT_DEV5_BULK || !(ctx->cfg.assembly == EXA_ASSEMBLY_PA || ctx->ea_matfree))
+   const bool p1 = exa_p1_full(ctx), p2 = ctx->p == 2;      // p = 2: plain or B-bar, behind the geometry pre-pass (a Jacobian field is part of it)
+   if (!(p1 || p2) || (!ctx->qblk && !p1) || ctx->tangent_form != EXA_TANGENT_DEV5_BULK || !exa_acts_from_records(ctx))
       return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_model_setup_lvec_records: needs p = 1 full integration (either layout) or p = 2 (element-blocked layout), the compact tangent form and PA or matrix-free EA");
    if (p2 && !J_out) return fail(ctx, EXA_ERR_ARG, "exa_model_setup_lvec_records: at p = 2 the Jacobian field is not optional (the pre-pass writes it, the launch and the residual read it)");
    const int npair = p1 ? PAC_PAIRS : PAC_PAIRS_GEO;
    if (ctx->pa_c && ctx->pac_pairs != npair) return fail(ctx, EXA_ERR_STATE, "exa_model_setup_lvec_records: compact records of another shape exist");
    if (!ctx->pa_c) {
       ctx->pac_pairs = npair;
-      EXA_HIP_CHECK(ctx, hipMalloc(&ctx->pa_c, (size_t)((ctx->E + PA_BLK - 1) / PA_BLK) * ctx->Q * 2 * npair * PA_BLK * sizeof(double)));
-      EXA_HIP_CHECK(ctx, hipMemsetAsync(ctx->pa_c, 0, (size_t)((ctx->E + PA_BLK - 1) / PA_BLK) * ctx->Q * 2 * npair * PA_BLK * sizeof(double), S(s)));
+      EXA_HIP_CHECK(ctx, hipMalloc(&ctx->pa_c, exa_pac_bytes(ctx)));
+      EXA_HIP_CHECK(ctx, hipMemsetAsync(ctx->pa_c, 0, exa_pac_bytes(ctx), S(s)));
    }
    const int rc = p2 ? exa_launch_model_setup_p2(ctx, dt, J_out, v_lvec, x_lvec, stress0, state0, stress1, state1, nullptr, true, S(s))
                      : !ctx->qblk ? exa_launch_model_setup_aos_rec(ctx, dt, J_out, v_lvec, x_lvec, stress0, state0, stress1, state1, S(s))
                      : exa_launch_model_setup_rec(ctx, dt, J_out, v_lvec, x_lvec, stress0, state0, stress1, state1, S(s));
-   if (rc == EXA_OK) { ctx->have_grad = true; ctx->emat_valid = false; ctx->grad_records_only = true; }
+   if (rc == EXA_OK) { ctx->grad_src = EXA_GRAD_FROM_MODEL_RECORDS; ctx->emat_valid = false; }
    return cap_controller(ctx, rc, state1, s);
 }
 
@@ -245,7 +260,7 @@ int exa_model_setup_checked(exa_ctx* ctx, double dt, const double* J, const doub
 int exa_set_lean_state(exa_ctx* ctx, int on) { if (!ctx) return EXA_ERR_ARG; ctx->lean_state = on != 0; return EXA_OK; }
 int exa_get_lean_state(exa_ctx* ctx) {
    if (!ctx) return EXA_ERR_ARG;
-   return ctx->lean_state && ctx->qblk && exa_is_hex(ctx) && ((ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL) || ctx->p == 2) ? 1 : 0;
+   return ctx->lean_state && ctx->qblk && exa_is_hex(ctx) && (exa_p1_full(ctx) || ctx->p == 2) ? 1 : 0;
 }
 int exa_slip_rates_from_state(exa_ctx* ctx, double* state, exa_stream s) {
    if (!ctx || !state) return fail(ctx, EXA_ERR_ARG, "exa_slip_rates_from_state: null pointer");
@@ -315,7 +330,7 @@ int exa_residual_setup(exa_ctx* ctx, const double* J, const double* stress1, exa
    if (ctx->qblk) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_residual_setup: E-vector residual is AOS-only; with the element-blocked layout use exa_residual_lvec");
    ctx->have_resid = true;
    if (ctx->cfg.integ == EXA_INTEG_BBAR) {      // ICExaNLFIntegrator::AssemblePA: element-average gradient; J and sigma are read by AddMultPA
-      if (!ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, sizeof(double) * 3 * ctx->n * PA_BLK * (size_t)((ctx->E + PA_BLK - 1) / PA_BLK)));
+      if (!ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, exa_eds_bytes(ctx)));
       ctx->resid_J = J; ctx->resid_S = stress1;
       return exa_launch_eds(ctx, J, S(s));
    }
@@ -330,16 +345,10 @@ int exa_residual_apply(exa_ctx* ctx, double* y, exa_stream s) {
    return exa_launch_residual_apply(ctx, y, S(s));
 }
 
-// element-assembly contexts whose L-vector action is computed from the point records (exa_set_ea_matrix_free)
-static bool ea_from_records(const exa_ctx* ctx) {
-   return exa_is_hex(ctx) && ctx->ea_matfree && (ctx->n == 27 || (ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL));
-}
-
 // element matrices from the point records (and eDS) of the last exa_grad_setup
 static int assemble_ea(exa_ctx* ctx, hipStream_t s) {
    if (ctx->emat_valid) return EXA_OK;
-   const size_t nblocks = (size_t)((ctx->E + PA_BLK - 1) / PA_BLK), nd = 3 * (size_t)ctx->n;
-   if (!ctx->emat) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->emat, nblocks * nd * nd * PA_BLK * sizeof(double)));
+   if (!ctx->emat) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->emat, exa_emat_bytes(ctx)));
    const int rc = ctx->ea_generic ? exa_launch_assemble_ea_gen(ctx, s) : exa_launch_assemble_ea_p1(ctx, s);
    ctx->emat_valid = (rc == EXA_OK);
    return rc;
@@ -348,9 +357,9 @@ static int assemble_ea(exa_ctx* ctx, hipStream_t s) {
 int exa_set_tangent_form(exa_ctx* ctx, int form) {
    if (!ctx || (form != EXA_TANGENT_FULL && form != EXA_TANGENT_DEV5_BULK && form != EXA_TANGENT_DEV5_BULK_GEO)) return fail(ctx, EXA_ERR_ARG, "exa_set_tangent_form: bad argument");
    if (form != EXA_TANGENT_FULL && !exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_set_tangent_form: the compact records serve the hexahedron actions");
-   if (form == EXA_TANGENT_DEV5_BULK_GEO && !(ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL && ctx->cfg.assembly == EXA_ASSEMBLY_PA))
+   if (form == EXA_TANGENT_DEV5_BULK_GEO && !(exa_p1_full(ctx) && ctx->cfg.assembly == EXA_ASSEMBLY_PA))
       return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_set_tangent_form: the compact record with geometry serves the E-vector action of p = 1 partial assembly");
-   if (form != ctx->tangent_form && ctx->pa_c) { (void)hipFree(ctx->pa_c); ctx->pa_c = nullptr; ctx->pac_pairs = 0; ctx->have_grad = false; }      // (records of another shape)
+   if (form != ctx->tangent_form && ctx->pa_c) { (void)hipFree(ctx->pa_c); ctx->pa_c = nullptr; ctx->pac_pairs = 0; exa_forget_grad(ctx); }      // (records of another shape)
    ctx->tangent_form = form;
    return EXA_OK;
 }
@@ -379,51 +388,41 @@ int exa_set_ea_matrix_free(exa_ctx* ctx, int on) {
 
 int exa_grad_setup(exa_ctx* ctx, double dt, const double* J, const double* C, exa_stream s) {
    if (!ctx || !J || !C) return fail(ctx, EXA_ERR_ARG, "exa_grad_setup: null pointer");
-   if (!ctx->pa) { EXA_HIP_CHECK(ctx, hipMalloc(&ctx->pa, pa_bytes(ctx->E, ctx->Q))); EXA_HIP_CHECK(ctx, hipMemsetAsync(ctx->pa, 0, pa_bytes(ctx->E, ctx->Q), S(s))); }
-   if (ctx->tangent_form == EXA_TANGENT_DEV5_BULK_GEO && !ctx->pa_c) {
-      ctx->pac_pairs = PAC_PAIRS_GEO;
-      EXA_HIP_CHECK(ctx, hipMalloc(&ctx->pa_c, (size_t)((ctx->E + PA_BLK - 1) / PA_BLK) * ctx->Q * 2 * ctx->pac_pairs * PA_BLK * sizeof(double)));
+   if (!ctx->pa) { EXA_HIP_CHECK(ctx, hipMalloc(&ctx->pa, exa_pa_bytes(ctx))); EXA_HIP_CHECK(ctx, hipMemsetAsync(ctx->pa, 0, exa_pa_bytes(ctx), S(s))); }
+   if (!ctx->pa_c) {   // compact records in the shape the selected form has here, for the actions that can stream them
+      int npair = ctx->tangent_form == EXA_TANGENT_DEV5_BULK_GEO ? PAC_PAIRS_GEO : 0;
+      if (ctx->tangent_form == EXA_TANGENT_DEV5_BULK && exa_acts_from_records(ctx)) npair = exa_p1_full(ctx) ? PAC_PAIRS : (ctx->n == 27 ? PAC_PAIRS_GEO : 0);   // k_grad_apply_p1<.., GEO, CMP> : k_mf_apply_p2<.., CMP>
+      if (npair) { ctx->pac_pairs = npair; EXA_HIP_CHECK(ctx, hipMalloc(&ctx->pa_c, exa_pac_bytes(ctx))); }
    }
-   if (ctx->tangent_form == EXA_TANGENT_DEV5_BULK && !ctx->pa_c) {   // compact records for the actions that can stream them
-      const bool p1 = ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL && (ctx->cfg.assembly == EXA_ASSEMBLY_PA || ctx->ea_matfree);   // k_grad_apply_p1<.., GEO, CMP>
-      const bool p2 = ctx->n == 27 && (ctx->cfg.assembly == EXA_ASSEMBLY_PA || ctx->ea_matfree);               // k_mf_apply_p2<.., CMP>
-      if (p1 || p2) {
-         ctx->pac_pairs = p1 ? PAC_PAIRS : PAC_PAIRS_GEO;
-         EXA_HIP_CHECK(ctx, hipMalloc(&ctx->pa_c, (size_t)((ctx->E + PA_BLK - 1) / PA_BLK) * ctx->Q * 2 * ctx->pac_pairs * PA_BLK * sizeof(double)));
-      }
-   }
+   ctx->setup_J = J; ctx->setup_C = C; ctx->setup_dt = dt;
    int rc = exa_launch_grad_setup_pa(ctx, dt, J, C, S(s));
    if (rc) return rc;
-   ctx->grad_records_only = false;
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
       const bool bbar = ctx->cfg.integ == EXA_INTEG_BBAR;
       ctx->ea_generic = bbar || ctx->p != 1 || !exa_is_hex(ctx);
       if (bbar) {
-         if (!ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, sizeof(double) * 3 * ctx->n * PA_BLK * (size_t)((ctx->E + PA_BLK - 1) / PA_BLK)));
+         if (!ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, exa_eds_bytes(ctx)));
          rc = exa_launch_eds(ctx, J, S(s));
          if (rc) return rc;
       }
       ctx->emat_valid = false;
-      if (!ea_from_records(ctx) && !(ctx->ea_matfree && !exa_is_hex(ctx))) rc = assemble_ea(ctx, S(s));   // matrix-free: assembled on demand only
+      if (!exa_ea_from_records(ctx) && !(ctx->ea_matfree && !exa_is_hex(ctx))) rc = assemble_ea(ctx, S(s));   // matrix-free: assembled on demand only
    } else if (ctx->p != 1 || !exa_is_hex(ctx)) {
       if (!ctx->tbuf) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->tbuf, sizeof(double) * 9 * ctx->P));
    }
    if (rc == EXA_OK && !exa_is_hex(ctx) && ctx->p == 1) {
       // element records of the fused p = 1 action: built here where that action runs (PA or matrix-free EA, atomic mode, not switched off),
-      // otherwise by the first exa_grad_apply_lvec that needs them (J and C must then stay as they are until the next exa_grad_setup)
-      ctx->tet_J = J; ctx->tet_C = C; ctx->tet_dt = dt;
-      const bool fused = ctx->tet_fused && !ctx->det && (ctx->cfg.assembly == EXA_ASSEMBLY_PA || ctx->ea_matfree);
-      ctx->tet_rec_stale = !fused;
+      // otherwise by the first exa_grad_apply_lvec that needs them (exa_ctx, tet_pending)
+      const bool fused = ctx->tet_fused && !ctx->det && exa_acts_from_records(ctx);
+      ctx->tet_pending = !fused;
       if (fused) rc = exa_launch_tet_setup(ctx, dt, J, C, S(s));
    }
-   ctx->have_grad = (rc == EXA_OK);
+   ctx->grad_src = rc == EXA_OK ? EXA_GRAD_FROM_SETUP : EXA_GRAD_NONE;
    return rc;
 }
 
 int exa_grad_apply(exa_ctx* ctx, const double* x, double* y, exa_stream s) {
-   if (!ctx || !x || !y) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply: null pointer");
-   if (!ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply called before exa_grad_setup");
-   if (ctx->grad_records_only) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply: the gradient data are the compact records of exa_model_setup_lvec_records; call exa_grad_setup for the full records");
+   if (int rc = grad_ready(ctx, "exa_grad_apply", x && y, NEEDS_FULL_RECORDS)) return rc;
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
       if (int rc = assemble_ea(ctx, S(s))) return rc;
       return ctx->ea_generic ? exa_launch_ea_apply_gen(ctx, x, y, false, nullptr, nullptr, S(s)) : exa_launch_ea_apply_p1(ctx, x, y, false, nullptr, nullptr, S(s));
@@ -433,9 +432,7 @@ int exa_grad_apply(exa_ctx* ctx, const double* x, double* y, exa_stream s) {
 }
 
 int exa_grad_diagonal(exa_ctx* ctx, double* d, exa_stream s) {
-   if (!ctx || !d) return fail(ctx, EXA_ERR_ARG, "exa_grad_diagonal: null pointer");
-   if (!ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_diagonal called before exa_grad_setup");
-   if (ctx->grad_records_only) return fail(ctx, EXA_ERR_STATE, "exa_grad_diagonal: the gradient data are the compact records of exa_model_setup_lvec_records; call exa_grad_setup for the full records");
+   if (int rc = grad_ready(ctx, "exa_grad_diagonal", d != nullptr, NEEDS_FULL_RECORDS)) return rc;
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
       if (int rc = assemble_ea(ctx, S(s))) return rc;
       return ctx->ea_generic ? exa_launch_ea_diag_gen(ctx, d, S(s)) : exa_launch_ea_diag_p1(ctx, d, S(s));
@@ -445,9 +442,8 @@ int exa_grad_diagonal(exa_ctx* ctx, double* d, exa_stream s) {
 }
 
 int exa_grad_get_ea(exa_ctx* ctx, double* emat, exa_stream s) {
-   if (!ctx || !emat) return fail(ctx, EXA_ERR_ARG, "exa_grad_get_ea: null pointer");
-   if (!ctx->have_grad || ctx->cfg.assembly != EXA_ASSEMBLY_EA) return fail(ctx, EXA_ERR_STATE, "exa_grad_get_ea: no element matrices assembled");
-   if (ctx->grad_records_only) return fail(ctx, EXA_ERR_STATE, "exa_grad_get_ea: the gradient data are the compact records of exa_model_setup_lvec_records; call exa_grad_setup first");
+   if (int rc = grad_ready(ctx, "exa_grad_get_ea", emat != nullptr, NEEDS_FULL_RECORDS)) return rc;
+   if (ctx->cfg.assembly != EXA_ASSEMBLY_EA) return fail(ctx, EXA_ERR_STATE, "exa_grad_get_ea: no element matrices assembled");
    if (int rc = assemble_ea(ctx, S(s))) return rc;
    return ctx->ea_generic ? exa_launch_ea_export_gen(ctx, emat, S(s)) : exa_launch_ea_export_p1(ctx, emat, S(s));
 }
@@ -488,7 +484,7 @@ int exa_det_prepare(exa_ctx* ctx) {
    EXA_HIP_CHECK(ctx, hipMalloc(&ctx->n2e_off, sizeof(int32_t) * off.size())); EXA_HIP_CHECK(ctx, hipMalloc(&ctx->n2e_idx, sizeof(int32_t) * ne));
    EXA_HIP_CHECK(ctx, hipMemcpy(ctx->n2e_off, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
    EXA_HIP_CHECK(ctx, hipMemcpy(ctx->n2e_idx, idx.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice));
-   if (!ctx->ev_det) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->ev_det, sizeof(double) * 24 * PA_BLK * (size_t)((ctx->E + PA_BLK - 1) / PA_BLK)));
+   if (!ctx->ev_det) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->ev_det, sizeof(double) * 24 * PA_BLK * (size_t)exa_nblocks(ctx)));
    ctx->det_conn = ctx->conn; ctx->det_nnodes = ctx->nnodes;
    return EXA_OK;
 }
@@ -499,23 +495,18 @@ extern "C" {
 // driver-internal: the p = 1 record-based action on the 64-element blocks [blk0, blk0 + nblk) only (partial assembly and element assembly
 // from records; atomic scatter).  Returns EXA_ERR_UNSUPPORTED for contexts that have no such kernel: the caller then runs the whole action.
 int exa_grad_apply_lvec_blocks(exa_ctx* ctx, const double* x, double* y, const uint8_t* mask, const double* gate, int blk0, int nblk, exa_stream s) {
-   if (!ctx || !x || !y) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_blocks: null pointer");
-   if (!ctx->conn || !ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_blocks: connectivity / gradient data not set");
-   if (ctx->grad_records_only && !ctx->coords_lvec) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_blocks: name the nodal coordinates with exa_grad_set_coords");
+   if (int rc = grad_ready(ctx, "exa_grad_apply_lvec_blocks", x && y, NEEDS_CONN | NEEDS_GEOMETRY)) return rc;
    if (!exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_grad_apply_lvec_blocks: block ranges are built for the hexahedron p = 1 action");
-   if (ctx->det || ctx->p != 1 || ctx->cfg.integ != EXA_INTEG_FULL) return EXA_ERR_UNSUPPORTED;
+   if (ctx->det || !exa_p1_full(ctx)) return EXA_ERR_UNSUPPORTED;
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
-      if (!ea_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
+      if (!exa_ea_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
       return exa_launch_grad_apply_p1(ctx, x, y, true, mask, gate, S(s), true, blk0, nblk);
    }
    return exa_launch_grad_apply_p1(ctx, x, y, true, mask, gate, S(s), false, blk0, nblk);
 }
 
 int exa_grad_apply_lvec_gated(exa_ctx* ctx, const double* x, double* y, const uint8_t* mask, const double* gate, exa_stream s) {
-   if (!ctx || !x || !y) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec: null pointer");
-   if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec: connectivity not set");
-   if (!ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec called before exa_grad_setup");
-   if (ctx->grad_records_only && !ctx->coords_lvec) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec: name the nodal coordinates with exa_grad_set_coords (the compact records hold no geometry)");
+   if (int rc = grad_ready(ctx, "exa_grad_apply_lvec", x && y, NEEDS_CONN | NEEDS_GEOMETRY)) return rc;
    if (!exa_is_hex(ctx)) {   // tetrahedra: the fused action of tet_kernels.hip (PA, and EA from the records); assembled EA matrices through the generic kernel
       if (ctx->det) return fail(ctx, EXA_ERR_UNSUPPORTED, "deterministic mode: the fused tetrahedron action scatters with atomics; use exa_restrict + exa_grad_apply + exa_restrict_transpose_add");
       if (ctx->cfg.assembly == EXA_ASSEMBLY_EA && !ctx->ea_matfree) {
@@ -524,11 +515,11 @@ int exa_grad_apply_lvec_gated(exa_ctx* ctx, const double* x, double* y, const ui
       }
       return exa_launch_tet_apply(ctx, x, y, mask, gate, S(s));
    }
-   if (ctx->det && (ctx->p != 1 || ctx->cfg.integ != EXA_INTEG_FULL))
+   if (ctx->det && !exa_p1_full(ctx))
       return fail(ctx, EXA_ERR_UNSUPPORTED, "deterministic mode: the fused L-vector action is ordered for p = 1 full integration only; use exa_restrict + exa_grad_apply + exa_restrict_transpose_add");
    if (ctx->cfg.assembly == EXA_ASSEMBLY_EA) {
       if (ctx->ea_matfree && ctx->n == 27) return exa_launch_mf_apply_p2(ctx, x, y, mask, gate, true, S(s));
-      if (ea_from_records(ctx)) return exa_launch_grad_apply_p1(ctx, x, y, true, mask, gate, S(s), true);
+      if (exa_ea_from_records(ctx)) return exa_launch_grad_apply_p1(ctx, x, y, true, mask, gate, S(s), true);
       if (ctx->det) return fail(ctx, EXA_ERR_UNSUPPORTED, "deterministic mode: the L-vector action of assembled element matrices scatters with atomics; use exa_set_ea_matrix_free or exa_grad_apply + exa_restrict_transpose_add");
       if (int rc = assemble_ea(ctx, S(s))) return rc;
       return ctx->ea_generic ? exa_launch_ea_apply_gen(ctx, x, y, true, mask, gate, S(s)) : exa_launch_ea_apply_p1(ctx, x, y, true, mask, gate, S(s));
@@ -543,18 +534,15 @@ int exa_grad_apply_lvec_gated(exa_ctx* ctx, const double* x, double* y, const ui
 // record action with atomic scatter (partial assembly, or element assembly from the records); every other context gets EXA_ERR_UNSUPPORTED
 // and loops exa_grad_apply_lvec_gated.  nch: columns per pass over the record stream (1 .. 3; 0: EXA_GRAD_COLS_DEFAULT).
 int exa_grad_apply_lvec_cols_w(exa_ctx* ctx, int nch, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, exa_stream s) {
-   if (!ctx || !x || !y) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: null pointer");
    if (ncols < 1 || ncols > EXA_GRAD_COLS_MAX) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: between 1 and 16 columns");
    if (nch < 0 || nch > 3) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: 1, 2 or 3 columns per pass");
-   if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_cols: connectivity not set");
-   if (!ctx->have_grad) return fail(ctx, EXA_ERR_STATE, "exa_grad_apply_lvec_cols called before exa_grad_setup");
+   if (int rc = grad_ready(ctx, "exa_grad_apply_lvec_cols", x && y, NEEDS_CONN)) return rc;   // (the refusals below are silent: the driver falls back to single columns)
    const int64_t nd = 3 * (int64_t)ctx->nnodes;
    if (ncols > 1 && (ldx < nd || ldy < nd)) return fail(ctx, EXA_ERR_ARG, "exa_grad_apply_lvec_cols: column stride shorter than an L-vector");
-   if (!exa_is_hex(ctx) || ctx->det || ctx->p != 1 || ctx->cfg.integ != EXA_INTEG_FULL || !ctx->coords_lvec) return EXA_ERR_UNSUPPORTED;
+   if (!exa_is_hex(ctx) || ctx->det || !exa_p1_full(ctx) || !ctx->coords_lvec) return EXA_ERR_UNSUPPORTED;
    const bool ea = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
-   if (ea && !ea_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
-   const bool cmp = ctx->pa_c && ctx->pac_pairs == PAC_PAIRS;
-   if (!cmp && (ctx->grad_records_only || ctx->pa_lazy || !ctx->pa)) return EXA_ERR_UNSUPPORTED;   // (no 46-double records to read the tangent from)
+   if (ea && !exa_ea_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
+   if (!exa_has_compact(ctx) && (ctx->grad_src == EXA_GRAD_FROM_MODEL_RECORDS || ctx->pa_pending || !ctx->pa)) return EXA_ERR_UNSUPPORTED;   // (no 46-double records to read the tangent from)
    return exa_launch_grad_apply_p1_cols(ctx, ncols, x, ldx, y, ldy, mask, gates, ea, nch ? nch : EXA_GRAD_COLS_DEFAULT, S(s));
 }
 int exa_grad_apply_lvec_cols(exa_ctx* ctx, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, exa_stream s) {
@@ -573,15 +561,15 @@ int exa_grad_apply_lvec(exa_ctx* ctx, const double* x, double* y, const uint8_t*
 int exa_residual_lvec(exa_ctx* ctx, const double* J, const double* stress1, double* y, exa_stream s) {
    if (!ctx || !stress1 || !y) return fail(ctx, EXA_ERR_ARG, "exa_residual_lvec: null pointer");
    if (!ctx->conn) return fail(ctx, EXA_ERR_STATE, "exa_residual_lvec: connectivity not set");
-   if (!J && !(ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL && ctx->coords_lvec))
+   if (!J && !(exa_p1_full(ctx) && ctx->coords_lvec))
       return fail(ctx, EXA_ERR_ARG, "exa_residual_lvec: a null Jacobian field needs p = 1 full integration and nodal coordinates (exa_grad_set_coords)");
    if (!exa_is_hex(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_residual_lvec: the fused residual is built for hexahedra; use exa_residual_setup/apply + exa_restrict_transpose_add");
    if (ctx->det && ctx->p == 2) return fail(ctx, EXA_ERR_UNSUPPORTED, "deterministic mode: the fused p = 2 residual scatters with atomics; use exa_residual_setup/apply + exa_restrict_transpose_add");
    if (ctx->p == 2) {
-      if (ctx->cfg.integ == EXA_INTEG_BBAR && !ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, sizeof(double) * 3 * ctx->n * PA_BLK * (size_t)((ctx->E + PA_BLK - 1) / PA_BLK)));
+      if (ctx->cfg.integ == EXA_INTEG_BBAR && !ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, exa_eds_bytes(ctx)));
       return exa_launch_residual_p2(ctx, J, stress1, y, S(s));
    }
-   if (ctx->p != 1 || ctx->cfg.integ != EXA_INTEG_FULL) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_residual_lvec: fused path is built for p = 1 full integration and p = 2; use exa_residual_setup/apply + exa_restrict_transpose_add");
+   if (!exa_p1_full(ctx)) return fail(ctx, EXA_ERR_UNSUPPORTED, "exa_residual_lvec: fused path is built for p = 1 full integration and p = 2; use exa_residual_setup/apply + exa_restrict_transpose_add");
    return exa_launch_residual_p1(ctx, J, stress1, y, true, S(s));
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
+#include <type_traits>
 #include <cstdint>
 #include <cstdlib>
 #include "../../include/exaconstit_hip.h"
@@ -23,6 +24,8 @@
 constexpr int PA_SLOTS = 46;
 constexpr int PA_PAIRS = 23;
 constexpr int PA_BLK = 64;
+// who wrote the gradient data a context holds
+enum exa_grad_source { EXA_GRAD_NONE = 0, EXA_GRAD_FROM_SETUP, EXA_GRAD_FROM_MODEL_RECORDS };   // nobody yet | exa_grad_setup | exa_model_setup_lvec_records
 
 struct exa_ctx {
    exa_config cfg;
@@ -32,7 +35,6 @@ struct exa_ctx {
    int geom = EXA_GEOM_HEX; // EXA_GEOM_*: tetrahedra take the table-driven kernels and the fused action of tet_kernels.hip, never a hexahedron fast path
    double* tet_rec = nullptr;               // tetrahedra, p = 1: element records of the fused action (tet_kernels.hip)
    bool tet_fused = true;                   // tetrahedra: exa_grad_setup builds the element records for the fused action (exa_tet_set_fused_action)
-   bool tet_rec_stale = false; const double* tet_J = nullptr; const double* tet_C = nullptr; double tet_dt = 0.0;   // records not built yet: built by the first action
    int nstatev;
    int device;
    std::string err;
@@ -47,21 +49,28 @@ struct exa_ctx {
    double* tbuf = nullptr;                  // generic PA action: per-point T (3,3,Q,E)
    double* vgrad_ref = nullptr;             // p = 2 element-blocked constitutive launch: reference-space velocity gradients of its geometry pre-pass (3,3,Q,E)
    const double* resid_J = nullptr; const double* resid_S = nullptr;   // B-bar residual reads J and sigma at apply time, like the reference
-   bool ea_generic = false;
-   bool ea_matfree = false, emat_valid = false;   // EA, p = 2: L-vector action computed from the point records, matrices assembled on demand
+   bool ea_matfree = false;                 // EA: L-vector action computed from the point records, matrices assembled on demand (exa_set_ea_matrix_free)
    bool qblk = false;                       // quadrature functions in the element-blocked layout (see QView below)
    bool aos_stage = true;                   // AOS layout: constitutive launches move a wave's contiguous point rows coalesced and transpose them through LDS (exa_set_aos_staging)
-   bool have_resid = false, have_grad = false;
-   bool pa_lazy = false; const double* lazy_J = nullptr; const double* lazy_C = nullptr; double lazy_dt = 0.0;   // 46-double records not built yet (pa_kernels.hip, pa_full_on_demand)
-   bool grad_records_only = false;          // gradient data = compact records written by the constitutive launch: no 46-double records, no element matrices
+   bool have_resid = false;
+   // ---- gradient data: which exist, and who builds the rest (the buffers are pa, pa_c, emat, tet_rec above and below) ----
+   int grad_src = EXA_GRAD_NONE;            // exa_grad_source.  FROM_MODEL_RECORDS: the compact records alone - no 46-double records, no element matrices, no geometry
+   // what the last exa_grad_setup was given.  Borrowed: the caller leaves J and C untouched until the next set-up, because a record set marked pending
+   // below is built from them by the first call that reads it (they do stay in a Newton iteration: the reference calls AssembleGradDiagonalPA right after
+   // AssembleGradPA, src/mechanics_operator.cpp:436-443)
+   const double* setup_J = nullptr; const double* setup_C = nullptr; double setup_dt = 0.0;
+   bool pa_pending = false;                 // the set-up wrote the compact records only: `pa` waits for the diagonal, the E-vector action or an action without coordinates
+   bool tet_pending = false;                // the set-up did not expect the fused tetrahedron action: `tet_rec` waits for the first exa_grad_apply_lvec
+   bool emat_valid = false;                 // EA: `emat` holds the matrices of the last set-up (assembled in it, or on demand in matrix-free contexts)
+   bool ea_generic = false;                 // EA: the matrices have the generic layout (B-bar, p != 1, tetrahedra), not the p = 1 one
+   int tangent_form = 0;                    // EXA_TANGENT_*: the form the next set-up writes
+   int pac_pairs = 0;                       // 16-byte pairs per point of the records in pa_c: PAC_PAIRS (D, K) or PAC_PAIRS_GEO (+ geometry); 0 without pa_c
+   const double* coords_lvec = nullptr;     // optional: nodal coordinates the Jacobians of the set-up came from (geometry recomputed in the apply; exa_grad_set_coords)
    // L-vector support
    const int32_t* conn = nullptr; int nnodes = 0;
-   double* pa_c = nullptr;                  // compact tangent records (25 + 1 per point) of the geometry-recomputing p = 1 action; allocated when the form is selected
-   int tangent_form = 0;                    // EXA_TANGENT_*
-   int pac_pairs = 0;                       // 16-byte pairs per point of the compact record: 13 (D, K) at p = 1, 18 (+ geometry) at p = 2
+   double* pa_c = nullptr;                  // compact tangent records (25 + 1 per point, + 10 of geometry in the 18-pair shape); allocated when the form is first set up
    // deterministic E->L (exa_set_deterministic): node -> (element, local node) table in element order + per-element output scratch
    int det = 0; int32_t* n2e_off = nullptr; int32_t* n2e_idx = nullptr; double* ev_det = nullptr; int det_nnodes = 0; const int32_t* det_conn = nullptr;
-   const double* coords_lvec = nullptr;     // optional: nodal coordinates the Jacobians of exa_grad_setup came from (geometry recomputed in the apply)
    // status
    int* fail_count_dev = nullptr;
    int newton_cap = 0; int* tail_dev = nullptr;   // tail split of the constitutive launch: [0] = count, [1..] = deferred point ids
@@ -191,4 +200,41 @@ __device__ __forceinline__ void d55_apply(const double D[25], const double K, co
 }
 #endif
 
-static inline size_t pa_bytes(int E, int Q) { return (size_t)((E + PA_BLK - 1) / PA_BLK) * Q * PA_SLOTS * PA_BLK * sizeof(double); }
+// ---- forms of the gradient data, named once (host) ------------------------------------------------------------------------------
+static inline unsigned exa_nblocks(const exa_ctx* ctx) { return (unsigned)((ctx->E + PA_BLK - 1) / PA_BLK); }   // 64-element blocks
+static inline bool exa_p1_full(const exa_ctx* ctx) { return ctx->p == 1 && ctx->cfg.integ == EXA_INTEG_FULL; }
+// the L-vector action runs from the point records: partial assembly, or element assembly switched to matrix-free ...
+static inline bool exa_acts_from_records(const exa_ctx* ctx) { return ctx->cfg.assembly == EXA_ASSEMBLY_PA || ctx->ea_matfree; }
+// ... which on hexahedra has kernels for the transposed tangent at p = 2 and at p = 1 full integration
+static inline bool exa_ea_from_records(const exa_ctx* ctx) { return exa_is_hex(ctx) && ctx->ea_matfree && (ctx->n == 27 || exa_p1_full(ctx)); }
+static inline bool exa_has_compact(const exa_ctx* ctx) { return ctx->pa_c && ctx->pac_pairs == PAC_PAIRS; }           // compact p = 1 record
+static inline bool exa_has_compact_geo(const exa_ctx* ctx) { return ctx->pa_c && ctx->pac_pairs == PAC_PAIRS_GEO; }   // compact record with geometry
+// this p = 1 launch streams the compact record (and recomputes the geometry): picks the kernel AND sizes its record stream
+static inline bool exa_streams_compact(const exa_ctx* ctx, bool lvec) { return lvec && ctx->coords_lvec && exa_has_compact(ctx); }
+static inline size_t exa_pa_bytes(const exa_ctx* ctx) { return (size_t)exa_nblocks(ctx) * ctx->Q * PA_SLOTS * PA_BLK * sizeof(double); }
+static inline size_t exa_pac_bytes(const exa_ctx* ctx) { return (size_t)exa_nblocks(ctx) * ctx->Q * 2 * ctx->pac_pairs * PA_BLK * sizeof(double); }
+static inline size_t exa_eds_bytes(const exa_ctx* ctx) { return sizeof(double) * 3 * ctx->n * PA_BLK * (size_t)exa_nblocks(ctx); }
+static inline size_t exa_emat_bytes(const exa_ctx* ctx) { const size_t nd = 3 * (size_t)ctx->n; return (size_t)exa_nblocks(ctx) * nd * nd * PA_BLK * sizeof(double); }
+static inline void exa_forget_grad(exa_ctx* ctx) { ctx->grad_src = EXA_GRAD_NONE; }   // the next action is refused until a set-up
+// a record set marked pending, built now from what the last exa_grad_setup was given
+template <class Build>
+static inline int exa_build_pending(exa_ctx* ctx, bool& pending, Build build, hipStream_t s) {
+   if (!pending) return EXA_OK;
+   const int rc = build(ctx, ctx->setup_dt, ctx->setup_J, ctx->setup_C, s);
+   if (rc == EXA_OK) pending = false;
+   return rc;
+}
+
+// ---- launching ------------------------------------------------------------------------------------------------------------------
+// Run-time flags to template arguments: f is called once, with std::true_type / std::false_type in place of each flag, and holds the one launch line
+// (a generic lambda: `[&](auto qb, auto nt) { hipLaunchKernelGGL((k<qb.value, nt.value>), ...); }`).  Every combination of the flags handed in is
+// instantiated; where a kernel leaves combinations out, branch before the call and hand in the flags that remain.
+template <class F> static inline void exa_dispatch(F&& f) { f(); }
+template <class F, class... Bs>
+static inline void exa_dispatch(F&& f, bool b, Bs... bs) {
+   if (b) exa_dispatch([&](auto... t) { f(std::true_type(), t...); }, bs...);
+   else exa_dispatch([&](auto... t) { f(std::false_type(), t...); }, bs...);
+}
+constexpr std::true_type EXA_YES{}; constexpr std::false_type EXA_NO{};
+// the tail of every launcher
+static inline int exa_launched(exa_ctx* ctx) { EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK; }

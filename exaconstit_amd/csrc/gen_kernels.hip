@@ -579,47 +579,31 @@ inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); 
 }  // namespace
 
 int exa_launch_residual_apply_from(exa_ctx* ctx, const double* D, double* Y, hipStream_t s);   // pa_kernels.hip
-int exa_launch_eds(exa_ctx* ctx, const double* J, hipStream_t s);
 
 int exa_launch_eds(exa_ctx* ctx, const double* J, hipStream_t s) {
-   if (ctx->qblk) hipLaunchKernelGGL(k_eds<true>, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->E, ctx->W_dev, ctx->G_dev, J, ctx->eDS);
-   else hipLaunchKernelGGL(k_eds<false>, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->E, ctx->W_dev, ctx->G_dev, J, ctx->eDS);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto qb) { hipLaunchKernelGGL(k_eds<qb.value>, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->E, ctx->W_dev, ctx->G_dev, J, ctx->eDS); }, ctx->qblk);
+   return exa_launched(ctx);
 }
 int exa_launch_residual_bbar(exa_ctx* ctx, const double* J, const double* S, double* Y, hipStream_t s) {
    hipLaunchKernelGGL(k_residual_bbar, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->E, ctx->W_dev, ctx->G_dev, J, S, ctx->eDS, Y);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   return exa_launched(ctx);
 }
 int exa_launch_assemble_ea_gen(exa_ctx* ctx, hipStream_t s) {
    const bool bbar = ctx->cfg.integ == EXA_INTEG_BBAR;
-   const dim3 grid(nblk(ctx->E, PA_BLK), 3 * ctx->n); const size_t lds = exa_g_lds_bytes(ctx->n, ctx->Q);
-   if (ctx->n == 8) {
-      if (bbar) hipLaunchKernelGGL((k_assemble_ea_gen<8, true>), grid, dim3(PA_BLK), lds, s, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat);
-      else hipLaunchKernelGGL((k_assemble_ea_gen<8, false>), grid, dim3(PA_BLK), lds, s, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat);
-   } else if (ctx->n == 27) {
-      if (bbar) hipLaunchKernelGGL((k_assemble_ea_gen<27, true>), grid, dim3(PA_BLK), lds, s, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat);
-      else hipLaunchKernelGGL((k_assemble_ea_gen<27, false>), grid, dim3(PA_BLK), lds, s, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat);
-   } else {   // any other order: run-time kernels
-      const dim3 g3(nblk(ctx->E, PA_BLK), 3 * ctx->n, ctx->n);
-      if (bbar) hipLaunchKernelGGL((k_assemble_ea_rt<true>), g3, dim3(PA_BLK), 0, s, ctx->n, ctx->Q, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat);
-      else hipLaunchKernelGGL((k_assemble_ea_rt<false>), g3, dim3(PA_BLK), 0, s, ctx->n, ctx->Q, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat);
-   }
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   const dim3 grid(exa_nblocks(ctx), 3 * ctx->n), g3(exa_nblocks(ctx), 3 * ctx->n, ctx->n); const size_t lds = exa_g_lds_bytes(ctx->n, ctx->Q);
+   if (ctx->n == 8 || ctx->n == 27) exa_dispatch([&](auto p2, auto bb) {
+      hipLaunchKernelGGL((k_assemble_ea_gen<p2.value ? 27 : 8, bb.value>), grid, dim3(PA_BLK), lds, s, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat); }, ctx->n == 27, bbar);
+   else exa_dispatch([&](auto bb) {   // any other order: run-time kernels
+      hipLaunchKernelGGL((k_assemble_ea_rt<bb.value>), g3, dim3(PA_BLK), 0, s, ctx->n, ctx->Q, ctx->E, ctx->pa, ctx->G_dev, ctx->W_dev, ctx->eDS, ctx->emat); }, bbar);
+   return exa_launched(ctx);
 }
 int exa_launch_ea_apply_gen(exa_ctx* ctx, const double* x, double* y, bool lvec, const uint8_t* mask, const double* gate, hipStream_t s) {
-   const unsigned nb = nblk(ctx->E, PA_BLK);
-   if (ctx->n == 8) {
-      if (lvec) hipLaunchKernelGGL((k_ea_apply_gen<8, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-      else hipLaunchKernelGGL((k_ea_apply_gen<8, false>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-   } else if (ctx->n == 27) {
-      if (lvec) hipLaunchKernelGGL((k_ea_apply_gen<27, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-      else hipLaunchKernelGGL((k_ea_apply_gen<27, false>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-   } else {
-      const dim3 g2(nb, 3 * ctx->n);
-      if (lvec) hipLaunchKernelGGL((k_ea_apply_rt<true>), g2, dim3(PA_BLK), 0, s, ctx->n, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-      else hipLaunchKernelGGL((k_ea_apply_rt<false>), g2, dim3(PA_BLK), 0, s, ctx->n, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-   }
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   const unsigned nb = exa_nblocks(ctx);
+   if (ctx->n == 8 || ctx->n == 27) exa_dispatch([&](auto p2, auto lv) {
+      hipLaunchKernelGGL((k_ea_apply_gen<p2.value ? 27 : 8, lv.value>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate); }, ctx->n == 27, lvec);
+   else exa_dispatch([&](auto lv) {
+      hipLaunchKernelGGL((k_ea_apply_rt<lv.value>), dim3(nb, 3 * ctx->n), dim3(PA_BLK), 0, s, ctx->n, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate); }, lvec);
+   return exa_launched(ctx);
 }
 // one-dimensional basis tables of the p = 2 kernels + a check of the node numbering they have compiled in
 int exa_ensure_p2_tables(exa_ctx* ctx) {
@@ -636,58 +620,49 @@ int exa_ensure_p2_tables(exa_ctx* ctx) {
 int exa_launch_geom_p2(exa_ctx* ctx, const double* xl, const double* vl, double* J, double* Lx, hipStream_t s) {
    if (ctx->n != 27 || !ctx->qblk) { ctx->err = "geometry pre-pass: p = 2, element-blocked layout"; return EXA_ERR_UNSUPPORTED; }
    if (int rc = exa_ensure_p2_tables(ctx)) return rc;
-   hipLaunchKernelGGL(k_geom_p2, dim3(nblk(ctx->E, PA_BLK)), dim3(PA_BLK), 0, s, ctx->E, ctx->T1_dev, xl, vl, ctx->conn, ctx->nnodes, J, Lx);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   hipLaunchKernelGGL(k_geom_p2, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->T1_dev, xl, vl, ctx->conn, ctx->nnodes, J, Lx);
+   return exa_launched(ctx);
 }
 // element-average gradients of the B-bar integrator from a Jacobian field (driver: the record route has no exa_grad_setup pass that would refresh them)
 int exa_grad_refresh_bbar(exa_ctx* ctx, const double* J, hipStream_t s) {
    if (ctx->cfg.integ != EXA_INTEG_BBAR) return EXA_OK;
-   if (!ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, sizeof(double) * 3 * ctx->n * PA_BLK * (size_t)((ctx->E + PA_BLK - 1) / PA_BLK)));
+   if (!ctx->eDS) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDS, exa_eds_bytes(ctx)));
    return exa_launch_eds(ctx, J, s);
 }
 // residual on L-vectors at p = 2 (B-bar: element-average gradients refreshed from J first)
 int exa_launch_residual_p2(exa_ctx* ctx, const double* J, const double* S, double* y, hipStream_t s) {
    if (int rc = exa_ensure_p2_tables(ctx)) return rc;
-   const bool bbar = ctx->cfg.integ == EXA_INTEG_BBAR; const unsigned nb = nblk(ctx->E, PA_BLK);
+   const bool bbar = ctx->cfg.integ == EXA_INTEG_BBAR;
    if (bbar) { if (int rc = exa_launch_eds(ctx, J, s)) return rc; }
-#define RES_LAUNCH(B, QBV) hipLaunchKernelGGL((k_residual_p2<B, QBV>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->T1_dev, ctx->W_dev, J, S, ctx->eDS, y, ctx->conn, ctx->nnodes)
-   if (bbar) { if (ctx->qblk) RES_LAUNCH(true, true); else RES_LAUNCH(true, false); }
-   else { if (ctx->qblk) RES_LAUNCH(false, true); else RES_LAUNCH(false, false); }
-#undef RES_LAUNCH
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto bb, auto qb) {
+      hipLaunchKernelGGL((k_residual_p2<bb.value, qb.value>), dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->T1_dev, ctx->W_dev, J, S, ctx->eDS, y, ctx->conn, ctx->nnodes); }, bbar, ctx->qblk);
+   return exa_launched(ctx);
 }
 // matrix-free p = 2 action on L-vectors; `trans` selects the operator of the assembled matrices (EA) instead of the PA one
 int exa_launch_mf_apply_p2(exa_ctx* ctx, const double* x, double* y, const uint8_t* mask, const double* gate, bool trans, hipStream_t s) {
    if (ctx->n != 27 || ctx->Q != 27) { ctx->err = "matrix-free action is built for p = 2 (27 nodes, 27 points)"; return EXA_ERR_UNSUPPORTED; }
-   const unsigned nb = nblk(ctx->E, PA_BLK); const bool bbar = ctx->cfg.integ == EXA_INTEG_BBAR;
    if (int rc = exa_ensure_p2_tables(ctx)) return rc;
-#define MF_LAUNCH(B, T, CM) hipLaunchKernelGGL((k_mf_apply_p2<B, T, CM>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, CM ? ctx->pa_c : ctx->pa, ctx->T1_dev, ctx->W_dev, ctx->eDS, x, y, ctx->conn, ctx->nnodes, mask, gate)
-   const bool cm = ctx->pa_c != nullptr && ctx->pac_pairs == PAC_PAIRS_GEO;
-   if (cm) {
-      if (bbar) { if (trans) MF_LAUNCH(true, true, true); else MF_LAUNCH(true, false, true); }
-      else { if (trans) MF_LAUNCH(false, true, true); else MF_LAUNCH(false, false, true); }
-   } else {
-      if (bbar) { if (trans) MF_LAUNCH(true, true, false); else MF_LAUNCH(true, false, false); }
-      else { if (trans) MF_LAUNCH(false, true, false); else MF_LAUNCH(false, false, false); }
-   }
-#undef MF_LAUNCH
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto bb, auto t, auto cm) {
+      hipLaunchKernelGGL((k_mf_apply_p2<bb.value, t.value, cm.value>), dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, cm.value ? ctx->pa_c : ctx->pa, ctx->T1_dev, ctx->W_dev, ctx->eDS, x, y,
+                         ctx->conn, ctx->nnodes, mask, gate); }, ctx->cfg.integ == EXA_INTEG_BBAR, trans, exa_has_compact_geo(ctx));
+   return exa_launched(ctx);
 }
 int exa_launch_ea_diag_gen(exa_ctx* ctx, double* y, hipStream_t s) {
-   hipLaunchKernelGGL(k_ea_diag_gen, dim3(nblk(ctx->E, PA_BLK)), dim3(PA_BLK), 0, s, ctx->E, 3 * ctx->n, ctx->emat, y);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   hipLaunchKernelGGL(k_ea_diag_gen, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, 3 * ctx->n, ctx->emat, y);
+   return exa_launched(ctx);
 }
 int exa_launch_ea_export_gen(exa_ctx* ctx, double* out, hipStream_t s) {
-   hipLaunchKernelGGL(k_ea_export_gen, dim3(nblk(ctx->E, PA_BLK)), dim3(PA_BLK), 0, s, ctx->E, 3 * ctx->n, ctx->emat, out);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   hipLaunchKernelGGL(k_ea_export_gen, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, 3 * ctx->n, ctx->emat, out);
+   return exa_launched(ctx);
 }
 // generic PA action on E-vectors: stage 1 into the (3,3,Q,E) scratch `dmat`, stage 2 = the AddMultPA contraction
 int exa_launch_pa_apply_gen(exa_ctx* ctx, const double* x, double* y, hipStream_t s) {
    hipLaunchKernelGGL(k_pa_apply_stage1, dim3(nblk(ctx->P, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->P, ctx->G_dev, ctx->pa, x, ctx->tbuf);
-   EXA_HIP_CHECK(ctx, hipGetLastError());
+   if (int rc = exa_launched(ctx)) return rc;
    return exa_launch_residual_apply_from(ctx, ctx->tbuf, y, s);
 }
 int exa_launch_pa_diag_gen(exa_ctx* ctx, double* y, hipStream_t s) {
    hipLaunchKernelGGL(k_pa_diag_gen, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->E, ctx->G_dev, ctx->pa, y);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   return exa_launched(ctx);
 }
+

@@ -136,7 +136,7 @@ __global__ void k_residual_apply(const int Q, const int n, const int E, const do
 // pa record for every point of an element; one lane per element (coalesced 16-byte stores).  CMP: also the compact record.
 // TRD: the compact record holds D^T (element-assembly contexts: their action applies C^T, and the kernels then run the same code)
 // FULL = false: only the compact records are written - all that the L-vector action with recomputed geometry reads (46 of the 117 doubles this pass moves per
-// point otherwise); the 46-double records are then built on demand from the same arrays (exa_launch_grad_setup_pa, pa_lazy).
+// point otherwise); the 46-double records are then built on demand from the same arrays (exa_launch_grad_setup_pa, pa_pending).
 // (Round 6, measured at 128^3 on the reference layout: one lane per POINT - contiguous 16-byte loads of its own 288-byte row, stores of 8 x 128-byte segments -
 //  is slower than this form, 5.2 against 2.5 ms for the 46-double records: 64 separate lines per load instruction either way, and the stores lose their 1 KB rows.)
 template <bool QB, int CMP, bool TRD, bool FULL = true>
@@ -603,164 +603,130 @@ __global__ void k_vol_avg_partial(const int Q, const int64_t P, const int vdim, 
 static inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 int exa_launch_jacobians(exa_ctx* ctx, const double* xe, double* J, hipStream_t s) {
-   if (ctx->qblk) hipLaunchKernelGGL(k_jacobians<true>, dim3(nblk(ctx->P, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->P, ctx->G_dev, xe, J);
-   else hipLaunchKernelGGL(k_jacobians<false>, dim3(nblk(ctx->P, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->P, ctx->G_dev, xe, J);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto qb) { hipLaunchKernelGGL(k_jacobians<qb.value>, dim3(nblk(ctx->P, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->P, ctx->G_dev, xe, J); }, ctx->qblk);
+   return exa_launched(ctx);
 }
 int exa_launch_jacobians_from_geom(exa_ctx* ctx, const double* gj, double* J, hipStream_t s) {
-   if (ctx->qblk) hipLaunchKernelGGL(k_jacobians_from_geom<true>, dim3(nblk(ctx->P, 256)), dim3(256), 0, s, ctx->Q, ctx->P, gj, J);
-   else hipLaunchKernelGGL(k_jacobians_from_geom<false>, dim3(nblk(ctx->P, 256)), dim3(256), 0, s, ctx->Q, ctx->P, gj, J);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto qb) { hipLaunchKernelGGL(k_jacobians_from_geom<qb.value>, dim3(nblk(ctx->P, 256)), dim3(256), 0, s, ctx->Q, ctx->P, gj, J); }, ctx->qblk);
+   return exa_launched(ctx);
 }
 int exa_launch_grad_calc(exa_ctx* ctx, const double* J, const double* fe, double* out, hipStream_t s) {
-   if (ctx->qblk) hipLaunchKernelGGL(k_grad_calc<true>, dim3(nblk(ctx->P, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->P, J, ctx->G_dev, fe, out);
-   else hipLaunchKernelGGL(k_grad_calc<false>, dim3(nblk(ctx->P, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->P, J, ctx->G_dev, fe, out);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto qb) { hipLaunchKernelGGL(k_grad_calc<qb.value>, dim3(nblk(ctx->P, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->P, J, ctx->G_dev, fe, out); }, ctx->qblk);
+   return exa_launched(ctx);
 }
 int exa_launch_residual_setup(exa_ctx* ctx, const double* J, const double* S, hipStream_t s) {
    hipLaunchKernelGGL(k_residual_setup, dim3(nblk(ctx->P, 256)), dim3(256), 0, s, ctx->Q, ctx->P, ctx->W_dev, J, S, ctx->dmat);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
-}
-int exa_launch_residual_apply(exa_ctx* ctx, double* Y, hipStream_t s) {
-   hipLaunchKernelGGL(k_residual_apply, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->E, ctx->G_dev, ctx->dmat, Y);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   return exa_launched(ctx);
 }
 int exa_launch_residual_apply_from(exa_ctx* ctx, const double* D, double* Y, hipStream_t s) {
    hipLaunchKernelGGL(k_residual_apply, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), exa_g_lds_bytes(ctx->n, ctx->Q), s, ctx->Q, ctx->n, ctx->E, ctx->G_dev, D, Y);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   return exa_launched(ctx);
 }
+int exa_launch_residual_apply(exa_ctx* ctx, double* Y, hipStream_t s) { return exa_launch_residual_apply_from(ctx, ctx->dmat, Y, s); }
 int exa_det_prepare(exa_ctx* ctx);   // capi.hip: builds the node -> element table on first use
 static int det_gather(exa_ctx* ctx, double* y, const double* gate, hipStream_t s) {
    hipLaunchKernelGGL(k_e2l_gather<true>, dim3(nblk(ctx->nnodes, 256)), dim3(256), 0, s, ctx->n, ctx->nnodes, ctx->n2e_off, ctx->n2e_idx, ctx->ev_det, y, gate);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   return exa_launched(ctx);
 }
 int exa_launch_residual_p1(exa_ctx* ctx, const double* J, const double* S, double* y, bool lvec, hipStream_t s) {
-   const unsigned nb = nblk(ctx->E, PA_BLK);
    double* ev = nullptr;
    if (lvec && ctx->det) { if (int rc = exa_det_prepare(ctx)) return rc; ev = ctx->ev_det; }
-   if (lvec && J == nullptr) {   // geometry from the nodal coordinates registered with exa_grad_set_coords
-      if (ctx->qblk) hipLaunchKernelGGL((k_residual_p1<true, true, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->W_dev, J, S, y, ctx->conn, ctx->nnodes, ev, ctx->coords_lvec);
-      else hipLaunchKernelGGL((k_residual_p1<true, false, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->W_dev, J, S, y, ctx->conn, ctx->nnodes, ev, ctx->coords_lvec);
-   } else if (lvec && ctx->qblk) hipLaunchKernelGGL((k_residual_p1<true, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->W_dev, J, S, y, ctx->conn, ctx->nnodes, ev);
-   else if (lvec) hipLaunchKernelGGL((k_residual_p1<true, false>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->W_dev, J, S, y, ctx->conn, ctx->nnodes, ev);
-   else if (ctx->qblk) hipLaunchKernelGGL((k_residual_p1<false, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->W_dev, J, S, y, ctx->conn, ctx->nnodes);
-   else hipLaunchKernelGGL((k_residual_p1<false, false>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->W_dev, J, S, y, ctx->conn, ctx->nnodes);
-   EXA_HIP_CHECK(ctx, hipGetLastError());
-   if (ev) return det_gather(ctx, y, nullptr, s);
-   return EXA_OK;
-}
-// the 46-double records of a context whose last exa_grad_setup wrote the compact ones only: built now, from the arrays that call was given
-static int pa_full_on_demand(exa_ctx* ctx, hipStream_t s) {
-   if (!ctx->pa_lazy) return EXA_OK;
-   const dim3 grid(nblk(ctx->E, PA_BLK));
-   if (ctx->qblk) hipLaunchKernelGGL((k_grad_setup_pa<true, 0, false>), grid, dim3(PA_BLK), 0, s, ctx->Q, ctx->E, ctx->lazy_dt, ctx->W_dev, ctx->lazy_J, ctx->lazy_C, ctx->pa, ctx->pa_c);
-   else hipLaunchKernelGGL((k_grad_setup_pa<false, 0, false>), grid, dim3(PA_BLK), 0, s, ctx->Q, ctx->E, ctx->lazy_dt, ctx->W_dev, ctx->lazy_J, ctx->lazy_C, ctx->pa, ctx->pa_c);
-   EXA_HIP_CHECK(ctx, hipGetLastError());
-   ctx->pa_lazy = false;
-   return EXA_OK;
+   auto go = [&](auto lv, auto qb, auto geo) {
+      hipLaunchKernelGGL((k_residual_p1<lv.value, qb.value, geo.value>), dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->W_dev, J, S, y, ctx->conn, ctx->nnodes, ev, geo.value ? ctx->coords_lvec : nullptr);
+   };
+   // a null J: geometry from the nodal coordinates registered with exa_grad_set_coords.  (GEO needs the connectivity: no E-vector instantiation of it)
+   if (lvec) exa_dispatch([&](auto qb, auto geo) { go(EXA_YES, qb, geo); }, ctx->qblk, J == nullptr);
+   else exa_dispatch([&](auto qb) { go(EXA_NO, qb, EXA_NO); }, ctx->qblk);
+   if (int rc = exa_launched(ctx)) return rc;
+   return ev ? det_gather(ctx, y, nullptr, s) : EXA_OK;
 }
 
+// k_grad_setup_pa<QB, NP, TRD, FULL> on the context's buffers
+template <int NP, bool TRD, bool FULL>
+static int setup_pa(exa_ctx* ctx, double dt, const double* J, const double* C, hipStream_t s) {
+   exa_dispatch([&](auto qb) { hipLaunchKernelGGL((k_grad_setup_pa<qb.value, NP, TRD, FULL>), dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->Q, ctx->E, dt, ctx->W_dev, J, C, ctx->pa, ctx->pa_c); }, ctx->qblk);
+   return exa_launched(ctx);
+}
+// the 46-double records of a context whose last exa_grad_setup wrote the compact ones only
+static int pa_full_on_demand(exa_ctx* ctx, hipStream_t s) { return exa_build_pending(ctx, ctx->pa_pending, setup_pa<0, false, true>, s); }
+
 int exa_launch_grad_setup_pa(exa_ctx* ctx, double dt, const double* J, const double* C, hipStream_t s) {
-   ctx->pa_lazy = false;
-   const dim3 grid(nblk(ctx->E, PA_BLK));
-#define GS_LAUNCH(QBV, NP, TR) hipLaunchKernelGGL((k_grad_setup_pa<QBV, NP, TR>), grid, dim3(PA_BLK), 0, s, ctx->Q, ctx->E, dt, ctx->W_dev, J, C, ctx->pa, ctx->pa_c)
-#define GS_LAUNCH2(NP, TR) do { if (ctx->qblk) GS_LAUNCH(true, NP, TR); else GS_LAUNCH(false, NP, TR); } while (0)
-   const bool trd = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
+   ctx->pa_pending = false;
+   if (!ctx->pa_c) return setup_pa<0, false, true>(ctx, dt, J, C, s);
+   const bool trd = ctx->cfg.assembly == EXA_ASSEMBLY_EA, cmp = exa_has_compact(ctx);
    static const bool lazy_off = [] { const char* e = std::getenv("EXA_GRAD_SETUP_LAZY"); return e && std::strcmp(e, "off") == 0; }();   // A/B switch: both record sets in one pass, as in rounds 3-5
-   if (ctx->pa_c && ctx->pac_pairs == PAC_PAIRS && !trd && !lazy_off) {
-      // p = 1 partial assembly: the L-vector action with recomputed geometry streams the compact records alone (exa_grad_set_coords); the diagonal, the
-      // E-vector action and an action without coordinates need the 46-double ones, which are built on demand - J and C must stay as they are until the next
-      // exa_grad_setup (they do in a Newton iteration: the reference calls AssembleGradDiagonalPA right after AssembleGradPA, src/mechanics_operator.cpp:436-443)
-      if (ctx->qblk) hipLaunchKernelGGL((k_grad_setup_pa<true, PAC_PAIRS, false, false>), grid, dim3(PA_BLK), 0, s, ctx->Q, ctx->E, dt, ctx->W_dev, J, C, ctx->pa, ctx->pa_c);
-      else hipLaunchKernelGGL((k_grad_setup_pa<false, PAC_PAIRS, false, false>), grid, dim3(PA_BLK), 0, s, ctx->Q, ctx->E, dt, ctx->W_dev, J, C, ctx->pa, ctx->pa_c);
-      ctx->pa_lazy = true; ctx->lazy_J = J; ctx->lazy_C = C; ctx->lazy_dt = dt;
+   // p = 1 partial assembly: the L-vector action with recomputed geometry streams the compact records alone (exa_grad_set_coords), and so does the E-vector action
+   // on the compact records with geometry; the diagonal and the other actions need the 46-double ones, which are then built on demand (exa_ctx, pa_pending)
+   if (!trd && !lazy_off && (cmp || (exa_has_compact_geo(ctx) && ctx->n == 8))) {
+      ctx->pa_pending = true;
+      return cmp ? setup_pa<PAC_PAIRS, false, false>(ctx, dt, J, C, s) : setup_pa<PAC_PAIRS_GEO, false, false>(ctx, dt, J, C, s);
    }
-   else if (ctx->pa_c && ctx->pac_pairs == PAC_PAIRS_GEO && ctx->n == 8 && !trd && !lazy_off) {      // p = 1, E-vector action on the compact records with geometry: same scheme
-      if (ctx->qblk) hipLaunchKernelGGL((k_grad_setup_pa<true, PAC_PAIRS_GEO, false, false>), grid, dim3(PA_BLK), 0, s, ctx->Q, ctx->E, dt, ctx->W_dev, J, C, ctx->pa, ctx->pa_c);
-      else hipLaunchKernelGGL((k_grad_setup_pa<false, PAC_PAIRS_GEO, false, false>), grid, dim3(PA_BLK), 0, s, ctx->Q, ctx->E, dt, ctx->W_dev, J, C, ctx->pa, ctx->pa_c);
-      ctx->pa_lazy = true; ctx->lazy_J = J; ctx->lazy_C = C; ctx->lazy_dt = dt;
-   }
-   else if (ctx->pa_c && ctx->pac_pairs == PAC_PAIRS) { if (trd) GS_LAUNCH2(PAC_PAIRS, true); else GS_LAUNCH2(PAC_PAIRS, false); }
-   else if (ctx->pa_c) { if (trd) GS_LAUNCH2(PAC_PAIRS_GEO, true); else GS_LAUNCH2(PAC_PAIRS_GEO, false); }
-   else GS_LAUNCH2(0, false);
-#undef GS_LAUNCH2
-#undef GS_LAUNCH
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   if (cmp) return trd ? setup_pa<PAC_PAIRS, true, true>(ctx, dt, J, C, s) : setup_pa<PAC_PAIRS, false, true>(ctx, dt, J, C, s);
+   return trd ? setup_pa<PAC_PAIRS_GEO, true, true>(ctx, dt, J, C, s) : setup_pa<PAC_PAIRS_GEO, false, true>(ctx, dt, J, C, s);
 }
 // blk0 / nblk_range: sub-range of the 64-element blocks (nblk_range < 0: all of them)
 int exa_launch_grad_apply_p1(exa_ctx* ctx, const double* x, double* y, bool lvec, const uint8_t* mask, const double* gate, hipStream_t s, bool trans, int blk0, int nblk_range) {
-   const unsigned nball = nblk(ctx->E, PA_BLK);
    const bool ranged = nblk_range >= 0;
-   if (ranged && (!lvec || ctx->det || blk0 < 0 || (unsigned)(blk0 + nblk_range) > nball)) { ctx->err = "exa_launch_grad_apply_p1: block ranges are for the atomic L-vector action"; return EXA_ERR_ARG; }
-   const unsigned nb = ranged ? (unsigned)nblk_range : nball;
+   if (ranged && (!lvec || ctx->det || blk0 < 0 || (unsigned)(blk0 + nblk_range) > exa_nblocks(ctx))) { ctx->err = "exa_launch_grad_apply_p1: block ranges are for the atomic L-vector action"; return EXA_ERR_ARG; }
+   const unsigned nb = ranged ? (unsigned)nblk_range : exa_nblocks(ctx);
    if (!ranged) blk0 = 0;
    if (nb == 0) return EXA_OK;
-   if (!(lvec && ctx->coords_lvec && ctx->pa_c && ctx->pac_pairs == PAC_PAIRS) && !(!lvec && ctx->pa_c && ctx->pac_pairs == PAC_PAIRS_GEO && ctx->n == 8)) {
-      if (int rc = pa_full_on_demand(ctx, s)) return rc;   // every other form streams the 46-double records
-   }
+   const bool cmp = exa_streams_compact(ctx, lvec), geo = lvec && ctx->coords_lvec;   // L-vector forms: compact record, or the 46-double one with / without recomputed geometry
+   const bool cg = !lvec && exa_has_compact_geo(ctx) && ctx->n == 8;                   // E-vector action on the compact records with geometry
+   if (!cmp && !cg) { if (int rc = pa_full_on_demand(ctx, s)) return rc; }             // every other form streams the 46-double records
    double* ev = nullptr;
    if (lvec && ctx->det) { if (int rc = exa_det_prepare(ctx)) return rc; ev = ctx->ev_det; }
    // record stream of this launch: non-temporal loads only when it is larger than what the caches keep from one launch to the next (exa_internal.hpp, exa_stream_nt)
-   const bool nt = exa_stream_nt((size_t)ctx->P * 16 * ((lvec && ctx->coords_lvec && ctx->pa_c && ctx->pac_pairs == PAC_PAIRS) ? PAC_PAIRS : ((lvec && ctx->coords_lvec) ? 18 : PA_PAIRS)));
-#define GA_LAUNCH(G, CM, T, REC, CRD) do { if (nt) hipLaunchKernelGGL((k_grad_apply_p1<true, G, CM, T, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, REC, x, y, ctx->conn, ctx->nnodes, mask, gate, CRD, ev, blk0); \
-      else hipLaunchKernelGGL((k_grad_apply_p1<true, G, CM, T, false>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, REC, x, y, ctx->conn, ctx->nnodes, mask, gate, CRD, ev, blk0); } while (0)
-   const double* none = nullptr;
-   if (lvec && ctx->coords_lvec && ctx->pa_c && ctx->pac_pairs == PAC_PAIRS) GA_LAUNCH(true, true, false, ctx->pa_c, ctx->coords_lvec);   // D or D^T in the record
-   else if (lvec && ctx->coords_lvec) { if (trans) GA_LAUNCH(true, false, true, ctx->pa, ctx->coords_lvec); else GA_LAUNCH(true, false, false, ctx->pa, ctx->coords_lvec); }
-   else if (lvec) { if (trans) GA_LAUNCH(false, false, true, ctx->pa, none); else GA_LAUNCH(false, false, false, ctx->pa, none); }
-   else if (ctx->pa_c && ctx->pac_pairs == PAC_PAIRS_GEO && ctx->n == 8)      // E-vector action on the compact records with geometry
-      hipLaunchKernelGGL((k_grad_apply_p1<false, false, false, false, true, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->pa_c, x, y, ctx->conn, ctx->nnodes, mask, gate, none);
-   else hipLaunchKernelGGL((k_grad_apply_p1<false, false>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->pa, x, y, ctx->conn, ctx->nnodes, mask, gate, none);
-#undef GA_LAUNCH
-   EXA_HIP_CHECK(ctx, hipGetLastError());
-   if (ev) return det_gather(ctx, y, gate, s);
-   return EXA_OK;
+   const bool nt = exa_stream_nt((size_t)ctx->P * 16 * (cmp ? PAC_PAIRS : (geo ? 18 : PA_PAIRS)));
+   auto go = [&](auto lv, auto g, auto cm, auto t, auto n, auto cgv) {
+      hipLaunchKernelGGL((k_grad_apply_p1<lv.value, g.value, cm.value, t.value, n.value, cgv.value>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, (cm.value || cgv.value) ? ctx->pa_c : ctx->pa, x, y,
+                         ctx->conn, ctx->nnodes, mask, gate, lv.value ? ctx->coords_lvec : nullptr, ev, blk0);
+   };
+   if (cmp) exa_dispatch([&](auto n) { go(EXA_YES, EXA_YES, EXA_YES, EXA_NO, n, EXA_NO); }, nt);   // D or D^T in the record: no compact + TRANS instantiation
+   else if (lvec) exa_dispatch([&](auto g, auto t, auto n) { go(EXA_YES, g, EXA_NO, t, n, EXA_NO); }, geo, trans, nt);
+   else exa_dispatch([&](auto cgv) { go(EXA_NO, EXA_NO, EXA_NO, EXA_NO, EXA_YES, cgv); }, cg);
+   if (int rc = exa_launched(ctx)) return rc;
+   return ev ? det_gather(ctx, y, gate, s) : EXA_OK;
 }
 // max over the points of the relative deviation of C from the compact tangent form; result as the bit pattern of a double in *out_dev
 int exa_launch_tangent_defect(exa_ctx* ctx, const double* C, unsigned long long* out_dev, hipStream_t s) {
    EXA_HIP_CHECK(ctx, hipMemsetAsync(out_dev, 0, sizeof(unsigned long long), s));
-   if (ctx->qblk) hipLaunchKernelGGL(k_tangent_defect<true>, dim3(nblk(ctx->P, 256)), dim3(256), 0, s, ctx->Q, ctx->P, C, out_dev);
-   else hipLaunchKernelGGL(k_tangent_defect<false>, dim3(nblk(ctx->P, 256)), dim3(256), 0, s, ctx->Q, ctx->P, C, out_dev);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto qb) { hipLaunchKernelGGL(k_tangent_defect<qb.value>, dim3(nblk(ctx->P, 256)), dim3(256), 0, s, ctx->Q, ctx->P, C, out_dev); }, ctx->qblk);
+   return exa_launched(ctx);
 }
 int exa_launch_grad_diag_p1(exa_ctx* ctx, double* y, hipStream_t s) {
    if (int rc = pa_full_on_demand(ctx, s)) return rc;
-   hipLaunchKernelGGL(k_grad_diag_p1, dim3(nblk(ctx->E, PA_BLK)), dim3(PA_BLK), 0, s, ctx->E, ctx->pa, y);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   hipLaunchKernelGGL(k_grad_diag_p1, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->pa, y);
+   return exa_launched(ctx);
 }
 int exa_launch_assemble_ea_p1(exa_ctx* ctx, hipStream_t s) {
-   hipLaunchKernelGGL(k_assemble_ea_p1, dim3(nblk(ctx->E, PA_BLK), 24), dim3(PA_BLK), 0, s, ctx->E, ctx->pa, ctx->emat);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   hipLaunchKernelGGL(k_assemble_ea_p1, dim3(exa_nblocks(ctx), 24), dim3(PA_BLK), 0, s, ctx->E, ctx->pa, ctx->emat);
+   return exa_launched(ctx);
 }
 int exa_launch_ea_apply_p1(exa_ctx* ctx, const double* x, double* y, bool lvec, const uint8_t* mask, const double* gate, hipStream_t s) {
-   const unsigned nb = nblk(ctx->E, PA_BLK);
-   if (lvec) hipLaunchKernelGGL(k_ea_apply_p1<true>, dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-   else hipLaunchKernelGGL(k_ea_apply_p1<false>, dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto lv) { hipLaunchKernelGGL(k_ea_apply_p1<lv.value>, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, x, y, ctx->conn, ctx->nnodes, mask, gate); }, lvec);
+   return exa_launched(ctx);
 }
 int exa_launch_ea_diag_p1(exa_ctx* ctx, double* y, hipStream_t s) {
-   hipLaunchKernelGGL(k_ea_diag_p1, dim3(nblk(ctx->E, PA_BLK)), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, y);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   hipLaunchKernelGGL(k_ea_diag_p1, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, y);
+   return exa_launched(ctx);
 }
 int exa_launch_ea_export_p1(exa_ctx* ctx, double* out, hipStream_t s) {
-   hipLaunchKernelGGL(k_ea_export_p1, dim3(nblk(ctx->E, PA_BLK)), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, out);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   hipLaunchKernelGGL(k_ea_export_p1, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->emat, out);
+   return exa_launched(ctx);
 }
 int exa_launch_restrict(exa_ctx* ctx, const double* L, double* Ev, hipStream_t s) {
    hipLaunchKernelGGL(k_restrict, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), 0, s, ctx->n, ctx->E, ctx->nnodes, ctx->conn, L, Ev);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   return exa_launched(ctx);
 }
 int exa_launch_restrict_T(exa_ctx* ctx, const double* Ev, double* L, hipStream_t s) {
    if (ctx->det) {
       if (int rc = exa_det_prepare(ctx)) return rc;
       hipLaunchKernelGGL(k_e2l_gather<false>, dim3(nblk(ctx->nnodes, 256)), dim3(256), 0, s, ctx->n, ctx->nnodes, ctx->n2e_off, ctx->n2e_idx, Ev, L, (const double*)nullptr);
-      EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
-   }
-   hipLaunchKernelGGL(k_restrict_T, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), 0, s, ctx->n, ctx->E, ctx->nnodes, ctx->conn, Ev, L);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   } else hipLaunchKernelGGL(k_restrict_T, dim3(nblk((int64_t)ctx->n * ctx->E, 256)), dim3(256), 0, s, ctx->n, ctx->E, ctx->nnodes, ctx->conn, Ev, L);
+   return exa_launched(ctx);
 }
 int exa_launch_vol_avg(exa_ctx* ctx, const double* J, const double* qf, int vdim, double* partial, int nb, hipStream_t s) {
-   if (ctx->qblk) hipLaunchKernelGGL(k_vol_avg_partial<true>, dim3(nb), dim3(256), sizeof(double) * 256, s, ctx->Q, ctx->P, vdim, ctx->W_dev, J, qf, partial);
-   else hipLaunchKernelGGL(k_vol_avg_partial<false>, dim3(nb), dim3(256), sizeof(double) * 256, s, ctx->Q, ctx->P, vdim, ctx->W_dev, J, qf, partial);
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto qb) { hipLaunchKernelGGL(k_vol_avg_partial<qb.value>, dim3(nb), dim3(256), sizeof(double) * 256, s, ctx->Q, ctx->P, vdim, ctx->W_dev, J, qf, partial); }, ctx->qblk);
+   return exa_launched(ctx);
 }

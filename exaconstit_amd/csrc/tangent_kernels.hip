@@ -250,21 +250,20 @@ inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); 
 
 template <int NCH>
 int launch_cols(exa_ctx* ctx, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, bool trans, hipStream_t s) {
-   const unsigned nb = nblk(ctx->E, PA_BLK);
+   const unsigned nb = exa_nblocks(ctx);
    if (nb == 0) return EXA_OK;
    ColGates<NCH> G;
    for (int k = 0; k < NCH; k++) G.g[k] = gates ? gates[k] : nullptr;
-   const bool cmp = ctx->pa_c && ctx->pac_pairs == PAC_PAIRS;
+   const bool cmp = exa_has_compact(ctx);
    if constexpr (NCH == 3) { if (!cmp) { ctx->err = "three columns per pass are built for the compact record"; return EXA_ERR_ARG; } }
    // (the hint follows the size of the record stream, as in exa_launch_grad_apply_p1)
    const bool nt = exa_stream_nt((size_t)ctx->P * 16 * (cmp ? PAC_PAIRS : 18));
-#define GC_LAUNCH(CM, T, REC) do { if (nt) hipLaunchKernelGGL((k_grad_apply_p1_cols<NCH, CM, T, true>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, REC, x, ldx, y, ldy, ctx->conn, ctx->nnodes, mask, G, ctx->coords_lvec); \
-      else hipLaunchKernelGGL((k_grad_apply_p1_cols<NCH, CM, T, false>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, REC, x, ldx, y, ldy, ctx->conn, ctx->nnodes, mask, G, ctx->coords_lvec); } while (0)
-   if (cmp) GC_LAUNCH(true, false, ctx->pa_c);
-   else if constexpr (NCH < 3) { if (trans) GC_LAUNCH(false, true, ctx->pa); else GC_LAUNCH(false, false, ctx->pa); }
-#undef GC_LAUNCH
-   EXA_HIP_CHECK(ctx, hipGetLastError());
-   return EXA_OK;
+   auto go = [&](auto cm, auto t, auto n) {
+      hipLaunchKernelGGL((k_grad_apply_p1_cols<NCH, cm.value, t.value, n.value>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, cm.value ? ctx->pa_c : ctx->pa, x, ldx, y, ldy, ctx->conn, ctx->nnodes, mask, G, ctx->coords_lvec);
+   };
+   if (cmp) exa_dispatch([&](auto n) { go(EXA_YES, EXA_NO, n); }, nt);   // D or D^T in the record
+   else if constexpr (NCH < 3) exa_dispatch([&](auto t, auto n) { go(EXA_NO, t, n); }, trans, nt);   // (no three-column instantiation on the 46-double record)
+   return exa_launched(ctx);
 }
 
 }  // namespace
@@ -274,7 +273,7 @@ int launch_cols(exa_ctx* ctx, const double* x, int64_t ldx, double* y, int64_t l
 int exa_launch_grad_apply_p1_cols(exa_ctx* ctx, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, bool trans,
                                   int nch, hipStream_t s) {
    // (the 36-double record and its successor next to three columns' sums do not fit the register file: two columns per pass there)
-   if (nch > 2 && !(ctx->pa_c && ctx->pac_pairs == PAC_PAIRS)) nch = 2;
+   if (nch > 2 && !exa_has_compact(ctx)) nch = 2;
    int k = 0;
    while (k < ncols) {
       const int left = ncols - k;
@@ -293,8 +292,7 @@ int exa_launch_grad_apply_p1_cols(exa_ctx* ctx, int ncols, const double* x, int6
 int exa_launch_affine_columns(exa_ctx* ctx, int nn, const double* xc, const double* org3, double* out, int64_t ld, hipStream_t s) {
    double3v o; for (int i = 0; i < 3; i++) o.a[i] = org3[i];
    if (nn > 0) hipLaunchKernelGGL(k_affine_columns, dim3(nblk(nn, 256)), dim3(256), 0, s, nn, xc, o, out, ld);
-   EXA_HIP_CHECK(ctx, hipGetLastError());
-   return EXA_OK;
+   return exa_launched(ctx);
 }
 
 // out[9 m + 3 k + l], m < ncols; work: >= EXA_MACRO_BLOCKS * 9 * 9 doubles
@@ -314,8 +312,7 @@ int exa_launch_macro_contract(exa_ctx* ctx, int nn, int ncols, const double* y, 
          m += 1;
       }
    }
-   EXA_HIP_CHECK(ctx, hipGetLastError());
-   return EXA_OK;
+   return exa_launched(ctx);
 }
 
 // private (scratch) bytes per lane of the kernels of this file in the loaded code object: out8 = { k_grad_apply_p1_cols<1>, <2>, <3> (the largest

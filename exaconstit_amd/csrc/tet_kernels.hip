@@ -207,7 +207,6 @@ __global__ __launch_bounds__(PA_BLK) void k_tet_apply_p2(const int E, const doub
       for (int a = 0; a < N; a++) atomicAdd(&y[g[a] + (int64_t)nnodes * c], Y[c][a]);
 }
 
-inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
 
 }  // namespace
 
@@ -215,15 +214,11 @@ inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); 
 int exa_launch_tet_setup(exa_ctx* ctx, double dt, const double* J, const double* C, hipStream_t s) {
    if (ctx->geom != EXA_GEOM_TET) { ctx->err = "tetrahedron set-up on a hexahedron context"; return EXA_ERR_STATE; }
    if (ctx->p != 1) return EXA_OK;
-   const size_t bytes = (size_t)nblk(ctx->E, PA_BLK) * TET_PAIRS * 2 * PA_BLK * sizeof(double);
+   const size_t bytes = (size_t)exa_nblocks(ctx) * TET_PAIRS * 2 * PA_BLK * sizeof(double);
    if (!ctx->tet_rec) { EXA_HIP_CHECK(ctx, hipMalloc(&ctx->tet_rec, bytes)); EXA_HIP_CHECK(ctx, hipMemsetAsync(ctx->tet_rec, 0, bytes, s)); }
-   const bool trd = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
-   const dim3 grid(nblk(ctx->E, PA_BLK));
-   if (ctx->qblk) { if (trd) hipLaunchKernelGGL((k_tet_setup_p1<true, true>), grid, dim3(PA_BLK), 0, s, ctx->E, dt, ctx->W_dev, J, C, ctx->tet_rec);
-                    else hipLaunchKernelGGL((k_tet_setup_p1<true, false>), grid, dim3(PA_BLK), 0, s, ctx->E, dt, ctx->W_dev, J, C, ctx->tet_rec); }
-   else { if (trd) hipLaunchKernelGGL((k_tet_setup_p1<false, true>), grid, dim3(PA_BLK), 0, s, ctx->E, dt, ctx->W_dev, J, C, ctx->tet_rec);
-          else hipLaunchKernelGGL((k_tet_setup_p1<false, false>), grid, dim3(PA_BLK), 0, s, ctx->E, dt, ctx->W_dev, J, C, ctx->tet_rec); }
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   exa_dispatch([&](auto qb, auto trd) { hipLaunchKernelGGL((k_tet_setup_p1<qb.value, trd.value>), dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, dt, ctx->W_dev, J, C, ctx->tet_rec); },
+                ctx->qblk, ctx->cfg.assembly == EXA_ASSEMBLY_EA);
+   return exa_launched(ctx);
 }
 
 // driver-internal: whether exa_grad_setup builds the element records of the fused p = 1 action (off: the action is not going to run - table-driven
@@ -237,27 +232,19 @@ int exa_tet_set_fused_action(exa_ctx* ctx, int on) {
 // p = 1 with nodal coordinates registered (exa_grad_set_coords): J^-1 recomputed from them (GEO)
 int exa_launch_tet_apply(exa_ctx* ctx, const double* x, double* y, const uint8_t* mask, const double* gate, hipStream_t s) {
    if (ctx->geom != EXA_GEOM_TET) { ctx->err = "tetrahedron action on a hexahedron context"; return EXA_ERR_STATE; }
-   const unsigned nb = nblk(ctx->E, PA_BLK);
+   const unsigned nb = exa_nblocks(ctx);
    if (nb == 0) return EXA_OK;
    if (ctx->p == 1) {
-      if (ctx->tet_rec_stale) {   // (exa_grad_setup did not expect this action; never inside the driver's captured PCG chunk, whose setup builds them)
-         if (int rc = exa_launch_tet_setup(ctx, ctx->tet_dt, ctx->tet_J, ctx->tet_C, s)) return rc;
-         ctx->tet_rec_stale = false;
-      }
+      // (records the set-up did not build; never inside the driver's captured PCG chunk, whose set-up builds them)
+      if (int rc = exa_build_pending(ctx, ctx->tet_pending, exa_launch_tet_setup, s)) return rc;
       if (!ctx->tet_rec) { ctx->err = "tetrahedron action: no element records (exa_grad_setup)"; return EXA_ERR_STATE; }
       const bool geo = ctx->coords_lvec != nullptr;
-      const bool nt = exa_stream_nt((size_t)nb * PA_BLK * (geo ? 18 : TET_PAIRS) * 16);
-#define TET1(NTV, G) hipLaunchKernelGGL((k_tet_apply_p1<NTV, G>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->tet_rec, x, y, ctx->conn, ctx->nnodes, mask, gate, ctx->coords_lvec)
-      if (geo) { if (nt) TET1(true, true); else TET1(false, true); }
-      else { if (nt) TET1(true, false); else TET1(false, false); }
-#undef TET1
+      exa_dispatch([&](auto nt, auto g) { hipLaunchKernelGGL((k_tet_apply_p1<nt.value, g.value>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->tet_rec, x, y, ctx->conn, ctx->nnodes, mask, gate, ctx->coords_lvec); },
+                   exa_stream_nt((size_t)nb * PA_BLK * (geo ? 18 : TET_PAIRS) * 16), geo);
    } else {
       if (ctx->n != 10 || ctx->Q != 14) { ctx->err = "tetrahedron action: p = 1 or 2"; return EXA_ERR_UNSUPPORTED; }
-      const bool nt = exa_stream_nt((size_t)ctx->P * PA_PAIRS * 16), tr = ctx->cfg.assembly == EXA_ASSEMBLY_EA;
-#define TET2(T, NTV) hipLaunchKernelGGL((k_tet_apply_p2<T, NTV>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->pa, ctx->G_dev, x, y, ctx->conn, ctx->nnodes, mask, gate)
-      if (tr) { if (nt) TET2(true, true); else TET2(true, false); }
-      else { if (nt) TET2(false, true); else TET2(false, false); }
-#undef TET2
+      exa_dispatch([&](auto tr, auto nt) { hipLaunchKernelGGL((k_tet_apply_p2<tr.value, nt.value>), dim3(nb), dim3(PA_BLK), 0, s, ctx->E, ctx->pa, ctx->G_dev, x, y, ctx->conn, ctx->nnodes, mask, gate); },
+                   ctx->cfg.assembly == EXA_ASSEMBLY_EA, exa_stream_nt((size_t)ctx->P * PA_PAIRS * 16));
    }
-   EXA_HIP_CHECK(ctx, hipGetLastError()); return EXA_OK;
+   return exa_launched(ctx);
 }
