@@ -39,6 +39,7 @@ int exa_launch_assemble_ea_gen(exa_ctx*, hipStream_t);
 int exa_launch_ea_apply_gen(exa_ctx*, const double*, double*, bool, const uint8_t*, const double*, hipStream_t);
 int exa_launch_mf_apply_p2(exa_ctx*, const double*, double*, const uint8_t*, const double*, bool, hipStream_t);
 int exa_launch_residual_p2(exa_ctx*, const double*, const double*, double*, hipStream_t);
+int exa_launch_mg_p2_build(exa_ctx*, const int*, const int32_t*, const uint8_t*, const uint8_t*, double*, double*, bool, hipStream_t);
 int exa_launch_tangent_defect(exa_ctx*, const double*, unsigned long long*, hipStream_t);
 int exa_launch_ea_diag_gen(exa_ctx*, double*, hipStream_t);
 int exa_launch_ea_export_gen(exa_ctx*, double*, hipStream_t);
@@ -547,6 +548,18 @@ int exa_grad_apply_lvec_cols_w(exa_ctx* ctx, int nch, int ncols, const double* x
 }
 int exa_grad_apply_lvec_cols(exa_ctx* ctx, int ncols, const double* x, int64_t ldx, double* y, int64_t ldy, const uint8_t* mask, const double* const* gates, exa_stream s) {
    return exa_grad_apply_lvec_cols_w(ctx, 0, ncols, x, ldx, y, ldy, mask, gates, s);
+}
+
+// Level 1 of the p = 2 multigrid hierarchy and the diagonal of the constrained p = 2 operator, this rank's part of each, from the point records
+// exa_grad_apply_lvec reads (gen_kernels.hip; include/exaconstit_hip.h).  EXA_ERR_UNSUPPORTED, nothing written, where that action does not run
+// from records of a generated p = 2 box: the caller probes instead.
+int exa_grad_mg_p2_build(exa_ctx* ctx, const int* ne, const int32_t* elem_at, const uint8_t* mask0, const uint8_t* mask1, double* Sten, double* diag, exa_stream s) {
+   if (int rc = grad_ready(ctx, "exa_grad_mg_p2_build", ne && elem_at && (Sten || diag) && (!Sten || mask1) && (!diag || mask0), NEEDS_CONN)) return rc;
+   if (!exa_is_hex(ctx) || ctx->n != 27 || ctx->Q != 27 || ctx->cfg.integ == EXA_INTEG_BBAR || ctx->det || !exa_acts_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
+   if (ne[0] < 1 || ne[1] < 1 || ne[2] < 1 || (int64_t)ne[0] * ne[1] * ne[2] != ctx->E || (int64_t)(2 * ne[0] + 1) * (2 * ne[1] + 1) * (2 * ne[2] + 1) != ctx->nnodes)
+      return fail(ctx, EXA_ERR_ARG, "exa_grad_mg_p2_build: the element box does not match the context's elements and nodes");
+   if (!exa_has_compact_geo(ctx) && (ctx->grad_src == EXA_GRAD_FROM_MODEL_RECORDS || ctx->pa_pending || !ctx->pa)) return EXA_ERR_UNSUPPORTED;   // (no records with geometry to read)
+   return exa_launch_mg_p2_build(ctx, ne, elem_at, mask0, mask1, Sten, diag, ctx->cfg.assembly == EXA_ASSEMBLY_EA, S(s));
 }
 
 int exa_grad_set_coords(exa_ctx* ctx, const double* coords_lvec) {

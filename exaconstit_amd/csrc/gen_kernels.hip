@@ -514,6 +514,167 @@ __global__ __launch_bounds__(PA_BLK) void k_residual_p2(const int E, const doubl
    }
 }
 
+// ---- p = 2 multigrid (host/multigrid.hpp, DESIGN 4.6 "p = 2"): level 1 and the fine diagonal in one pass each over the point records -----------------
+// Level 1 of the p = 2 hierarchy is the trilinear space on the element vertices, Q1 in Q2 on every element, so the Galerkin product P^T A_0 P is the
+// trilinear rediscretisation on the 27 points of the p = 2 rule:  (a,i ; b,k) += b_a . Sm(Ct eps(b_b, k))[., i]  with b_a = adj^T grad phi_a, exactly the
+// point arithmetic of mf_point_p2 on the eight trilinear functions.  Their values and derivatives at a Gauss abscissa come through the Q2 tables
+// (phi_0 = N_0 + N_1 / 2, phi_1 = N_1 / 2 + N_2: the embedding mg_prolong applies), so the product agrees with the probed one to rounding.
+// Gather, no atomics: a thread owns level-1 node I and the pair (dy, dz) of the neighbour offset, i.e. the three stencil blocks (dx, dy, dz), walks the
+// elements that hold both I and the neighbours (at most 8) and their 27 points in a fixed order, and keeps 27 accumulators; the record of a point is
+// loaded with plain loads (the threads of neighbouring nodes and the other eight pairs read it again: it should stay in the caches).  Threads of
+// a wave are consecutive nodes of one pair, i.e. consecutive elements: the record loads are contiguous across the wave like the action's.
+// elem_at: local element index at every position of the rank's element box (Partition::order_boundary_first permutes the elements).
+constexpr int MGP2_BS = 128;
+template <bool TRANS, bool CMP>
+__device__ __forceinline__ void mgp2_load(const double* __restrict__ pa, const int e, const int q, double (&v)[2 * (CMP ? PAC_PAIRS_GEO : PA_PAIRS)]) {
+   constexpr int NPR = CMP ? PAC_PAIRS_GEO : PA_PAIRS;
+   const int64_t blk = e >> 6; const int lane = e & 63;
+   const double2* r = reinterpret_cast<const double2*>(pa + (CMP ? pac_off<PAC_PAIRS_GEO>(blk, P2N, q, 0) : pa_off(blk, P2N, q, 0))) + lane;
+#pragma unroll
+   for (int pr = 0; pr < NPR; pr++) { const double2 t = r[pr * PA_BLK]; v[2 * pr] = t.x; v[2 * pr + 1] = t.y; }
+}
+// K(i, k) += ba . Sm(C eps(bb, k))[., i]: the 3 x 3 block of row function a and column function b at one point (out[3 i + k])
+template <bool TRANS, bool CMP>
+__device__ __forceinline__ void mgp2_block(const double* v, const double (&ba)[3], const double (&bb)[3], double (&out)[9]) {
+#pragma unroll
+   for (int k = 0; k < 3; k++) {
+      double eps[6]; b_row(k, bb, 0.0, eps);
+      double sg[6];
+      if (CMP) d55_apply(v, v[25], eps, sg);   // (the compact record holds D or D^T as the context needs)
+      else {
+#pragma unroll
+         for (int i = 0; i < 6; i++) { double t = 0;
+#pragma unroll
+            for (int j = 0; j < 6; j++) t += (TRANS ? v[j + 6 * i] : v[i + 6 * j]) * eps[j];
+            sg[i] = t; }
+      }
+      out[k] += ba[0] * sg[0] + ba[1] * sg[5] + ba[2] * sg[4];
+      out[3 + k] += ba[0] * sg[5] + ba[1] * sg[1] + ba[2] * sg[3];
+      out[6 + k] += ba[0] * sg[4] + ba[1] * sg[3] + ba[2] * sg[2];
+   }
+}
+__device__ __forceinline__ void mgp2_scaled_grad(const double* adj, const double g0, const double g1, const double g2, double (&b)[3]) {
+#pragma unroll
+   for (int t = 0; t < 3; t++) b[t] = g0 * adj[t] + g1 * adj[3 + t] + g2 * adj[6 + t];
+}
+
+template <bool TRANS, bool CMP>
+__global__ __launch_bounds__(MGP2_BS) void k_mg_p2_level1(const int ne0, const int ne1, const int ne2, const int32_t* __restrict__ elem_at, const double* __restrict__ pa,
+                                                          const double* __restrict__ T1, const uint8_t* __restrict__ mask1, double* __restrict__ S) {
+   const int n0 = ne0 + 1, n1 = ne1 + 1, n2 = ne2 + 1;
+   const int64_t nn = (int64_t)n0 * n1 * n2;
+   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   if (t >= 9 * nn) return;
+   const int pair = (int)(t / nn); const int64_t node = t - (int64_t)pair * nn;
+   const int dy = pair % 3 - 1, dz = pair / 3 - 1;
+   const int I = (int)(node % n0), J = (int)((node / n0) % n1), K = (int)(node / ((int64_t)n0 * n1));
+   double acc[3][9];
+#pragma unroll
+   for (int o = 0; o < 3; o++)
+#pragma unroll
+      for (int i = 0; i < 9; i++) acc[o][i] = 0.0;
+   const cptr t1 = as_const(T1);
+#pragma unroll 1
+   for (int ez = 0; ez < 2; ez++) {
+      const int eK = K + ez - 1, az = 1 - ez, bz = az + dz;
+      if (eK < 0 || eK >= ne2 || bz < 0 || bz > 1) continue;
+#pragma unroll 1
+      for (int ey = 0; ey < 2; ey++) {
+         const int eJ = J + ey - 1, ay = 1 - ey, by = ay + dy;
+         if (eJ < 0 || eJ >= ne1 || by < 0 || by > 1) continue;
+#pragma unroll 1
+         for (int q = 0; q < P2N; q++) {
+            const int qi = q % 3, qj = (q / 3) % 3, qk = q / 9;
+            // the two linear functions of a direction at its abscissa, value and derivative, through the Q2 tables (wave-uniform)
+            const double lx[2] = { t1[6 * qi] + 0.5 * t1[6 * qi + 1], 0.5 * t1[6 * qi + 1] + t1[6 * qi + 2] };
+            const double gx[2] = { t1[6 * qi + 3] + 0.5 * t1[6 * qi + 4], 0.5 * t1[6 * qi + 4] + t1[6 * qi + 5] };
+            const double ly0 = t1[6 * qj] + 0.5 * t1[6 * qj + 1], ly1 = 0.5 * t1[6 * qj + 1] + t1[6 * qj + 2];
+            const double gy0 = t1[6 * qj + 3] + 0.5 * t1[6 * qj + 4], gy1 = 0.5 * t1[6 * qj + 4] + t1[6 * qj + 5];
+            const double lz0 = t1[6 * qk] + 0.5 * t1[6 * qk + 1], lz1 = 0.5 * t1[6 * qk + 1] + t1[6 * qk + 2];
+            const double gz0 = t1[6 * qk + 3] + 0.5 * t1[6 * qk + 4], gz1 = 0.5 * t1[6 * qk + 4] + t1[6 * qk + 5];
+            const double lay = ay ? ly1 : ly0, gay = ay ? gy1 : gy0, laz = az ? lz1 : lz0, gaz = az ? gz1 : gz0;
+            const double lby = by ? ly1 : ly0, gby = by ? gy1 : gy0, lbz = bz ? lz1 : lz0, gbz = bz ? gz1 : gz0;
+#pragma unroll
+            for (int ex = 0; ex < 2; ex++) {
+               const int eI = I + ex - 1, ax = 1 - ex;
+               if (eI < 0 || eI >= ne0) continue;
+               const int e = elem_at[eI + (int64_t)ne0 * (eJ + (int64_t)ne1 * eK)];
+               double v[2 * (CMP ? PAC_PAIRS_GEO : PA_PAIRS)];
+               mgp2_load<TRANS, CMP>(pa, e, q, v);
+               const double* adj = v + (CMP ? 26 : 36);
+               double ba[3]; mgp2_scaled_grad(adj, gx[ax] * lay * laz, lx[ax] * gay * laz, lx[ax] * lay * gaz, ba);
+#pragma unroll
+               for (int bx = 0; bx < 2; bx++) {
+                  double bb[3]; mgp2_scaled_grad(adj, gx[bx] * lby * lbz, lx[bx] * gby * lbz, lx[bx] * lby * gbz, bb);
+                  mgp2_block<TRANS, CMP>(v, ba, bb, acc[bx - ax + 1]);
+               }
+            }
+         }
+      }
+   }
+   // rows and columns of masked level-1 dofs are zero; a neighbour outside the box gets zeros (no element reaches it)
+   uint8_t mr[3];
+#pragma unroll
+   for (int r = 0; r < 3; r++) mr[r] = mask1[node + nn * r];
+   const bool in_yz = J + dy >= 0 && J + dy < n1 && K + dz >= 0 && K + dz < n2;
+#pragma unroll
+   for (int dx = -1; dx <= 1; dx++) {
+      const bool in = in_yz && I + dx >= 0 && I + dx < n0;
+      const int64_t nb = in ? node + dx + (int64_t)n0 * (dy + (int64_t)n1 * dz) : node;
+      const int o = (dx + 1) + 3 * (dy + 1) + 9 * (dz + 1);
+#pragma unroll
+      for (int c = 0; c < 3; c++) {
+         const bool mc = !in || mask1[nb + nn * c];
+#pragma unroll
+         for (int r = 0; r < 3; r++) S[(int64_t)(o * 9 + 3 * r + c) * nn + node] = (mc || mr[r]) ? 0.0 : acc[dx + 1][3 * r + c];
+      }
+   }
+}
+
+// this rank's part of the diagonal of the constrained p = 2 operator, diag(n, i) = sum_e sum_q b_n . Sm(Ct eps(b_n, i))[., i] with the Q2 gradient of fine
+// node n, zero on essential dofs: one thread per fine node, its (at most 8) elements and their 27 points in a fixed order
+template <bool TRANS, bool CMP>
+__global__ __launch_bounds__(MGP2_BS) void k_mg_p2_diag(const int ne0, const int ne1, const int ne2, const int32_t* __restrict__ elem_at, const double* __restrict__ pa,
+                                                        const double* __restrict__ T1, const uint8_t* __restrict__ mask0, double* __restrict__ diag) {
+   const int n0 = 2 * ne0 + 1, n1 = 2 * ne1 + 1, n2 = 2 * ne2 + 1;
+   const int64_t nn = (int64_t)n0 * n1 * n2;
+   const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   if (node >= nn) return;
+   const int i = (int)(node % n0), j = (int)((node / n0) % n1), k = (int)(node / ((int64_t)n0 * n1));
+   // per direction: an odd index is the midpoint of one element, an even one the last node of element idx / 2 - 1 and the first of idx / 2
+   const int cx = (i & 1) ? 1 : 2, cy = (j & 1) ? 1 : 2, cz = (k & 1) ? 1 : 2;
+   double acc[9];
+#pragma unroll
+   for (int m = 0; m < 9; m++) acc[m] = 0.0;
+#pragma unroll 1
+   for (int mz = 0; mz < cz; mz++) {
+      const int eK = (k & 1) ? k >> 1 : (k >> 1) - 1 + mz, lk = (k & 1) ? 1 : 2 - 2 * mz;
+      if (eK < 0 || eK >= ne2) continue;
+#pragma unroll 1
+      for (int my = 0; my < cy; my++) {
+         const int eJ = (j & 1) ? j >> 1 : (j >> 1) - 1 + my, lj = (j & 1) ? 1 : 2 - 2 * my;
+         if (eJ < 0 || eJ >= ne1) continue;
+#pragma unroll 1
+         for (int mx = 0; mx < cx; mx++) {
+            const int eI = (i & 1) ? i >> 1 : (i >> 1) - 1 + mx, li = (i & 1) ? 1 : 2 - 2 * mx;
+            if (eI < 0 || eI >= ne0) continue;
+            const int e = elem_at[eI + (int64_t)ne0 * (eJ + (int64_t)ne1 * eK)];
+#pragma unroll 1
+            for (int q = 0; q < P2N; q++) {
+               const int qi = q % 3, qj = (q / 3) % 3, qk = q / 9;
+               const double bx = T1[6 * qi + li], dx = T1[6 * qi + 3 + li], by = T1[6 * qj + lj], dy = T1[6 * qj + 3 + lj], bz = T1[6 * qk + lk], dz = T1[6 * qk + 3 + lk];
+               double v[2 * (CMP ? PAC_PAIRS_GEO : PA_PAIRS)];
+               mgp2_load<TRANS, CMP>(pa, e, q, v);
+               double b[3]; mgp2_scaled_grad(v + (CMP ? 26 : 36), dx * by * bz, bx * dy * bz, bx * by * dz, b);
+               mgp2_block<TRANS, CMP>(v, b, b, acc);
+            }
+         }
+      }
+   }
+#pragma unroll
+   for (int c = 0; c < 3; c++) diag[node + nn * c] = mask0[node + nn * c] ? 0.0 : acc[4 * c];
+}
+
 __global__ __launch_bounds__(PA_BLK) void k_ea_diag_gen(const int E, const int nd, const double* __restrict__ emat, double* __restrict__ y) {
    const int lane = threadIdx.x; const int64_t blk = blockIdx.x; const int64_t e = blk * PA_BLK + lane;
    if (e >= E) return;
@@ -646,6 +807,31 @@ int exa_launch_mf_apply_p2(exa_ctx* ctx, const double* x, double* y, const uint8
       hipLaunchKernelGGL((k_mf_apply_p2<bb.value, t.value, cm.value>), dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, cm.value ? ctx->pa_c : ctx->pa, ctx->T1_dev, ctx->W_dev, ctx->eDS, x, y,
                          ctx->conn, ctx->nnodes, mask, gate); }, ctx->cfg.integ == EXA_INTEG_BBAR, trans, exa_has_compact_geo(ctx));
    return exa_launched(ctx);
+}
+// level-1 stencil (S, may be null) and fine diagonal (diag, may be null) of the p = 2 multigrid hierarchy from the records the matrix-free action reads
+int exa_launch_mg_p2_build(exa_ctx* ctx, const int* ne, const int32_t* elem_at, const uint8_t* mask0, const uint8_t* mask1, double* S, double* diag, bool trans, hipStream_t s) {
+   if (int rc = exa_ensure_p2_tables(ctx)) return rc;
+   const bool cmp = exa_has_compact_geo(ctx);
+   const double* rec = cmp ? ctx->pa_c : ctx->pa;
+   const int64_t nn1 = (int64_t)(ne[0] + 1) * (ne[1] + 1) * (ne[2] + 1), nn0 = (int64_t)(2 * ne[0] + 1) * (2 * ne[1] + 1) * (2 * ne[2] + 1);
+   exa_dispatch([&](auto t, auto cm) {
+      if (S) hipLaunchKernelGGL((k_mg_p2_level1<t.value, cm.value>), dim3(nblk(9 * nn1, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask1, S);
+      if (diag) hipLaunchKernelGGL((k_mg_p2_diag<t.value, cm.value>), dim3(nblk(nn0, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask0, diag);
+   }, trans, cmp);
+   return exa_launched(ctx);
+}
+// private-memory bytes per lane of the eight instantiations (level 1, diagonal) x (plain, transposed) x (46-double, compact records) in the loaded code object
+extern "C" int exa_mg_p2_scratch_bytes(int* out8) {
+   const void* f[8] = { reinterpret_cast<const void*>(k_mg_p2_level1<false, false>), reinterpret_cast<const void*>(k_mg_p2_level1<true, false>),
+                        reinterpret_cast<const void*>(k_mg_p2_level1<false, true>),  reinterpret_cast<const void*>(k_mg_p2_level1<true, true>),
+                        reinterpret_cast<const void*>(k_mg_p2_diag<false, false>),   reinterpret_cast<const void*>(k_mg_p2_diag<true, false>),
+                        reinterpret_cast<const void*>(k_mg_p2_diag<false, true>),    reinterpret_cast<const void*>(k_mg_p2_diag<true, true>) };
+   for (int k = 0; k < 8; k++) {
+      hipFuncAttributes a;
+      if (hipFuncGetAttributes(&a, f[k]) != hipSuccess) { (void)hipGetLastError(); return -1; }
+      out8[k] = (int)a.localSizeBytes;
+   }
+   return 0;
 }
 int exa_launch_ea_diag_gen(exa_ctx* ctx, double* y, hipStream_t s) {
    hipLaunchKernelGGL(k_ea_diag_gen, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, 3 * ctx->n, ctx->emat, y);

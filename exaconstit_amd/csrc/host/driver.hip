@@ -586,6 +586,10 @@ void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
    if (kind == 2) {
       if (part.periodic && !opt_.mg_periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
       if (ExaOptions::lower(opt_.integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
+      // p = 2 is opt-in (Solvers.Krylov.mg_p2); what stays refused with it says why, everything else keeps the constructor's message
+      if (opt_.mg_p2 && !part.from_file && part.geom == 0 && part.p > 2) throw std::runtime_error(ExaOptions::mg_p2_no_higher_order());
+      if (opt_.mg_p2 && part.p == 2 && part.periodic) throw std::runtime_error(ExaOptions::mg_p2_no_periodic());
+      op.mg_p2_allowed = opt_.mg_p2;
       op.mg.reset(new Multigrid(op, levels, degree));   // throws where no hierarchy can be built
    } else op.mg.reset();
    krylov_->DropGraph();
@@ -597,6 +601,7 @@ void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
    if (!L9) throw std::runtime_error("set_periodic: a 3 x 3 velocity gradient is required");
    for (int k = 0; k < 9; k++) if (!std::isfinite(L9[k])) throw std::runtime_error("set_periodic: the velocity gradient must be finite");
    if (part.from_file || part.geom != 0) throw std::runtime_error(ExaOptions::periodic_needs_generated_mesh());
+   if (oper_->precond == Precond::MULTIGRID && part.p == 2) throw std::runtime_error(ExaOptions::mg_p2_no_periodic());   // (with or without mg_periodic)
    if (oper_->precond == Precond::MULTIGRID && !opt_.mg_periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
    uint8_t f[9];
    const bool any = free_mask_bits(free9, f) != 0;

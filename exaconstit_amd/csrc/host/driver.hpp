@@ -138,6 +138,16 @@ class NonlinearMechOperator {
    DevBuf<int32_t> conn;
    Precond precond = Precond::IDENTITY;   // (SystemDriver::SetPreconditioner is its only writer)
    std::unique_ptr<Multigrid> mg;   // precond == MULTIGRID: rebuilt after every gradient set-up
+   // multigrid at p = 2 (host/multigrid.hpp; SystemDriver::SetPreconditioner writes the first, exa_driver_set_mg_p2_build the second)
+   bool mg_p2_allowed = false;      // Solvers.Krylov.mg_p2: Multigrid's constructor accepts a p = 2 partition
+   int mg_p2_build = 1;             // 1: level 1 and the fine diagonal from the point records where they can serve; 0: always probed
+   // The p = 2 matrix-free action reads point records this Newton iteration's set-up left, in the form the run streams: the compact records of the
+   // constitutive launch (record route), or the 46-double records of exa_grad_setup when the compact form is switched off (EXA_TANGENT_FORM=full).
+   // EXA_TANGENT_RECORDS=off, the deterministic mode and EXA_EA_ASSEMBLED=1 take the tangent-field routes: nothing is read off records there.
+   bool p2_records_readable() const {
+      return part_.p == 2 && part_.geom == 0 && routes_.lvec_grad && !routes_.det && (use_records() || !routes_.compact_tangent) &&
+             (opt_.assembly == Assembly::PA || routes_.ea_matrix_free);
+   }
    Timers timers;
    int model_calls = 0;
    std::vector<double> props;     // material parameters the context was created with (the adapter-route bench creates a second, AOS context from them)
@@ -204,6 +214,8 @@ class SystemDriver {
    // multigrid on a periodic cell is opt-in (Solvers.Krylov.mg_periodic; DESIGN 4.6, "periodic cells"): without it SetPreconditioner and SetPeriodic
    // refuse the combination with the options reader's message, as they always did
    void AllowPeriodicMultigrid(bool on) { opt_.mg_periodic = on; }
+   // ... and so is multigrid at p_refinement = 2 (Solvers.Krylov.mg_p2; DESIGN 4.6, "p = 2"): without it SetPreconditioner refuses the order as it always did
+   void AllowP2Multigrid(bool on) { opt_.mg_p2 = on; }
    // periodic boundary conditions under the macroscopic velocity gradient L9 (row by row) on a freshly created driver before its first step,
    // like SetPreconditioner: rebuilds the partition tables, weights, essential set and halo lists (every rank calls it).  Refuses file meshes
    // and, without AllowPeriodicMultigrid, the multigrid preconditioner with the messages of the options reader; a hierarchy that exists is made again.  The boundary-condition schedule becomes one entry: L from step 1.

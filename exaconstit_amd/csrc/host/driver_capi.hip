@@ -416,6 +416,11 @@ int exa_driver_newton_info(exa_driver* d, double* out2) { out2[0] = d->sd->last_
 // multigrid on a periodic cell is opt-in (Solvers.Krylov.mg_periodic): on != 0 lets exa_driver_set_preconditioner(2) and exa_driver_set_periodic meet
 int exa_driver_set_mg_periodic(exa_driver* d, int on) { d->sd->AllowPeriodicMultigrid(on != 0); return 0; }
 
+// multigrid at p_refinement = 2 is opt-in too (Solvers.Krylov.mg_p2): on != 0 before exa_driver_set_preconditioner(2)
+int exa_driver_set_mg_p2(exa_driver* d, int on) { d->sd->AllowP2Multigrid(on != 0); return 0; }
+// p = 2 hierarchy, from the next set-up on: 1 level 1 and the fine diagonal from the point records where they can serve, 0 always probed
+int exa_driver_set_mg_p2_build(exa_driver* d, int from_records) { d->sd->oper().mg_p2_build = from_records != 0 ? 1 : 0; return 0; }
+
 int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen) {
    try { d->sd->SetPreconditioner(kind, levels, degree); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
@@ -441,12 +446,22 @@ int exa_driver_mg_info(exa_driver* d, double* out) {
       Multigrid& mg = mg_of(d);
       out[0] = mg.levels(); out[1] = mg.setup_ms; out[2] = mg.vcycle_ms(); out[3] = mg.degree();
       for (int l = 0; l <= mg.levels(); l++) {
-         for (int k = 0; k < 3; k++) out[4 + 4 * l + k] = mg.grid(l).n[k] - 1;
+         for (int k = 0; k < 3; k++) out[4 + 4 * l + k] = (mg.grid(l).n[k] - 1) / mg.order(l);   // (element boxes: levels 0 and 1 of a p = 2 hierarchy carry the same one)
          out[4 + 4 * l + 3] = mg.lmax(l);
       }
       out[4 + 4 * (mg.levels() + 1)] = mg.periodic() ? 1.0 : 0.0; out[5 + 4 * (mg.levels() + 1)] = mg.control_dofs();
       return 0;
    } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_info: %s\n", e.what()); return -1; }
+}
+
+// out (>= 2 + L + 1 ints): { coarse levels L, level-1 build of the last set-up (0 probe, 1 records, -1 none yet / p = 1), order of every level }
+int exa_driver_mg_info_order(exa_driver* d, int* out) {
+   try {
+      Multigrid& mg = mg_of(d);
+      out[0] = mg.levels(); out[1] = mg.level1_build();
+      for (int l = 0; l <= mg.levels(); l++) out[2 + l] = mg.order(l);
+      return 0;
+   } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_info_order: %s\n", e.what()); return -1; }
 }
 
 // gradient set-up of the current state (what the next Newton iteration would do first) and the hierarchy build that follows it
@@ -869,6 +884,12 @@ int exa_options_query_solver(const char* toml_path, int* out3, char* err, int er
 }
 
 int exa_mg_level_count(const int* N, int nranks, int cap) { return (nranks < 1 || N[0] < 1 || N[1] < 1 || N[2] < 1) ? -1 : mg_level_count(N, nranks, cap); }
+int exa_mg_level_count_order(const int* N, int nranks, int cap, int order) {
+   return (nranks < 1 || N[0] < 1 || N[1] < 1 || N[2] < 1 || order < 1 || order > 2) ? -1 : mg_level_count_order(N, nranks, cap, order);
+}
+int exa_options_query_mg_p2(const char* toml_path, int* out1, char* err, int errlen) {
+   try { ExaOptions o; o.parse_options(toml_path); out1[0] = o.mg_p2 ? 1 : 0; return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
 
 int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen) {
    try {

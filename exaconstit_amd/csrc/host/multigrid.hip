@@ -10,10 +10,14 @@ namespace exa_host {
 Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op_(op), degree_(degree), levels_cap_(levels_cap) {
    const Partition& part = op.part();
    periodic_ = part.periodic; mixed_ = part.periodic && part.mixed; fused_ = part.periodic && !op.comm().active();
-   if (part.from_file || part.p != 1) throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\") at p_refinement = 1");
+   // (p = 2: opt-in, the operator was told - SystemDriver::SetPreconditioner; without it the refusal of every order but 1 stands)
+   if (part.from_file || part.geom != 0 || !(part.p == 1 || (part.p == 2 && op.mg_p2_allowed)))
+      throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\") at p_refinement = 1");
+   if (part.p == 2 && part.periodic) throw std::runtime_error(ExaOptions::mg_p2_no_periodic());
+   p_ = part.p;
    if (degree < 1 || degree > 8) throw std::runtime_error("Solvers.Krylov.mg_smoother_degree must lie in 1 ... 8");
    if (levels_cap < 0) throw std::runtime_error("Solvers.Krylov.mg_levels must be >= 0 (0: as many as the mesh allows)");
-   const int L = mg_level_count(part.N, part.nranks, levels_cap);
+   const int L = mg_level_count_order(part.N, part.nranks, levels_cap, p_);
    if (L < 1)
       throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\": no coarse level can be built for " + std::to_string(part.N[0]) + " x " + std::to_string(part.N[1]) + " x " +
                                std::to_string(part.N[2]) + " elements on " + std::to_string(part.nranks) + " rank(s) (every rank's element box must be even, with at least 2 elements per direction after coarsening)");
@@ -23,7 +27,7 @@ Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op
    for (int l = 0; l <= L; l++) {
       Level& v = lv_[l];
       v.stride = 1 << l;
-      for (int d = 0; d < 3; d++) { v.g.n[d] = (part.ne[d] >> l) + 1; v.g.g0[d] = part.e0[d] >> l; }
+      for (int d = 0; d < 3; d++) { v.g.n[d] = ((part.ne[d] * p_) >> l) + 1; v.g.g0[d] = (part.e0[d] * p_) >> l; }
       v.nn = (int64_t)v.g.n[0] * v.g.n[1] * v.g.n[2]; v.nd = 3 * v.nn;
       v.deg = l == L ? MG_COARSE_DEGREE : degree;
       v.diag.alloc(v.nd); v.dinv.alloc(v.nd); v.r.alloc(v.nd); v.d.alloc(v.nd); v.t.alloc(v.nd); v.u.alloc(v.nd); v.v.alloc(v.nd);
@@ -36,7 +40,18 @@ Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op
          v.w.upload(w, s); v.wp = v.w.p;
       }
    }
-   if ((int64_t)lv_[0].nn != part.NN) throw std::runtime_error("multigrid: the partition is not a structured p = 1 box");
+   if ((int64_t)lv_[0].nn != part.NN) throw std::runtime_error("multigrid: the partition is not a structured box of its order");
+   if (p_ == 2) {   // where every element of the box sits in the rank's element order (its first native node is its lowest vertex)
+      std::vector<int32_t> at((size_t)part.E, -1);
+      for (int e = 0; e < part.E; e++) {
+         const int g = part.conn[(size_t)part.n * e];
+         const int i = g % part.nn[0], j = (g / part.nn[0]) % part.nn[1], k = g / (part.nn[0] * part.nn[1]);
+         if ((i | j | k) & 1) throw std::runtime_error("multigrid: the partition is not a structured p = 2 box");
+         at[(size_t)(i >> 1) + (size_t)part.ne[0] * ((j >> 1) + (size_t)part.ne[1] * (k >> 1))] = e;
+      }
+      for (int32_t e : at) if (e < 0) throw std::runtime_error("multigrid: the partition is not a structured p = 2 box");
+      elem_at_.upload(at, s); closed_flag_.alloc(1);
+   }
    fine_tmp_.alloc(lv_[0].nd); partial_.alloc(DOT_BLOCKS * 4); scal_.alloc(4);
    if (mixed_) { mask0_.alloc(lv_[0].nd); ctrl_slot_.alloc(8); ctrl_dinv_.alloc(8); }
    EXA_HC(hipEventCreate(&ev0_)); EXA_HC(hipEventCreate(&ev1_));
@@ -123,6 +138,31 @@ double Multigrid::dot(int l, const double* a, const double* b) {
    return h;
 }
 
+// p = 2: this rank's part of A_1 = M_1 P^T A_0 P M_1 and of diag(A_0) read off the point records of the action (exa_grad_mg_p2_build), the halo sums
+// as after the probes.  Q1 in Q2 makes the product the trilinear rediscretisation, but only P^T K P: it equals P^T (M_0 K M_0) P on the free level-1
+// dofs when none of them interpolates onto an essential fine dof, which is checked here on every rank (whole box faces pass: they sit at even
+// indices).  False - nothing written, the caller probes - when the test hook asks for the probes, the action does not run from records
+// (deterministic mode, EXA_TANGENT_RECORDS=off, assembled element matrices), the check fails on any rank, or the library has no such records.
+bool Multigrid::BuildFromRecords() {
+   if (op_.mg_p2_build == 0 || !op_.p2_records_readable()) return false;
+   hipStream_t s = op_.stream();
+   Level& f = lv_[0]; Level& c = lv_[1];
+   closed_flag_.zero(s);
+   mg_mask_closed(f.g, c.g, f.mask, c.mask, closed_flag_.p, s);
+   int32_t open = 0; closed_flag_.download(&open, 1, s);
+   if (op_.comm().max_over_ranks(open ? 1.0 : 0.0) != 0.0) return false;
+   const Partition& part = op_.part();
+   exa_ctx* ctx = op_.GetModel()->ctx();
+   const int rc = exa_grad_mg_p2_build(ctx, part.ne, elem_at_.p, f.mask, c.mask, c.S.p, f.diag.p, s);
+   // (a property of the context, the same on every rank)
+   if (rc == EXA_ERR_UNSUPPORTED) return false;
+   if (rc < 0) throw std::runtime_error(std::string("exa_grad_mg_p2_build: ") + exa_last_error(ctx));
+   halo(0, f.diag.p);
+   mg_stencil_diag(c.g, c.S.p, c.diag.p, s);
+   halo(1, c.diag.p);
+   return true;
+}
+
 void Multigrid::Build() {
    const auto t0 = std::chrono::steady_clock::now();
    hipStream_t s = op_.stream();
@@ -130,20 +170,25 @@ void Multigrid::Build() {
    lv_[0].mask = op_.ess_mask.p; lv_[0].wp = op_.weight.p;
    if (mixed_) { BuildControlBlock(); lv_[0].mask = mask0_.p; }
    for (int l = 1; l <= L; l++) mg_mask_coarsen(lv_[l - 1].g, lv_[l].g, lv_[l - 1].mask, lv_[l].mask_own.p, s);
-   // fine diagonal: the fine operator couples nodes at most one apart, so probes of the 8 colours mod 2 (per component) read it off
-   {
+   // p = 2: level 1 and the fine diagonal in one pass each over the point records, where they can serve
+   const bool from_records = p_ == 2 && BuildFromRecords();
+   if (p_ == 2) level1_build_ = from_records ? 1 : 0;
+   // fine diagonal: the fine operator couples nodes at most p apart, so probes of the (p + 1)^3 colours mod p + 1 (per component) read it off
+   if (!from_records) {
       Level& f = lv_[0];
+      const int m = p_ + 1;
       f.diag.zero(s);
-      for (int colour = 0; colour < 8; colour++)
+      for (int colour = 0; colour < m * m * m; colour++)
          for (int c = 0; c < 3; c++) {
-            mg_probe(f.g, 2, colour, c, f.mask, f.t.p, s);
+            mg_probe(f.g, m, colour, c, f.mask, f.t.p, s);
             A(0, f.t.p, f.u.p);
-            mg_diag_probe(f.g, 2, colour, c, f.u.p, f.diag.p, s);
+            mg_diag_probe(f.g, m, colour, c, f.u.p, f.diag.p, s);
          }
    }
    // Galerkin stencils, level by level: probe, interpolate, this rank's part of the level l - 1 action, restrict, mask, read off
    for (int l = 1; l <= L; l++) {
       Level& c = lv_[l]; Level& f = lv_[l - 1];
+      if (l == 1 && from_records) continue;
       for (int colour = 0; colour < 27; colour++)
          for (int k = 0; k < 3; k++) {
             mg_probe(c.g, 3, colour, k, c.mask, c.x.p, s);
@@ -160,7 +205,7 @@ void Multigrid::Build() {
    for (int l = 0; l <= L; l++) {
       Level& v = lv_[l];
       mg_dinv(v.nd, v.mask, v.diag.p, v.dinv.p, s);
-      int ng[3]; for (int d = 0; d < 3; d++) ng[d] = (ng_[d] >> l) + 1;
+      int ng[3]; for (int d = 0; d < 3; d++) ng[d] = ((ng_[d] * p_) >> l) + 1;
       mg_seed(v.g, ng, periodic_, v.mask, v.v.p, s);
       double lam = 0.0;
       for (int it = 0; it < MG_POWER_ITERS; it++) {

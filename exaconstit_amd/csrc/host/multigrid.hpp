@@ -21,6 +21,12 @@
 // kernels mg_stencil_apply_periodic / mg_restrict_periodic (the sum over the images inside the launch).  Several ranks: the unfused kernels and
 // NonlinearMechOperator::SumLVector at the fine positions (PeriodicCell::Sum), never both.  Mixed loading: the hierarchy is that of the fluctuation
 // block (level-0 mask = essential set + every control slot), and Apply adds the control block z = r / d on the free control slots.
+//
+// p = 2 ("p = 2"; opt-in, Solvers.Krylov.mg_p2): the p = 2 node grid (2 ne + 1 nodes per direction) is level 0, the element vertices -
+// every second node - are level 1, and the trilinear interpolation between them is the embedding Q1 in Q2, so the hierarchy is the one above with
+// n = ((ne p) >> l) + 1.  The fine operator reaches two nodes: its diagonal is probed with the 27 colours mod 3.  Because Q1 in Q2, the level-1
+// product is the trilinear rediscretisation on the p = 2 rule, and Build reads it - and the fine diagonal - off the point records of the action in
+// one pass each (exa_grad_mg_p2_build) where those records exist and the essential set is closed under P; otherwise it probes as everywhere else.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -50,6 +56,8 @@ void mg_seed(const MgGrid& C, const int ng[3], bool periodic, const uint8_t* mas
 void mg_stencil_apply_periodic(const MgGrid& C, const double* S, const double* x, double* y, hipStream_t s);
 void mg_restrict_periodic(const MgGrid& F, const MgGrid& C, const double* rf, double* rc, hipStream_t s);
 void mg_control_block(int n, const int32_t* slot, const double* dinv, const double* r, double* z, hipStream_t s);                // z[slot] = dinv r[slot]
+// flag[0] = 1 when a free dof of C has a masked dof of F in the support of its interpolation (flag zeroed by the caller): M_F P M_C = P M_C fails
+void mg_mask_closed(const MgGrid& F, const MgGrid& C, const uint8_t* mf, const uint8_t* mc, int32_t* flag, hipStream_t s);
 void mg_to_fine(const MgGrid& F0, const MgGrid& C, int stride, const double* xc, double* x0, hipStream_t s);
 void mg_from_fine(const MgGrid& F0, const MgGrid& C, int stride, const double* x0, double* xc, hipStream_t s);
 
@@ -69,6 +77,14 @@ inline int mg_level_count(const int N[3], int nranks, int cap) {
          while (ne % (2 << l) == 0 && ne / (2 << l) >= 2) l++;
          L = std::min(L, l);
       }
+   return cap > 0 ? std::min(L, cap) : L;
+}
+
+// ... at polynomial order 2: level 1 is the trilinear space on the element vertices (every second node of the p = 2 node grid), which needs no
+// evenness, and the levels below it are those of order 1; cap > 0 limits the count of coarse levels as before.  Order 1: mg_level_count.
+inline int mg_level_count_order(const int N[3], int nranks, int cap, int order) {
+   if (order == 1) return mg_level_count(N, nranks, cap);
+   const int L = 1 + mg_level_count(N, nranks, 0);
    return cap > 0 ? std::min(L, cap) : L;
 }
 
@@ -98,7 +114,10 @@ class Multigrid {
    double setup_ms = 0.0;
    double vcycle_ms();
    const double* stencil(int l) const { return lv_[l].S.p; }
+   int order(int l) const { return l == 0 ? p_ : 1; }       // polynomial order of level l
+   int level1_build() const { return level1_build_; }       // p = 2, last Build: 1 level 1 and the fine diagonal from the point records, 0 probed; -1 at p = 1 / before
  private:
+   bool BuildFromRecords();                                 // p = 2: false (nothing written) where the records cannot serve, see Build
    struct Level {
       MgGrid g{}; int64_t nn = 0, nd = 0; int stride = 1;
       DevBuf<double> S, diag, dinv, w, b, x, r, d, t, u, v;
@@ -119,6 +138,8 @@ class Multigrid {
    DevBuf<uint8_t> mask0_;                                  // mixed loading: essential set + the free control slots
    DevBuf<int32_t> ctrl_slot_; DevBuf<double> ctrl_dinv_; int ctrl_local_ = 0, control_dofs_ = 0;   // this rank's free control slots and 1 / d
    int64_t ctrl_at_[8] = {}; double ctrl_d_[8] = {};
+   int p_ = 1, level1_build_ = -1;                          // order of level 0 (1 or 2)
+   DevBuf<int32_t> elem_at_, closed_flag_;                  // p = 2: local element at every position of the element box; result of the mask check
    int ng_[3] = { 0, 0, 0 };                                // global elements per direction at level 0
    DevBuf<double> fine_tmp_, partial_, scal_;
    hipEvent_t ev0_ = nullptr, ev1_ = nullptr; bool ev_pending_ = false; double vcycle_ms_ = 0.0;

@@ -109,6 +109,10 @@ struct ExaOptions {
          return "BCs.periodic_free: both entries of an off-diagonal pair (i, j), (j, i) are free - the rigid rotation would be free";
       return nullptr;
    }
+   // multigrid and the polynomial order (options reader, SystemDriver::SetPreconditioner / SetPeriodic)
+   static const char* mg_order_refusal() { return "Solvers.Krylov.preconditioner = \"multigrid\" is built for p_refinement = 1 only"; }   // (p_refinement = 2: opt-in, Solvers.Krylov.mg_p2 = true)
+   static const char* mg_p2_no_higher_order() { return "Solvers.Krylov.preconditioner = \"multigrid\": mg_p2 = true serves p_refinement = 2; p_refinement >= 3 has no hierarchy (its nodes are not a uniform grid)"; }
+   static const char* mg_p2_no_periodic() { return "Solvers.Krylov.preconditioner = \"multigrid\" at p_refinement = 2 is not built for BCs.periodic = true (the fine diagonal probe and the fused periodic kernels need p_refinement = 1), with or without mg_periodic"; }
    static const char* periodic_no_multigrid() { return "BCs.periodic = true runs under Solvers.Krylov.preconditioner = \"multigrid\" only where it is asked for: Solvers.Krylov.mg_periodic = true (Driver.set_preconditioner(\"multigrid\", periodic=True)); without it the combination is refused as before"; }
    static const char* periodic_needs_generated_mesh() { return "BCs.periodic = true needs a generated hexahedral mesh (Mesh.type = \"auto\"): file and tetrahedral meshes need node matching"; }
    XtalType xtal = XtalType::FCC; SlipType slip = SlipType::POWERVOCE;
@@ -183,6 +187,7 @@ struct ExaOptions {
    // decides), 1 "jacobi", 2 "multigrid" (host/multigrid.hpp) with mg_levels coarse levels at most (0: as many as the mesh allows) and a
    // Chebyshev smoother of degree mg_smoother_degree (1 ... 8)
    int precond = 0, mg_levels = 0, mg_degree = 2;
+   bool mg_p2 = false;         // Solvers.Krylov.mg_p2: multigrid at p_refinement = 2 ("p = 2"); refused without it, as before the hierarchy served p = 2
    bool mg_periodic = false;   // Solvers.Krylov.mg_periodic: multigrid on a periodic cell ("periodic cells"); refused without it, as before the hierarchy served periodic cells
    int ref_ser = 0, order = 1; int ncuts[3] = { 1, 1, 1 }; double length[3] = { 1, 1, 1 }; std::string mesh_type = "auto", mesh_file;
 
@@ -485,7 +490,13 @@ struct ExaOptions {
             if (lv < 0 || lv != std::floor(lv) || lv > 30) throw std::runtime_error("Solvers.Krylov.mg_levels must be a whole number >= 0 (0: as many levels as the mesh allows)");
             if (dg < 1 || dg > 8 || dg != std::floor(dg)) throw std::runtime_error("Solvers.Krylov.mg_smoother_degree must be a whole number in 1 ... 8");
             mg_levels = (int)lv; mg_degree = (int)dg;
-            if (order != 1) throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is built for p_refinement = 1 only");
+            if (const TomlValue* m2 = d.get("Solvers.Krylov.mg_p2")) {
+               if (m2->kind != TomlValue::BOOL) throw std::runtime_error("Solvers.Krylov.mg_p2 must be true or false");
+               mg_p2 = m2->b;
+            }
+            if (order != 1 && !mg_p2) throw std::runtime_error(mg_order_refusal());
+            if (order > 2) throw std::runtime_error(mg_p2_no_higher_order());
+            if (order == 2 && periodic) throw std::runtime_error(mg_p2_no_periodic());
             if (lower(integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
             if (mesh_type != "auto") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\"): file meshes need algebraic coarsening");
             if (const TomlValue* mp = d.get("Solvers.Krylov.mg_periodic")) {

@@ -1,7 +1,8 @@
-// Kernels of the geometric multigrid preconditioner (host/multigrid.hip) on generated p = 1 meshes.
+// Kernels of the geometric multigrid preconditioner (host/multigrid.hip) on generated meshes of order p = 1 and 2.
 //
-// Every level is a structured box of nodes: level l of a rank holds (ne >> l) + 1 nodes per direction, and its node (i, j, k) is node
-// (2i, 2j, 2k) of level l - 1 (the vertices nest).  Vectors are laid out like the fine L-vector, dof = node + NN * component, node =
+// Every level is a structured box of nodes: level l of a rank holds ((ne p) >> l) + 1 nodes per direction, and its node (i, j, k) is node
+// (2i, 2j, 2k) of level l - 1 (the vertices nest; at p = 2 level 0 is the p = 2 node grid and level 1 the element vertices, whose stencil and the
+// fine diagonal gen_kernels.hip reads off the point records).  Vectors are laid out like the fine L-vector, dof = node + NN * component, node =
 // i + n0 (j + n1 k).  A coarse operator is a 27-point stencil of 3 x 3 blocks per node: 243 doubles per node, structure of arrays,
 // S[(o * 9 + 3 r + c) * NN + node] with neighbour offset o = (dx + 1) + 3 (dy + 1) + 9 (dz + 1), row component r, column component c.
 //
@@ -234,6 +235,28 @@ __global__ __launch_bounds__(MG_BS) void k_mg_mask_coarsen(const MgGrid F, const
    for (int c = 0; c < 3; c++) mc[t + nnc * c] = mf[v + nnf * c];
 }
 
+// is the level-l mask closed under P?  flag[0] <- 1 by every thread whose free coarse dof interpolates onto a masked fine dof (all write the same value)
+__global__ __launch_bounds__(MG_BS) void k_mg_mask_closed(const MgGrid F, const MgGrid C, const uint8_t* __restrict__ mf, const uint8_t* __restrict__ mc, int32_t* __restrict__ flag) {
+   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+   const int64_t nnf = grid_nn(F), nnc = grid_nn(C);
+   if (t >= nnc) return;
+   const int I = (int)(t % C.n[0]), J = (int)((t / C.n[0]) % C.n[1]), K = (int)(t / ((int64_t)C.n[0] * C.n[1]));
+   bool bad = false;
+   for (int dz = -1; dz <= 1; dz++) {
+      const int fk = 2 * K + dz; if (fk < 0 || fk >= F.n[2]) continue;
+      for (int dy = -1; dy <= 1; dy++) {
+         const int fj = 2 * J + dy; if (fj < 0 || fj >= F.n[1]) continue;
+         for (int dx = -1; dx <= 1; dx++) {
+            const int fi = 2 * I + dx; if (fi < 0 || fi >= F.n[0]) continue;
+            const int64_t v = fi + (int64_t)F.n[0] * (fj + (int64_t)F.n[1] * fk);
+#pragma unroll
+            for (int c = 0; c < 3; c++) bad = bad || (!mc[t + nnc * c] && mf[v + nnf * c]);
+         }
+      }
+   }
+   if (bad) flag[0] = 1;
+}
+
 // Chebyshev step (Saad, Iterative Methods, Alg. 12.1, preconditioned by D^-1): first: d = c2 D^-1 r, x = d;
 // otherwise r -= A d, d = c1 d + c2 D^-1 r, x += d
 __global__ __launch_bounds__(MG_BS) void k_mg_cheb(const int64_t n, double* __restrict__ x, double* __restrict__ r, double* __restrict__ d, const double* __restrict__ Ad,
@@ -331,6 +354,9 @@ void mg_dinv(int64_t n, const uint8_t* mask, const double* diag, double* dinv, h
 }
 void mg_mask_coarsen(const MgGrid& F, const MgGrid& C, const uint8_t* mf, uint8_t* mc, hipStream_t s) {
    hipLaunchKernelGGL(k_mg_mask_coarsen, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, F, C, mf, mc); launched("k_mg_mask_coarsen");
+}
+void mg_mask_closed(const MgGrid& F, const MgGrid& C, const uint8_t* mf, const uint8_t* mc, int32_t* flag, hipStream_t s) {
+   hipLaunchKernelGGL(k_mg_mask_closed, dim3(blocks(grid_nn(C))), dim3(MG_BS), 0, s, F, C, mf, mc, flag); launched("k_mg_mask_closed");
 }
 void mg_cheb(int64_t n, double* x, double* r, double* d, const double* Ad, const double* dinv, double c1, double c2, bool first, hipStream_t s) {
    hipLaunchKernelGGL(k_mg_cheb, dim3(blocks(n)), dim3(MG_BS), 0, s, n, x, r, d, Ad, dinv, c1, c2, first ? 1 : 0); launched("k_mg_cheb");

@@ -545,6 +545,13 @@ exa_driver_get_nodal = _sig("exa_driver_get_nodal", C.c_int, C.c_void_p, C.c_int
 exa_periodic_sum_scratch_bytes = _sig("exa_periodic_sum_scratch_bytes", C.c_int)
 exa_driver_set_mg_periodic = _sig("exa_driver_set_mg_periodic", C.c_int, C.c_void_p, C.c_int)
 exa_mg_periodic_scratch_bytes = _sig("exa_mg_periodic_scratch_bytes", C.c_int, C.POINTER(C.c_int))
+exa_driver_set_mg_p2 = _sig("exa_driver_set_mg_p2", C.c_int, C.c_void_p, C.c_int)
+exa_driver_set_mg_p2_build = _sig("exa_driver_set_mg_p2_build", C.c_int, C.c_void_p, C.c_int)
+exa_driver_mg_info_order = _sig("exa_driver_mg_info_order", C.c_int, C.c_void_p, C.POINTER(C.c_int))
+exa_mg_level_count_order = _sig("exa_mg_level_count_order", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int)
+exa_options_query_mg_p2 = _sig("exa_options_query_mg_p2", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int)
+exa_mg_p2_scratch_bytes = _sig("exa_mg_p2_scratch_bytes", C.c_int, C.POINTER(C.c_int))
+exa_grad_mg_p2_build = _sig("exa_grad_mg_p2_build", C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 exa_driver_newton_info = _sig("exa_driver_newton_info", C.c_int, C.c_void_p, _dp)
 exa_options_query_bcs = _sig("exa_options_query_bcs", C.c_int, C.c_char_p, C.POINTER(C.c_int), _dp, C.c_int, C.c_char_p, C.c_int)
 exa_partition_query_periodic = _sig("exa_partition_query_periodic", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
@@ -718,6 +725,33 @@ def mg_level_count(N, nranks=1, cap=0):
     """coarse multigrid levels of an N0 x N1 x N2 element grid on nranks block ranks (0: multigrid refused), capped by cap > 0"""
     n = (C.c_int * 3)(*([int(N)] * 3 if isinstance(N, int) else [int(v) for v in N]))
     return exa_mg_level_count(n, int(nranks), int(cap))
+
+
+def mg_level_count_order(N, nranks=1, cap=0, order=1):
+    """... at polynomial order 1 (mg_level_count) or 2: one more level, the element vertices, which needs no evenness (so never 0)"""
+    n = (C.c_int * 3)(*([int(N)] * 3 if isinstance(N, int) else [int(v) for v in N]))
+    r = exa_mg_level_count_order(n, int(nranks), int(cap), int(order))
+    if r < 0:
+        raise ValueError("mg_level_count_order: order 1 or 2, positive sizes")
+    return r
+
+
+def options_mg_p2(path):
+    """[Solvers.Krylov] mg_p2 of an options file (read next to preconditioner = "multigrid"): True / False"""
+    out = (C.c_int * 1)()
+    err = C.create_string_buffer(512)
+    if exa_options_query_mg_p2(path.encode(), out, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return bool(out[0])
+
+
+def mg_p2_scratch_bytes():
+    """private (scratch) bytes per lane of the kernels behind exa_grad_mg_p2_build in the loaded code object: dict of eight (all must be 0)"""
+    o = (C.c_int * 8)()
+    if exa_mg_p2_scratch_bytes(o) != 0:
+        raise RuntimeError("exa_mg_p2_scratch_bytes: no device")
+    names = [f"{k}_{f}{t}" for k in ("level1", "diag") for f in ("full", "compact") for t in ("", "_trans")]
+    return dict(zip(names, [int(v) for v in o]))
 
 
 def options_checkpoint(path):
@@ -1188,12 +1222,15 @@ class Driver:
         return dict(pcg_ms=o[0], iters=int(o[1]), apply_ms=o[2])
 
     # ---- preconditioner (exa_driver_set_preconditioner) and the multigrid test hooks ---------------------------------------
-    def set_preconditioner(self, kind, levels=0, degree=2, periodic=False):
+    def set_preconditioner(self, kind, levels=0, degree=2, periodic=False, p2=False):
         """kind: "identity", "jacobi" or "multigrid" (or 0 / 1 / 2); levels: max coarse levels (0 = as many as the mesh allows); degree: Chebyshev degree;
-        periodic=True: multigrid may meet set_periodic, before or after this call (opt-in, like Solvers.Krylov.mg_periodic; refused without it)"""
+        periodic=True: multigrid may meet set_periodic, before or after this call (opt-in, like Solvers.Krylov.mg_periodic; refused without it);
+        p2=True: multigrid on a generated p = 2 mesh (opt-in, like Solvers.Krylov.mg_p2; refused without it)"""
         k = PRECOND_KINDS[kind] if isinstance(kind, str) else int(kind)
         if periodic:
             exa_driver_set_mg_periodic(self.h, 1)
+        if p2:
+            exa_driver_set_mg_p2(self.h, 1)
         self._chk(exa_driver_set_preconditioner(self.h, k, int(levels), int(degree), self._err, 512))
 
     def set_periodic(self, vel_grad, free=None):
@@ -1317,8 +1354,17 @@ class Driver:
             raise RuntimeError("exa_driver_mg_info failed (no multigrid preconditioner)")
         L = int(out[0])
         per = out[4:4 + 4 * (L + 1)].reshape(L + 1, 4)
+        oi = (C.c_int * 40)()
+        if exa_driver_mg_info_order(self.h, oi) != 0:
+            raise RuntimeError("exa_driver_mg_info_order failed (no multigrid preconditioner)")
         return dict(levels=L, setup_ms=float(out[1]), vcycle_ms=float(out[2]), degree=int(out[3]), boxes=per[:, :3].astype(int), lmax=per[:, 3].copy(),
-                    periodic=bool(out[4 + 4 * (L + 1)]), control_dofs=int(out[5 + 4 * (L + 1)]))
+                    periodic=bool(out[4 + 4 * (L + 1)]), control_dofs=int(out[5 + 4 * (L + 1)]), order=[int(oi[2 + l]) for l in range(L + 1)],
+                    level1_build={1: "records", 0: "probe"}.get(int(oi[1])))
+
+    def set_mg_p2_build(self, from_records=True):
+        """p = 2 hierarchy, from the next set-up on: level 1 and the fine diagonal from the point records where they can serve (default), or
+        always by probing (False: what the records build is compared against)"""
+        exa_driver_set_mg_p2_build(self.h, 1 if from_records else 0)
 
     def mg_setup(self):
         """gradient set-up of the current state + hierarchy build (the hooks then act on the operator the driver holds now)"""

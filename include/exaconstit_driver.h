@@ -112,7 +112,7 @@ int exa_checkpoint_info(const char* path, int64_t* out20, double* outd3, uint64_
 void exa_driver_destroy(exa_driver* d);
 /* Preconditioner of the PCG (Solvers.Krylov.preconditioner in an options file; this call overrides it), valid before the first step (so
  * synthetic and exa_driver_bench_prepare'd drivers can use it): kind 0 identity, 1 Jacobi, 2 geometric multigrid V-cycle (generated p = 1
- * meshes, not B-bar) with at most `levels` coarse levels (0: as many as the mesh allows) and a Chebyshev smoother of `degree` (1 ... 8).
+ * meshes, p = 2 after exa_driver_set_mg_p2, not B-bar) with at most `levels` coarse levels (0: as many as the mesh allows) and a Chebyshev smoother of `degree` (1 ... 8).
  * Refused (-1, err) where no coarse level can be built for the decomposition. */
 int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen);
 /* out (>= 6 + 4 (L + 1) doubles) = { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree, then per level
@@ -122,6 +122,17 @@ int exa_driver_mg_info(exa_driver* d, double* out);
 /* Multigrid on a periodic cell is opt-in ([Solvers.Krylov] mg_periodic = true in an options file): on != 0 before exa_driver_set_preconditioner(2) /
  * exa_driver_set_periodic lets the two meet, in either order; without it either call refuses the other, as before.  Returns 0. */
 int exa_driver_set_mg_periodic(exa_driver* d, int on);
+/* Multigrid at p_refinement = 2 is opt-in ([Solvers.Krylov] mg_p2 = true): on != 0 before exa_driver_set_preconditioner(2) makes a generated
+ * p = 2 mesh legal (level 1 = the trilinear space on the element vertices); without it the call refuses p = 2 as before.  B-bar, file and
+ * tetrahedral meshes, p >= 3 and periodic cells at p = 2 stay refused.  Returns 0. */
+int exa_driver_set_mg_p2(exa_driver* d, int on);
+/* How the p = 2 hierarchy builds level 1 and the fine diagonal from the next set-up on: 1 (default) from the point records in one pass each
+ * (exa_grad_mg_p2_build) where the action runs from records and the essential set is closed under the interpolation, by probing otherwise;
+ * 0 always by probing (what the tests compare the records build against).  Returns 0. */
+int exa_driver_set_mg_p2_build(exa_driver* d, int from_records);
+/* out (>= 2 + L + 1 ints) = { coarse levels L, level-1 build of the last set-up (0 probe, 1 records; -1 before the first set-up or at p = 1),
+ * then the polynomial order of every level l = 0 ... L }.  Returns 0 or -1 (no multigrid preconditioner). */
+int exa_driver_mg_info_order(exa_driver* d, int* out);
 /* Test hooks on the hierarchy of the last gradient set-up; host arrays of exa_driver_mg_level_dofs(level) doubles (node-major per component,
  * node = i + n0 (j + n1 k) of the rank's local box at that level).  Level 0 is the constrained operator the PCG applies. */
 int64_t exa_driver_mg_level_dofs(exa_driver* d, int level);
@@ -300,6 +311,10 @@ int exa_options_query_bcs(const char* toml_path, int* out2, double* vel_grad, in
 int exa_options_query_solver(const char* toml_path, int* out3, char* err, int errlen);
 /* number of coarse multigrid levels of an N0 x N1 x N2 element grid on nranks block ranks (0: multigrid refused), capped by cap > 0 */
 int exa_mg_level_count(const int* N, int nranks, int cap);
+/* ... at polynomial order 1 (the same) or 2: one more level, the element vertices, which needs no evenness (never 0); -1 for other orders */
+int exa_mg_level_count_order(const int* N, int nranks, int cap, int order);
+/* [Solvers.Krylov] mg_p2 of an options file (0 / 1; read next to preconditioner = "multigrid" only); returns 0 or -1 (err) */
+int exa_options_query_mg_p2(const char* toml_path, int* out1, char* err, int errlen);
 /* Visualizations table (reference src/option_parser.cpp:540-570): paraview (default 0), steps (1), light_up (0), floc ("results/exaconstit",
  * relative to the driver's output directory); returns 0 or -1 (err) */
 int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen);

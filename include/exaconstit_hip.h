@@ -283,6 +283,21 @@ int exa_grad_apply_lvec_cols(exa_ctx* ctx, int ncols, const double* x_dev, int64
 /* private (scratch) bytes per lane of the kernels behind exa_grad_apply_lvec_cols and the macroscopic tangent in the loaded code object:
  * out8 = { column action at 1, 2, 3 columns per pass, affine columns, contraction (9 columns, 1 column), its combine, 0 }; 0, or -1 without a device */
 int exa_tangent_scratch_bytes(int* out8);
+/* p = 2 multigrid (generated hexahedral box of ne[0] x ne[1] x ne[2] local elements, nodes numbered x fastest on the (2 ne + 1)^3 grid): this
+ * rank's part of the trilinear Galerkin product P^T K P on the element vertices and of the diagonal of K, both from the point records
+ * exa_grad_apply_lvec reads (compact records with geometry or 46-double records, the transposed tangent under element assembly), in one pass
+ * each, gathered in a fixed order (no atomics: the same bits for the same records).
+ *   elem_at_dev  local element index at position ex + ne[0] (ey + ne[1] ez) of the box
+ *   S_dev        (nullable) 243 doubles per vertex, [(o * 9 + 3 r + c) * NV + vertex], o = (dx+1) + 3 (dy+1) + 9 (dz+1), NV = prod (ne + 1); rows
+ *                and columns of the dofs marked in mask1_dev (3 NV bytes) are zero
+ *   diag_dev     (nullable) 3 nnodes doubles, zero on the dofs marked in mask0_dev (3 nnodes bytes)
+ * EXA_ERR_UNSUPPORTED, nothing written, where the L-vector action does not run from such records (B-bar, deterministic mode, assembled element
+ * matrices, other orders, tetrahedra). */
+int exa_grad_mg_p2_build(exa_ctx* ctx, const int* ne, const int32_t* elem_at_dev, const uint8_t* mask0_dev, const uint8_t* mask1_dev, double* S_dev,
+                         double* diag_dev, exa_stream s);
+/* private (scratch) bytes per lane of its kernels in the loaded code object: out8 = { vertex stencil: 46-double records plain, transposed, compact
+ * records plain, transposed; diagonal: the same four }; 0, or -1 without a device */
+int exa_mg_p2_scratch_bytes(int* out8);
 /* Optional (p = 1 partial assembly, L-vector action): the nodal coordinates (nnodes,3 byNODES) the Jacobians given to exa_grad_setup
  * were computed from.  When set, exa_grad_apply_lvec recomputes adj(J) from them instead of streaming it from its per-point record
  * (36 instead of 46 doubles per point from HBM); the array must stay unchanged until the next exa_grad_setup.  NULL switches it off. */
