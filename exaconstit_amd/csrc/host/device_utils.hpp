@@ -62,6 +62,30 @@ void vk_cg_step2z(int64_t n, double* S, double* z, const double* r, double* d, b
 void vk_dot_partial(int64_t n, int64_t nn, const double* w, const double* a, const double* b, const double* flag, double* partial, hipStream_t s);   // partial sums only (their consumer reduces them)
 void vk_mask_dot(int64_t n, int64_t nn, const double* w, const uint8_t* m, const double* a, double* b, const double* flag, double* partial, double* out, hipStream_t s,
                  double* fuse_den_S = nullptr);
+// GMRES (gmres_kernels.hip, ../gmres_slots.hpp).  S: the device record; V: basis vectors at a fixed stride; vectors and stride at
+// multiples of 16 bytes; gate 0: leave when FLAG is set, 1: also unless a second Gram-Schmidt pass was decided, 2: run regardless
+constexpr int GM_BLOCKS = 1024;   // most blocks of a multi-dot: rows of its partial-sum table (gmres::MAXK + 2 columns)
+struct GmStage {   // what the one-block scalar kernel does after summing reduce_cols columns of the table into the record
+   enum Kind : int { REDUCE = 0, START, RESTART, COEF, NORM, SOLVE };
+   int stage = REDUCE, reduce_cols = 0;
+   int col = 0;                            // column of H at work
+   int j0 = 0, k = 0;                      // COEF: RED[0 .. k) are the coefficients against v_j0 ... and go to (accumulate: are added to) rows j0 ... of the column
+   int accumulate = 0, with_norm = 0;      // with_norm: RED[k] is |w|^2 before the pass
+   int gate_reorth = 0;                    // a launch of the second pass
+   int decide = 0;                         // NORM: 0 finish the column, 1 second pass on the criterion, 2 always
+   int column_update = 1;                  // NORM: 0 only h_i+1,i (the orthogonalisation probe)
+   int max_iter = 0, force = 0;
+   double rel_tol = 0.0, abs_tol = 0.0;    // START
+};
+int gm_chunk();
+unsigned gm_blocks(int64_t n);
+void gm_multidot(int64_t n, int64_t nn, const double* wgt, const double* V, int64_t stride, int j0, int k, const double* w, bool with_norm, const double* S, int gate,
+                 double* table, hipStream_t s);
+void gm_multiaxpy(int64_t n, int64_t nn, const double* wgt, const double* V, int64_t stride, int j0, int k, const double* S, int coef, double sign, double* w, int gate,
+                  double* table /* may be null */, hipStream_t s);
+void gm_scale(int64_t n, double* dst, const double* src, const double* dinv /* may be null */, const double* S, int slot /* < 0: none */, hipStream_t s);
+void gm_resid(int64_t n, double* dst, const double* b, const double* t, const double* dinv /* may be null */, const double* S, hipStream_t s);
+void gm_scalar(double* S, const double* table, int nb, const GmStage& a, hipStream_t s);
 void vk_min3(int64_t nn, const double* x, double* partial /*>= DOT_BLOCKS*/, double* out3, hipStream_t s);
 void vk_vgrad_velocity(int64_t nn, const uint8_t* m, const double* x, const double* org3_dev, const double* L9_host, double* v, hipStream_t s);
 void vk_qf_eb64_to_aos(int W, int Q, int64_t E, const double* src_eb64, double* dst_aos, hipStream_t s);   // (W, Q, E) <- [block][q][W][lane]

@@ -454,7 +454,8 @@ void SystemDriver::init(const std::vector<double>& props, const std::vector<doub
    PCGSolver::Settings ks;
    ks.rel_tol = opt_.krylov_rel; ks.abs_tol = opt_.krylov_abs; ks.max_iter = opt_.krylov_iter;
    if (const char* g = std::getenv("EXA_PCG_GRAPH")) { if (std::string(g) == "0") ks.graph_max_dofs = 0; else if (std::string(g) == "all") ks.graph_max_dofs = INT64_MAX; }
-   krylov_.reset(new PCGSolver(*oper_, ks));
+   if (opt_.krylov_solver == "gmres") { ks.kdim = opt_.gmres_kdim; krylov_.reset(new GMRESSolver(*oper_, ks)); }
+   else krylov_.reset(new PCGSolver(*oper_, ks));
    analyses_.reset(new StepAnalyses(*oper_, comm, part, opt_, elem_attr, std::move(grain_qref)));
 }
 
@@ -594,6 +595,23 @@ void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
    } else op.mg.reset();
    krylov_->DropGraph();
    op.precond = kind == 0 ? Precond::IDENTITY : (kind == 1 ? Precond::JACOBI : Precond::MULTIGRID);
+}
+
+void SystemDriver::SetKrylov(const std::string& solver, int kdim) {
+   const std::string k = ExaOptions::lower(solver);
+   KrylovSolver::Settings ks = krylov_->set;
+   std::unique_ptr<KrylovSolver> next;
+   if (k == "gmres") {
+      if (kdim < 1 || kdim > 100) throw std::runtime_error(ExaOptions::gmres_kdim_range());
+      ks.kdim = kdim;
+      next.reset(new GMRESSolver(*oper_, ks));
+      opt_.gmres_kdim = kdim;
+   } else if (k == "pcg") next.reset(new PCGSolver(*oper_, ks));
+   else throw std::runtime_error("set_krylov: the solver is \"pcg\" or \"gmres\"");
+   // the diagnostics and totals are the run's, not the object's: they go on counting
+   next->diag = krylov_->diag; next->krylov_ms = krylov_->krylov_ms; next->krylov_iters = krylov_->krylov_iters;
+   krylov_ = std::move(next);
+   opt_.krylov_solver = k;
 }
 
 void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {

@@ -7,6 +7,7 @@
 //   MechOperatorJacobiSmoother           reference src/mechanics_operator_ext.cpp:11-55
 //   ExaNewtonSolver / ExaNewtonLSSolver  reference src/mechanics_solver.cpp:39-281
 //   PCGSolver (host/krylov.hpp)          MFEM CGSolver, set up at reference src/system_driver.cpp:166-177
+//   GMRESSolver (host/krylov.hpp)        MFEM GMRESSolver, set up at reference src/system_driver.cpp:152-164
 //   SystemDriver                         reference src/system_driver.cpp:221-558
 //   Comm (host/comm.hpp)               MPI in the reference (src/mechanics_driver.cpp:312, src/system_driver.cpp:167, src/mechanics_kernels.hpp:119,124)
 //   OperatorRoutes (host/routes.hpp)     the operator's EXA_* switches and which kernels it runs for them (no counterpart in the reference)
@@ -230,7 +231,11 @@ class SystemDriver {
    void MixedStepEnd();   // realised gradient and face resultants of the converged step
    const MixedLoading& mixed_loading() const { return mix_; }
    double last_newton_norm = 0.0, last_newton_bound = 0.0;   // final residual norm and max(rel |r0|, abs) of the last Newton solve
-   PCGSolver& krylov() { return *krylov_; }   // the run's linear solver
+   KrylovSolver& krylov() { return *krylov_; }   // the run's linear solver: PCG or GMRES
+   // the run's linear solver anew (exa_driver_set_krylov): "pcg", or "gmres" with its Krylov dimension; before the first step or between steps.
+   // Tolerances, cap and chunk stay, and the run's diagnostics and totals (solves not converged, worst reduction, Krylov ms and iterations) go on
+   // counting; the restarts and second passes of krylov_info are the new GMRES object's.
+   void SetKrylov(const std::string& solver, int kdim);
    StepAnalyses& analyses() { return *analyses_; }   // the run's in-situ analyses (host/analyses.hpp) ...
    StepState state() const { return { steps_done, time, step_dt_, out_dir, write_files, v_sol }; }   // ... and where the run stands, for their calls
    // Homogenised tangent d sigma_bar / d L_bar of the last solved step of a periodic cell (host/tangent.hip), every rank calls it.
@@ -250,6 +255,10 @@ class SystemDriver {
    // sc[2 m + 1] = the last (r, z).  Every rank calls it.  Leaves the run as it found it.
    void PcgSolveProbe(int nc, const double* b, double rel_tol, double abs_tol, int max_iter, int check_every, int graph, int mode, double* x, int* iters, int* flag,
                       double* reduction, int* indefinite, double* sc);
+   // probe of GMRES (exa_driver_gmres_solve), as PcgSolveProbe: a GMRESSolver of the probe's own, the columns in turn.  ortho: -1 EXA_GMRES_ORTHO,
+   // 0 ... 3 GMRESSolver::Ortho.  Per column sc[4 m ...] = beta0, the last residual norm, restarts, second Gram-Schmidt passes.
+   void GmresSolveProbe(int nc, const double* b, double rel_tol, double abs_tol, int max_iter, int kdim, int check_every, int ortho, double* x, int* iters, int* flag,
+                        double* reduction, double* sc);
    int tangent_nch = 0;                 // columns per pass of the multi-column action (0: the library's default; EXA_TANGENT_NCH)
    bool tangent_auto_batched = true;    // what batched = -1 picks where the batched route is available (EXA_TANGENT_BATCHED=0 | 1)
    std::vector<double> macro_tangent_rows;   // Visualizations.macro_tangent: MACRO_TANGENT_ROW values per written evaluation
@@ -278,7 +287,7 @@ class SystemDriver {
    void init(const std::vector<double>& props, const std::vector<double>& quats_local, std::vector<double> grain_qref);
    ExaOptions opt_;
    std::unique_ptr<NonlinearMechOperator> oper_;
-   std::unique_ptr<PCGSolver> krylov_;
+   std::unique_ptr<KrylovSolver> krylov_;
    std::unique_ptr<StepAnalyses> analyses_;
    DevBuf<double> r_, c_, xt_, ess_val_;
    std::vector<uint8_t> ess_host_; std::vector<double> ess_val_host_;

@@ -2,6 +2,8 @@
 // They expose the reference's run-time surface: `mechanics -opt options.toml` (reference src/mechanics_driver.cpp:139-144),
 // the per-step loop, the avg_* outputs (reference src/system_driver.cpp:444-553) and the timing regions the reference marks
 // with Caliper (ecmech_kernel, krylov_solver: src/mechanics_ecmech.cpp:237-257, src/mechanics_solver.cpp:99-103).
+#include "../gmres_slots.hpp"
+#include "../gmres_small.hpp"
 #include "driver.hpp"
 #include "multigrid.hpp"
 #include "rank_sync.hpp"
@@ -355,6 +357,59 @@ int exa_driver_pcg_solve(exa_driver* d, int nrhs, const double* b, double rel_to
    } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 
+// The run's linear solver: solver "pcg" or "gmres" (any case), kdim the Krylov dimension of GMRES (1 ... 100; ignored for PCG).  Legal before the
+// first step and between steps; tolerances and cap stay, the run's diagnostics and totals go on counting.  Every rank calls it.
+int exa_driver_set_krylov(exa_driver* d, const char* solver, int kdim, char* err, int errlen) {
+   try { d->sd->SetKrylov(solver ? solver : "", kdim); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+// out3i = { solver: 0 PCG, 1 GMRES; kdim (0 for PCG); chunk of the multi-dot kernel }, out3 = { restarts, second Gram-Schmidt passes - both over all
+// solves of the run's solver - and the bytes of its basis (0 before the first GMRES solve) }
+int exa_driver_krylov_info(exa_driver* d, int* out3i, int64_t* out3) {
+   KrylovSolver& k = d->sd->krylov();
+   out3i[0] = k.gmres() ? 1 : 0; out3i[1] = k.gmres() ? k.set.kdim : 0; out3i[2] = gm_chunk();
+   out3[0] = out3[1] = out3[2] = 0;
+   if (k.gmres()) { const GMRESSolver& g = static_cast<const GMRESSolver&>(k); out3[0] = g.restarts; out3[1] = g.reorth_passes; out3[2] = (int64_t)g.basis_bytes(); }
+   return 0;
+}
+int exa_gmres_multidot_chunk(void) { return gm_chunk(); }   // basis vectors per pass of the multi-dot kernel, a compile-time constant
+// Probe of GMRES, mirroring exa_driver_pcg_solve: K_uu x_m = b_m from x = 0 for nrhs <= 16 host columns in turn, in a GMRES solver of the probe's own
+// with the run's preconditioner.  ortho: -1 as EXA_GMRES_ORTHO says, 0 ifneeded, 1 always, 2 never, 3 mgs.  Per column: x, Arnoldi steps, flag,
+// reduction = last residual / beta0, scalars4[4 m ...] = { beta0, last residual norm, restarts, second Gram-Schmidt passes }.
+int exa_driver_gmres_solve(exa_driver* d, int nrhs, const double* b, double rel_tol, double abs_tol, int max_iter, int kdim, int check_every, int ortho, double* x, int* iters,
+                           int* flags, double* reduction, double* scalars4, char* err, int errlen) {
+   try {
+      d->sd->GmresSolveProbe(nrhs, b, rel_tol, abs_tol, max_iter, kdim, check_every, ortho, x, iters, flags, reduction, scalars4);
+      return 0;
+   } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+// The two bandwidth kernels of the orthogonalisation on any shape: w (n) against the k vectors V (k x n, row j = v_j) in the product weighted by
+// weight (n); flag != 0: the kernels' gate is closed.  mode as ortho above (>= 0).  h (k): the column of H; w_out (n); wnorm2 = |w_out|^2 from the
+// partial sums of the subtraction kernel; passes: 0 with the gate closed, else 1 + second passes.
+int exa_gmres_ortho_probe(int64_t n, int k, const double* weight, const double* V, const double* w, double flag, int mode, double* h, double* w_out, double* wnorm2, int* passes,
+                          char* err, int errlen) {
+   try { gmres_ortho_probe(n, k, weight, V, w, flag, mode, h, w_out, wnorm2, passes); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+// measurement hook of scripts/gmres_compare.py, no part of a run: timing of the same launches on device buffers of the call's own, ms per orthogonalisation (and normalisation) of column col, col + 1 basis vectors
+int exa_gmres_ortho_bench(int64_t n, int col, int mode, int reps, double* ms, char* err, int errlen) {
+   try { *ms = gmres_ortho_bench(n, col, mode, reps); return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
+}
+// Host only, no GPU call: the small algebra the scalar kernel runs (gmres_small.hpp).  Hbar: ncols columns at leading dimension ncols + 1, column i
+// holding h_0i ... h_i+1,i as Gram-Schmidt leaves them; beta: the first residual norm.  resid (ncols): |s_i+1| after column i; flags (ncols): what
+// the solver would decide after that column with the bound final_norm and no iteration cap; y (ncols): the back-substitution over all columns.
+// Returns 1 when the back-substitution met no zero pivot, 0 when it did (those y_i are 0).
+int exa_gmres_column_probe(int ncols, const double* Hbar, double beta, double final_norm, double* resid, int* flags, double* y) {
+   if (ncols < 1 || ncols > gmres::MAXK) return -1;
+   const int ld = ncols + 1;
+   std::vector<double> H(Hbar, Hbar + (size_t)ld * ncols), cs(ncols), sn(ncols), s(ncols + 1, 0.0);
+   s[0] = beta;
+   for (int i = 0; i < ncols; i++) {
+      const double hn = H[(size_t)i * ld + i + 1];
+      resid[i] = gmres::column_update(i, H.data() + (size_t)i * ld, cs.data(), sn.data(), s.data());
+      flags[i] = (int)gmres::step_flag(resid[i], final_norm, hn, i + 1.0, 1e300);
+   }
+   return gmres::back_substitute(ncols, H.data(), ld, s.data(), y) ? 1 : 0;
+}
+
 // columns per pass of the batched route (1 .. 3; 0: the library's default) and what the automatic route picks where both exist (batched != 0)
 int exa_driver_set_tangent_route(exa_driver* d, int nch, int auto_batched) {
    if (nch < 0 || nch > 3) return -1;
@@ -578,7 +633,7 @@ int exa_driver_get_stats(exa_driver* d, int* newton, int* krylov, int* model_cal
 // out[0] ms in the fused constitutive kernel, out[1] ms in PCG, out[2] ms in Solve (+SolveInit), out[3] qpt updates, out[4] PCG iterations
 void exa_driver_get_timers(exa_driver* d, double* out) {
    d->sd->oper().FlushModelTimers();
-   const Timers& t = d->sd->oper().timers; const PCGSolver& k = d->sd->krylov();
+   const Timers& t = d->sd->oper().timers; const KrylovSolver& k = d->sd->krylov();
    out[0] = t.t_model_ms; out[1] = k.krylov_ms; out[2] = t.t_solve_ms; out[3] = (double)t.qpt_updates; out[4] = (double)k.krylov_iters;
 }
 void exa_driver_reset_timers(exa_driver* d) { d->sd->oper().FlushModelTimers(); d->sd->oper().timers = Timers(); d->sd->krylov().ResetTotals(); }   // pending event pairs belong to the old totals
@@ -586,7 +641,7 @@ void exa_driver_reset_timers(exa_driver* d) { d->sd->oper().FlushModelTimers(); 
 // did not converge, out[2] PCG iterations that saw (Ad, d) < 0, out[3] flag of the last PCG solve (1 converged, 2 max_iter, -1 den == 0)
 void exa_driver_get_diagnostics(exa_driver* d, int64_t* out) {
    d->sd->oper().ReadModelStatus();
-   const PCGSolver::Diagnostics& k = d->sd->krylov().diag;
+   const KrylovSolver::Diagnostics& k = d->sd->krylov().diag;
    out[0] = d->sd->oper().model_fail_total; out[1] = k.not_converged; out[2] = k.indefinite_iters; out[3] = k.last_flag;
 }
 // launches of exa_slip_rates_from_state so far (lean end-of-step state: NonlinearMechOperator::EnsureSlipRates)

@@ -1,17 +1,22 @@
-// PCGSolver (host/krylov.hpp): three loops for one system - device scalars, single reduction, multigrid - and the lockstep loop for several,
-// between one prologue (Frame) and one epilogue (Finish).
+// The linear solvers (host/krylov.hpp).  PCGSolver: three loops for one system - device scalars, single reduction, multigrid - and the lockstep
+// loop for several; GMRESSolver: one loop; all between one prologue (Frame) and one epilogue (Finish).
 #include "driver.hpp"
 #include "multigrid.hpp"
 #include "roctx.hpp"
 #include "../pcg_slots.hpp"
+#include "../gmres_slots.hpp"
+#include "../gmres_small.hpp"
 #include <cmath>
 #include <iostream>
 
 namespace exa_host {
 
-static_assert(sizeof(PCGSolver::last) / sizeof(PCGSolver::Last) == EXA_GRAD_COLS_MAX, "one entry per column of the lockstep solve");
+static_assert(sizeof(KrylovSolver::last) / sizeof(KrylovSolver::Last) == EXA_GRAD_COLS_MAX, "one entry per column of the lockstep solve");
+static_assert(gmres::F_RUNNING == pcg::RUNNING && gmres::F_CONVERGED == pcg::CONVERGED && gmres::F_MAX_ITER == pcg::MAX_ITER && gmres::F_BREAKDOWN == pcg::BREAKDOWN, "one set of flags");
 
-PCGSolver::PCGSolver(NonlinearMechOperator& op, const Settings& set_) : set(set_), op_(op), comm_(op.comm()) {
+KrylovSolver::KrylovSolver(NonlinearMechOperator& op, const Settings& set_, const char* name) : set(set_), op_(op), comm_(op.comm()), name_(name) {}
+
+PCGSolver::PCGSolver(NonlinearMechOperator& op, const Settings& set_) : KrylovSolver(op, set_, "PCG") {
    const size_t nd = (size_t)op.Height();
    r_.alloc(nd); z_.alloc(nd); d_.alloc(nd);
    S_.alloc((size_t)EXA_GRAD_COLS_MAX * pcg::LEN); S_.zero(op.stream());
@@ -24,7 +29,7 @@ void PCGSolver::DropGraph() {
    graph_key_ = GraphKey();
 }
 
-struct PCGSolver::Frame {
+struct KrylovSolver::Frame {
    ProfRegion prof; hipStream_t s; hipEvent_t e0 = nullptr, e1 = nullptr;
    explicit Frame(hipStream_t s_) : prof("krylov_solver"), s(s_) { EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1)); EXA_HC(hipEventRecord(e0, s)); }
    float stop() { EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1)); float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e0, e1)); return ms; }
@@ -43,7 +48,7 @@ void PCGSolver::ReadRecords(int n, bool in_flight, Outcome* out) {
    }
 }
 
-void PCGSolver::Finish(Frame& f, const Outcome* o, int n) {
+void KrylovSolver::Finish(Frame& f, const Outcome* o, int n) {
    krylov_ms += f.stop();
    for (int m = 0; m < n; m++) {
       const bool converged = o[m].flag == (int)pcg::CONVERGED;
@@ -55,9 +60,9 @@ void PCGSolver::Finish(Frame& f, const Outcome* o, int n) {
       if (!converged) diag.worst_capped_reduction = std::max(diag.worst_capped_reduction, diag.last_reduction);
       // what MFEM prints (CGSolver::Mult): breakdown, indefinite operator, no convergence within max_iter
       if (comm_.rank == 0 && (set.verbose || std::getenv("EXA_VERBOSE"))) {
-         if (o[m].indefinite > 0) std::cerr << "PCG: The operator is not positive definite. (Ad, d) < 0 in " << o[m].indefinite << " iteration(s)\n";
-         if (o[m].flag == (int)pcg::BREAKDOWN) std::cerr << "PCG: (Ad, d) = 0, stopping after " << o[m].iters << " iterations\n";
-         else if (!converged) std::cerr << "PCG: No convergence! (" << o[m].iters << " iterations)\n";
+         if (o[m].indefinite > 0) std::cerr << name_ << ": The operator is not positive definite. (Ad, d) < 0 in " << o[m].indefinite << " iteration(s)\n";
+         if (o[m].flag == (int)pcg::BREAKDOWN) std::cerr << name_ << (gmres() ? ": breakdown, stopping after " : ": (Ad, d) = 0, stopping after ") << o[m].iters << " iterations\n";
+         else if (!converged) std::cerr << name_ << ": No convergence! (" << o[m].iters << " iterations)\n";
       }
    }
 }
@@ -303,6 +308,192 @@ void PCGSolver::SolveColumns(int nc, const double* B, double* X, int64_t ld, int
       reduction[m] = o[m].reduction();
       flag[m] = o[m].flag == (int)pcg::RUNNING ? (int)pcg::MAX_ITER : o[m].flag;
    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// GMRES(kdim).  One Arnoldi step at column i is a fixed sequence of launches on the device record S: action (+ preconditioner), multi-dot against
+// v_0 ... v_i with |w|^2 as one more column, scalar kernel (column of H, coefficients), multi-axpy with the partial sums of the new |w|^2, scalar
+// kernel (second pass or not; else h_i+1,i, rotations, residual, flag), the four launches of the second pass (they leave at once when it was
+// not decided), normalisation.  w lives where v_i+1 will: the normalisation is in place.  The host polls the head of the record every check_every
+// steps (multigrid: every step) and at the end of a cycle, and enqueues the back-substitution and x += V y when it sees a stop.
+GMRESSolver::GMRESSolver(NonlinearMechOperator& op, const Settings& set_) : KrylovSolver(op, set_, "GMRES") {
+   if (set.kdim < 1 || set.kdim > gmres::MAXK) throw std::runtime_error("GMRES: the Krylov dimension (gmres_kdim) is a whole number in 1 ... 100");
+   S_.alloc(gmres::LEN); S_.zero(op.stream());
+}
+
+bool GMRESSolver::parse_ortho(const char* name, Ortho* out) {
+   const std::string v = name ? name : "";
+   if (v.empty() || v == "ifneeded") *out = Ortho::IFNEEDED; else if (v == "always") *out = Ortho::ALWAYS; else if (v == "never") *out = Ortho::NEVER;
+   else if (v == "mgs") *out = Ortho::MGS; else return false;
+   return true;
+}
+
+// (Several ranks: the launch that only reduces and the all-reduce are enqueued by the host, so they also run for the launches that leave at once -
+//  after a stop, up to the next poll, and for a second pass that was not decided.  The stale sums they move are never read: needless collectives,
+//  at most check_every steps' worth per stop, the price of not asking the device before every one.)
+void GMRESSolver::Scalar(GmStage a, int cols) {
+   hipStream_t s = op_.stream();
+   if (comm_.active() && cols > 0) {
+      GmStage r; r.stage = GmStage::REDUCE; r.reduce_cols = cols; r.force = a.force; r.gate_reorth = a.gate_reorth;
+      gm_scalar(S_.p, table_.p, nb_, r, s);
+      comm_.allreduce_sum(S_.p + gmres::RED, cols, s);
+      a.reduce_cols = 0;
+   } else a.reduce_cols = cols;
+   gm_scalar(S_.p, table_.p, nb_, a, s);
+}
+
+namespace {
+// the orthogonalisation of w against v_0 ... v_i, for the solver and for the probe: scalar(stage, columns of the table to sum first)
+template <typename ScalarFn>
+void gm_orthogonalise(int64_t n, int64_t nn, const double* wgt, const double* V, int64_t stride, int i, double* w, double* S, double* table, GMRESSolver::Ortho mode, int max_iter,
+                      bool column_update, hipStream_t s, ScalarFn&& scalar) {
+   GmStage coef; coef.stage = GmStage::COEF; coef.col = i;
+   GmStage norm; norm.stage = GmStage::NORM; norm.col = i; norm.max_iter = max_iter; norm.column_update = column_update ? 1 : 0;
+   if (mode == GMRESSolver::Ortho::MGS) {   // MFEM's order: one basis vector at a time through the same two kernels
+      for (int j = 0; j <= i; j++) {
+         gm_multidot(n, nn, wgt, V, stride, j, 1, w, false, S, 0, table, s);
+         coef.j0 = j; coef.k = 1; scalar(coef, 1);
+         gm_multiaxpy(n, nn, wgt, V, stride, j, 1, S, gmres::COEF, -1.0, w, 0, j == i ? table : nullptr, s);
+      }
+      scalar(norm, 1);
+      return;
+   }
+   const int k = i + 1;
+   gm_multidot(n, nn, wgt, V, stride, 0, k, w, true, S, 0, table, s);
+   coef.k = k; coef.with_norm = 1; scalar(coef, k + 1);
+   gm_multiaxpy(n, nn, wgt, V, stride, 0, k, S, gmres::COEF, -1.0, w, 0, table, s);
+   norm.decide = mode == GMRESSolver::Ortho::IFNEEDED ? 1 : (mode == GMRESSolver::Ortho::ALWAYS ? 2 : 0);
+   scalar(norm, 1);
+   if (mode == GMRESSolver::Ortho::NEVER) return;
+   // the second pass: c = V^T W w, w -= V c, h += c.  Always enqueued; every launch leaves at once unless the decision was taken.
+   gm_multidot(n, nn, wgt, V, stride, 0, k, w, false, S, 1, table, s);
+   coef.with_norm = 0; coef.accumulate = 1; coef.gate_reorth = 1; scalar(coef, k);
+   gm_multiaxpy(n, nn, wgt, V, stride, 0, k, S, gmres::COEF, -1.0, w, 1, table, s);
+   norm.decide = 0; norm.gate_reorth = 1; scalar(norm, 1);
+}
+}  // namespace
+
+void GMRESSolver::Step(int i, Ortho mode, bool mg, bool ident) {
+   NonlinearMechOperator& op = op_;
+   hipStream_t s = op.stream();
+   double* S = S_.p;
+   const double* vi = V_.p + (size_t)i * stride_;
+   double* w = V_.p + (size_t)(i + 1) * stride_;
+   // w = M^-1 K v_i, the input masked and the output zero on essential rows
+   if (mg) { op.GradMult(vi, t_.p, true, S + gmres::FLAG); op.mg->Apply(t_.p, w); }
+   else if (ident) op.GradMult(vi, w, true, S + gmres::FLAG);
+   else { op.GradMult(vi, t_.p, true, S + gmres::FLAG); gm_scale(nd_, w, t_.p, op.dinv.p, S, -1, s); }
+   gm_orthogonalise(nd_, nn_, op.weight.p, V_.p, stride_, i, w, S, table_.p, mode, set.max_iter, true, s, [&](const GmStage& a, int cols) { Scalar(a, cols); });
+   gm_scale(nd_, w, w, nullptr, S, gmres::SCALE, s);   // v_i+1 = w / h_i+1,i
+}
+
+int GMRESSolver::Solve(const double* b, double* x) {
+   NonlinearMechOperator& op = op_;
+   hipStream_t s = op.stream();
+   const int64_t nd = op.Height();
+   const int kdim = set.kdim;
+   if (kdim < 1 || kdim > gmres::MAXK) throw std::runtime_error("GMRES: the Krylov dimension (gmres_kdim) is a whole number in 1 ... 100");
+   if ((reinterpret_cast<uintptr_t>(x) & 15) != 0 || (reinterpret_cast<uintptr_t>(b) & 15) != 0) throw std::runtime_error("GMRES: the vectors must start at multiples of 16 bytes");
+   Ortho mode = ortho;
+   if (!ortho_forced && !parse_ortho(std::getenv("EXA_GMRES_ORTHO"), &mode)) throw std::runtime_error("EXA_GMRES_ORTHO is one of ifneeded, always, never, mgs");
+   // (kdim + 2) nd doubles, at the first solve: the basis with the vector at work as its last column, and K v
+   const int64_t stride = (nd + 31) / 32 * 32;
+   if (nd_ != nd || V_.n < (size_t)(kdim + 1) * stride) {
+      nd_ = nd; nn_ = op.part().NN; stride_ = stride; nb_ = (int)gm_blocks(nd);
+      V_.alloc((size_t)(kdim + 1) * stride); t_.alloc(nd); table_.alloc((size_t)(gmres::MAXK + 2) * GM_BLOCKS);
+   }
+   Frame frame(s);
+   double* S = S_.p; double* V0 = V_.p;
+   const bool mg = op.precond == Precond::MULTIGRID, ident = op.precond == Precond::IDENTITY;
+   EXA_HC(hipMemsetAsync(x, 0, sizeof(double) * nd, s));
+   EXA_HC(hipMemsetAsync(S, 0, sizeof(double) * gmres::LEN, s));
+   // r = M^-1 b, beta = |r|
+   if (mg) op.mg->Apply(b, V0); else gm_scale(nd, V0, b, ident ? nullptr : op.dinv.p, S, -1, s);
+   gm_multidot(nd, nn_, op.weight.p, V_.p, stride_, 0, 0, V0, true, S, 0, table_.p, s);
+   { GmStage a; a.stage = GmStage::START; a.force = 1; a.rel_tol = set.rel_tol; a.abs_tol = set.abs_tol; Scalar(a, 1); }
+   gm_scale(nd, V0, V0, nullptr, S, gmres::SCALE, s);
+   const int every = mg ? 1 : std::max(1, set.check_every);
+   double head[gmres::HEAD];
+   int i = 0, launched = 0, since_poll = 0;
+   for (;;) {
+      if (launched < set.max_iter && i < kdim) { Step(i, mode, mg, ident); i++; launched++; since_poll++; }
+      if (launched < set.max_iter && i < kdim && since_poll < every) continue;
+      S_.download(head, gmres::HEAD, s); since_poll = 0;
+      if (head[gmres::FLAG] != pcg::RUNNING) break;
+      if (launched >= set.max_iter) { head[gmres::FLAG] = pcg::MAX_ITER; break; }   // (a cap of 0: the device never saw a column)
+      if (i == kdim) {
+         // end of a cycle: x += V y, r = M^-1 (b - K x), beta = |r|.  The flag was just seen RUNNING, so nothing here needs its gate.
+         { GmStage a; a.stage = GmStage::SOLVE; Scalar(a, 0); }
+         gm_multiaxpy(nd, nn_, op.weight.p, V_.p, stride_, 0, kdim, S, gmres::Y, 1.0, x, 0, nullptr, s);
+         op.GradMult(x, t_.p, true, S + gmres::FLAG);
+         if (mg) { vk_axpby(nd, 1.0, b, -1.0, t_.p, s); op.mg->Apply(t_.p, V0); }
+         else gm_resid(nd, V0, b, t_.p, ident ? nullptr : op.dinv.p, S, s);
+         gm_multidot(nd, nn_, op.weight.p, V_.p, stride_, 0, 0, V0, true, S, 0, table_.p, s);
+         { GmStage a; a.stage = GmStage::RESTART; Scalar(a, 1); }
+         gm_scale(nd, V0, V0, nullptr, S, gmres::SCALE, s);
+         i = 0;
+      }
+   }
+   // the iterate of the columns that are complete (none after a stop at the start of a cycle)
+   if ((int)head[gmres::NCOL] > 0) {
+      { GmStage a; a.stage = GmStage::SOLVE; a.force = 1; Scalar(a, 0); }
+      gm_multiaxpy(nd, nn_, op.weight.p, V_.p, stride_, 0, (int)head[gmres::NCOL], S, gmres::Y, 1.0, x, 2, nullptr, s);
+   }
+   Outcome o; o.flag = (int)head[gmres::FLAG]; o.iters = (int)head[gmres::ITERS];
+   o.r0z0 = head[gmres::BETA0] * head[gmres::BETA0]; o.betanom = head[gmres::RESID] * head[gmres::RESID];
+   if (!std::isfinite(o.betanom)) o.betanom = 0.0;
+   last_beta0 = head[gmres::BETA0]; last_resid = head[gmres::RESID]; last_restarts = (int)head[gmres::RESTARTS]; last_reorth = (int)head[gmres::REORTH_PASSES];
+   restarts += last_restarts; reorth_passes += last_reorth;
+   Finish(frame, &o, 1);
+   return o.iters;
+}
+
+void gmres_ortho_probe(int64_t n, int k, const double* weight, const double* V, const double* w, double flag, int mode, double* h, double* w_out, double* wnorm2, int* passes) {
+   if (n < 1 || k < 1 || k > gmres::MAXK) throw std::runtime_error("gmres_ortho_probe: n >= 1 and 1 <= k <= 100");
+   if (mode < 0 || mode > 3) throw std::runtime_error("gmres_ortho_probe: mode 0 (ifneeded), 1 (always), 2 (never) or 3 (mgs)");
+   hipStream_t s = nullptr;
+   const int64_t stride = (n + 31) / 32 * 32;
+   const int nb = (int)gm_blocks(n);
+   DevBuf<double> dV((size_t)(k + 1) * stride), dwgt((size_t)n), S((size_t)gmres::LEN), table((size_t)(gmres::MAXK + 2) * GM_BLOCKS);
+   dV.zero(s); S.zero(s);
+   for (int j = 0; j < k; j++) EXA_HC(hipMemcpyAsync(dV.p + (size_t)j * stride, V + (size_t)j * n, sizeof(double) * n, hipMemcpyHostToDevice, s));
+   double* dw = dV.p + (size_t)k * stride;
+   EXA_HC(hipMemcpyAsync(dw, w, sizeof(double) * n, hipMemcpyHostToDevice, s));
+   EXA_HC(hipMemcpyAsync(dwgt.p, weight, sizeof(double) * n, hipMemcpyHostToDevice, s));
+   EXA_HC(hipMemcpyAsync(S.p + gmres::FLAG, &flag, sizeof(double), hipMemcpyHostToDevice, s));
+   EXA_HC(hipStreamSynchronize(s));
+   gm_orthogonalise(n, n, dwgt.p, dV.p, stride, k - 1, dw, S.p, table.p, (GMRESSolver::Ortho)mode, 0, false, s,
+                    [&](GmStage a, int cols) { a.reduce_cols = cols; gm_scalar(S.p, table.p, nb, a, s); });
+   std::vector<double> rec = S.to_host(s);
+   EXA_HC(hipMemcpyAsync(w_out, dw, sizeof(double) * n, hipMemcpyDeviceToHost, s)); EXA_HC(hipStreamSynchronize(s));
+   for (int j = 0; j < k; j++) h[j] = rec[gmres::H + (k - 1) * gmres::LDH + j];
+   *wnorm2 = rec[gmres::HNEXT] * rec[gmres::HNEXT];
+   *passes = flag != 0.0 ? 0 : 1 + (int)rec[gmres::REORTH_PASSES];
+}
+
+double gmres_ortho_bench(int64_t n, int col, int mode, int reps) {
+   if (n < 1 || col < 0 || col >= gmres::MAXK || reps < 1 || mode < 0 || mode > 3) throw std::runtime_error("gmres_ortho_bench: n >= 1, 0 <= col < 100, reps >= 1, mode 0 ... 3");
+   hipStream_t s = nullptr;
+   const int64_t stride = (n + 31) / 32 * 32;
+   const int nb = (int)gm_blocks(n), k = col + 1;
+   DevBuf<double> V((size_t)(k + 1) * stride), wgt((size_t)n), S((size_t)gmres::LEN), table((size_t)(gmres::MAXK + 2) * GM_BLOCKS);
+   // constant vectors of unit norm in the span of one direction: the first pass leaves w = 0 and every later one keeps it there - plain numbers, the same traffic
+   vk_fill_if((int64_t)(k + 1) * stride, nullptr, 1.0 / std::sqrt((double)n * k), V.p, s);
+   vk_fill_if(n, nullptr, 1.0, wgt.p, s);
+   S.zero(s);
+   double* w = V.p + (size_t)k * stride;
+   auto once = [&]() {
+      gm_orthogonalise(n, n, wgt.p, V.p, stride, col, w, S.p, table.p, (GMRESSolver::Ortho)mode, 0, false, s, [&](GmStage a, int cols) { a.reduce_cols = cols; gm_scalar(S.p, table.p, nb, a, s); });
+      gm_scale(n, w, w, nullptr, S.p, gmres::SCALE, s);
+   };
+   once(); once();
+   hipEvent_t e0, e1; EXA_HC(hipEventCreate(&e0)); EXA_HC(hipEventCreate(&e1));
+   EXA_HC(hipEventRecord(e0, s));
+   for (int r = 0; r < reps; r++) once();
+   EXA_HC(hipEventRecord(e1, s)); EXA_HC(hipEventSynchronize(e1));
+   float ms = 0; EXA_HC(hipEventElapsedTime(&ms, e0, e1));
+   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+   return (double)ms / reps;
 }
 
 }  // namespace exa_host

@@ -112,6 +112,7 @@ struct ExaOptions {
    // multigrid and the polynomial order (options reader, SystemDriver::SetPreconditioner / SetPeriodic)
    static const char* mg_order_refusal() { return "Solvers.Krylov.preconditioner = \"multigrid\" is built for p_refinement = 1 only"; }   // (p_refinement = 2: opt-in, Solvers.Krylov.mg_p2 = true)
    static const char* mg_p2_no_higher_order() { return "Solvers.Krylov.preconditioner = \"multigrid\": mg_p2 = true serves p_refinement = 2; p_refinement >= 3 has no hierarchy (its nodes are not a uniform grid)"; }
+   static const char* gmres_kdim_range() { return "Solvers.Krylov.gmres_kdim must be a whole number in 1 ... 100 (the Krylov dimension of GMRES; MFEM's default is 50)"; }
    static const char* mg_p2_no_periodic() { return "Solvers.Krylov.preconditioner = \"multigrid\" at p_refinement = 2 is not built for BCs.periodic = true (the fine diagonal probe and the fused periodic kernels need p_refinement = 1), with or without mg_periodic"; }
    static const char* periodic_no_multigrid() { return "BCs.periodic = true runs under Solvers.Krylov.preconditioner = \"multigrid\" only where it is asked for: Solvers.Krylov.mg_periodic = true (Driver.set_preconditioner(\"multigrid\", periodic=True)); without it the combination is refused as before"; }
    static const char* periodic_needs_generated_mesh() { return "BCs.periodic = true needs a generated hexahedral mesh (Mesh.type = \"auto\"): file and tetrahedral meshes need node matching"; }
@@ -182,7 +183,7 @@ struct ExaOptions {
    }
    Assembly assembly = Assembly::EA; NLSolver nl_solver = NLSolver::NR; std::string integ_model = "FULL";
    int newton_iter = 25; double newton_rel = 1e-5, newton_abs = 1e-10;
-   int krylov_iter = 200; double krylov_rel = 1e-10, krylov_abs = 1e-30; std::string krylov_solver = "PCG";
+   int krylov_iter = 200; double krylov_rel = 1e-10, krylov_abs = 1e-30; std::string krylov_solver = "PCG"; int gmres_kdim = 0;   // gmres_kdim: Krylov dimension, the opt-in of solver = "GMRES"
    // Solvers.Krylov.preconditioner (not a key of the reference, whose TOML reader ignores it): 0 absent (the jacobi flag of exa_driver_create
    // decides), 1 "jacobi", 2 "multigrid" (host/multigrid.hpp) with mg_levels coarse levels at most (0: as many as the mesh allows) and a
    // Chebyshev smoother of degree mg_smoother_degree (1 ... 8)
@@ -459,13 +460,21 @@ struct ExaOptions {
         if (nl == "nr") nl_solver = NLSolver::NR; else if (nl == "nrls") nl_solver = NLSolver::NRLS;
         else throw std::runtime_error("Solvers.NR.nl_solver was not provided a valid type."); }
       krylov_iter = (int)d.num("Solvers.Krylov.iter", 200); krylov_rel = d.num("Solvers.Krylov.rel_tol", 1e-10); krylov_abs = d.num("Solvers.Krylov.abs_tol", 1e-30);
-      // reference src/option_parser.cpp:647-662: GMRES (its default), PCG or MINRES, anything else aborts.  Only PCG is built here (the
-      // north-star path; the ExaCMech tangents the driver sees are symmetric to round-off, exa_grad_tangent_defect).  A file that asks
-      // for - or defaults to - one of the other two is refused instead of silently running CG.
+      // reference src/option_parser.cpp:647-662: GMRES (its default), PCG or MINRES, anything else aborts.  PCG and GMRES are built here, and GMRES
+      // is what the operator calls for: the plastic tangent is not symmetric (DESIGN 4.6 measures |A - A^T| / |A| = 1.9e-4).  GMRES is opt-in
+      // through Solvers.Krylov.gmres_kdim (the Krylov dimension, MFEM's default is 50): a file that asks for - or defaults to - GMRES without it,
+      // or for MINRES, is refused instead of silently running CG.
       krylov_solver = lower(d.str("Solvers.Krylov.solver", "GMRES"));
-      if (krylov_solver == "gmres" || krylov_solver == "minres")
-         throw std::runtime_error("Solvers.Krylov.solver = \"" + krylov_solver + "\" (the reference's default is GMRES) is not built in this driver: set Solvers.Krylov.solver = \"PCG\"");
-      if (krylov_solver != "pcg") throw std::runtime_error("Solvers.Krylov.solver was not provided a valid type.");
+      const TomlValue* kd = d.get("Solvers.Krylov.gmres_kdim");
+      if (kd) {
+         if (kd->kind != TomlValue::NUM || kd->num != std::floor(kd->num) || kd->num < 1 || kd->num > 100) throw std::runtime_error(gmres_kdim_range());
+         if (krylov_solver == "pcg") throw std::runtime_error("Solvers.Krylov.gmres_kdim stands next to solver = \"GMRES\" (or no solver key: the reference's default), not next to solver = \"PCG\"");
+         gmres_kdim = (int)kd->num;
+      }
+      if (krylov_solver == "minres" || (krylov_solver == "gmres" && !kd))
+         throw std::runtime_error("Solvers.Krylov.solver = \"" + krylov_solver + "\" (the reference's default is GMRES) is not built in this driver: set Solvers.Krylov.solver = \"PCG\""
+                                  + (krylov_solver == "gmres" ? ", or add Solvers.Krylov.gmres_kdim = <1 ... 100> (MFEM's default is 50) to run GMRES" : ""));
+      if (krylov_solver != "pcg" && krylov_solver != "gmres") throw std::runtime_error("Solvers.Krylov.solver was not provided a valid type.");
       ref_ser = (int)d.num("Mesh.ref_ser", 0); order = (int)d.num("Mesh.p_refinement", 1);   // tests write "prefinement": ignored like the reference (src/option_parser.cpp:677)
       mesh_type = lower(d.str("Mesh.type", "other"));
       mesh_file = d.str("Mesh.floc", "");

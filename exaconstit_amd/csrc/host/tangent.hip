@@ -216,6 +216,36 @@ void SystemDriver::PcgSolveProbe(int nc, const double* b, double rel_tol, double
    scope.close();
 }
 
+void SystemDriver::GmresSolveProbe(int nc, const double* b, double rel_tol, double abs_tol, int max_iter, int kdim, int check_every, int ortho, double* x, int* iters, int* flag,
+                                   double* reduction, double* sc) {
+   if (nc < 1 || nc > EXA_GRAD_COLS_MAX) throw std::runtime_error("gmres_solve: between 1 and 16 columns");
+   if (!step_solved_) throw std::runtime_error("gmres_solve: no solved step - the operator is that of the converged iterate of the last step");
+   if (kdim < 1 || kdim > 100) throw std::runtime_error("gmres_solve: " + std::string(ExaOptions::gmres_kdim_range()));
+   if (ortho < -1 || ortho > 3) throw std::runtime_error("gmres_solve: ortho -1 (EXA_GMRES_ORTHO), 0 ifneeded, 1 always, 2 never or 3 mgs");
+   if (max_iter < 0 || check_every < 0 || !(rel_tol >= 0.0) || !(abs_tol >= 0.0)) throw std::runtime_error("gmres_solve: tolerances, max_iter and check_every must not be negative");
+   NonlinearMechOperator& op = *oper_;
+   hipStream_t s = op.stream();
+   const int64_t nd = op.Height();
+   TangentScope scope(*this);
+   op.GetGradient();
+   KrylovSolver::Settings ks = krylov_->set;
+   ks.rel_tol = rel_tol; ks.abs_tol = abs_tol; ks.max_iter = max_iter; ks.kdim = kdim;
+   if (check_every > 0) ks.check_every = check_every;
+   GMRESSolver gm(op, ks);
+   if (ortho >= 0) { gm.ortho_forced = true; gm.ortho = (GMRESSolver::Ortho)ortho; }
+   DevBuf<double> B((size_t)nc * nd), X((size_t)nc * nd), tmp((size_t)nd), bm((size_t)nd);
+   B.upload(b, (size_t)nc * nd, s);
+   for (int m = 0; m < nc; m++) {
+      EXA_HC(hipMemcpyAsync(bm.p, B.p + (size_t)m * nd, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
+      iters[m] = gm.Solve(bm.p, tmp.p);
+      flag[m] = gm.diag.last_flag; reduction[m] = gm.diag.last_reduction;
+      sc[4 * m] = gm.last_beta0; sc[4 * m + 1] = gm.last_resid; sc[4 * m + 2] = gm.last_restarts; sc[4 * m + 3] = gm.last_reorth;
+      EXA_HC(hipMemcpyAsync(X.p + (size_t)m * nd, tmp.p, sizeof(double) * nd, hipMemcpyDeviceToDevice, s));
+   }
+   X.download(x, (size_t)nc * nd, s);
+   scope.close();
+}
+
 void SystemDriver::WriteMacroTangent(int step) {
    MacroTangentResult r;
    MacroTangent(opt_.macro_tangent_rel_tol, opt_.macro_tangent_max_iter, -1, r);

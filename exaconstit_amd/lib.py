@@ -568,6 +568,62 @@ exa_driver_grad_apply_columns = _sig("exa_driver_grad_apply_columns", C.c_int, C
 exa_driver_pcg_solve = _sig("exa_driver_pcg_solve", C.c_int, C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int),
                             C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), _dp, C.c_char_p, C.c_int)
 exa_driver_set_tangent_route = _sig("exa_driver_set_tangent_route", C.c_int, C.c_void_p, C.c_int, C.c_int)
+exa_driver_set_krylov = _sig("exa_driver_set_krylov", C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
+exa_driver_krylov_info = _sig("exa_driver_krylov_info", C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64))
+exa_driver_gmres_solve = _sig("exa_driver_gmres_solve", C.c_int, C.c_void_p, C.c_int, _dp, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int),
+                              C.POINTER(C.c_int), _dp, _dp, C.c_char_p, C.c_int)
+exa_gmres_ortho_probe = _sig("exa_gmres_ortho_probe", C.c_int, C.c_int64, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int), C.c_char_p, C.c_int)
+exa_gmres_ortho_bench = _sig("exa_gmres_ortho_bench", C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _dp, C.c_char_p, C.c_int)
+exa_gmres_column_probe = _sig("exa_gmres_column_probe", C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp, C.POINTER(C.c_int), _dp)
+exa_gmres_multidot_chunk = _sig("exa_gmres_multidot_chunk", C.c_int)
+GMRES_MULTIDOT_CHUNK = int(exa_gmres_multidot_chunk())   # basis vectors per pass of the multi-dot kernel (krylov_info()["multidot_chunk"])
+GMRES_ORTHO = {"ifneeded": 0, "always": 1, "never": 2, "mgs": 3}   # EXA_GMRES_ORTHO and the ortho argument of the probes
+
+
+def gmres_ortho_probe(weight, V, w, flag=0.0, mode="ifneeded"):
+    """The two bandwidth kernels of GMRES's Gram-Schmidt on any shape (one GPU): w (n) against the rows of V (k, n) in the product weighted by
+    weight (n).  flag != 0: the kernels' gate is closed.  dict(h (k) the column of H, w_out (n), wnorm2 = |w_out|^2 from the partial sums of the
+    subtraction kernel, passes: 0 with the gate closed, else 1 + second passes)"""
+    import numpy as np
+    V = np.ascontiguousarray(np.atleast_2d(V), dtype=np.float64)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    weight = np.ascontiguousarray(weight, dtype=np.float64)
+    k, n = V.shape
+    if w.shape != (n,) or weight.shape != (n,):
+        raise ValueError("gmres_ortho_probe: weight and w have the length of V's rows")
+    h, wo, n2 = np.zeros(k), np.zeros(n), np.zeros(1)
+    ps = C.c_int(0)
+    err = C.create_string_buffer(512)
+    if exa_gmres_ortho_probe(n, k, weight.ctypes.data_as(_dp), V.ctypes.data_as(_dp), w.ctypes.data_as(_dp), float(flag), GMRES_ORTHO[mode], h.ctypes.data_as(_dp),
+                             wo.ctypes.data_as(_dp), n2.ctypes.data_as(_dp), C.byref(ps), err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return dict(h=h, w_out=wo, wnorm2=float(n2[0]), passes=int(ps.value))
+
+
+def gmres_ortho_bench(n, col, mode="ifneeded", reps=20):
+    """measurement hook of scripts/gmres_compare.py: ms per orthogonalisation and normalisation of column col (col + 1 basis vectors of n entries) on device buffers of the call's own"""
+    ms = C.c_double(0.0)
+    err = C.create_string_buffer(512)
+    if exa_gmres_ortho_bench(int(n), int(col), GMRES_ORTHO[mode], int(reps), C.byref(ms), err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return float(ms.value)
+
+
+def gmres_column_probe(Hbar, beta, final_norm=0.0):
+    """Host only: the small algebra of GMRES's scalar kernel on the (m + 1, m) Hessenberg matrix Hbar as Gram-Schmidt leaves it and the first residual
+    norm beta.  dict(resid (m) the residual norm after each column, flags (m) what the solver decides after it with the bound final_norm (0 running,
+    1 converged, -1 breakdown), y (m) the back-substitution over all columns, ok: False when it met a zero pivot (those y_i are 0))"""
+    import numpy as np
+    Hbar = np.asarray(Hbar, dtype=np.float64)
+    m = Hbar.shape[1]
+    if Hbar.shape != (m + 1, m):
+        raise ValueError("gmres_column_probe: Hbar is (m + 1, m)")
+    Hc = np.ascontiguousarray(Hbar.T)   # column i contiguous, leading dimension m + 1
+    resid, y, fl = np.zeros(m), np.zeros(m), np.zeros(m, np.int32)
+    rc = exa_gmres_column_probe(m, Hc.ctypes.data_as(_dp), float(beta), float(final_norm), resid.ctypes.data_as(_dp), fl.ctypes.data_as(C.POINTER(C.c_int)), y.ctypes.data_as(_dp))
+    if rc < 0:
+        raise ValueError("gmres_column_probe: 1 to 100 columns")
+    return dict(resid=resid, flags=fl.astype(int), y=y, ok=bool(rc))
 exa_macro_tangent_condense = _sig("exa_macro_tangent_condense", C.c_int, _dp, C.POINTER(C.c_int), _dp)
 exa_options_macro_tangent = _sig("exa_options_macro_tangent", C.c_int, C.c_char_p, C.POINTER(C.c_int), _dp, C.c_char_p, C.c_int, C.c_char_p, C.c_int)
 exa_tangent_scratch_bytes = _sig("exa_tangent_scratch_bytes", C.c_int, C.POINTER(C.c_int))
@@ -1316,6 +1372,38 @@ class Driver:
                                        int(bool(columns)), x.ctypes.data_as(_dp), it.ctypes.data_as(ip), fl.ctypes.data_as(ip), red.ctypes.data_as(_dp), ind.ctypes.data_as(ip),
                                        sc.ctypes.data_as(_dp), self._err, 512))
         return dict(x=x, iters=it.astype(int), flags=fl.astype(int), reduction=red, indefinite=ind.astype(int), r0z0=sc[:, 0].copy(), rz=sc[:, 1].copy())
+
+    def set_krylov(self, solver, kdim=50):
+        """The run's linear solver: "pcg", or "gmres" with the Krylov dimension kdim (1 ... 100) of a restart cycle.  Before the first
+        step or between steps; every rank calls it.  Tolerances and cap stay; the run's diagnostics() and timers() go on counting (the restarts and
+        reorth_passes of krylov_info() are the new GMRES object's)."""
+        self._chk(exa_driver_set_krylov(self.h, str(solver).encode(), int(kdim), self._err, 512))
+
+    def krylov_info(self):
+        """dict(solver "pcg" / "gmres", kdim (0 for PCG), multidot_chunk: basis vectors per pass of the multi-dot kernel, restarts and reorth_passes over
+        all solves of the run's solver, basis_bytes: device memory of its basis, 0 before the first GMRES solve)"""
+        i3, o3 = (C.c_int * 3)(), (C.c_int64 * 3)()
+        assert exa_driver_krylov_info(self.h, i3, o3) == 0
+        return dict(solver="gmres" if i3[0] else "pcg", kdim=int(i3[1]), multidot_chunk=int(i3[2]), restarts=int(o3[0]), reorth_passes=int(o3[1]), basis_bytes=int(o3[2]))
+
+    def gmres_solve(self, b, rel_tol, abs_tol, max_iter, kdim, check_every=0, ortho=None):
+        """Probe of GMRES(kdim), as pcg_solve: K_uu x_m = b_m from x = 0 for b (nrhs, local dofs) in turn, in a solver of the probe's own with the run's
+        preconditioner; every rank calls it.  ortho None: as EXA_GMRES_ORTHO says; "ifneeded", "always", "never", "mgs".
+        dict(x, iters (Arnoldi steps), flags (1 converged, 2 max_iter, -1 breakdown), reduction = resid / beta0, beta0 = |M^-1 b|, resid the last
+        residual norm, restarts, reorth_passes)"""
+        import numpy as np
+        b = np.ascontiguousarray(np.atleast_2d(b), dtype=np.float64)
+        if b.shape[1] != exa_driver_local_dofs(self.h) or not 1 <= b.shape[0] <= 16:
+            raise RuntimeError("gmres_solve: b holds 1 to 16 columns of %d local dofs" % exa_driver_local_dofs(self.h))
+        n = b.shape[0]
+        x, red, sc = np.zeros_like(b), np.zeros(n), np.zeros((n, 4))
+        it, fl = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        ip = C.POINTER(C.c_int)
+        self._chk(exa_driver_gmres_solve(self.h, n, b.ctypes.data_as(_dp), float(rel_tol), float(abs_tol), int(max_iter), int(kdim), int(check_every),
+                                         -1 if ortho is None else GMRES_ORTHO[ortho], x.ctypes.data_as(_dp), it.ctypes.data_as(ip), fl.ctypes.data_as(ip), red.ctypes.data_as(_dp),
+                                         sc.ctypes.data_as(_dp), self._err, 512))
+        return dict(x=x, iters=it.astype(int), flags=fl.astype(int), reduction=red, beta0=sc[:, 0].copy(), resid=sc[:, 1].copy(), restarts=sc[:, 2].astype(int),
+                    reorth_passes=sc[:, 3].astype(int))
 
     def set_tangent_route(self, nch=0, auto_batched=True):
         assert exa_driver_set_tangent_route(self.h, int(nch), int(bool(auto_batched))) == 0

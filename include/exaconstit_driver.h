@@ -269,6 +269,34 @@ int exa_driver_grad_apply_columns(exa_driver* d, int ncols, const double* x, dou
  * step; every rank calls it.  The run's solver, captured chunk, diagnostics and totals are not touched. */
 int exa_driver_pcg_solve(exa_driver* d, int nrhs, const double* b, double rel_tol, double abs_tol, int max_iter, int check_every, int graph, int mode, double* x, int* iters,
                          int* flags, double* reduction, int* indefinite, double* scalars2, char* err, int errlen);
+/* The run's linear solver: solver "pcg" or "gmres" (any case), kdim the Krylov dimension of restarted GMRES (1 ... 100, MFEM's default
+ * is 50; ignored for PCG).  Legal before the first step and between steps; tolerances and cap stay, and the run's diagnostics and totals
+ * (exa_driver_get_diagnostics, _get_pcg_reduction, _get_timers) go on counting.  Every rank calls it.  Returns 0 or -1 (err). */
+int exa_driver_set_krylov(exa_driver* d, const char* solver, int kdim, char* err, int errlen);
+/* out3i = { 0 PCG / 1 GMRES, kdim (0 for PCG), chunk of the multi-dot kernel }; out3 = { restarts, second Gram-Schmidt passes (both over all solves of
+ * the run's solver), bytes of the basis (0 before the first GMRES solve) } */
+int exa_driver_krylov_info(exa_driver* d, int* out3i, int64_t* out3);
+int exa_gmres_multidot_chunk(void);   /* basis vectors per pass of the multi-dot kernel, a compile-time constant (8 ... 16) */
+/* Probe of GMRES, mirroring exa_driver_pcg_solve: K_uu x_m = b_m from x = 0 for nrhs <= 16 host columns in turn, in a GMRES(kdim) solver of the probe's
+ * own with the run's preconditioner and chunk (check_every 0: the run's).  ortho: -1 as EXA_GMRES_ORTHO says, 0 ifneeded, 1 always, 2 never, 3 mgs.
+ * Per column: x, Arnoldi steps, flag (1 converged, 2 max_iter, -1 breakdown), reduction = last residual / beta0, scalars4[4 m ...] = { beta0 = |M^-1 b|,
+ * last residual norm, restarts, second Gram-Schmidt passes }.  Needs a solved step; every rank calls it; the run's solver is not touched. */
+int exa_driver_gmres_solve(exa_driver* d, int nrhs, const double* b, double rel_tol, double abs_tol, int max_iter, int kdim, int check_every, int ortho, double* x, int* iters,
+                           int* flags, double* reduction, double* scalars4, char* err, int errlen);
+/* The two bandwidth kernels of the orthogonalisation on any shape (host arrays in and out, one GPU): w (n) against the k <= 100 vectors V (k x n, row j
+ * = v_j) in the product weighted by weight (n); flag != 0: the kernels' gate is closed.  mode 0 ifneeded, 1 always, 2 never, 3 mgs.  h (k): the column
+ * of H; w_out (n); wnorm2 = |w_out|^2 from the partial sums of the subtraction kernel; passes: 0 with the gate closed, else 1 + second passes. */
+int exa_gmres_ortho_probe(int64_t n, int k, const double* weight, const double* V, const double* w, double flag, int mode, double* h, double* w_out, double* wnorm2,
+                          int* passes, char* err, int errlen);
+/* measurement hook of scripts/gmres_compare.py, no part of a run (as exa_driver_bench_pcg is for bench.py): timing of the same launches on device
+ * buffers of the call's own, ms per orthogonalisation and normalisation of column col (col + 1 basis vectors of n
+ * entries), the mean of reps back-to-back repetitions after two warm-up ones */
+int exa_gmres_ortho_bench(int64_t n, int col, int mode, int reps, double* ms, char* err, int errlen);
+/* Host only, no GPU call: the small algebra of the scalar kernel.  Hbar: ncols <= 100 columns at leading dimension ncols + 1, column i holding
+ * h_0i ... h_i+1,i as Gram-Schmidt leaves them; beta: the first residual norm.  resid (ncols): |s_i+1| after column i; flags (ncols): what the solver
+ * decides after that column with the bound final_norm and no iteration cap (0 running, 1 converged, -1 breakdown); y (ncols): the back-substitution
+ * over all columns.  Returns 1, 0 when the back-substitution met a zero pivot (those y_i are 0), -1 on a bad ncols. */
+int exa_gmres_column_probe(int ncols, const double* Hbar, double beta, double final_norm, double* resid, int* flags, double* y);
 /* columns per pass of the batched route (1 .. 3, 0: the default) and whether the automatic route takes it where it exists */
 int exa_driver_set_tangent_route(exa_driver* d, int nch, int auto_batched);
 /* host only: the condensed tangent of the prescribed entries, C_pp - C_pf C_ff^-1 C_fp, of the 9 x 9 c81[9 (kl) + (mn)] for the free mask of a mixed
