@@ -15,6 +15,7 @@ int exa_launch_qf_pack(exa_ctx*, int, const double*, double*, unsigned long long
 int exa_launch_qf_unpack(exa_ctx*, int, const double*, double*, unsigned long long*, hipStream_t);
 int exa_launch_nfev_hist(exa_ctx*, const double*, int*, hipStream_t);
 int exa_launch_selftest_km_math(const double*, double*, int, hipStream_t);
+int exa_launch_selftest_rot_math(const double*, double*, int, hipStream_t);
 int exa_launch_calc_dp(exa_ctx*, const double*, double*, hipStream_t);
 int exa_launch_jacobians(exa_ctx*, const double*, double*, hipStream_t);
 int exa_launch_jacobians_from_geom(exa_ctx*, const double*, double*, hipStream_t);
@@ -291,6 +292,10 @@ int exa_model_nfev_hist(exa_ctx* ctx, const double* state, int* hist64_host, exa
 int exa_selftest_km_math(const double* x_dev, double* out_dev, int n, exa_stream s) {
    if (!x_dev || !out_dev || n <= 0) return EXA_ERR_ARG;
    return exa_launch_selftest_km_math(x_dev, out_dev, n, S(s));
+}
+int exa_selftest_rot_math(const double* x_dev, double* out_dev, int n, exa_stream s) {
+   if (!x_dev || !out_dev || n <= 0) return EXA_ERR_ARG;
+   return exa_launch_selftest_rot_math(x_dev, out_dev, n, S(s));
 }
 int exa_model_tail_count(exa_ctx* ctx, exa_stream s) {
    if (!ctx) return EXA_ERR_ARG;

@@ -89,6 +89,26 @@ int exa_launch_selftest_km_math(const double* x, double* out, int n, hipStream_t
    return hipGetLastError() == hipSuccess ? EXA_OK : EXA_ERR_HIP;
 }
 
+// self-test hook of the rotation arithmetic (ecm_device.hpp: sincos_s, exp_map): out[2 i], out[2 i + 1] = sin, cos of x[i] by sincos_s; after
+// those 2 n numbers, for every whole triple (x[3 t], x[3 t + 1], x[3 t + 2]) taken as a rotation vector, the 9 entries of A and the 9 of Tr
+__global__ void k_selftest_rot_math(const double* __restrict__ x, double* __restrict__ out, const int n) {
+   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+   if (i >= n) return;
+   double sn, cs; ecmdev::sincos_s(x[i], sn, cs);
+   out[2 * (int64_t)i] = sn; out[2 * (int64_t)i + 1] = cs;
+   if (i < n / 3) {
+      const double xi[3] = { x[3 * i], x[3 * i + 1], x[3 * i + 2] };
+      double A[9], Tr[9]; ecmdev::exp_map(xi, A, Tr);
+      double* o = out + 2 * (int64_t)n + 18 * (int64_t)i;
+#pragma unroll
+      for (int k = 0; k < 9; k++) { o[k] = A[k]; o[9 + k] = Tr[k]; }
+   }
+}
+int exa_launch_selftest_rot_math(const double* x, double* out, int n, hipStream_t s) {
+   hipLaunchKernelGGL(k_selftest_rot_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, out, n);
+   return hipGetLastError() == hipSuccess ? EXA_OK : EXA_ERR_HIP;
+}
+
 int exa_launch_nfev_hist(exa_ctx* ctx, const double* state, int* hist_dev, hipStream_t s) {
    EXA_HIP_CHECK(ctx, hipMemsetAsync(hist_dev, 0, sizeof(int) * 64, s));
    if (ctx->qblk) hipLaunchKernelGGL(k_nfev_hist<true>, dim3(1024), dim3(256), 0, s, ctx->Q, ctx->P, state, hist_dev);

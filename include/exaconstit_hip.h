@@ -329,6 +329,11 @@ int exa_set_ea_matrix_free(exa_ctx* ctx, int on);
 /* self-test hook (tests/test_gpu_point_fixtures.py): the Kocks-Mecking kinetics' own exp and near-1 log evaluated on the device,
  * out[0..n) = exp(x), out[n..2n) = log(x) (the latter meaningful for x in [0.75, 1.25]); no context needed */
 int exa_selftest_km_math(const double* x_dev, double* out_dev, int n, exa_stream s);
+/* self-test hook (tests/test_gpu_offpath_constitutive.py): the rotation arithmetic of the point update evaluated on the device.
+ * out[2 i], out[2 i + 1] = sine, cosine of x[i] by the kernel's own sincos (i < n); then, for each whole triple
+ * (x[3 t], x[3 t + 1], x[3 t + 2]), t < n / 3, taken as a rotation vector, out[2 n + 18 t ...] = the exponential map's rotation matrix A
+ * (9 numbers, row-major) and right Jacobian Tr (9 numbers).  out_dev holds 2 n + 18 (n / 3) doubles; no context needed */
+int exa_selftest_rot_math(const double* x_dev, double* out_dev, int n, exa_stream s);
 /* Bit-reproducible E->L sums (reference: mfem::ElementRestriction::MultTranspose; the fused kernels here scatter with FP64 atomics, whose
  * order - and therefore the last bits of the L-vector, and from there every CG iterate - changes from run to run).  With `on` != 0
  * exa_residual_lvec, exa_grad_apply_lvec (partial assembly and element assembly from the point records) and exa_restrict_transpose_add

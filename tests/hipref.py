@@ -195,6 +195,73 @@ def velocity_field(rve, scale=1.0, seed=7):
     return v.ravel()
 
 
+# ---- load paths off the tension history of velocity_field (tests/offpath.py runs them; tests/test_offpath_inputs_host.py asserts on the oracle
+# alone that each reaches the branch of the point update it was built for) ------------------------------------------------------------------
+PATH_T = np.diag([-0.45e-3, -0.45e-3, 1.0e-3])                     # the tension rate every path starts with
+PATH_START_DTS = (0.005, 0.195, 0.4, 0.4)                           # ... for these steps, so that a path branches off in plastic flow
+PATH_SPIN_AXIS = np.array([0.3, -0.5, 0.8]) / np.linalg.norm([0.3, -0.5, 0.8])
+PATH_NAMES = ("reversal", "shear", "volume", "rate", "hold", "rotation")
+# The rate factors 10, 100, 1000, 100, 10, 1, 0.1, 0.1, 1 in an order in which every down-jump starts above the flow stress of the new rate.
+# With one strain increment of 4e-4 per step the Kocks-Mecking stress is still climbing elastically at 100 x and 1000 x, so in the order
+# 1000 -> 100 -> 10 it goes on rising through the two down-jumps (measured on the oracle: 3.25 -> 4.05 -> 4.73); the same steps reordered
+# rise on every up-jump and fall on every down-jump, which is what tests/test_offpath_inputs_host.py asserts.
+PATH_RATE_FACTORS = (10.0, 100.0, 1000.0, 1.0, 0.1, 0.1, 1.0, 10.0, 100.0)
+# The pure spin that ends `rotation`: (angle, dt).  With D = 0 the solver scales its residual by 1 / max(|dev D|, 1 / (1e6 dt)), here 1e6 dt,
+# and the rotation rows of the residual are a difference of two numbers of size |W|: their round-off, |W| 1e6 dt 1.1e-16 = angle x 1.1e-10, is
+# at the Voce tolerance of 1e-10 when the angle is 0.3 rad (the oracle itself then fails at 37 of 1728 points, and at 2 at 0.1 rad).  0.02 rad
+# is still the large-angle branch (th2 = 4e-4 >= 1e-4) and leaves a factor of 50.
+PATH_PURE_SPIN = (0.02, 0.02)
+
+
+def spin_matrix(angle_rate, axis=PATH_SPIN_AXIS):
+    """skew W with axial vector angle_rate * axis: W x = w cross x"""
+    a = angle_rate * np.asarray(axis, dtype=np.float64)
+    return np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+
+
+def load_path(name):
+    """the steps (D, W, dt) of a named load path: D symmetric, W skew, 3 x 3, rates per second"""
+    Z = np.zeros((3, 3))
+    T = PATH_T
+    start = [(T, Z, dt) for dt in PATH_START_DTS]
+    if name == "reversal":       # elastic unloading, the zero crossing of every resolved shear stress, reverse yield
+        return start + [(-T, Z, dt) for dt in (0.05, 0.2, 0.25, 0.5, 0.5, 1.0)]
+    if name == "shear":          # simple shear from the first step: D and W of equal size, other slip systems than tension's
+        Ls = np.zeros((3, 3)); Ls[0, 1] = 1.0e-3
+        return [(0.5 * (Ls + Ls.T), 0.5 * (Ls - Ls.T), dt) for dt in (0.005, 0.2, 0.5, 1.0, 2.0, 5.0)]
+    if name == "volume":         # relative volume up to ~1.009, then down to 0.970 ... 0.978 (the last step at dt = 1.4, not 1.0: the jitter has a trace,
+        # and at 1.0 a third of the points ended between 0.980 and 0.983, above the 0.98 tests/test_offpath_inputs_host.py asserts for every point)
+        return start + [(T + k * np.eye(3), Z, dt) for k, dt in ((2.0e-3, 0.5), (2.0e-3, 1.0), (-5.0e-3, 1.0), (-5.0e-3, 1.4))]
+    if name == "rate":           # jumps of the strain rate over four decades at a constant strain increment per step
+        return start + [(f * T, Z, 0.4 / f) for f in PATH_RATE_FACTORS]
+    if name == "hold":           # exactly zero velocity, then rates below and just above the solver's "no deformation" threshold.  The last step
+        # (1e-3, not part of the first statement of this path) is the one whose |dev D| = 1.2e-6 lies between 1e-8 gam_w and 1e-6 / dt for
+        # every model: at 1e-7 |dev D| = 1.2e-10 is still below 1e-8 gam_w (gam_w = 1 /s Voce, ~30 /s Kocks-Mecking)
+        return start + [(f * T, Z, dt) for f, dt in ((0.0, 1.0), (1.0e-12, 1.0), (1.0e-7, 1.0), (1.0e-5, 0.5), (1.0e-3, 0.5))]
+    if name == "rotation":       # lattice-rotation increments of 0.02 ... 0.5 rad in one step under tension, then a pure spin (D = 0)
+        # (the 0.5 rad step at dt = 0.2, not 0.4: at 0.4 one point of the FCC Voce models needs 106 evaluations on the oracle, and the oracle itself
+        #  runs into its limit of 200 there when its Jacobians are perturbed in the last bit - tests/test_offpath_inputs_host.py asserts the margin)
+        steps = [(T, spin_matrix(ang / dt), dt) for ang, dt in ((0.02, 0.2), (0.05, 0.2), (0.2, 0.2), (0.5, 0.2))]
+        return start + steps + [(Z, spin_matrix(PATH_PURE_SPIN[0] / PATH_PURE_SPIN[1]), PATH_PURE_SPIN[1])]
+    raise KeyError(name)
+
+
+def path_step(rve, x0, D, W, dt, rng):
+    """One step of a load path on byNODES coordinates x0: end-of-step coordinates x1 = x0 + dt D x0 and nodal velocity v = (D + W) x1 + jitter.
+    ModelSetup takes the Jacobians of x1 and the velocity independently, so the point update sees the velocity gradient D + W up to the
+    jitter, tr L = tr D, and a spin of any size costs no spurious stretch.  The jitter is sized by |D| alone (a tenth of it across an element,
+    the proportion of velocity_field; by 1e-6 /s where D = 0 and W != 0; none where both vanish: a hold at exactly zero velocity)."""
+    NN = rve["NN"]
+    X0 = np.asarray(x0).reshape(3, NN)
+    X1 = X0 + dt * (D @ X0)
+    v = (D + W) @ X1
+    dn = np.linalg.norm(D)
+    size = 0.1 * dn if dn > 0 else (1.0e-6 if np.any(W != 0) else 0.0)
+    if size > 0:
+        v = v + size / (rve["N"] * rve["p"]) * rng.uniform(-1, 1, v.shape)
+    return X1.ravel(), v.ravel()
+
+
 class Dev:
     """torch-backed device buffers (allocator only)."""
 
