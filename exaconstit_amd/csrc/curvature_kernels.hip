@@ -7,11 +7,11 @@
 //   launch 3 (elements): vertex values Omega_a = sum V omega / sum V (the element's own omega_e at a mixed node) -> kappa at the centroid through
 //                        the trilinear / linear vertex functions on the current vertex coordinates, alpha_ij = kappa_ji - delta_ij kappa_kk,
 //                        KAM = mean |Omega_a - omega_e| over the unmixed vertices -> rows [E][EXA_NCURV]
-//   launch 4 + 5 (summary): sum V, sum V GROD, sum V KAM, sum V GND and the three maxima, partial sums per block, then one block
-// Design.  None of the launches is compute-bound; what matters is how the bytes move:
+//   launch 4 + 5 (summary): sum V, sum V GROD, sum V KAM, sum V GND and the three maxima: the two-launch summary of analysis_device.hpp
+// Design.  None of the launches is compute-bound; what matters is how the bytes move (staging, write-out and summary: analysis_device.hpp):
 //   1: the rows are 296 bytes each and 5 of their 37 doubles are needed (volume, orientation).  A block of 64 lanes stages the leading 31 columns of
-//      its 64 rows through LDS with wave-wide loads (flat index 64 j + lane over the rows: every load instruction reads 512 bytes that are
-//      contiguous row by row), as grain_kernels.hip does; the records go back through LDS as one contiguous run of 64 x 5 doubles.
+//      its 64 rows through LDS with wave-wide loads (stage_rows, dense: every load instruction reads 512 bytes that are contiguous row by
+//      row); the records go back through the same LDS (store_tile) as one contiguous run of 64 x 5 doubles.
 //   2: one lane per node walks the context's node -> (element, local node) table in its stored order (ascending element): a gather of 40-byte
 //      records that neighbouring nodes share (L2), planar stores.  No atomics, a fixed order of every sum.
 //   3: lane = element gathers 9 nodal values and 3 coordinates per vertex (the nodal planes are shared by the 8 elements of a node and stay in
@@ -19,10 +19,12 @@
 //      as one contiguous run of 64 x 16 doubles.
 //   4: lane = element reads V of its field row and 3 of the 16 doubles of its result row (one 128-byte line).
 // Every launch gives the same bits on every call.
-#include "exa_internal.hpp"
+#include "analysis_device.hpp"
 #include <cmath>
 
 int exa_det_prepare(exa_ctx* ctx);   // capi.hip: builds the node -> element table on first use
+
+using namespace exa_analysis;
 
 namespace {
 
@@ -32,29 +34,18 @@ constexpr int NC1 = EXA_F_ORIENTATION + 4;           // launch 1 stages columns 
 constexpr int REC = 5;                               // record: omega (3), V, grain id (as a double: exact for any int32)
 constexpr int NPL = 9;                               // nodal planes: three nodal 3-vectors
 constexpr int LDO = NCV + 1;                         // padded row of the output tile in LDS
-constexpr int NSUM = 7;
 constexpr int S_THREADS = 256, S_WAVES = S_THREADS / 64, S_MAX_BLOCKS = 960;
-constexpr double RAD2DEG = 57.295779513082320876798154814105;
 
 __global__ __launch_bounds__(CH) void k_curv_rotvec(const int64_t E, const double* __restrict__ F, const int32_t* __restrict__ grain, const int G,
                                                     const double* __restrict__ qbar, double* __restrict__ rec) {
    __shared__ double sm[NC1 * CH];
-   const int lane = threadIdx.x;
-   const int64_t base = (int64_t)blockIdx.x * CH;
-   const int nv = (int)(E - base < CH ? E - base : CH);
+   const BlockView bv(E);
+   const int lane = bv.lane, nv = bv.nv;
+   const int64_t base = bv.base;
    const int32_t g = lane < nv ? grain[base + lane] : 0;
    double qr[4] = { 1.0, 0.0, 0.0, 0.0 };            // an id outside 1 .. G reads no mean: the identity stands in
    if (g >= 1 && g <= G) for (int k = 0; k < 4; k++) qr[k] = qbar[4 * (int64_t)(g - 1) + k];
-   // all loads are issued before the first LDS write; rows past nv of a last, partial block repeat row nv - 1
-   double st[NC1];
-#pragma unroll
-   for (int j = 0; j < NC1; j++) {
-      const int i = j * CH + lane, r = i / NC1, col = i - r * NC1;
-      const int rr = r < nv ? r : nv - 1;
-      st[j] = F[(base + rr) * NF + col];
-   }
-#pragma unroll
-   for (int j = 0; j < NC1; j++) sm[j * CH + lane] = st[j];
+   stage_rows<NC1, NC1>(sm, nv, lane, F, [&](int r) { return (base + r) * NF; }, IdentityCol());
    __syncthreads();
    double v[REC] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
    if (lane < nv) {
@@ -76,11 +67,7 @@ __global__ __launch_bounds__(CH) void k_curv_rotvec(const int64_t E, const doubl
       for (int k = 0; k < REC; k++) sm[lane * REC + k] = v[k];
    }
    __syncthreads();
-#pragma unroll
-   for (int j = 0; j < REC; j++) {
-      const int i = j * CH + lane;
-      if (i < nv * REC) rec[base * REC + i] = sm[i];
-   }
+   store_tile<REC, REC>(rec, base, sm, nv, lane);
 }
 
 __global__ __launch_bounds__(256) void k_curv_nodal(const int n, const int nvert, const int nnodes, const int32_t* __restrict__ off,
@@ -111,9 +98,9 @@ __global__ __launch_bounds__(CH) void k_curv_elements(const int64_t E, const int
                                                       const double* __restrict__ rec, const double* __restrict__ nodal, const double* __restrict__ xe,
                                                       const double inv_b, double* __restrict__ out) {
    __shared__ double sm[CH * LDO];
-   const int lane = threadIdx.x;
-   const int64_t base = (int64_t)blockIdx.x * CH, e = base + lane;
-   const int nv = (int)(E - base < CH ? E - base : CH);
+   const BlockView bv(E);
+   const int lane = bv.lane, nv = bv.nv;
+   const int64_t base = bv.base, e = base + lane;
    if (lane < nv) {
       const double* r = rec + e * REC;
       const double w[3] = { r[0], r[1], r[2] };
@@ -176,23 +163,30 @@ __global__ __launch_bounds__(CH) void k_curv_elements(const int64_t E, const int
       o[EXA_C_NYENORM] = nye; o[EXA_C_GND] = nye * inv_b;
    }
    __syncthreads();
-#pragma unroll
-   for (int j = 0; j < NCV; j++) {
-      const int i = j * CH + lane, r = i / NCV, k = i - r * NCV;
-      if (r < nv) out[base * NCV + i] = sm[r * LDO + k];
-   }
+   store_tile<NCV, LDO>(out, base, sm, nv, lane);
 }
 
-__device__ __forceinline__ double wave_red(double x, const bool is_max) {
+// sum V, sum V GROD, sum V KAM, sum V GND | max GROD, max KAM, max GND.  The three are >= 0: 0 is the neutral element of the maxima
+struct CurvSummary {
+   static constexpr int N = 7;
+   static __device__ __forceinline__ void init(double* v) {
 #pragma unroll
-   for (int d = 32; d > 0; d >>= 1) { const double y = __shfl_down(x, d); x = is_max ? fmax(x, y) : x + y; }
-   return x;   // lane 0
-}
+      for (int k = 0; k < N; k++) v[k] = 0.0;
+   }
+   static __device__ __forceinline__ void merge(double* v, const double* y) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] += y[k];
+#pragma unroll
+      for (int k = 4; k < N; k++) v[k] = fmax(v[k], y[k]);
+   }
+};
+constexpr int NSUM = CurvSummary::N;
 
 __global__ __launch_bounds__(S_THREADS) void k_curv_partial(const int64_t E, const double* __restrict__ F, const double* __restrict__ C, double* __restrict__ partial) {
    __shared__ double sm[S_WAVES][NSUM];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   double acc[NSUM] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };   // GROD, KAM and the GND density are >= 0: 0 is the neutral element of the maxima
+   double acc[NSUM];
+   CurvSummary::init(acc);
    const int64_t nblk = (E + 63) / 64, stride = (int64_t)gridDim.x * S_WAVES;
    for (int64_t b = (int64_t)blockIdx.x * S_WAVES + wave; b < nblk; b += stride) {
       const int64_t e = b * 64 + lane;
@@ -203,31 +197,11 @@ __global__ __launch_bounds__(S_THREADS) void k_curv_partial(const int64_t E, con
       acc[0] += V; acc[1] += V * gr; acc[2] += V * ka; acc[3] += V * gn;
       acc[4] = fmax(acc[4], gr); acc[5] = fmax(acc[5], ka); acc[6] = fmax(acc[6], gn);
    }
-#pragma unroll
-   for (int k = 0; k < NSUM; k++) {
-      const double w = wave_red(acc[k], k >= 4);
-      if (lane == 0) sm[wave][k] = w;
-   }
-   __syncthreads();
-   if (threadIdx.x < NSUM) {
-      const bool is_max = threadIdx.x >= 4;
-      double t = sm[0][threadIdx.x];
-#pragma unroll
-      for (int w = 1; w < S_WAVES; w++) t = is_max ? fmax(t, sm[w][threadIdx.x]) : t + sm[w][threadIdx.x];
-      partial[(int64_t)blockIdx.x * NSUM + threadIdx.x] = t;
-   }
+   summary_block_partial<CurvSummary>(acc, sm, partial);
 }
 
-// one wave: lanes over the blocks in a fixed stride, then the shuffle tree
 __global__ __launch_bounds__(64) void k_curv_reduce(const int nb, const double* __restrict__ partial, double* __restrict__ out) {
-   const int lane = threadIdx.x;
-   for (int k = 0; k < NSUM; k++) {
-      const bool is_max = k >= 4;
-      double t = 0.0;
-      for (int b = lane; b < nb; b += 64) { const double x = partial[(int64_t)b * NSUM + k]; t = is_max ? fmax(t, x) : t + x; }
-      t = wave_red(t, is_max);
-      if (lane == 0) out[k] = t;
-   }
+   summary_reduce<CurvSummary>(nb, partial, out);
 }
 
 int check_common(exa_ctx* ctx, const char* who, bool ok) {
@@ -280,9 +254,8 @@ extern "C" int exa_curvature_summary(exa_ctx* ctx, const double* fields_dev, con
    if (!out_dev || (ctx->E > 0 && (!fields_dev || !curv_dev))) { ctx->err = "exa_curvature_summary: fields, curvature rows and an output are required"; return EXA_ERR_ARG; }
    hipStream_t s = reinterpret_cast<hipStream_t>(str);
    if (ctx->E == 0) { EXA_HIP_CHECK(ctx, hipMemsetAsync(out_dev, 0, sizeof(double) * NSUM, s)); return EXA_OK; }
-   const int64_t need = ((int64_t)ctx->E + S_THREADS - 1) / S_THREADS;
-   const int nb = (int)(need < S_MAX_BLOCKS ? need : S_MAX_BLOCKS);
-   if (sizeof(double) * (size_t)nb * NSUM > ctx->scratch_bytes) { ctx->err = "exa_curvature_summary: reduction scratch too small"; return EXA_ERR_UNSUPPORTED; }
+   int nb;
+   if (int rc = summary_grid(ctx, "exa_curvature_summary", S_THREADS, S_MAX_BLOCKS, NSUM, &nb)) return rc;
    hipLaunchKernelGGL(k_curv_partial, dim3(nb), dim3(S_THREADS), 0, s, (int64_t)ctx->E, fields_dev, curv_dev, ctx->scratch_dev);
    hipLaunchKernelGGL(k_curv_reduce, dim3(1), dim3(64), 0, s, nb, (const double*)ctx->scratch_dev, out_dev);
    EXA_HIP_CHECK(ctx, hipGetLastError());

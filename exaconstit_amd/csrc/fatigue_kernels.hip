@@ -5,19 +5,22 @@
 //                        sigma_n,a = n_a^T sigma n_a on the slip plane, n_a = R(q) m_a; RESET: the window restarts from the values of this call
 //   launch 2 (evaluation): planar accumulators -> rows [E][EXA_NFIP]
 //   launch 3 + 4 (summary): sum V, sum V FIP, sum V AccumulatedSlip, the three maxima and the global id of the element of the largest FIP (ties: the
-//                        smallest id), partials per block, then one wave
+//                        smallest id): the two-launch summary of analysis_device.hpp
 // Design.  Launch 1 is the hot path and moves bytes: per element one 296-byte row, of which 22 doubles are needed (stress, shear rates,
 // orientation), and 480 bytes of accumulators read and written.
-//   1: a block of 64 lanes stages the 22 columns of its 64 rows through LDS with wave-wide loads (flat index 64 j + lane over (row, column): every
+//   1: a block of 64 lanes stages the 22 columns of its 64 rows through LDS with wave-wide loads (stage_rows with the column map field_col: every
 //      load instruction walks the rows contiguously, 48 + 128 bytes per row), rows padded to 23 in LDS (odd stride: lane = row reads hit distinct
 //      banks).  Lane = element then reads and writes each accumulator plane at [plane][base + lane]: one 512-byte run per wave and instruction.  The 12 unit
 //      plane normals arrive by value (kernel arguments: scalar registers under the unrolled system loop).  RESET reads 24 planes instead of 60.
-//   2: lane = element reads its 60 planar values, the 6 results go out through an LDS tile as one contiguous run of 64 x 6 doubles.
+//   2: lane = element reads its 60 planar values, the 6 results go out through an LDS tile (store_tile, rows padded to 7) as one contiguous
+//      run of 64 x 6 doubles.
 //   3: lane = element reads V of its field row and its 48-byte result row.
 // No atomics, fixed summation orders: every launch gives the same bits on every call.
-#include "exa_internal.hpp"
+#include "analysis_device.hpp"
 #include <cmath>
 #include <limits>
+
+using namespace exa_analysis;
 
 namespace {
 
@@ -27,7 +30,6 @@ constexpr int NCOL = 6 + NS + 4;                     // staged columns: stress |
 constexpr int LDR = NCOL + 1;                        // padded row of the staging tile
 constexpr int C_SIG = 0, C_RATE = 6, C_Q = 6 + NS;   // their places in a staged row
 constexpr int P_GAM = EXA_ACC_SLIP, P_ABS = EXA_ACC_ABS, P_MIN = EXA_ACC_MIN, P_MAX = EXA_ACC_MAX, P_NMX = EXA_ACC_NMAX;   // accumulator planes
-constexpr int NSUM = 7;
 constexpr int S_THREADS = 256, S_WAVES = S_THREADS / 64, S_MAX_BLOCKS = 960;
 
 struct Normals { double m[NS][3]; };
@@ -38,22 +40,10 @@ template <bool RESET>
 __global__ __launch_bounds__(CH) void k_slip_accumulate(const int64_t E, const int64_t Epad, const double* __restrict__ F, const Normals nrm, const double dt,
                                                         double* __restrict__ acc) {
    __shared__ double sm[LDR * CH];
-   const int lane = threadIdx.x;
-   const int64_t base = (int64_t)blockIdx.x * CH;
-   const int nv = (int)(E - base < CH ? E - base : CH);
-   // all loads are issued before the first LDS write; rows past nv of a last, partial block repeat row nv - 1
-   double st[NCOL];
-#pragma unroll
-   for (int j = 0; j < NCOL; j++) {
-      const int i = j * CH + lane, r = i / NCOL, c = i - r * NCOL;
-      const int rr = r < nv ? r : nv - 1;
-      st[j] = F[(base + rr) * NF + field_col(c)];
-   }
-#pragma unroll
-   for (int j = 0; j < NCOL; j++) {
-      const int i = j * CH + lane, r = i / NCOL, c = i - r * NCOL;
-      sm[r * LDR + c] = st[j];
-   }
+   const BlockView bv(E);
+   const int lane = bv.lane, nv = bv.nv;
+   const int64_t base = bv.base;
+   stage_rows<NCOL, LDR>(sm, nv, lane, F, [&](int r) { return (base + r) * NF; }, [](int c) { return field_col(c); });
    __syncthreads();
    if (lane >= nv) return;   // lanes beyond E store nothing
    const double* f = sm + lane * LDR;
@@ -80,9 +70,9 @@ __global__ __launch_bounds__(CH) void k_slip_accumulate(const int64_t E, const i
 
 __global__ __launch_bounds__(CH) void k_fip_rows(const int64_t E, const int64_t Epad, const double* __restrict__ acc, const double k_over_sy, double* __restrict__ out) {
    __shared__ double sm[CH * (NFP + 1)];
-   const int lane = threadIdx.x;
-   const int64_t base = (int64_t)blockIdx.x * CH;
-   const int nv = (int)(E - base < CH ? E - base : CH);
+   const BlockView bv(E);
+   const int lane = bv.lane, nv = bv.nv;
+   const int64_t base = bv.base;
    if (lane < nv) {
       const double* a0 = acc + base + lane;
       double best = 0.0, brange = 0.0, bn = 0.0, asum = 0.0, net = 0.0; int bsys = 0;
@@ -100,36 +90,35 @@ __global__ __launch_bounds__(CH) void k_fip_rows(const int64_t E, const int64_t 
       o[EXA_FIP_ACCUMULATEDSLIP] = asum; o[EXA_FIP_NETSLIPMAX] = net;
    }
    __syncthreads();
-#pragma unroll
-   for (int j = 0; j < NFP; j++) {
-      const int i = j * CH + lane, r = i / NFP, k = i - r * NFP;
-      if (r < nv) out[base * NFP + i] = sm[r * (NFP + 1) + k];
-   }
+   store_tile<NFP, NFP + 1>(out, base, sm, nv, lane);
 }
 
-// sums: plain; maxima: fmax; the pair (largest FIP, id): the larger FIP, on a tie the smaller id
+// the pair (largest FIP, id): the larger FIP, on a tie the smaller id
 __device__ __forceinline__ void best_of(double& f, double& id, const double f2, const double id2) {
    if (f2 > f || (f2 == f && id2 < id)) { f = f2; id = id2; }
 }
-__device__ __forceinline__ void wave_red7(double v[NSUM]) {
-#pragma unroll
-   for (int d = 32; d > 0; d >>= 1) {
-      double y[NSUM];
-#pragma unroll
-      for (int k = 0; k < NSUM; k++) y[k] = __shfl_down(v[k], d);
+constexpr double NEG_INF = -std::numeric_limits<double>::infinity();
+constexpr double NO_ID = 9007199254740992.0;   // 2^53: above every element id
+
+// sum V, sum V FIP, sum V AccumulatedSlip | max FIP, max ShearRange, max AccumulatedSlip | id of max FIP.  FIP carries no clamp and may be
+// negative: -inf is the neutral element of the maxima
+struct FipSummary {
+   static constexpr int N = 7;
+   static __device__ __forceinline__ void init(double* v) { v[0] = v[1] = v[2] = 0.0; v[3] = v[4] = v[5] = NEG_INF; v[6] = NO_ID; }
+   static __device__ __forceinline__ void merge(double* v, const double* y) {
       v[0] += y[0]; v[1] += y[1]; v[2] += y[2];
       best_of(v[3], v[6], y[3], y[6]);
       v[4] = fmax(v[4], y[4]); v[5] = fmax(v[5], y[5]);
    }
-}
-constexpr double NEG_INF = -std::numeric_limits<double>::infinity();
-constexpr double NO_ID = 9007199254740992.0;   // 2^53: above every element id
+};
+constexpr int NSUM = FipSummary::N;
 
 __global__ __launch_bounds__(S_THREADS) void k_fip_partial(const int64_t E, const double* __restrict__ F, const double* __restrict__ P, const int64_t* __restrict__ gid,
                                                            double* __restrict__ partial) {
    __shared__ double sm[S_WAVES][NSUM];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   double v[NSUM] = { 0.0, 0.0, 0.0, NEG_INF, NEG_INF, NEG_INF, NO_ID };   // FIP carries no clamp and may be negative: -inf is the neutral element
+   double v[NSUM];
+   FipSummary::init(v);
    const int64_t nblk = (E + 63) / 64, stride = (int64_t)gridDim.x * S_WAVES;
    for (int64_t b = (int64_t)blockIdx.x * S_WAVES + wave; b < nblk; b += stride) {
       const int64_t e = b * 64 + lane;
@@ -141,42 +130,11 @@ __global__ __launch_bounds__(S_THREADS) void k_fip_partial(const int64_t E, cons
       best_of(v[3], v[6], fip, (double)gid[e]);
       v[4] = fmax(v[4], rg); v[5] = fmax(v[5], as);
    }
-   wave_red7(v);
-   if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < NSUM; k++) sm[wave][k] = v[k];
-   }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      double t[NSUM];
-#pragma unroll
-      for (int k = 0; k < NSUM; k++) t[k] = sm[0][k];
-#pragma unroll
-      for (int w = 1; w < S_WAVES; w++) {
-         t[0] += sm[w][0]; t[1] += sm[w][1]; t[2] += sm[w][2];
-         best_of(t[3], t[6], sm[w][3], sm[w][6]);
-         t[4] = fmax(t[4], sm[w][4]); t[5] = fmax(t[5], sm[w][5]);
-      }
-#pragma unroll
-      for (int k = 0; k < NSUM; k++) partial[(int64_t)blockIdx.x * NSUM + k] = t[k];
-   }
+   summary_block_partial<FipSummary>(v, sm, partial);
 }
 
-// one wave: lanes over the blocks in a fixed stride, then the shuffle tree
 __global__ __launch_bounds__(64) void k_fip_reduce(const int nb, const double* __restrict__ partial, double* __restrict__ out) {
-   const int lane = threadIdx.x;
-   double v[NSUM] = { 0.0, 0.0, 0.0, NEG_INF, NEG_INF, NEG_INF, NO_ID };
-   for (int b = lane; b < nb; b += 64) {
-      const double* p = partial + (int64_t)b * NSUM;
-      v[0] += p[0]; v[1] += p[1]; v[2] += p[2];
-      best_of(v[3], v[6], p[3], p[6]);
-      v[4] = fmax(v[4], p[4]); v[5] = fmax(v[5], p[5]);
-   }
-   wave_red7(v);
-   if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < NSUM; k++) out[k] = v[k];
-   }
+   summary_reduce<FipSummary>(nb, partial, out);
 }
 
 inline int64_t pad64(int64_t E) { return (E + 63) / 64 * 64; }
@@ -226,9 +184,8 @@ extern "C" int exa_fip_summary(exa_ctx* ctx, const double* fields_dev, const dou
    if (!ctx) return EXA_ERR_ARG;
    if (!out7_dev || (ctx->E > 0 && (!fields_dev || !fip_dev || !elem_gid_dev))) { ctx->err = "exa_fip_summary: fields, FIP rows, element ids and an output are required"; return EXA_ERR_ARG; }
    hipStream_t s = reinterpret_cast<hipStream_t>(str);
-   const int64_t need = ((int64_t)ctx->E + S_THREADS - 1) / S_THREADS;
-   const int nb = (int)(need < S_MAX_BLOCKS ? need : S_MAX_BLOCKS);   // (no rows: the reduce launch alone writes the neutral elements)
-   if (sizeof(double) * (size_t)nb * NSUM > ctx->scratch_bytes) { ctx->err = "exa_fip_summary: reduction scratch too small"; return EXA_ERR_UNSUPPORTED; }
+   int nb;   // (no rows: nb = 0, the reduce launch alone writes the neutral elements)
+   if (int rc = summary_grid(ctx, "exa_fip_summary", S_THREADS, S_MAX_BLOCKS, NSUM, &nb)) return rc;
    if (nb > 0) hipLaunchKernelGGL(k_fip_partial, dim3(nb), dim3(S_THREADS), 0, s, (int64_t)ctx->E, fields_dev, fip_dev, elem_gid_dev, ctx->scratch_dev);
    hipLaunchKernelGGL(k_fip_reduce, dim3(1), dim3(64), 0, s, nb, (const double*)ctx->scratch_dev, out7_dev);
    EXA_HIP_CHECK(ctx, hipGetLastError());

@@ -5,8 +5,8 @@
 //   pass 2: given the grain means qbar: sum V theta and max theta, theta = 2 atan2(|d_vec|, |d_0|) (degrees), d = conj(qbar) (x) q
 // Design (HBM-bound: the rows are 296 bytes each, read once per pass).  The elements are taken in a grain-sorted order (exa_grain_plan, built
 // once per grain map), cut into 64-element chunks, one chunk per 64-lane block:
-//   1. the chunk's 64 rows are staged through LDS with wave-wide loads: flat index i = 64 j + lane over the rows' leading columns, so every
-//      load instruction reads 512 contiguous-by-row bytes (whole cache lines) instead of one 8-byte piece of 64 different rows;
+//   1. the chunk's 64 rows are staged through LDS with wave-wide loads (stage_rows, analysis_device.hpp: the rows' leading columns, dense), so
+//      every load instruction reads 512 contiguous-by-row bytes (whole cache lines) instead of one 8-byte piece of 64 different rows;
 //   2. lane r turns staged row r into its K values (39 in pass 1, 2 in pass 2) and writes them back to LDS as a [64][K] tile;
 //   3. lane k < K walks the tile's rows in order and sums column k per segment (a run of equal grain), flushing at every segment change.
 // A segment wholly inside the chunk is final: row gid of the dense output.  A chunk's first and last segment may continue into the
@@ -14,11 +14,13 @@
 // (items instead of gathered rows).  Every item list is at most 2 / 64 of the one before, so the levels stay few (4 at 2M elements) and the
 // work is O(E) for any grain sizes: one grain of the whole mesh, one grain per element or anything between.  No atomics, a fixed order of
 // every sum given the sorted order: every launch on the same data gives the same bits, whatever the grid.
-#include "exa_internal.hpp"
+#include "analysis_device.hpp"
 #include <algorithm>
 #include <cmath>
 #include <numeric>
 #include <vector>
+
+using namespace exa_analysis;
 
 namespace {
 
@@ -26,7 +28,6 @@ constexpr int NF = EXA_NFIELDS;
 constexpr int K1 = EXA_GRAIN_NSUMS, K2 = 2;
 constexpr int CH = 64;                 // elements (items) per chunk = threads per block
 constexpr int P2_COLS = EXA_F_ORIENTATION + 4;   // pass 2 reads columns 0 .. 30 (volume .. orientation)
-constexpr double RAD2DEG = 57.295779513082320876798154814105;
 
 // plan (int32): [0] L levels, [1] the largest grain id, [2 .. 2 + L) n_l items per level (n_0 = E), then order[n_0] and per level
 // row_l[n_l] (grain id - 1 of every item: a segment is a run of equal rows) and slots_l[2 nch_l] (item slot of the next level for the chunk's
@@ -57,9 +58,9 @@ __global__ __launch_bounds__(CH) void k_grain_chunk(const int64_t n, const doubl
    constexpr int TILE = (NC > K ? NC : K) * CH;
    __shared__ double sm[TILE];
    __shared__ int32_t s_seg[CH], s_row[CH];
-   const int lane = threadIdx.x;
-   const int64_t c = blockIdx.x, base = c * CH;
-   const int nv = (int)(n - base < CH ? n - base : CH);
+   const BlockView bv(n);
+   const int lane = bv.lane, nv = bv.nv;
+   const int64_t c = blockIdx.x, base = bv.base;
    const int slot_first = slots[2 * c], slot_last = slots[2 * c + 1];   // block-uniform, issued first
    const int my_row = lane < nv ? seg[base + lane] : -1;
    s_seg[lane] = my_row;
@@ -70,16 +71,8 @@ __global__ __launch_bounds__(CH) void k_grain_chunk(const int64_t n, const doubl
    }
    __syncthreads();
    // 1. stage rows 0 .. nv-1 (NC leading columns each) as the flat [nv][NC] tile: all NC loads are issued before the first LDS write (a load
-   //    guarded by r < nv and stored at once would wait for each load in turn); rows past nv of a last, partial chunk repeat row nv - 1
-   double st[NC];
-#pragma unroll
-   for (int j = 0; j < NC; j++) {
-      const int i = j * CH + lane, r = i / NC, col = i - r * NC;
-      const int rr = r < nv ? r : nv - 1;
-      st[j] = src[(GATHER ? (int64_t)s_row[rr] : base + rr) * SRC_LD + col];
-   }
-#pragma unroll
-   for (int j = 0; j < NC; j++) sm[j * CH + lane] = st[j];
+   //    guarded by r < nv and stored at once would wait for each load in turn); the rows are the gathered order's or the item list's
+   stage_rows<NC, NC>(sm, nv, lane, src, [&](int r) { return (GATHER ? (int64_t)s_row[r] : base + r) * SRC_LD; }, IdentityCol());
    __syncthreads();
    // 2. per-element values (level 0 only; items are values already)
    if constexpr (GATHER) {
@@ -94,16 +87,13 @@ __global__ __launch_bounds__(CH) void k_grain_chunk(const int64_t n, const doubl
             for (int k = 0; k < 6; k++) v[2 + k] = V * f[EXA_F_STRESS + k];
             const double* e = f + EXA_F_XTALELASTICSTRAIN;
             const double T[3][3] = { { e[0], e[5], e[4] }, { e[5], e[1], e[3] }, { e[4], e[3], e[2] } };
-            const double x0 = q[0], x1 = q[1], x2 = q[2], x3 = q[3];   // R(q) row-major (quat_to_mat, ecm_device.hpp)
-            const double R[3][3] = { { x0 * x0 + x1 * x1 - x2 * x2 - x3 * x3, 2.0 * (x1 * x2 - x0 * x3), 2.0 * (x1 * x3 + x0 * x2) },
-                                     { 2.0 * (x1 * x2 + x0 * x3), x0 * x0 - x1 * x1 + x2 * x2 - x3 * x3, 2.0 * (x2 * x3 - x0 * x1) },
-                                     { 2.0 * (x1 * x3 - x0 * x2), 2.0 * (x2 * x3 + x0 * x1), x0 * x0 - x1 * x1 - x2 * x2 + x3 * x3 } };
+            double R[9]; ecmdev::quat_to_mat(q, R);   // row-major
             double M[3][3];   // R T
 #pragma unroll
             for (int a = 0; a < 3; a++)
 #pragma unroll
-               for (int b = 0; b < 3; b++) M[a][b] = R[a][0] * T[0][b] + R[a][1] * T[1][b] + R[a][2] * T[2][b];
-            auto es = [&](int a, int b) { return M[a][0] * R[b][0] + M[a][1] * R[b][1] + M[a][2] * R[b][2]; };   // (R T R^T)_ab
+               for (int b = 0; b < 3; b++) M[a][b] = R[3 * a] * T[0][b] + R[3 * a + 1] * T[1][b] + R[3 * a + 2] * T[2][b];
+            auto es = [&](int a, int b) { return M[a][0] * R[3 * b] + M[a][1] * R[3 * b + 1] + M[a][2] * R[3 * b + 2]; };   // (R T R^T)_ab
             v[8] = V * es(0, 0); v[9] = V * es(1, 1); v[10] = V * es(2, 2); v[11] = V * es(1, 2); v[12] = V * es(0, 2); v[13] = V * es(0, 1);
 #pragma unroll
             for (int k = 0; k < 6; k++) v[14 + k] = V * e[k];

@@ -7,11 +7,14 @@
 //   eps_s = u_e^T eps_e u_e                   = s^T (R eps_e R^T) s
 // and the launch leaves the 2H + 1 local sums  sum_{e in j} V_e eps_s, sum_{e in j} V_e (j = 0 .. H-1), sum_e V_e  in out_dev.
 // Design (HBM-bound: each lane reads 11 of the 37 doubles of its own row, a wave's loads cover the 64 rows of its block): lane = element,
-// 64-element blocks dealt to the waves of a fixed grid in a grid-stride loop; per-lane sums -> __shfl_down tree per wave -> the block's four waves
-// in wave order through LDS -> partial sums per block in ctx->scratch_dev -> one-block reduction in block order.  No atomics, the grid depends
-// on E alone: every launch on the same data gives the same bits.
-#include "exa_internal.hpp"
+// 64-element blocks dealt to the waves of a fixed grid in a grid-stride loop, then the two-launch summary of analysis_device.hpp (wave tree ->
+// the block's waves in wave order -> partials per block -> one wave), written out here because the number of values, 2H + 1, is a run-time
+// count and the per-lane sums acc[2 MAXH + 1] are compacted on the way to LDS; lanes k < 2H + 1 combine the waves, one value each.  No atomics,
+// the grid depends on E alone: every launch on the same data gives the same bits.
+#include "analysis_device.hpp"
 #include <cmath>
+
+using namespace exa_analysis;
 
 namespace {
 
@@ -20,9 +23,8 @@ constexpr int MAXH = EXA_LATTICE_MAX_HKL, MAXAX = 24 * MAXH, MAXV = 2 * MAXH + 1
 constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int MAX_BLOCKS = 960;   // partial sums: MAX_BLOCKS x MAXV doubles of ctx->scratch_dev (32768 doubles, capi.hip)
 
-// The axes of a family are signed permutations of its first axis (cubic orbit), so they travel by value as 16-bit codes (~0.9 KB of kernel
-// arguments instead of 9 KB of doubles): component i of axis a of family j = (code >> (6 + i) & 1 ? -1 : 1) * v[j][(code >> 2 i) & 3].
-// The decoded axes are the host's doubles bit for bit (a sign flip and a permutation are exact).
+// The axes of a family travel by value as the signed-permutation codes of its first axis (perm_code / perm_apply, analysis_device.hpp): ~0.9 KB
+// of kernel arguments instead of 9 KB of doubles
 struct LatArgs {
    double v[MAXH][3];
    uint16_t code[MAXAX];
@@ -31,12 +33,6 @@ struct LatArgs {
    double cos_tol;
    int nhkl;
 };
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-   for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d);
-   return x;   // lane 0
-}
 
 __global__ __launch_bounds__(THREADS) void k_lattice_partial(const int64_t E, const double* __restrict__ F, double* __restrict__ partial, const LatArgs A) {
    __shared__ double sm[WAVES][MAXV];
@@ -51,17 +47,14 @@ __global__ __launch_bounds__(THREADS) void k_lattice_partial(const int64_t E, co
       if (e >= E) continue;
       const double* r = F + e * NF;
       const double V = r[EXA_F_VOLUME];
-      const double x0 = r[EXA_F_ORIENTATION], x1 = r[EXA_F_ORIENTATION + 1], x2 = r[EXA_F_ORIENTATION + 2], x3 = r[EXA_F_ORIENTATION + 3];
+      const double q[4] = { r[EXA_F_ORIENTATION], r[EXA_F_ORIENTATION + 1], r[EXA_F_ORIENTATION + 2], r[EXA_F_ORIENTATION + 3] };
       double eps[6];
 #pragma unroll
       for (int k = 0; k < 6; k++) eps[k] = r[EXA_F_XTALELASTICSTRAIN + k];
-      // R(q) row-major (quat_to_mat, ecm_device.hpp = ExaModel::Quat2RMat); u = R^T s
-      const double R0 = x0 * x0 + x1 * x1 - x2 * x2 - x3 * x3, R1 = 2.0 * (x1 * x2 - x0 * x3), R2 = 2.0 * (x1 * x3 + x0 * x2);
-      const double R3 = 2.0 * (x1 * x2 + x0 * x3), R4 = x0 * x0 - x1 * x1 + x2 * x2 - x3 * x3, R5 = 2.0 * (x2 * x3 - x0 * x1);
-      const double R6 = 2.0 * (x1 * x3 - x0 * x2), R7 = 2.0 * (x2 * x3 + x0 * x1), R8 = x0 * x0 - x1 * x1 - x2 * x2 + x3 * x3;
-      const double u0 = R0 * A.s[0] + R3 * A.s[1] + R6 * A.s[2];
-      const double u1 = R1 * A.s[0] + R4 * A.s[1] + R7 * A.s[2];
-      const double u2 = R2 * A.s[0] + R5 * A.s[1] + R8 * A.s[2];
+      double R[9]; ecmdev::quat_to_mat(q, R);   // row-major, = ExaModel::Quat2RMat; u = R^T s
+      const double u0 = R[0] * A.s[0] + R[3] * A.s[1] + R[6] * A.s[2];
+      const double u1 = R[1] * A.s[0] + R[4] * A.s[1] + R[7] * A.s[2];
+      const double u2 = R[2] * A.s[0] + R[5] * A.s[1] + R[8] * A.s[2];
       // eps (11, 22, 33, 23, 13, 12), tensor components
       const double es = u0 * u0 * eps[0] + u1 * u1 * eps[1] + u2 * u2 * eps[2] + 2.0 * (u1 * u2 * eps[3] + u0 * u2 * eps[4] + u0 * u1 * eps[5]);
       const double Ves = V * es;
@@ -71,6 +64,7 @@ __global__ __launch_bounds__(THREADS) void k_lattice_partial(const int64_t E, co
          if (j >= H) continue;   // kernel-uniform (no break: the loop is unrolled so that acc stays in registers)
          double m = 0.0;
          for (int a = A.off[j]; a < A.off[j + 1]; a++) {
+            // perm_apply's three lines in place: as a call the launch measured 8.06 us against the parent's 7.22 .. 7.76 (profiles/analysis_helpers_speed.txt)
             const int c = A.code[a];
             const double c0 = ((c >> 6) & 1) ? -A.v[j][c & 3] : A.v[j][c & 3];
             const double c1 = ((c >> 7) & 1) ? -A.v[j][(c >> 2) & 3] : A.v[j][(c >> 2) & 3];
@@ -127,21 +121,8 @@ extern "C" int exa_lattice_strains(exa_ctx* ctx, const double* fields_dev, int n
       A.off[j] = (int16_t)a0; A.off[j + 1] = (int16_t)a1;
       const double* v = axes + 3 * (size_t)a0;
       for (int i = 0; i < 3; i++) A.v[j][i] = v[i];
-      for (int a = a0; a < a1; a++) {   // code of axis a: the signed permutation of v it is
-         const double* c = axes + 3 * (size_t)a;
-         int code = -1;
-         for (int p = 0; p < 6 && code < 0; p++) {
-            static const int P[6][3] = { { 0, 1, 2 }, { 0, 2, 1 }, { 1, 0, 2 }, { 1, 2, 0 }, { 2, 0, 1 }, { 2, 1, 0 } };
-            int cd = P[p][0] | (P[p][1] << 2) | (P[p][2] << 4);
-            bool ok = true;
-            for (int i = 0; i < 3 && ok; i++) {
-               const double x = v[P[p][i]];
-               if (c[i] == x) continue;
-               if (c[i] == -x) { cd |= 1 << (6 + i); continue; }
-               ok = false;
-            }
-            if (ok) code = cd;
-         }
+      for (int a = a0; a < a1; a++) {
+         const int code = perm_code(v, axes + 3 * (size_t)a);
          if (code < 0) { ctx->err = "exa_lattice_strains: the axes of a family must be signed permutations of its first axis (a cubic orbit)"; return EXA_ERR_ARG; }
          A.code[a] = (uint16_t)code;
       }
@@ -149,9 +130,8 @@ extern "C" int exa_lattice_strains(exa_ctx* ctx, const double* fields_dev, int n
    const int nv = 2 * nhkl + 1;
    hipStream_t s = reinterpret_cast<hipStream_t>(str);
    if (ctx->E == 0) { EXA_HIP_CHECK(ctx, hipMemsetAsync(out_dev, 0, sizeof(double) * nv, s)); return EXA_OK; }
-   const int64_t need = ((int64_t)ctx->E + THREADS - 1) / THREADS;
-   const int nb = (int)(need < MAX_BLOCKS ? need : MAX_BLOCKS);
-   if (sizeof(double) * (size_t)nb * nv > ctx->scratch_bytes) { ctx->err = "exa_lattice_strains: reduction scratch too small"; return EXA_ERR_UNSUPPORTED; }
+   int nb;
+   if (int rc = summary_grid(ctx, "exa_lattice_strains", THREADS, MAX_BLOCKS, nv, &nb)) return rc;
    hipLaunchKernelGGL(k_lattice_partial, dim3(nb), dim3(THREADS), 0, s, (int64_t)ctx->E, fields_dev, ctx->scratch_dev, A);
    hipLaunchKernelGGL(k_lattice_reduce, dim3(1), dim3(64), 0, s, nb, nv, (const double*)ctx->scratch_dev, out_dev);
    EXA_HIP_CHECK(ctx, hipGetLastError());
@@ -164,24 +144,20 @@ extern "C" int exa_cubic_fiber_axes(int h, int k, int l, double* out, int max) {
    if (h == 0 && k == 0 && l == 0) return -1;
    const double n = std::sqrt((double)h * h + (double)k * k + (double)l * l);
    const double c[3] = { h / n, k / n, l / n };
-   static const int P[6][3] = { { 0, 1, 2 }, { 1, 2, 0 }, { 2, 0, 1 }, { 0, 2, 1 }, { 2, 1, 0 }, { 1, 0, 2 } };   // even permutations first
+   uint16_t rot[24];
+   cubic_proper_rotations(rot);
    int cnt = 0;
    std::vector<double> ax;
-   for (int p = 0; p < 6; p++) {
-      const int parity = p < 3 ? 1 : -1;
-      for (int sg = 0; sg < 8; sg++) {
-         const int s0 = (sg & 1) ? -1 : 1, s1 = (sg & 2) ? -1 : 1, s2 = (sg & 4) ? -1 : 1;
-         if (parity * s0 * s1 * s2 != 1) continue;   // det = parity x product of the signs
-         // row i of the rotation has its entry s_i in column P[p][i]: (S c)_i = s_i c[P[p][i]]
-         double a[3] = { s0 * c[P[p][0]], s1 * c[P[p][1]], s2 * c[P[p][2]] };
-         const double lead = a[0] != 0.0 ? a[0] : (a[1] != 0.0 ? a[1] : a[2]);
-         if (lead < 0.0) for (double& x : a) x = -x;
-         for (double& x : a) if (x == 0.0) x = 0.0;   // no -0
-         bool dup = false;
-         for (int i = 0; i < cnt && !dup; i++) dup = ax[3 * i] == a[0] && ax[3 * i + 1] == a[1] && ax[3 * i + 2] == a[2];
-         if (dup) continue;
-         ax.insert(ax.end(), a, a + 3); cnt++;
-      }
+   for (int r = 0; r < 24; r++) {   // in the order of the rotations: the axis order is part of the output
+      double a[3];
+      perm_apply(c, rot[r], a[0], a[1], a[2]);
+      const double lead = a[0] != 0.0 ? a[0] : (a[1] != 0.0 ? a[1] : a[2]);
+      if (lead < 0.0) for (double& x : a) x = -x;
+      for (double& x : a) if (x == 0.0) x = 0.0;   // no -0
+      bool dup = false;
+      for (int i = 0; i < cnt && !dup; i++) dup = ax[3 * i] == a[0] && ax[3 * i + 1] == a[1] && ax[3 * i + 2] == a[2];
+      if (dup) continue;
+      ax.insert(ax.end(), a, a + 3); cnt++;
    }
    if (out) for (int i = 0; i < cnt && i < max; i++) for (int d = 0; d < 3; d++) out[3 * i + d] = ax[3 * i + d];
    return cnt;

@@ -1,17 +1,20 @@
 // In-situ texture (gfx950): pole figures of {hkl} families and inverse pole figures of sample directions on the per-element rows of
 // exa_element_fields (include/exaconstit_hip.h), binned on an (alpha, beta) grid of the upper hemisphere.  Per element e
-// (V = EXA_F_VOLUME, unit quaternion q = EXA_F_ORIENTATION, R = quat_to_mat(q): crystal -> sample, as lattice_kernels.hip):
+// (V = EXA_F_VOLUME, unit quaternion q = EXA_F_ORIENTATION, R = quat_to_mat(q): crystal -> sample):
 //   pole figure of family j:           poles p = R c for the N_j axes c of the family's cubic orbit, each of weight V / N_j
 //   inverse pole figure of direction d: u = R^T d, images p = S_k u for the 24 proper cubic rotations S_k, each of weight V / 24
 // Every pole is folded onto the upper hemisphere and binned by texture_bin (below: the one statement of the binning rules, host and device).
 // Exact, order-independent sums: a pole's weight is quantized to the unsigned 64-bit integer rint(V 2^-quantum_log2 / N); the counts are
 // summed as integers (LDS atomics per workgroup, then one integer atomic add per non-empty bin and workgroup into the output), so the
 // result has the same bits for any grid, element order or rank split of the same rows.  No float atomics.
-// Design: lane = element, 64-element blocks dealt to the waves of a fixed grid (lattice_kernels.hip); each element's 5 doubles are read
+// Design: lane = element, 64-element blocks dealt to the waves of a fixed grid in a grid-stride loop; each element's 5 doubles are read
 // once per launch for all the sets whose histograms share the workgroup's LDS: the sets are cut into chunks of at most 64 KiB of counters
-// (blockIdx.y = chunk); at the default 5 degrees every set up to 6 fits in one chunk.
-#include "exa_internal.hpp"
+// (blockIdx.y = chunk); at the default 5 degrees every set up to 6 fits in one chunk.  The largest volume, which sizes the quantum, comes
+// from the two-launch summary of analysis_device.hpp; the axes and rotations travel as its signed-permutation codes.
+#include "analysis_device.hpp"
 #include <cmath>
+
+using namespace exa_analysis;
 
 namespace {
 
@@ -20,13 +23,12 @@ constexpr int MAXSET = EXA_TEXTURE_MAX_HKL + EXA_TEXTURE_MAX_DIRS, MAXCODE = 24 
 constexpr int THREADS = 256, WAVES = THREADS / 64;
 constexpr int LDS_BINS = 8192;     // 64 KiB of 64-bit counters per workgroup: one set at 2 degrees (45 x 180 = 8100 bins)
 constexpr int MAX_BLOCKS = 512;    // per chunk; each workgroup adds its non-empty bins to the output once
+constexpr int VMAX_BLOCKS = 1024;  // the volume maximum's summary grid
 
-// component i of the image of a vector b under signed-permutation code c: ((c >> (6 + i)) & 1 ? -1 : 1) * b[(c >> 2 i) & 3]
-// (the fibre-axis codes of lattice_kernels.hip; a sign flip and a permutation are exact)
 struct TexArgs {
    double v[MAXSET][3];      // pole figure: the family's first unit axis (crystal frame); inverse pole figure: the unit direction (sample frame)
    double wscale[MAXSET];    // 2^-quantum_log2 / N_set: count of a pole = rint(V wscale)
-   uint16_t code[MAXCODE];
+   uint16_t code[MAXCODE];   // perm_apply: a family's axes from its first axis, the 24 cubic images of u
    int16_t off[MAXSET + 1];
    int8_t chunk[MAXSET + 1]; // chunk c holds the sets chunk[c] .. chunk[c + 1] - 1
    int npf, na, nb;
@@ -54,12 +56,6 @@ __host__ __device__ inline void texture_bin(double x, double y, double z, double
 
 namespace {
 
-__device__ __forceinline__ void perm(const double* b, int c, double& p0, double& p1, double& p2) {
-   p0 = ((c >> 6) & 1) ? -b[c & 3] : b[c & 3];
-   p1 = ((c >> 7) & 1) ? -b[(c >> 2) & 3] : b[(c >> 2) & 3];
-   p2 = ((c >> 8) & 1) ? -b[(c >> 4) & 3] : b[(c >> 4) & 3];
-}
-
 __global__ __launch_bounds__(THREADS) void k_texture(const int64_t E, const double* __restrict__ F, unsigned long long* __restrict__ out, const TexArgs A) {
    extern __shared__ unsigned long long hist[];
    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -73,29 +69,26 @@ __global__ __launch_bounds__(THREADS) void k_texture(const int64_t E, const doub
       if (e >= E) continue;
       const double* r = F + e * NF;
       const double V = r[EXA_F_VOLUME];
-      const double x0 = r[EXA_F_ORIENTATION], x1 = r[EXA_F_ORIENTATION + 1], x2 = r[EXA_F_ORIENTATION + 2], x3 = r[EXA_F_ORIENTATION + 3];
-      // R(q) row-major (quat_to_mat, ecm_device.hpp)
-      const double R0 = x0 * x0 + x1 * x1 - x2 * x2 - x3 * x3, R1 = 2.0 * (x1 * x2 - x0 * x3), R2 = 2.0 * (x1 * x3 + x0 * x2);
-      const double R3 = 2.0 * (x1 * x2 + x0 * x3), R4 = x0 * x0 - x1 * x1 + x2 * x2 - x3 * x3, R5 = 2.0 * (x2 * x3 - x0 * x1);
-      const double R6 = 2.0 * (x1 * x3 - x0 * x2), R7 = 2.0 * (x2 * x3 + x0 * x1), R8 = x0 * x0 - x1 * x1 - x2 * x2 + x3 * x3;
+      const double q[4] = { r[EXA_F_ORIENTATION], r[EXA_F_ORIENTATION + 1], r[EXA_F_ORIENTATION + 2], r[EXA_F_ORIENTATION + 3] };
+      double R[9]; ecmdev::quat_to_mat(q, R);   // row-major
       for (int j = s0; j < s1; j++) {   // kernel-uniform bounds
          const unsigned long long w = (unsigned long long)rint(V * A.wscale[j]);
          unsigned long long* h = hist + (j - s0) * nbins;
          double u[3];
          if (j >= A.npf) {   // inverse pole figure: u = R^T d, images S_k u
             const double* d = A.v[j];
-            u[0] = R0 * d[0] + R3 * d[1] + R6 * d[2];
-            u[1] = R1 * d[0] + R4 * d[1] + R7 * d[2];
-            u[2] = R2 * d[0] + R5 * d[1] + R8 * d[2];
+            u[0] = R[0] * d[0] + R[3] * d[1] + R[6] * d[2];
+            u[1] = R[1] * d[0] + R[4] * d[1] + R[7] * d[2];
+            u[2] = R[2] * d[0] + R[5] * d[1] + R[8] * d[2];
          }
          for (int a = A.off[j]; a < A.off[j + 1]; a++) {
             double c0, c1, c2, p0, p1, p2;
             if (j < A.npf) {   // pole figure: p = R c
-               perm(A.v[j], A.code[a], c0, c1, c2);
-               p0 = R0 * c0 + R1 * c1 + R2 * c2;
-               p1 = R3 * c0 + R4 * c1 + R5 * c2;
-               p2 = R6 * c0 + R7 * c1 + R8 * c2;
-            } else perm(u, A.code[a], p0, p1, p2);
+               perm_apply(A.v[j], A.code[a], c0, c1, c2);
+               p0 = R[0] * c0 + R[1] * c1 + R[2] * c2;
+               p1 = R[3] * c0 + R[4] * c1 + R[5] * c2;
+               p2 = R[6] * c0 + R[7] * c1 + R[8] * c2;
+            } else perm_apply(u, A.code[a], p0, p1, p2);
             int i, k;
             texture_bin(p0, p1, p2, A.res_deg, A.na, A.nb, i, k);
             atomicAdd(&h[i * A.nb + k], w);
@@ -110,46 +103,23 @@ __global__ __launch_bounds__(THREADS) void k_texture(const int64_t E, const doub
    }
 }
 
-// largest EXA_F_VOLUME of the rows: per-block maxima in scratch, then one wave (max is exact: any order gives the same value)
+// largest EXA_F_VOLUME of the rows (max is exact: any order gives the same value); volumes are > 0: 0 is the neutral element
+struct VolumeMax {
+   static constexpr int N = 1;
+   static __device__ __forceinline__ void init(double* v) { v[0] = 0.0; }
+   static __device__ __forceinline__ void merge(double* v, const double* y) { v[0] = fmax(v[0], y[0]); }
+};
+
 __global__ __launch_bounds__(THREADS) void k_vmax_partial(const int64_t E, const double* __restrict__ F, double* __restrict__ partial) {
-   __shared__ double sm[WAVES];
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-   double m = 0.0;
-   for (int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x; e < E; e += (int64_t)gridDim.x * THREADS) m = fmax(m, F[e * NF + EXA_F_VOLUME]);
-#pragma unroll
-   for (int d = 32; d > 0; d >>= 1) m = fmax(m, __shfl_down(m, d));
-   if (lane == 0) sm[wave] = m;
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      double t = sm[0];
-      for (int w = 1; w < WAVES; w++) t = fmax(t, sm[w]);
-      partial[blockIdx.x] = t;
-   }
+   __shared__ double sm[WAVES][1];
+   double m[1];
+   VolumeMax::init(m);
+   for (int64_t e = (int64_t)blockIdx.x * THREADS + threadIdx.x; e < E; e += (int64_t)gridDim.x * THREADS) m[0] = fmax(m[0], F[e * NF + EXA_F_VOLUME]);
+   summary_block_partial<VolumeMax>(m, sm, partial);
 }
 
 __global__ __launch_bounds__(64) void k_vmax_reduce(const int nb, const double* __restrict__ partial, double* __restrict__ out) {
-   double m = 0.0;
-   for (int b = threadIdx.x; b < nb; b += 64) m = fmax(m, partial[b]);
-#pragma unroll
-   for (int d = 32; d > 0; d >>= 1) m = fmax(m, __shfl_down(m, d));
-   if (threadIdx.x == 0) out[0] = m;
-}
-
-// the signed-permutation code taking v to c, or -1
-int perm_code(const double* v, const double* c) {
-   static const int P[6][3] = { { 0, 1, 2 }, { 0, 2, 1 }, { 1, 0, 2 }, { 1, 2, 0 }, { 2, 0, 1 }, { 2, 1, 0 } };
-   for (int p = 0; p < 6; p++) {
-      int cd = P[p][0] | (P[p][1] << 2) | (P[p][2] << 4);
-      bool ok = true;
-      for (int i = 0; i < 3 && ok; i++) {
-         const double x = v[P[p][i]];
-         if (c[i] == x) continue;
-         if (c[i] == -x) { cd |= 1 << (6 + i); continue; }
-         ok = false;
-      }
-      if (ok) return cd;
-   }
-   return -1;
+   summary_reduce<VolumeMax>(nb, partial, out);
 }
 
 }  // namespace
@@ -182,9 +152,8 @@ extern "C" int exa_texture_volume_max(exa_ctx* ctx, const double* fields_dev, do
    if (!fields_dev || !out_dev) { ctx->err = "exa_texture_volume_max: fields and output are required"; return EXA_ERR_ARG; }
    hipStream_t s = reinterpret_cast<hipStream_t>(str);
    if (ctx->E == 0) { EXA_HIP_CHECK(ctx, hipMemsetAsync(out_dev, 0, sizeof(double), s)); return EXA_OK; }
-   const int64_t need = ((int64_t)ctx->E + THREADS - 1) / THREADS;
-   const int nb = (int)(need < 1024 ? need : 1024);
-   if (sizeof(double) * (size_t)nb > ctx->scratch_bytes) { ctx->err = "exa_texture_volume_max: reduction scratch too small"; return EXA_ERR_UNSUPPORTED; }
+   int nb;
+   if (int rc = summary_grid(ctx, "exa_texture_volume_max", THREADS, VMAX_BLOCKS, VolumeMax::N, &nb)) return rc;
    hipLaunchKernelGGL(k_vmax_partial, dim3(nb), dim3(THREADS), 0, s, (int64_t)ctx->E, fields_dev, ctx->scratch_dev);
    hipLaunchKernelGGL(k_vmax_reduce, dim3(1), dim3(64), 0, s, nb, (const double*)ctx->scratch_dev, out_dev);
    EXA_HIP_CHECK(ctx, hipGetLastError());
@@ -220,16 +189,8 @@ extern "C" int exa_texture_weights(exa_ctx* ctx, const double* fields_dev, int n
       A.off[j] = (int16_t)a0; A.off[j + 1] = (int16_t)a1;
       A.wscale[j] = scale / (a1 - a0);
    }
-   // the 24 proper rotations of the cubic group: the signed permutations of determinant +1
-   uint16_t rot[24]; int nrot = 0;
-   {
-      static const int P[6][3] = { { 0, 1, 2 }, { 1, 2, 0 }, { 2, 0, 1 }, { 0, 2, 1 }, { 2, 1, 0 }, { 1, 0, 2 } };   // even permutations first
-      for (int p = 0; p < 6; p++)
-         for (int sg = 0; sg < 8; sg++) {
-            const int par = p < 3 ? 1 : -1, sgn = ((sg & 1) ? -1 : 1) * ((sg & 2) ? -1 : 1) * ((sg & 4) ? -1 : 1);
-            if (par * sgn == 1) rot[nrot++] = (uint16_t)(P[p][0] | (P[p][1] << 2) | (P[p][2] << 4) | (sg << 6));
-         }
-   }
+   uint16_t rot[24];
+   cubic_proper_rotations(rot);
    for (int m = 0; m < nipf; m++) {
       const int j = npf + m;
       const double* d = ipf_dirs + 3 * (size_t)m;
