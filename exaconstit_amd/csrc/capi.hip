@@ -125,7 +125,7 @@ void exa_destroy(exa_ctx* ctx) {
    if (!ctx) return;
    (void)hipFree(ctx->n2e_off); (void)hipFree(ctx->n2e_idx); (void)hipFree(ctx->ev_det);
    (void)hipFree(ctx->G_dev); (void)hipFree(ctx->W_dev); (void)hipFree(ctx->fail_count_dev); (void)hipFree(ctx->tail_dev); (void)hipFree(ctx->tail2_dev); (void)hipFree(ctx->resume_dev[0]); (void)hipFree(ctx->resume_dev[1]); (void)hipFree(ctx->scratch_dev);
-   (void)hipFree(ctx->dmat); (void)hipFree(ctx->pa); (void)hipFree(ctx->emat); (void)hipFree(ctx->eDS); (void)hipFree(ctx->T1_dev); (void)hipFree(ctx->pa_c); (void)hipFree(ctx->tbuf); (void)hipFree(ctx->vgrad_ref); (void)hipFree(ctx->tet_rec);
+   (void)hipFree(ctx->dmat); (void)hipFree(ctx->pa); (void)hipFree(ctx->emat); (void)hipFree(ctx->eDS); (void)hipFree(ctx->eDSP); (void)hipFree(ctx->T1_dev); (void)hipFree(ctx->pa_c); (void)hipFree(ctx->tbuf); (void)hipFree(ctx->vgrad_ref); (void)hipFree(ctx->tet_rec);
    delete ctx;
 }
 
@@ -560,7 +560,7 @@ int exa_grad_apply_lvec_cols(exa_ctx* ctx, int ncols, const double* x, int64_t l
 // from records of a generated p = 2 box: the caller probes instead.
 int exa_grad_mg_p2_build(exa_ctx* ctx, const int* ne, const int32_t* elem_at, const uint8_t* mask0, const uint8_t* mask1, double* Sten, double* diag, exa_stream s) {
    if (int rc = grad_ready(ctx, "exa_grad_mg_p2_build", ne && elem_at && (Sten || diag) && (!Sten || mask1) && (!diag || mask0), NEEDS_CONN)) return rc;
-   if (!exa_is_hex(ctx) || ctx->n != 27 || ctx->Q != 27 || ctx->cfg.integ == EXA_INTEG_BBAR || ctx->det || !exa_acts_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
+   if (!exa_is_hex(ctx) || ctx->n != 27 || ctx->Q != 27 || ctx->det || !exa_acts_from_records(ctx)) return EXA_ERR_UNSUPPORTED;
    if (ne[0] < 1 || ne[1] < 1 || ne[2] < 1 || (int64_t)ne[0] * ne[1] * ne[2] != ctx->E || (int64_t)(2 * ne[0] + 1) * (2 * ne[1] + 1) * (2 * ne[2] + 1) != ctx->nnodes)
       return fail(ctx, EXA_ERR_ARG, "exa_grad_mg_p2_build: the element box does not match the context's elements and nodes");
    if (!exa_has_compact_geo(ctx) && (ctx->grad_src == EXA_GRAD_FROM_MODEL_RECORDS || ctx->pa_pending || !ctx->pa)) return EXA_ERR_UNSUPPORTED;   // (no records with geometry to read)

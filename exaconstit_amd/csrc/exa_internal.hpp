@@ -46,6 +46,7 @@ struct exa_ctx {
    double* emat = nullptr;                  // EA: p=1 full integration [block][24][12 pairs][64][2]; otherwise [block][3n][3n][64]
    double* T1_dev = nullptr;                // p = 2 matrix-free action: one-dimensional basis tables (3 x 6)
    double* eDS = nullptr;                   // B-bar: element-average shape gradient [block][n x 3][64 lanes]
+   double* eDSP = nullptr;                  // B-bar, p = 2 multigrid: average gradients of the eight embedded trilinear functions [block][8 x 3][64 lanes]
    double* tbuf = nullptr;                  // generic PA action: per-point T (3,3,Q,E)
    double* vgrad_ref = nullptr;             // p = 2 element-blocked constitutive launch: reference-space velocity gradients of its geometry pre-pass (3,3,Q,E)
    const double* resid_J = nullptr; const double* resid_S = nullptr;   // B-bar residual reads J and sigma at apply time, like the reference

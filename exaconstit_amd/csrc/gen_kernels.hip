@@ -534,11 +534,17 @@ __device__ __forceinline__ void mgp2_load(const double* __restrict__ pa, const i
    for (int pr = 0; pr < NPR; pr++) { const double2 t = r[pr * PA_BLK]; v[2 * pr] = t.x; v[2 * pr + 1] = t.y; }
 }
 // K(i, k) += ba . Sm(C eps(bb, k))[., i]: the 3 x 3 block of row function a and column function b at one point (out[3 i + k])
-template <bool TRANS, bool CMP>
-__device__ __forceinline__ void mgp2_block(const double* v, const double (&ba)[3], const double (&bb)[3], double (&out)[9]) {
+// BBAR (the point arithmetic of mf_point_p2<true, ...> on a unit column): eps carries the volumetric correction (detJ gbar_b[k] - bb[k]) / 3, the row
+// function collects - ba[i] tr(s) / 3 as well, and sbar[k] += detJ tr(s) / 3 is the element-constant part the caller multiplies with gbar_a after
+// the element's last point
+template <bool TRANS, bool CMP, bool BBAR = false>
+__device__ __forceinline__ void mgp2_block(const double* v, const double (&ba)[3], const double (&bb)[3], double (&out)[9], const double detJ = 0.0,
+                                           const double* gb = nullptr, double* sbar = nullptr) {
 #pragma unroll
    for (int k = 0; k < 3; k++) {
-      double eps[6]; b_row(k, bb, 0.0, eps);
+      double eps[6];
+      if constexpr (BBAR) b_row(k, bb, (detJ * gb[k] - bb[k]) * (1.0 / 3.0), eps);
+      else b_row(k, bb, 0.0, eps);
       double sg[6];
       if (CMP) d55_apply(v, v[25], eps, sg);   // (the compact record holds D or D^T as the context needs)
       else {
@@ -551,6 +557,41 @@ __device__ __forceinline__ void mgp2_block(const double* v, const double (&ba)[3
       out[k] += ba[0] * sg[0] + ba[1] * sg[5] + ba[2] * sg[4];
       out[3 + k] += ba[0] * sg[5] + ba[1] * sg[1] + ba[2] * sg[3];
       out[6 + k] += ba[0] * sg[4] + ba[1] * sg[3] + ba[2] * sg[2];
+      if constexpr (BBAR) {
+         const double tr3 = (sg[0] + sg[1] + sg[2]) * (1.0 / 3.0);
+         out[k] -= ba[0] * tr3; out[3 + k] -= ba[1] * tr3; out[6 + k] -= ba[2] * tr3;
+         sbar[k] += detJ * tr3;
+      }
+   }
+}
+// B-bar: average gradients of the eight trilinear functions embedded in Q2, gbarP = P^T gbar (weights 1, 1/2, 1/4, 1/8 on the 27 entries of eDS per
+// component), element-blocked like eDS: [block][B + 8 c][64 lanes], B = bx + 2 by + 4 bz
+__device__ __forceinline__ int64_t gp_off(int64_t e, int B, int c) { return ((e / PA_BLK) * 24 + B + 8 * c) * PA_BLK + (e % PA_BLK); }
+// one lane per element, loads and stores contiguous across the wave (like k_eds' output); fixed summation order
+__global__ __launch_bounds__(PA_BLK) void k_mg_p2_gbar(const int E, const double* __restrict__ eDS, double* __restrict__ gP) {
+   const int64_t e = (int64_t)blockIdx.x * PA_BLK + threadIdx.x;
+   if (e >= E) return;
+#pragma unroll
+   for (int c = 0; c < 3; c++) {
+      double g[27];
+#pragma unroll
+      for (int l = 0; l < 27; l++) g[l] = eDS[eds_off(e, P2N, p2::NAT[l], c)];
+#pragma unroll
+      for (int B = 0; B < 8; B++) {
+         const int ox = 2 * (B & 1) - 1, oy = 2 * ((B >> 1) & 1) - 1, oz = 2 * (B >> 2) - 1;   // the vertex sits at lexicographic index 1 + o per direction
+         double s = 0.0;
+#pragma unroll
+         for (int lk = 0; lk < 3; lk++)
+#pragma unroll
+            for (int lj = 0; lj < 3; lj++)
+#pragma unroll
+               for (int li = 0; li < 3; li++) {
+                  if (li == 1 - ox || lj == 1 - oy || lk == 1 - oz) continue;      // the far vertex of a direction: weight 0
+                  const double w = (li == 1 ? 0.5 : 1.0) * (lj == 1 ? 0.5 : 1.0) * (lk == 1 ? 0.5 : 1.0);
+                  s += w * g[li + 3 * lj + 9 * lk];
+               }
+         gP[gp_off(e, B, c)] = s;
+      }
    }
 }
 __device__ __forceinline__ void mgp2_scaled_grad(const double* adj, const double g0, const double g1, const double g2, double (&b)[3]) {
@@ -558,9 +599,13 @@ __device__ __forceinline__ void mgp2_scaled_grad(const double* adj, const double
    for (int t = 0; t < 3; t++) b[t] = g0 * adj[t] + g1 * adj[3 + t] + g2 * adj[6 + t];
 }
 
-template <bool TRANS, bool CMP>
+// BBAR: gP = the element's eight average gradients (k_mg_p2_gbar), W = the quadrature weights (detJ = W detJ / W[q], as in mf_point_p2).  The element-constant part
+// needs the sum over the element's 27 points first: 12 accumulators (element ex, column function bx, column component k) run along the point loop
+// and are folded into the stencil blocks with gbarP of the row function after it, in a fixed order
+template <bool TRANS, bool CMP, bool BBAR = false>
 __global__ __launch_bounds__(MGP2_BS) void k_mg_p2_level1(const int ne0, const int ne1, const int ne2, const int32_t* __restrict__ elem_at, const double* __restrict__ pa,
-                                                          const double* __restrict__ T1, const uint8_t* __restrict__ mask1, double* __restrict__ S) {
+                                                          const double* __restrict__ T1, const uint8_t* __restrict__ mask1, double* __restrict__ S,
+                                                          const double* __restrict__ gP = nullptr, const double* __restrict__ W = nullptr) {
    const int n0 = ne0 + 1, n1 = ne1 + 1, n2 = ne2 + 1;
    const int64_t nn = (int64_t)n0 * n1 * n2;
    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -582,9 +627,16 @@ __global__ __launch_bounds__(MGP2_BS) void k_mg_p2_level1(const int ne0, const i
       for (int ey = 0; ey < 2; ey++) {
          const int eJ = J + ey - 1, ay = 1 - ey, by = ay + dy;
          if (eJ < 0 || eJ >= ne1 || by < 0 || by > 1) continue;
+         [[maybe_unused]] double sbar[2][2][3];
+         if constexpr (BBAR) {
+#pragma unroll
+            for (int m = 0; m < 12; m++) sbar[m / 6][(m / 3) % 2][m % 3] = 0.0;
+         }
 #pragma unroll 1
          for (int q = 0; q < P2N; q++) {
             const int qi = q % 3, qj = (q / 3) % 3, qk = q / 9;
+            [[maybe_unused]] double iw = 0.0;
+            if constexpr (BBAR) iw = 1.0 / as_const(W)[q];
             // the two linear functions of a direction at its abscissa, value and derivative, through the Q2 tables (wave-uniform)
             const double lx[2] = { t1[6 * qi] + 0.5 * t1[6 * qi + 1], 0.5 * t1[6 * qi + 1] + t1[6 * qi + 2] };
             const double gx[2] = { t1[6 * qi + 3] + 0.5 * t1[6 * qi + 4], 0.5 * t1[6 * qi + 4] + t1[6 * qi + 5] };
@@ -606,7 +658,28 @@ __global__ __launch_bounds__(MGP2_BS) void k_mg_p2_level1(const int ne0, const i
 #pragma unroll
                for (int bx = 0; bx < 2; bx++) {
                   double bb[3]; mgp2_scaled_grad(adj, gx[bx] * lby * lbz, lx[bx] * gby * lbz, lx[bx] * lby * gbz, bb);
-                  mgp2_block<TRANS, CMP>(v, ba, bb, acc[bx - ax + 1]);
+                  if constexpr (BBAR) {
+                     const int B = bx + 2 * by + 4 * bz;
+                     const double gb[3] = { gP[gp_off(e, B, 0)], gP[gp_off(e, B, 1)], gP[gp_off(e, B, 2)] };
+                     mgp2_block<TRANS, CMP, true>(v, ba, bb, acc[bx - ax + 1], v[CMP ? 35 : 45] * iw, gb, sbar[ex][bx]);
+                  } else mgp2_block<TRANS, CMP>(v, ba, bb, acc[bx - ax + 1]);
+               }
+            }
+         }
+         if constexpr (BBAR) {   // + gbarP_a[i] sum_q detJ tr(s_q) / 3, per element (a skipped element left zeros and adds nothing)
+#pragma unroll
+            for (int ex = 0; ex < 2; ex++) {
+               const int eI = I + ex - 1, ax = 1 - ex;
+               if (eI < 0 || eI >= ne0) continue;
+               const int e = elem_at[eI + (int64_t)ne0 * (eJ + (int64_t)ne1 * eK)];
+               const int A = ax + 2 * ay + 4 * az;
+#pragma unroll
+               for (int i = 0; i < 3; i++) {
+                  const double ga = gP[gp_off(e, A, i)];
+#pragma unroll
+                  for (int bx = 0; bx < 2; bx++)
+#pragma unroll
+                     for (int k = 0; k < 3; k++) acc[bx - ax + 1][3 * i + k] += ga * sbar[ex][bx][k];
                }
             }
          }
@@ -633,9 +706,11 @@ __global__ __launch_bounds__(MGP2_BS) void k_mg_p2_level1(const int ne0, const i
 
 // this rank's part of the diagonal of the constrained p = 2 operator, diag(n, i) = sum_e sum_q b_n . Sm(Ct eps(b_n, i))[., i] with the Q2 gradient of fine
 // node n, zero on essential dofs: one thread per fine node, its (at most 8) elements and their 27 points in a fixed order
-template <bool TRANS, bool CMP>
+// BBAR: a = b is the fine node with its own entry of eDS; the element-constant part accumulates in the point loop the thread already runs
+template <bool TRANS, bool CMP, bool BBAR = false>
 __global__ __launch_bounds__(MGP2_BS) void k_mg_p2_diag(const int ne0, const int ne1, const int ne2, const int32_t* __restrict__ elem_at, const double* __restrict__ pa,
-                                                        const double* __restrict__ T1, const uint8_t* __restrict__ mask0, double* __restrict__ diag) {
+                                                        const double* __restrict__ T1, const uint8_t* __restrict__ mask0, double* __restrict__ diag,
+                                                        const double* __restrict__ eDS = nullptr, const double* __restrict__ W = nullptr) {
    const int n0 = 2 * ne0 + 1, n1 = 2 * ne1 + 1, n2 = 2 * ne2 + 1;
    const int64_t nn = (int64_t)n0 * n1 * n2;
    const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -659,6 +734,12 @@ __global__ __launch_bounds__(MGP2_BS) void k_mg_p2_diag(const int ne0, const int
             const int eI = (i & 1) ? i >> 1 : (i >> 1) - 1 + mx, li = (i & 1) ? 1 : 2 - 2 * mx;
             if (eI < 0 || eI >= ne0) continue;
             const int e = elem_at[eI + (int64_t)ne0 * (eJ + (int64_t)ne1 * eK)];
+            [[maybe_unused]] double ge[3], sbar[3];
+            if constexpr (BBAR) {
+               const int a = p2::NAT[li + 3 * lj + 9 * lk];
+#pragma unroll
+               for (int c = 0; c < 3; c++) { ge[c] = eDS[eds_off(e, P2N, a, c)]; sbar[c] = 0.0; }
+            }
 #pragma unroll 1
             for (int q = 0; q < P2N; q++) {
                const int qi = q % 3, qj = (q / 3) % 3, qk = q / 9;
@@ -666,7 +747,12 @@ __global__ __launch_bounds__(MGP2_BS) void k_mg_p2_diag(const int ne0, const int
                double v[2 * (CMP ? PAC_PAIRS_GEO : PA_PAIRS)];
                mgp2_load<TRANS, CMP>(pa, e, q, v);
                double b[3]; mgp2_scaled_grad(v + (CMP ? 26 : 36), dx * by * bz, bx * dy * bz, bx * by * dz, b);
-               mgp2_block<TRANS, CMP>(v, b, b, acc);
+               if constexpr (BBAR) mgp2_block<TRANS, CMP, true>(v, b, b, acc, v[CMP ? 35 : 45] / W[q], ge, sbar);
+               else mgp2_block<TRANS, CMP>(v, b, b, acc);
+            }
+            if constexpr (BBAR) {
+#pragma unroll
+               for (int c = 0; c < 3; c++) acc[4 * c] += ge[c] * sbar[c];      // (only the diagonal of the 3 x 3 block is kept)
             }
          }
       }
@@ -814,11 +900,37 @@ int exa_launch_mg_p2_build(exa_ctx* ctx, const int* ne, const int32_t* elem_at, 
    const bool cmp = exa_has_compact_geo(ctx);
    const double* rec = cmp ? ctx->pa_c : ctx->pa;
    const int64_t nn1 = (int64_t)(ne[0] + 1) * (ne[1] + 1) * (ne[2] + 1), nn0 = (int64_t)(2 * ne[0] + 1) * (2 * ne[1] + 1) * (2 * ne[2] + 1);
+   if (ctx->cfg.integ == EXA_INTEG_BBAR) {   // the B-bar forms read the element-average gradients the action reads (the caller has refreshed them)
+      if (!ctx->eDS) { ctx->err = "exa_grad_mg_p2_build: no element-average gradients yet (exa_grad_setup or the driver's refresh writes them)"; return EXA_ERR_STATE; }
+      if (S && !ctx->eDSP) EXA_HIP_CHECK(ctx, hipMalloc(&ctx->eDSP, sizeof(double) * 24 * PA_BLK * (size_t)exa_nblocks(ctx)));
+      if (S) hipLaunchKernelGGL(k_mg_p2_gbar, dim3(exa_nblocks(ctx)), dim3(PA_BLK), 0, s, ctx->E, ctx->eDS, ctx->eDSP);
+      exa_dispatch([&](auto t, auto cm) {
+         if (S) hipLaunchKernelGGL((k_mg_p2_level1<t.value, cm.value, true>), dim3(nblk(9 * nn1, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask1, S,
+                                   ctx->eDSP, ctx->W_dev);
+         if (diag) hipLaunchKernelGGL((k_mg_p2_diag<t.value, cm.value, true>), dim3(nblk(nn0, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask0, diag,
+                                      ctx->eDS, ctx->W_dev);
+      }, trans, cmp);
+      return exa_launched(ctx);
+   }
    exa_dispatch([&](auto t, auto cm) {
-      if (S) hipLaunchKernelGGL((k_mg_p2_level1<t.value, cm.value>), dim3(nblk(9 * nn1, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask1, S);
-      if (diag) hipLaunchKernelGGL((k_mg_p2_diag<t.value, cm.value>), dim3(nblk(nn0, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask0, diag);
+      if (S) hipLaunchKernelGGL((k_mg_p2_level1<t.value, cm.value>), dim3(nblk(9 * nn1, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask1, S, nullptr, nullptr);
+      if (diag) hipLaunchKernelGGL((k_mg_p2_diag<t.value, cm.value>), dim3(nblk(nn0, MGP2_BS)), dim3(MGP2_BS), 0, s, ne[0], ne[1], ne[2], elem_at, rec, ctx->T1_dev, mask0, diag, nullptr, nullptr);
    }, trans, cmp);
    return exa_launched(ctx);
+}
+// ... and of the B-bar forms in the same order, then of the pre-pass that writes the eight average gradients per element
+extern "C" int exa_mg_p2_bbar_scratch_bytes(int* out9) {
+   const void* f[9] = { reinterpret_cast<const void*>(k_mg_p2_level1<false, false, true>), reinterpret_cast<const void*>(k_mg_p2_level1<true, false, true>),
+                        reinterpret_cast<const void*>(k_mg_p2_level1<false, true, true>),  reinterpret_cast<const void*>(k_mg_p2_level1<true, true, true>),
+                        reinterpret_cast<const void*>(k_mg_p2_diag<false, false, true>),   reinterpret_cast<const void*>(k_mg_p2_diag<true, false, true>),
+                        reinterpret_cast<const void*>(k_mg_p2_diag<false, true, true>),    reinterpret_cast<const void*>(k_mg_p2_diag<true, true, true>),
+                        reinterpret_cast<const void*>(k_mg_p2_gbar) };
+   for (int k = 0; k < 9; k++) {
+      hipFuncAttributes a;
+      if (hipFuncGetAttributes(&a, f[k]) != hipSuccess) { (void)hipGetLastError(); return -1; }
+      out9[k] = (int)a.localSizeBytes;
+   }
+   return 0;
 }
 // private-memory bytes per lane of the eight instantiations (level 1, diagonal) x (plain, transposed) x (46-double, compact records) in the loaded code object
 extern "C" int exa_mg_p2_scratch_bytes(int* out8) {

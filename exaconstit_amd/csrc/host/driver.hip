@@ -234,6 +234,8 @@ void NonlinearMechOperator::GetGradient() {
       // (B-bar, p = 2: the element-average gradients the action reads; the residual refreshes them as well, but GetUpdateBCsAction applies the gradient first)
       if (!routes_.fast_p1) abi_check(ctx_, exa_grad_refresh_bbar(ctx_, el_jac.p, stream_), "exa_grad_refresh_bbar");
       vk_jacobi_setup(nd_, ess_mask.p, diag.p, 1, dinv.p, stream_);
+      // (B-bar multigrid at p = 2: the records build reads eDS next to the records - refreshed two lines up, on the same stream, for the state the
+      //  records belong to; the probes go through the action, which reads the same eDS.  The tangent-field routes below refresh it in exa_grad_setup)
       if (precond == Precond::MULTIGRID) mg->Build();
       return;
    }
@@ -585,12 +587,14 @@ void SystemDriver::SetPreconditioner(int kind, int levels, int degree) {
    if (kind < 0 || kind > 2) throw std::runtime_error("preconditioner kind must be 0 (identity), 1 (jacobi) or 2 (multigrid)");
    NonlinearMechOperator& op = *oper_;
    if (kind == 2) {
+      const bool bbar = ExaOptions::lower(opt_.integ_model) == "bbar";
+      if (bbar && opt_.mg_bbar && part.periodic) throw std::runtime_error(ExaOptions::mg_bbar_no_periodic());   // (with or without mg_periodic)
       if (part.periodic && !opt_.mg_periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
-      if (ExaOptions::lower(opt_.integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
+      if (bbar && !opt_.mg_bbar) throw std::runtime_error(ExaOptions::mg_no_bbar());
       // p = 2 is opt-in (Solvers.Krylov.mg_p2); what stays refused with it says why, everything else keeps the constructor's message
       if (opt_.mg_p2 && !part.from_file && part.geom == 0 && part.p > 2) throw std::runtime_error(ExaOptions::mg_p2_no_higher_order());
       if (opt_.mg_p2 && part.p == 2 && part.periodic) throw std::runtime_error(ExaOptions::mg_p2_no_periodic());
-      op.mg_p2_allowed = opt_.mg_p2;
+      op.mg_p2_allowed = opt_.mg_p2; op.mg_bbar_allowed = opt_.mg_bbar;
       op.mg.reset(new Multigrid(op, levels, degree));   // throws where no hierarchy can be built
    } else op.mg.reset();
    krylov_->DropGraph();
@@ -620,6 +624,7 @@ void SystemDriver::SetPeriodic(const double* L9, const uint8_t* free9) {
    for (int k = 0; k < 9; k++) if (!std::isfinite(L9[k])) throw std::runtime_error("set_periodic: the velocity gradient must be finite");
    if (part.from_file || part.geom != 0) throw std::runtime_error(ExaOptions::periodic_needs_generated_mesh());
    if (oper_->precond == Precond::MULTIGRID && part.p == 2) throw std::runtime_error(ExaOptions::mg_p2_no_periodic());   // (with or without mg_periodic)
+   if (oper_->precond == Precond::MULTIGRID && ExaOptions::lower(opt_.integ_model) == "bbar") throw std::runtime_error(ExaOptions::mg_bbar_no_periodic());
    if (oper_->precond == Precond::MULTIGRID && !opt_.mg_periodic) throw std::runtime_error(ExaOptions::periodic_no_multigrid());
    uint8_t f[9];
    const bool any = free_mask_bits(free9, f) != 0;

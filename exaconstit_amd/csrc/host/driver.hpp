@@ -141,6 +141,7 @@ class NonlinearMechOperator {
    std::unique_ptr<Multigrid> mg;   // precond == MULTIGRID: rebuilt after every gradient set-up
    // multigrid at p = 2 (host/multigrid.hpp; SystemDriver::SetPreconditioner writes the first, exa_driver_set_mg_p2_build the second)
    bool mg_p2_allowed = false;      // Solvers.Krylov.mg_p2: Multigrid's constructor accepts a p = 2 partition
+   bool mg_bbar_allowed = false;    // Solvers.Krylov.mg_bbar: Multigrid's constructor accepts a B-bar operator (written by SetPreconditioner too)
    int mg_p2_build = 1;             // 1: level 1 and the fine diagonal from the point records where they can serve; 0: always probed
    // The p = 2 matrix-free action reads point records this Newton iteration's set-up left, in the form the run streams: the compact records of the
    // constitutive launch (record route), or the 46-double records of exa_grad_setup when the compact form is switched off (EXA_TANGENT_FORM=full).
@@ -217,6 +218,8 @@ class SystemDriver {
    void AllowPeriodicMultigrid(bool on) { opt_.mg_periodic = on; }
    // ... and so is multigrid at p_refinement = 2 (Solvers.Krylov.mg_p2; DESIGN 4.6, "p = 2"): without it SetPreconditioner refuses the order as it always did
    void AllowP2Multigrid(bool on) { opt_.mg_p2 = on; }
+   // ... and multigrid under integ_model = "BBAR" (Solvers.Krylov.mg_bbar; DESIGN 4.6, "B-bar"); the key permits, a FULL run does not read it
+   void AllowBbarMultigrid(bool on) { opt_.mg_bbar = on; }
    // periodic boundary conditions under the macroscopic velocity gradient L9 (row by row) on a freshly created driver before its first step,
    // like SetPreconditioner: rebuilds the partition tables, weights, essential set and halo lists (every rank calls it).  Refuses file meshes
    // and, without AllowPeriodicMultigrid, the multigrid preconditioner with the messages of the options reader; a hierarchy that exists is made again.  The boundary-condition schedule becomes one entry: L from step 1.

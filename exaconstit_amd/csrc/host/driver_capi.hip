@@ -473,6 +473,8 @@ int exa_driver_set_mg_periodic(exa_driver* d, int on) { d->sd->AllowPeriodicMult
 
 // multigrid at p_refinement = 2 is opt-in too (Solvers.Krylov.mg_p2): on != 0 before exa_driver_set_preconditioner(2)
 int exa_driver_set_mg_p2(exa_driver* d, int on) { d->sd->AllowP2Multigrid(on != 0); return 0; }
+// ... and so is multigrid under integ_model = "BBAR" (Solvers.Krylov.mg_bbar)
+int exa_driver_set_mg_bbar(exa_driver* d, int on) { d->sd->AllowBbarMultigrid(on != 0); return 0; }
 // p = 2 hierarchy, from the next set-up on: 1 level 1 and the fine diagonal from the point records where they can serve, 0 always probed
 int exa_driver_set_mg_p2_build(exa_driver* d, int from_records) { d->sd->oper().mg_p2_build = from_records != 0 ? 1 : 0; return 0; }
 
@@ -517,6 +519,11 @@ int exa_driver_mg_info_order(exa_driver* d, int* out) {
       for (int l = 0; l <= mg.levels(); l++) out[2 + l] = mg.order(l);
       return 0;
    } catch (const std::exception& e) { std::fprintf(stderr, "exa_driver_mg_info_order: %s\n", e.what()); return -1; }
+}
+
+// 1 where the hierarchy stands on the B-bar operator (Solvers.Krylov.mg_bbar), 0 otherwise, -1 without a multigrid preconditioner
+int exa_driver_mg_bbar(exa_driver* d) {
+   try { return mg_of(d).bbar() ? 1 : 0; } catch (const std::exception&) { return -1; }
 }
 
 // gradient set-up of the current state (what the next Newton iteration would do first) and the hierarchy build that follows it
@@ -941,6 +948,9 @@ int exa_options_query_solver(const char* toml_path, int* out3, char* err, int er
 int exa_mg_level_count(const int* N, int nranks, int cap) { return (nranks < 1 || N[0] < 1 || N[1] < 1 || N[2] < 1) ? -1 : mg_level_count(N, nranks, cap); }
 int exa_mg_level_count_order(const int* N, int nranks, int cap, int order) {
    return (nranks < 1 || N[0] < 1 || N[1] < 1 || N[2] < 1 || order < 1 || order > 2) ? -1 : mg_level_count_order(N, nranks, cap, order);
+}
+int exa_options_query_mg_bbar(const char* toml_path, int* out1, char* err, int errlen) {
+   try { ExaOptions o; o.parse_options(toml_path); out1[0] = o.mg_bbar ? 1 : 0; return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }
 }
 int exa_options_query_mg_p2(const char* toml_path, int* out1, char* err, int errlen) {
    try { ExaOptions o; o.parse_options(toml_path); out1[0] = o.mg_p2 ? 1 : 0; return 0; } catch (const std::exception& e) { set_err(err, errlen, e.what()); return -1; }

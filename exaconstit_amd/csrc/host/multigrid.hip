@@ -14,6 +14,10 @@ Multigrid::Multigrid(NonlinearMechOperator& op, int levels_cap, int degree) : op
    if (part.from_file || part.geom != 0 || !(part.p == 1 || (part.p == 2 && op.mg_p2_allowed)))
       throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\") at p_refinement = 1");
    if (part.p == 2 && part.periodic) throw std::runtime_error(ExaOptions::mg_p2_no_periodic());
+   // (B-bar: opt-in as well, Solvers.Krylov.mg_bbar; the hierarchy itself is built the same way - DESIGN 4.6, "B-bar")
+   bbar_ = op.cfg_used.integ == EXA_INTEG_BBAR;
+   if (bbar_ && !op.mg_bbar_allowed) throw std::runtime_error(ExaOptions::mg_no_bbar());
+   if (bbar_ && part.periodic) throw std::runtime_error(ExaOptions::mg_bbar_no_periodic());
    p_ = part.p;
    if (degree < 1 || degree > 8) throw std::runtime_error("Solvers.Krylov.mg_smoother_degree must lie in 1 ... 8");
    if (levels_cap < 0) throw std::runtime_error("Solvers.Krylov.mg_levels must be >= 0 (0: as many as the mesh allows)");

@@ -115,6 +115,7 @@ class Multigrid {
    double vcycle_ms();
    const double* stencil(int l) const { return lv_[l].S.p; }
    int order(int l) const { return l == 0 ? p_ : 1; }       // polynomial order of level l
+   bool bbar() const { return bbar_; }                      // the fine operator is the B-bar one (Solvers.Krylov.mg_bbar)
    int level1_build() const { return level1_build_; }       // p = 2, last Build: 1 level 1 and the fine diagonal from the point records, 0 probed; -1 at p = 1 / before
  private:
    bool BuildFromRecords();                                 // p = 2: false (nothing written) where the records cannot serve, see Build
@@ -138,6 +139,7 @@ class Multigrid {
    DevBuf<uint8_t> mask0_;                                  // mixed loading: essential set + the free control slots
    DevBuf<int32_t> ctrl_slot_; DevBuf<double> ctrl_dinv_; int ctrl_local_ = 0, control_dofs_ = 0;   // this rank's free control slots and 1 / d
    int64_t ctrl_at_[8] = {}; double ctrl_d_[8] = {};
+   bool bbar_ = false;
    int p_ = 1, level1_build_ = -1;                          // order of level 0 (1 or 2)
    DevBuf<int32_t> elem_at_, closed_flag_;                  // p = 2: local element at every position of the element box; result of the mask check
    int ng_[3] = { 0, 0, 0 };                                // global elements per direction at level 0

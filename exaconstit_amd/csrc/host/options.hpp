@@ -114,6 +114,9 @@ struct ExaOptions {
    static const char* mg_p2_no_higher_order() { return "Solvers.Krylov.preconditioner = \"multigrid\": mg_p2 = true serves p_refinement = 2; p_refinement >= 3 has no hierarchy (its nodes are not a uniform grid)"; }
    static const char* gmres_kdim_range() { return "Solvers.Krylov.gmres_kdim must be a whole number in 1 ... 100 (the Krylov dimension of GMRES; MFEM's default is 50)"; }
    static const char* mg_p2_no_periodic() { return "Solvers.Krylov.preconditioner = \"multigrid\" at p_refinement = 2 is not built for BCs.periodic = true (the fine diagonal probe and the fused periodic kernels need p_refinement = 1), with or without mg_periodic"; }
+   // B-bar under multigrid is opt-in (Solvers.Krylov.mg_bbar; DESIGN 4.6, "B-bar"): the refusal without the key, and what stays refused with it
+   static const char* mg_no_bbar() { return "Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\""; }
+   static const char* mg_bbar_no_periodic() { return "Solvers.Krylov.preconditioner = \"multigrid\" with mg_bbar = true is not built for BCs.periodic = true (the fused periodic kernels and the control block of mixed loading were never run on the B-bar operator), with or without mg_periodic"; }
    static const char* periodic_no_multigrid() { return "BCs.periodic = true runs under Solvers.Krylov.preconditioner = \"multigrid\" only where it is asked for: Solvers.Krylov.mg_periodic = true (Driver.set_preconditioner(\"multigrid\", periodic=True)); without it the combination is refused as before"; }
    static const char* periodic_needs_generated_mesh() { return "BCs.periodic = true needs a generated hexahedral mesh (Mesh.type = \"auto\"): file and tetrahedral meshes need node matching"; }
    XtalType xtal = XtalType::FCC; SlipType slip = SlipType::POWERVOCE;
@@ -188,6 +191,7 @@ struct ExaOptions {
    // decides), 1 "jacobi", 2 "multigrid" (host/multigrid.hpp) with mg_levels coarse levels at most (0: as many as the mesh allows) and a
    // Chebyshev smoother of degree mg_smoother_degree (1 ... 8)
    int precond = 0, mg_levels = 0, mg_degree = 2;
+   bool mg_bbar = false;       // Solvers.Krylov.mg_bbar: multigrid under integ_model = "BBAR" ("B-bar"); refused without it, as before; nothing on a FULL run
    bool mg_p2 = false;         // Solvers.Krylov.mg_p2: multigrid at p_refinement = 2 ("p = 2"); refused without it, as before the hierarchy served p = 2
    bool mg_periodic = false;   // Solvers.Krylov.mg_periodic: multigrid on a periodic cell ("periodic cells"); refused without it, as before the hierarchy served periodic cells
    int ref_ser = 0, order = 1; int ncuts[3] = { 1, 1, 1 }; double length[3] = { 1, 1, 1 }; std::string mesh_type = "auto", mesh_file;
@@ -503,10 +507,15 @@ struct ExaOptions {
                if (m2->kind != TomlValue::BOOL) throw std::runtime_error("Solvers.Krylov.mg_p2 must be true or false");
                mg_p2 = m2->b;
             }
+            if (const TomlValue* mb = d.get("Solvers.Krylov.mg_bbar")) {
+               if (mb->kind != TomlValue::BOOL) throw std::runtime_error("Solvers.Krylov.mg_bbar must be true or false");
+               mg_bbar = mb->b;
+            }
             if (order != 1 && !mg_p2) throw std::runtime_error(mg_order_refusal());
             if (order > 2) throw std::runtime_error(mg_p2_no_higher_order());
             if (order == 2 && periodic) throw std::runtime_error(mg_p2_no_periodic());
-            if (lower(integ_model) == "bbar") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" is not built for integ_model = \"BBAR\"");
+            if (lower(integ_model) == "bbar" && !mg_bbar) throw std::runtime_error(mg_no_bbar());
+            if (lower(integ_model) == "bbar" && periodic) throw std::runtime_error(mg_bbar_no_periodic());
             if (mesh_type != "auto") throw std::runtime_error("Solvers.Krylov.preconditioner = \"multigrid\" needs a generated mesh (Mesh.type = \"auto\"): file meshes need algebraic coarsening");
             if (const TomlValue* mp = d.get("Solvers.Krylov.mg_periodic")) {
                if (mp->kind != TomlValue::BOOL) throw std::runtime_error("Solvers.Krylov.mg_periodic must be true or false");

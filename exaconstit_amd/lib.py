@@ -547,6 +547,10 @@ exa_periodic_sum_scratch_bytes = _sig("exa_periodic_sum_scratch_bytes", C.c_int)
 exa_driver_set_mg_periodic = _sig("exa_driver_set_mg_periodic", C.c_int, C.c_void_p, C.c_int)
 exa_mg_periodic_scratch_bytes = _sig("exa_mg_periodic_scratch_bytes", C.c_int, C.POINTER(C.c_int))
 exa_driver_set_mg_p2 = _sig("exa_driver_set_mg_p2", C.c_int, C.c_void_p, C.c_int)
+exa_driver_set_mg_bbar = _sig("exa_driver_set_mg_bbar", C.c_int, C.c_void_p, C.c_int)
+exa_driver_mg_bbar = _sig("exa_driver_mg_bbar", C.c_int, C.c_void_p)
+exa_options_query_mg_bbar = _sig("exa_options_query_mg_bbar", C.c_int, C.c_char_p, C.POINTER(C.c_int), C.c_char_p, C.c_int)
+exa_mg_p2_bbar_scratch_bytes = _sig("exa_mg_p2_bbar_scratch_bytes", C.c_int, C.POINTER(C.c_int))
 exa_driver_set_mg_p2_build = _sig("exa_driver_set_mg_p2_build", C.c_int, C.c_void_p, C.c_int)
 exa_driver_mg_info_order = _sig("exa_driver_mg_info_order", C.c_int, C.c_void_p, C.POINTER(C.c_int))
 exa_mg_level_count_order = _sig("exa_mg_level_count_order", C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int)
@@ -800,6 +804,25 @@ def options_mg_p2(path):
     if exa_options_query_mg_p2(path.encode(), out, err, 512) != 0:
         raise RuntimeError(err.value.decode())
     return bool(out[0])
+
+
+def options_mg_bbar(path):
+    """[Solvers.Krylov] mg_bbar of an options file (read next to preconditioner = "multigrid"): True / False"""
+    out = (C.c_int * 1)()
+    err = C.create_string_buffer(512)
+    if exa_options_query_mg_bbar(path.encode(), out, err, 512) != 0:
+        raise RuntimeError(err.value.decode())
+    return bool(out[0])
+
+
+def mg_p2_bbar_scratch_bytes():
+    """private (scratch) bytes per lane of the B-bar forms of the kernels behind exa_grad_mg_p2_build and of their per-element pre-pass in the
+    loaded code object: dict of nine (all must be 0)"""
+    o = (C.c_int * 9)()
+    if exa_mg_p2_bbar_scratch_bytes(o) != 0:
+        raise RuntimeError("exa_mg_p2_bbar_scratch_bytes: no device")
+    names = [f"{k}_{f}{t}_bbar" for k in ("level1", "diag") for f in ("full", "compact") for t in ("", "_trans")] + ["gbar_prepass"]
+    return dict(zip(names, [int(v) for v in o]))
 
 
 def mg_p2_scratch_bytes():
@@ -1279,15 +1302,19 @@ class Driver:
         return dict(pcg_ms=o[0], iters=int(o[1]), apply_ms=o[2])
 
     # ---- preconditioner (exa_driver_set_preconditioner) and the multigrid test hooks ---------------------------------------
-    def set_preconditioner(self, kind, levels=0, degree=2, periodic=False, p2=False):
+    def set_preconditioner(self, kind, levels=0, degree=2, periodic=False, p2=False, bbar=False):
         """kind: "identity", "jacobi" or "multigrid" (or 0 / 1 / 2); levels: max coarse levels (0 = as many as the mesh allows); degree: Chebyshev degree;
         periodic=True: multigrid may meet set_periodic, before or after this call (opt-in, like Solvers.Krylov.mg_periodic; refused without it);
-        p2=True: multigrid on a generated p = 2 mesh (opt-in, like Solvers.Krylov.mg_p2; refused without it)"""
+        p2=True: multigrid on a generated p = 2 mesh (opt-in, like Solvers.Krylov.mg_p2; refused without it);
+        bbar=True: multigrid under the B-bar integrator, at p = 1 and - with p2=True - at p = 2 (opt-in, like Solvers.Krylov.mg_bbar; refused
+        without it; it permits and does not require: nothing changes on a FULL driver)"""
         k = PRECOND_KINDS[kind] if isinstance(kind, str) else int(kind)
         if periodic:
             exa_driver_set_mg_periodic(self.h, 1)
         if p2:
             exa_driver_set_mg_p2(self.h, 1)
+        if bbar:
+            exa_driver_set_mg_bbar(self.h, 1)
         self._chk(exa_driver_set_preconditioner(self.h, k, int(levels), int(degree), self._err, 512))
 
     def set_periodic(self, vel_grad, free=None):
@@ -1436,7 +1463,8 @@ class Driver:
 
     def mg_info(self):
         """dict(levels, setup_ms, vcycle_ms, degree, boxes (L+1, 3) local elements per direction, lmax (L+1,), periodic, control_dofs: free
-        control entries of mixed loading the preconditioner scales by their diagonal)"""
+        control entries of mixed loading the preconditioner scales by their diagonal, order (L+1,), level1_build "records" / "probe" / None,
+        bbar: the fine operator is the B-bar one)"""
         import numpy as np
         out = np.zeros(6 + 4 * 32)
         if exa_driver_mg_info(self.h, out.ctypes.data_as(_dp)) != 0:
@@ -1448,7 +1476,7 @@ class Driver:
             raise RuntimeError("exa_driver_mg_info_order failed (no multigrid preconditioner)")
         return dict(levels=L, setup_ms=float(out[1]), vcycle_ms=float(out[2]), degree=int(out[3]), boxes=per[:, :3].astype(int), lmax=per[:, 3].copy(),
                     periodic=bool(out[4 + 4 * (L + 1)]), control_dofs=int(out[5 + 4 * (L + 1)]), order=[int(oi[2 + l]) for l in range(L + 1)],
-                    level1_build={1: "records", 0: "probe"}.get(int(oi[1])))
+                    level1_build={1: "records", 0: "probe"}.get(int(oi[1])), bbar=exa_driver_mg_bbar(self.h) == 1)
 
     def set_mg_p2_build(self, from_records=True):
         """p = 2 hierarchy, from the next set-up on: level 1 and the fine diagonal from the point records where they can serve (default), or

@@ -112,7 +112,7 @@ int exa_checkpoint_info(const char* path, int64_t* out20, double* outd3, uint64_
 void exa_driver_destroy(exa_driver* d);
 /* Preconditioner of the PCG (Solvers.Krylov.preconditioner in an options file; this call overrides it), valid before the first step (so
  * synthetic and exa_driver_bench_prepare'd drivers can use it): kind 0 identity, 1 Jacobi, 2 geometric multigrid V-cycle (generated p = 1
- * meshes, p = 2 after exa_driver_set_mg_p2, not B-bar) with at most `levels` coarse levels (0: as many as the mesh allows) and a Chebyshev smoother of `degree` (1 ... 8).
+ * meshes, p = 2 after exa_driver_set_mg_p2, B-bar after exa_driver_set_mg_bbar) with at most `levels` coarse levels (0: as many as the mesh allows) and a Chebyshev smoother of `degree` (1 ... 8).
  * Refused (-1, err) where no coarse level can be built for the decomposition. */
 int exa_driver_set_preconditioner(exa_driver* d, int kind, int levels, int degree, char* err, int errlen);
 /* out (>= 6 + 4 (L + 1) doubles) = { coarse levels L, ms of the last hierarchy set-up, ms of the last V-cycle, smoother degree, then per level
@@ -126,6 +126,11 @@ int exa_driver_set_mg_periodic(exa_driver* d, int on);
  * p = 2 mesh legal (level 1 = the trilinear space on the element vertices); without it the call refuses p = 2 as before.  B-bar, file and
  * tetrahedral meshes, p >= 3 and periodic cells at p = 2 stay refused.  Returns 0. */
 int exa_driver_set_mg_p2(exa_driver* d, int on);
+/* Multigrid under integ_model = "BBAR" is opt-in ([Solvers.Krylov] mg_bbar = true): on != 0 before exa_driver_set_preconditioner(2) makes a B-bar
+ * run on a generated mesh legal at p = 1, and at p = 2 together with exa_driver_set_mg_p2; without it the call refuses B-bar as before.  The key
+ * permits, it does not require: a FULL run is not changed by it.  Periodic cells stay refused under B-bar multigrid (either call order, with or
+ * without exa_driver_set_mg_periodic), and so does everything multigrid refuses without B-bar.  Returns 0. */
+int exa_driver_set_mg_bbar(exa_driver* d, int on);
 /* How the p = 2 hierarchy builds level 1 and the fine diagonal from the next set-up on: 1 (default) from the point records in one pass each
  * (exa_grad_mg_p2_build) where the action runs from records and the essential set is closed under the interpolation, by probing otherwise;
  * 0 always by probing (what the tests compare the records build against).  Returns 0. */
@@ -133,6 +138,8 @@ int exa_driver_set_mg_p2_build(exa_driver* d, int from_records);
 /* out (>= 2 + L + 1 ints) = { coarse levels L, level-1 build of the last set-up (0 probe, 1 records; -1 before the first set-up or at p = 1),
  * then the polynomial order of every level l = 0 ... L }.  Returns 0 or -1 (no multigrid preconditioner). */
 int exa_driver_mg_info_order(exa_driver* d, int* out);
+/* 1 where the hierarchy stands on the B-bar operator (exa_driver_set_mg_bbar), 0 otherwise; -1 (no multigrid preconditioner) */
+int exa_driver_mg_bbar(exa_driver* d);
 /* Test hooks on the hierarchy of the last gradient set-up; host arrays of exa_driver_mg_level_dofs(level) doubles (node-major per component,
  * node = i + n0 (j + n1 k) of the rank's local box at that level).  Level 0 is the constrained operator the PCG applies. */
 int64_t exa_driver_mg_level_dofs(exa_driver* d, int level);
@@ -343,6 +350,8 @@ int exa_mg_level_count(const int* N, int nranks, int cap);
 int exa_mg_level_count_order(const int* N, int nranks, int cap, int order);
 /* [Solvers.Krylov] mg_p2 of an options file (0 / 1; read next to preconditioner = "multigrid" only); returns 0 or -1 (err) */
 int exa_options_query_mg_p2(const char* toml_path, int* out1, char* err, int errlen);
+/* [Solvers.Krylov] mg_bbar of an options file, likewise */
+int exa_options_query_mg_bbar(const char* toml_path, int* out1, char* err, int errlen);
 /* Visualizations table (reference src/option_parser.cpp:540-570): paraview (default 0), steps (1), light_up (0), floc ("results/exaconstit",
  * relative to the driver's output directory); returns 0 or -1 (err) */
 int exa_options_query_vis(const char* toml_path, int* paraview, int* steps, int* light_up, char* floc, int floclen, char* err, int errlen);

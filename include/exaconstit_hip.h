@@ -291,13 +291,18 @@ int exa_tangent_scratch_bytes(int* out8);
  *   S_dev        (nullable) 243 doubles per vertex, [(o * 9 + 3 r + c) * NV + vertex], o = (dx+1) + 3 (dy+1) + 9 (dz+1), NV = prod (ne + 1); rows
  *                and columns of the dofs marked in mask1_dev (3 NV bytes) are zero
  *   diag_dev     (nullable) 3 nnodes doubles, zero on the dofs marked in mask0_dev (3 nnodes bytes)
- * EXA_ERR_UNSUPPORTED, nothing written, where the L-vector action does not run from such records (B-bar, deterministic mode, assembled element
+ * B-bar contexts: the same two products of the B-bar operator, with the element-average gradients the action reads (those of the
+ * last exa_grad_setup, or of the driver's refresh on the record route; EXA_ERR_STATE where there are none yet)
+ * (a small per-element pre-pass contracts them onto the eight embedded trilinear functions first).
+ * EXA_ERR_UNSUPPORTED, nothing written, where the L-vector action does not run from such records (deterministic mode, assembled element
  * matrices, other orders, tetrahedra). */
 int exa_grad_mg_p2_build(exa_ctx* ctx, const int* ne, const int32_t* elem_at_dev, const uint8_t* mask0_dev, const uint8_t* mask1_dev, double* S_dev,
                          double* diag_dev, exa_stream s);
 /* private (scratch) bytes per lane of its kernels in the loaded code object: out8 = { vertex stencil: 46-double records plain, transposed, compact
  * records plain, transposed; diagonal: the same four }; 0, or -1 without a device */
 int exa_mg_p2_scratch_bytes(int* out8);
+/* ... and of the B-bar forms of the same kernels, in the same order, then of the pre-pass: out9; 0, or -1 without a device */
+int exa_mg_p2_bbar_scratch_bytes(int* out9);
 /* Optional (p = 1 partial assembly, L-vector action): the nodal coordinates (nnodes,3 byNODES) the Jacobians given to exa_grad_setup
  * were computed from.  When set, exa_grad_apply_lvec recomputes adj(J) from them instead of streaming it from its per-point record
  * (36 instead of 46 doubles per point from HBM); the array must stay unchanged until the next exa_grad_setup.  NULL switches it off. */
