@@ -1,6 +1,12 @@
 """Per-element output fields on the GPU: exa_element_fields against a numpy restatement of its column table (include/exaconstit_hip.h), in both
 quadrature layouts, and the driver's ParaView output (Visualizations.paraview) built on it - cadence, bits of the files, agreement with the
-volume averages, several ranks, the executable."""
+volume averages, several ranks, the executable.
+
+Every launch form of the kernel is compared with the reference of tests/fieldref.py on data that can fail: the four p = 1 and the p = 2
+hexahedron forms in test_kernel_against_numpy, the run-time-order branch at p = 3 ... 6 (Gauss-Lobatto nodes differ from equispaced ones
+there) and the tetrahedron form at p = 1 and 2, straight-sided and curved, in the cases below it; the driver-level cases tie the fields
+of tetrahedral and p = 3 runs to the volume averages.  Bound: 1e-13 of a column's scale, 1e-12 for the elastic-strain columns
+(fieldref.gpu_bounds).  The new cases print what they measured; EXA_WRITE_RECORDS=1 keeps the lines in profiles/element_field_checks.txt."""
 import ctypes as C
 import os
 import shutil
@@ -11,6 +17,9 @@ import xml.etree.ElementTree as ET
 import numpy as np
 import pytest
 
+import fieldref as F
+import hipref
+from fieldref import element_fields_numpy
 from test_field_output_host import arrays, decode
 
 pytestmark = pytest.mark.gpu
@@ -60,32 +69,6 @@ def _from_layout(v, layout, E, Q, W):
         return v.reshape(E, Q, W)
     nb = (E + 63) // 64
     return v.reshape(nb, Q, W, 64).transpose(0, 3, 1, 2).reshape(nb * 64, Q, W)[:E]
-
-
-def element_fields_numpy(J, S, SV, W, xq):
-    """J (E,Q,9) column-major dx_i/dxi_j, S (E,Q,6), SV (E,Q,28), W (Q), xq (E,Q,3) -> (E,37)"""
-    Jm = J.reshape(J.shape[0], J.shape[1], 3, 3).transpose(0, 1, 3, 2)    # [.., i, j]
-    w = W[None, :] * np.linalg.det(Jm)
-    vol = w.sum(1)
-    avg = lambda f: np.einsum("eq,eqk->ek", w, f) / vol[:, None]      # noqa: E731
-    s = avg(S)
-    sv = avg(SV)
-    out = np.zeros((J.shape[0], 37))
-    out[:, 0] = vol
-    out[:, 1:4] = avg(xq)
-    out[:, 4:10] = s
-    out[:, 10] = np.sqrt(0.5 * ((s[:, 0] - s[:, 1]) ** 2 + (s[:, 1] - s[:, 2]) ** 2 + (s[:, 2] - s[:, 0]) ** 2 + 6 * (s[:, 3:6] ** 2).sum(1)))
-    out[:, 11] = s[:, :3].sum(1) / 3
-    out[:, 12] = sv[:, 0]
-    out[:, 13] = sv[:, 1]
-    out[:, 14] = sv[:, 13]
-    out[:, 15:27] = sv[:, 14:26]
-    qt = sv[:, 9:13]
-    out[:, 27:31] = qt / np.linalg.norm(qt, axis=1)[:, None]
-    e = sv[:, 4:9]
-    t1, t2, v = e[:, 0] / np.sqrt(2), e[:, 1] / np.sqrt(6), np.log(sv[:, 26])
-    out[:, 31:37] = np.stack([t1 - t2 + v, -t1 - t2 + v, np.sqrt(2.0 / 3.0) * e[:, 1] + v, e[:, 4] / np.sqrt(2), e[:, 3] / np.sqrt(2), e[:, 2] / np.sqrt(2)], 1)
-    return out
 
 
 def _close(got, ref):
@@ -147,6 +130,104 @@ def test_kernel_against_numpy(oracle, p, N, layout):
         with pytest.raises(RuntimeError):
             ctx.check(L.exa_element_fields(ctx.h, None, hipref.ptr(d_S), hipref.ptr(d_SV), hipref.ptr(d_xe), hipref.ptr(d_out), None))
     ctx.close()
+
+
+# ---- the other instantiations: hexahedra at p = 3 ... 6 and tetrahedra (reference: tests/fieldref.py, none of the library's tables;
+# tests/test_element_field_inputs_host.py asserts that these inputs tell a wrong node table, point decode, weight table or staged row apart)
+def _props():
+    return np.loadtxt(os.path.join(REFDATA, "props_cp_voce.txt")).ravel()
+
+
+def _close_to(ck, what, got, ref, tol):
+    """_close with a bound per column (fieldref.gpu_bounds: the bounds of _close unless the reference itself is less precise); prints first"""
+    err = F.column_errors(got, ref)
+    worst = int(np.argmax(err / tol))
+    ck.say(f"{what}: worst column {worst}: {err[worst]:.2e} of scale (<= {tol[worst]:.0e}); volume {err[0]:.2e}, centroid {err[1:4].max():.2e}, "
+           f"averages {err[4:31].max():.2e}, elastic strain {err[31:].max():.2e}")
+    assert np.all(err <= tol), (what, worst, err[worst])
+
+
+def _launch(L, dev, c, E, geometry, with_J=True):
+    """exa_element_fields on the first E elements of a case (AOS, a context of its own): rows (E, 37), or the return code and message when it refuses"""
+    Q, n = c["Q"], c["n"]
+    ctx = L.Context(L.EXA_FCC_VOCE, _props(), 298.0, c["p"], E, geometry=geometry)
+    assert (ctx.n, ctx.Q) == (n, Q) and L.exa_qf_size(ctx.h, 9) == 9 * Q * E
+    d = {k: dev.up(np.array(c[k][:E], dtype=np.float64).ravel()) for k in ("J", "S", "SV", "xe")}
+    d_out = dev.zeros(F.NF * E)
+    rc = L.exa_element_fields(ctx.h, hipref.ptr(d["J"]) if with_J else None, hipref.ptr(d["S"]), hipref.ptr(d["SV"]), hipref.ptr(d["xe"]), hipref.ptr(d_out), None)
+    msg = (L.exa_last_error(ctx.h) or b"").decode()
+    dev.sync()
+    out = d_out.cpu().numpy().reshape(E, F.NF)
+    ctx.close()
+    return (rc, msg) if rc != 0 else out
+
+
+NEEDS_J = ("exa_element_fields: a Jacobian field is required at p > 1 and for tetrahedra (only the p = 1 hexahedron recomputes det J from the "
+           "coordinates)")
+
+
+def _kernel_case(L, ck, what, c, tol, ref, geometry, edges):
+    """the checks every new instantiation gets: the reference, the same bits from two launches, the refusal without a Jacobian field, and - at
+    `edges` - contexts over the first E' elements, whose rows are the first rows of the full run bit for bit (each lane sums its own element
+    in a fixed order, so nothing but the block arithmetic differs)"""
+    dev = hipref.Dev()
+    E = c["E"]
+    got = _launch(L, dev, c, E, geometry)
+    _close_to(ck, what, got, ref, tol)
+    assert np.array_equal(_launch(L, dev, c, E, geometry), got)
+    rc, msg = _launch(L, dev, c, E, geometry, with_J=False)
+    ck.say(f"{what}: without a Jacobian field: {rc}, '{msg[:60]}...'")
+    assert rc == L.EXA_ERR_ARG and msg == NEEDS_J
+    for E1 in edges:
+        part = _launch(L, dev, c, E1, geometry)
+        ck.say(f"{what}: the first {E1} element(s) alone: {'the same bits' if np.array_equal(part, got[:E1]) else 'DIFFERENT'}")
+        assert np.array_equal(part, got[:E1]), E1
+    return got
+
+
+@pytest.mark.parametrize("p,N", [(3, 5), (4, 2), (5, 2), (6, 2)])
+def test_high_order_hexahedra_against_numpy(oracle, p, N):
+    """the run-time-order branch (Basis1D by value, nat[], np = p + 1 up to 7) on the warped meshes of hipref.ho_inputs with the oracle's
+    Jacobians: E = 125 at p = 3 (a full and a partial block), E = 8 above (343 points and nodes per element at p = 6)"""
+    import exaconstit_amd.lib as L
+    ck = F.Check(f"gpu hexahedra p={p} N={N}")
+    c = F.hex_case(oracle, p, N)
+    tol, prec = F.gpu_bounds(c["ref"], F.hex_case(oracle, p, N, np.longdouble)["ref"])
+    ck.say(f"hex p={p} N={N}: E = {c['E']}, Q = {c['Q']}; float64 reference vs longdouble {prec.max():.2e}; bounds {tol[0]:.0e} / {tol[36]:.0e}")
+    _kernel_case(L, ck, f"hex p={p} N={N}", c, tol, c["ref"], L.EXA_GEOM_HEX, (1, 64, 65) if p == 3 else ())
+    ck.record()
+
+
+@pytest.fixture(scope="module")
+def tet_dir(tmp_path_factory):
+    return tmp_path_factory.mktemp("fieldref")
+
+
+@pytest.mark.parametrize("p,warped", [(1, False), (2, False), (2, True)])
+def test_tetrahedra_against_numpy(tet_dir, p, warped):
+    """TET = true on the perturbed, shuffled Kuhn mesh with E = 162 (three blocks, the last with 34 elements); at p = 2 also with every node
+    moved by hipref.warp_nodes, so that det J varies inside an element.  Volume against sum_q W_q det J_q, the centroid against the mean of the
+    four vertices, everything else against the det J-weighted averages"""
+    import exaconstit_amd.lib as L
+    what = f"tet p={p}{' warped' if warped else ''}"
+    ck = F.Check("gpu " + what)
+    c = F.tet_case(L, tet_dir, p, warped)
+    tol, prec = F.gpu_bounds(c["ref"], F.tet_case(L, tet_dir, p, warped, np.longdouble)["ref"])
+    ck.say(f"{what}: E = {c['E']}, Q = {c['Q']}; float64 reference vs longdouble {prec.max():.2e}; bounds {tol[0]:.0e} / {tol[36]:.0e}")
+    ref = np.array(c["ref"])
+    ref[:, 1:4] = c["vertex_mean"]
+    got = _kernel_case(L, ck, what, c, tol, ref, L.EXA_GEOM_TET, (1, 64, 65) if p == 1 else ())
+    if not warped:                                                   # straight-sided: the volume is that of the four vertices
+        import tet_mesh_util as T
+        vol = T.tet_volumes(c["X"].reshape(3, c["NN"]).T, c["conn"].reshape(c["E"], c["n"])[:, :4].astype(np.int64))
+        dv = np.abs(got[:, 0] - vol).max() / vol.max()
+        ck.say(f"{what}: volume vs tet_volumes {dv:.2e} (<= 1e-13)")
+        assert dv <= 1e-13
+    # the element-blocked layout stays refused on tetrahedra
+    ctx = L.Context(L.EXA_FCC_VOCE, _props(), 298.0, p, c["E"], geometry=L.EXA_GEOM_TET)
+    assert L.exa_set_quadrature_layout(ctx.h, L.EXA_QLAYOUT_EB64) == L.EXA_ERR_UNSUPPORTED
+    ctx.close()
+    ck.record()
 
 
 def _stage(tmp_path, vis_lines, nsteps=5):
@@ -234,6 +315,68 @@ def test_driver_paraview_output(oracle, tmp_path):
     assert d.run() == 2
     assert not os.path.exists(str(t2 / "results"))
     d.close()
+
+
+def _volume_average_identity(ck, what, d, f):
+    """sum_e V_e Stress_e / sum_e V_e is the last row of the volume averages, as test_driver_paraview_output holds for p = 1 hexahedra"""
+    vol = f["ElementVolume"][:, 0]
+    avg = d.avgs(0, 6)[-1]
+    err = np.max(np.abs((vol[:, None] * f["Stress"]).sum(0) / vol.sum() - avg)) / np.abs(avg).max()
+    spread = np.abs(f["Stress"] - avg).max() / np.abs(avg).max()
+    ck.say(f"{what}: volume-weighted mean of the element stresses vs the volume average {err:.2e} (<= 1e-12); element stresses differ from it by up to {spread:.2f} of it")
+    assert spread > 0.05                                                             # several grains: the state is not uniform
+    assert err <= 1e-12
+
+
+@pytest.mark.parametrize("p", [1, 2])
+def test_driver_fields_on_a_tetrahedral_polycrystal(tmp_path, p):
+    """two steps on the 384-tetrahedron file mesh of test_gpu_tetrahedra._poly (several grains): the fields against the volume averages; at
+    p = 1, where the elements stay straight-sided, also Stress against the W_q-weighted mean of the point stresses (det J is one number per
+    element) and ElementVolume against the tetrahedra of the coordinates the fields were taken in"""
+    import exaconstit_amd.lib as L
+    import tet_mesh_util as T
+    from test_gpu_tetrahedra import _poly, _steps, _toml
+    ck = F.Check(f"gpu driver tet p={p}")
+    mesh = _poly(tmp_path)
+    d = _steps(L, _toml(tmp_path, "fields%d" % p, mesh=mesh, p=p), 2, tmp_path)
+    f = d.element_fields()
+    E = len(f["GlobalElementId"])
+    assert E == 384 and len(set(f["attribute"].tolist())) > 10
+    _volume_average_identity(ck, f"tet p={p}", d, f)
+    if p == 1:
+        _, W, _ = T.ref_tables_numpy(1)
+        S = np.stack([d.qf_component(2, k).reshape(E, W.size) for k in range(6)], 2)
+        ref = np.einsum("q,eqk->ek", W, S) / W.sum()
+        err = np.max(np.abs(ref - f["Stress"])) / np.abs(ref).max()
+        inside = np.abs(S - S[:, :1]).max() / np.abs(ref).max()
+        ck.say(f"tet p=1: Stress vs sum_q W_q S_q / sum_q W_q of the point stresses {err:.2e} (<= 1e-12); the point stresses of an element differ by {inside:.1e} "
+               f"(a linear tetrahedron has one velocity gradient: this pins which rows are read, not the weights - test_tetrahedra_against_numpy does that)")
+        assert err <= 1e-12
+        # one rank: the driver keeps the reader's element and node order
+        _, NN, n, conn, X0 = F.tet_mesh_arrays(L, mesh, 1)
+        assert np.array_equal(f["GlobalElementId"], np.arange(E)) and np.array_equal(d.nodal_field("coords_ref"), X0.reshape(3, NN).T)
+        vol = T.tet_volumes(d.nodal_field("coords"), conn.reshape(E, n).astype(np.int64))
+        dv = np.abs(f["ElementVolume"][:, 0] - vol).max() / vol.max()
+        moved = np.abs(vol - T.tet_volumes(X0.reshape(3, NN).T, conn.reshape(E, n).astype(np.int64))).max() / vol.max()
+        ck.say(f"tet p=1: ElementVolume vs the tetrahedra of the end-of-step coordinates {dv:.2e} (<= 1e-13); the step moved the volumes by {moved:.2e}")
+        assert dv <= 1e-13 and moved > 1e-9
+    d.close()
+    ck.record()
+
+
+def test_driver_fields_on_order3_hexahedra(oracle, tmp_path):
+    """two steps of the generated 5^3 mesh at p_refinement = 3 (125 grains): the run-time-order branch under the driver"""
+    import exaconstit_amd.lib as L
+    from test_gpu_driver import _variant_toml
+    ck = F.Check("gpu driver hex p=3")
+    toml = _variant_toml(tmp_path, "voce_pa.toml", [("prefinement = 1", "p_refinement = 3"), ("ref_ser = 1", "ref_ser = 0")], "p3fields")
+    d = L.Driver.from_toml(toml, out_dir=str(tmp_path), write_files=False)
+    for ti in (1, 2):
+        assert d.step(ti)
+    assert d.mesh_info()["order"] == 3 and d.mesh_info()["elements"] == 125
+    _volume_average_identity(ck, "hex p=3", d, d.element_fields())
+    d.close()
+    ck.record()
 
 
 def test_two_loopback_ranks_match_one(oracle, tmp_path):

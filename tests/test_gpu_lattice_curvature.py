@@ -249,13 +249,13 @@ def test_grain_boundary_abi():
     assert ref[:, 3].max() < 5.0 and ref[:, 4].max() < 1.0                       # degrees: nothing of the 20 degree jump leaks in
 
 
-def test_hexahedra_p2_abi(oracle):
-    """2^3 hexahedra at p = 2 (27 nodes per element): the recovery runs over the first 8 entries of the connectivity, the vertices in the order
-    of HEX_SIGNS, and leaves the 98 edge, face and interior nodes alone"""
+def _hexahedra_abi(oracle, p):
+    """2^3 hexahedra at order p: the recovery runs over the first 8 entries of the connectivity, the vertices in the order of HEX_SIGNS under
+    the Gauss-Lobatto numbering too, and leaves the edge, face and interior nodes alone"""
     import exaconstit_amd.lib as L
-    rve = hipref.make_rve(oracle, 2, p=2)
+    rve = hipref.make_rve(oracle, 2, p=p)
     E, n, NN = rve["E"], rve["n"], rve["NN"]
-    assert (E, n, NN) == (8, 27, 125)
+    assert (E, n, NN) == (8, (p + 1) ** 3, (2 * p + 1) ** 3)
     conn = rve["conn"].reshape(E, n); X = rve["X"].reshape(3, NN).T
     xv = X[conn[:, :8]]
     assert np.allclose(xv - xv[:, :1], (HEX_SIGNS + 1) / 4, rtol=0, atol=1e-14)          # corners of the element's cell, in vertex order
@@ -268,13 +268,23 @@ def test_hexahedra_p2_abi(oracle):
     q = np.array([_qmul(_axis_quat(AXIS if g == 2 else n2, t), q0[int(g)]) for g, t in zip(grain, th)])
     qbar = grain_means_numpy(V, q, grain, q0)
     ref, rsum = curvature_numpy(V, q, grain, qbar, conn[:, :8], xv, 1.0)
-    ctx = L.Context(L.EXA_FCC_VOCE, _props(), 298.0, 2, E)
+    ctx = L.Context(L.EXA_FCC_VOCE, _props(), 298.0, p, E)
     got, gsum, nodal = run_abi(L, ctx, _rows(V, cen, q), grain, G, _qbar_array(qbar, G), conn, NN, X, 1.0)
     ctx.close()
-    _close(got, ref, what="hex p=2")
-    _close_summary(gsum, rsum, what="hex p=2")
+    _close(got, ref, what=f"hex p={p}")
+    _close_summary(gsum, rsum, what=f"hex p={p}")
     vertex = np.zeros(NN, bool); vertex[conn[:, :8].ravel()] = True
     assert vertex.sum() == 27 and np.all(nodal[4][~vertex] == 0) and np.all(nodal[4][vertex] > 0)
+
+
+def test_hexahedra_p2_abi(oracle):
+    """27 nodes per element, 98 of the 125 nodes are no vertices"""
+    _hexahedra_abi(oracle, 2)
+
+
+def test_hexahedra_p3_abi(oracle):
+    """64 nodes per element (k_curv_nodal with n = 64, nvert = 8), 316 of the 343 nodes are no vertices"""
+    _hexahedra_abi(oracle, 3)
 
 
 @pytest.mark.parametrize("p", [1, 2])
